@@ -4,7 +4,7 @@
 Workload (BASELINE.json configs[1], "C2"): a batch of 4096 stereo 44.1 kHz long-block frames
 (n = 2048, window long/long), Floor1 + Residue2 + coupling, setup and side information taken from the
 254 long/long packets of TestFiles/3test.ogg (tests/golden/3test.ogg) tiled to 4096 ("G-real" of
-SURVEY 8d).  A step is one pass of the whole hot path (residue adds -> inverse coupling + floor ->
+SURVEY 8d).  A pass is one run of the whole hot path (residue adds -> inverse coupling + floor ->
 IMDCT + window -> overlap-add + interleave + clip) over that batch, descriptors already resident in
 HBM, PCM written to HBM.  Weak scaling: every rank owns one GPU and one such batch, no collective in
 the data path.
@@ -16,12 +16,15 @@ look-ahead batch (k_synth over the odd frames, k_synth_emit over the even ones);
 timed region.  After the timed region the PCM of every resident batch is hashed and compared with the digest the CPU oracle
 produced for the same packets (tests/golden/bench_pcm_digests.json, tools/gen_bench_digests.py): `pcm_digest_ok`.
 
-Launch: python bench.py --gpus N --steps K --warmup W.  For N > 1 the script starts its own ranks (it re-executes
-itself under torch.distributed.run, one rank per GPU over RCCL) unless it already runs as a rank (WORLD_SIZE set).
+Launch: python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR].  For N > 1 the script starts its own ranks (a child
+torch.distributed.run, one rank per GPU over RCCL; the launching process never touches the GPU) unless it already runs as a rank
+(WORLD_SIZE set).
 
-A step is `passes_per_step` passes, chosen from a calibration run so that the timed region lasts at least ~2 s whatever
---steps says (a 20-step run of one 45 us pass each would time 0.9 ms of launch jitter, and an outside observer sampling GPU
-activity would see nothing); the line states it in config, and `value` counts every pass.
+A step is one pass over every resident batch (`passes_per_step` = streams x resident batches per stream, fixed by --streams and
+--working-set-mib, never by the clock): W untimed steps, then exactly K timed steps.  `ms_per_step` is what one timed step took, so
+that the K of a later run can be chosen from it; `value` counts every pass.  --dump-outputs DIR writes the PCM the last timed step
+produced (a fixed, seeded sample of it, at most 64 MB in all) as DIR/<name>.npy, float32: two builds run with the same arguments
+decode the same packets and can be compared output for output.
 
 Working set: the passes rotate over `--streams` decoder instances (default 3; own nvh_ctx / HIP stream each, as a corpus
 transcoder's workers have) x R resident 4096-frame batches each, R chosen so that what the passes touch (slabs + the odd frames'
@@ -42,7 +45,6 @@ import argparse
 import datetime
 import json
 import os
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")  # before the HIP runtime initialises (nvorbis_amd.configure_process says why)
 os.environ.setdefault("NVH_CORPUS_MALLOPT", "1")  # this process is a corpus job: the allocator settings of nvorbis_amd.corpus._tune_malloc (opt-in)
 import sys
 import time
@@ -53,7 +55,9 @@ if ROOT not in sys.path:
 
 FRAMES = 4096
 BLOCK = 2048
-HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak
+DUMP_BYTES = 48 << 20  # --dump-outputs: at most this much PCM in all (below 64 MB with the .npy headers)
+DUMP_SEED = 20261015   # --dump-outputs: the sample positions inside a batch whose PCM does not fit whole
 
 
 def ll_packets(nv, path):
@@ -244,6 +248,36 @@ def check_digests(insts, seeds, no_check=False):
     if n < total:
         sys.stderr.write("bench.py: %d of %d timed batches have no committed digest (tools/gen_bench_digests.py)\n" % (total - n, total))
     return ok, n, total
+
+
+def sample_outputs(torch, insts, world, rank):
+    """What the last timed step handed its caller: the PCM of every resident batch, {name: float32 host array}.  A batch whose
+    PCM does not fit this rank's share of DUMP_BYTES whole contributes the samples at one fixed set of positions (DUMP_SEED,
+    ascending), the same for every batch and every run."""
+    import numpy as np
+    pcms = [(k, j, pcm) for k, (_, _, _, batches_k) in enumerate(insts) for j, (_, pcm) in enumerate(batches_k)]
+    per = max(1, DUMP_BYTES // world // 4 // len(pcms))
+    idx = {}
+    out = {}
+    prefix = "rank%d_" % rank if world > 1 else ""
+    for k, j, pcm in pcms:
+        n = pcm.numel()
+        if n <= per:
+            got = pcm
+        else:
+            if n not in idx:
+                pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, per, replace=False))
+                idx[n] = torch.from_numpy(pos).to(pcm.device)
+            got = pcm.index_select(0, idx[n])
+        out["%spcm_stream%d_batch%d" % (prefix, k, j)] = got.cpu().numpy().astype(np.float32, copy=False)
+    return out
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def config_lines(nv, torch, ctx, root):
@@ -515,27 +549,29 @@ def main():
                     help="independent decoder instances (own nvh_ctx / HIP stream) the passes rotate over")
     ap.add_argument("--working-set-mib", type=float, default=512.0,
                     help="lower bound of what the rotating passes touch (resident batches per stream follow from it)")
-    ap.add_argument("--min-timed-ms", type=float, default=2000.0, help="lower bound of the timed region (sets passes_per_step)")
+    ap.add_argument("--min-timed-ms", type=float, default=2000.0,
+                    help="four times the length of the L3-resident comparison loop (roofline.l3_resident); the headline times --steps steps")
     ap.add_argument("--no-unfused", action="store_true",
                     help="skip the short NVH_NO_EMIT=1 run (overlap-add in k_ola_compact) that roofline.unfused reports beside the fused kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the PCM of the last timed step (a fixed, seeded sample, at most 64 MB) as DIR/<name>.npy, float32")
     args = ap.parse_args()
-
-    import torch
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # started plainly with --gpus N: become N ranks (one per GPU of this node, RCCL over xGMI)
-        have = torch.cuda.device_count() if torch.cuda.is_available() else 0
-        if have < args.gpus and not os.environ.get("NVH_BENCH_SHARE_GPU"):
-            sys.stderr.write("bench.py --gpus %d: this node shows %d HIP device(s); the multi-GPU run needs %d\n" % (args.gpus, have, args.gpus))
-            raise SystemExit(2)
+        # started plainly with --gpus N: become N ranks (one per GPU of this node, RCCL over xGMI) in a child launcher; this
+        # process does not initialise the GPU (the ranks check the device count) and ends with the launcher's exit status
         import socket
+        import subprocess
         sock = socket.socket()
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
         sock.close()
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        raise SystemExit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+                                          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
 
+    import torch
     import nvorbis_amd as nv
 
     rank = int(os.environ.get("RANK", "0"))
@@ -549,6 +585,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device: there is no CPU path to measure")
+    if world > 1 and not share_gpu and torch.cuda.device_count() < world:
+        raise SystemExit("bench.py: %d ranks but this node shows %d HIP device(s); the multi-GPU run needs one per rank" % (world, torch.cuda.device_count()))
     if world != args.gpus:
         sys.stderr.write("bench.py: --gpus %d but WORLD_SIZE=%d; reporting n_gpus=%d (the ranks that actually run)\n" % (args.gpus, world, world))
     torch.cuda.set_device(local_rank)
@@ -604,47 +642,40 @@ def main():
     def make_order(r):
         return [insts[k][3][j] for j in range(r) for k in range(nin)]
 
-    def timed(order, steps, warmup, min_ms):
-        """`steps` steps of passes_per_step passes rotating over `order`; returns (elapsed s, passes, passes_per_step)."""
-        pos = [0]
-
-        def run_passes(n):
-            i = pos[0]
-            for _ in range(n):
-                b, p = order[i % len(order)]
+    def timed(order, steps, warmup):
+        """`warmup` untimed steps, then `steps` timed steps; a step is one pass over every batch of `order`, in order.
+        Returns the seconds the timed steps took (the slowest rank's)."""
+        def step():
+            for b, p in order:
                 b.synth(p.data_ptr(), cap)
-                i += 1
-            pos[0] = i
 
-        run_passes(2 * len(order))  # calibration (untimed): how long one pass takes here
-        barrier()
-        t0 = time.perf_counter()
-        run_passes(64)
-        barrier()
-        pass_ms = (time.perf_counter() - t0) / 64 * 1e3
-        if dist is not None:
-            t = torch.tensor([pass_ms], dtype=torch.float64, device="cuda")
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            pass_ms = float(t.item())
-        pps = max(1, int(1.35 * min_ms / max(steps, 1) / max(pass_ms, 1e-6) + 0.999))  # 35 % margin: the calibration passes are slower than steady state
         for _ in range(warmup):
-            run_passes(pps)
+            step()
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
-            run_passes(pps)
+            step()
         barrier()
         el = time.perf_counter() - t0
         if dist is not None:
             t = torch.tensor([el], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        return el, steps * pps, pps
+        return el
 
     # ---- the timed region of the headline: W warmup steps, exactly K steps, working set past the Infinity Cache ----
-    elapsed, total_passes, passes_per_step = timed(make_order(reps), args.steps, args.warmup, args.min_timed_ms)
-    # the same loop over one batch per stream (L3-resident, the regime of the round-1 / round-2 lines), shorter
-    el_l3, passes_l3, _ = timed(make_order(1), max(args.steps // 4, 1), max(args.warmup // 4, 1), args.min_timed_ms / 4)
+    order = make_order(reps)
+    passes_per_step = len(order)
+    elapsed = timed(order, args.steps, args.warmup)
+    total_passes = args.steps * passes_per_step
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, sample_outputs(torch, insts, world, rank))
+    # the same loop over one batch per stream (L3-resident, the regime of the round-1 / round-2 lines), about a quarter of
+    # --min-timed-ms long at the headline's rate (the same count on every rank: `elapsed` is the slowest rank's)
+    order_l3 = make_order(1)
+    steps_l3 = max(1, int(args.min_timed_ms / 4 / (elapsed / total_passes * 1e3 * len(order_l3)) + 0.5))
+    el_l3 = timed(order_l3, steps_l3, max(args.warmup // 4, 1))
+    passes_l3 = steps_l3 * len(order_l3)
 
     # per-kernel durations, hipEvents on the launch stream (rank 0 reports): rotating over instance 0's batches one launch
     # at a time (HBM-resident when reps > 1) and repeated on one batch (L3-resident)
@@ -738,13 +769,15 @@ def main():
             import subprocess
             env = dict(os.environ)
             env["NVH_NO_EMIT"] = "1"
+            # (about 0.4 s of timed steps at the fused rate)
+            unfused_steps = max(40, int(400.0 / (elapsed / args.steps * 1e3) + 0.5))
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", "40", "--warmup", "4", "--min-timed-ms", "400",
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(unfused_steps), "--warmup", "4", "--min-timed-ms", "400",
                                     "--streams", str(nin), "--working-set-mib", str(args.working_set_mib), "--no-configs",
-                                    "--no-cpu-baseline", "--no-unfused"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
+                                    "--no-cpu-baseline", "--no-unfused", "--c5-scale", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
                                    text=True, timeout=600)
                 uj = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-                unfused = {"what": "NVH_NO_EMIT=1: every overlap-add in k_ola_compact (the path of GPU-parsed batches and of more than two channels); same loop, 40 steps",
+                unfused = {"what": "NVH_NO_EMIT=1: every overlap-add in k_ola_compact (the path of GPU-parsed batches and of more than two channels); same loop, %d steps" % unfused_steps,
                            "frames_per_s": uj["value"], "ms_per_pass": uj["config"]["ms_per_pass"], "kernels_ms": uj["kernels_ms"],
                            "frac": uj["roofline"]["frac"], "whole_pass_frac": uj["roofline"]["whole_pass_frac"]}
             except Exception as e:  # the headline does not depend on it

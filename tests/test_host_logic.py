@@ -600,3 +600,41 @@ def test_committed_profiles_belong_to_the_committed_sources():
         assert abs(r["achieved"] - r["algorithmic_bytes_per_launch"] / (r["avg_launch_ms"] * 1e-3) / 1e9) < 1e-6 * r["achieved"]
         assert r["algorithmic_bytes_per_launch"] == 2048 * 2 * (1024 * 4 + 1024 * 4)  # n/2 floats in, n/2 out per channel-frame
         assert 0.95 < r["traffic"] / r["algorithmic_bytes_per_launch"] < 1.10  # PMC bytes per launch: no wasted re-reads
+
+
+def test_bench_output_dump_is_a_fixed_bounded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the PCM of every resident batch as the last timed step left it, float32, at most 64 MB in all, at
+    sample positions that are the same for every batch and every run (so that two builds compare output for output).  Host logic
+    on CPU tensors whose float bits encode their batch and position."""
+    import torch
+    monkeypatch.delenv("NVH_CORPUS_MALLOPT", raising=False)  # (bench.py opts its own process in at import; not this one)
+    import bench
+    n = 4096 * 1024 * 2  # one resident batch of the headline: 4096 stereo frames of 1024 samples
+
+    def insts(streams, batches, size):
+        return [(None, None, None, [(None, (torch.arange(size, dtype=torch.int32) + (k * batches + j) * size).view(torch.float32))
+                                    for j in range(batches)]) for k in range(streams)]
+
+    big = insts(3, 3, n)
+    a, b = bench.sample_outputs(torch, big, 1, 0), bench.sample_outputs(torch, big, 1, 0)
+    assert sorted(a) == ["pcm_stream%d_batch%d" % (k, j) for k in range(3) for j in range(3)]
+    pos = None
+    for k in range(3):
+        for j in range(3):
+            x = a["pcm_stream%d_batch%d" % (k, j)]
+            assert x.dtype == np.float32 and np.array_equal(x.view(np.int32), b["pcm_stream%d_batch%d" % (k, j)].view(np.int32))
+            p = x.view(np.int32) - (k * 3 + j) * n
+            assert 0 <= p[0] and p[-1] < n and np.all(np.diff(p) > 0) and 0 < p.size < n
+            assert pos is None or np.array_equal(p, pos)
+            pos = p
+    bench.write_outputs(str(tmp_path / "dump"), a)
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files == sorted(k + ".npy" for k in a)
+    assert sum(os.path.getsize(tmp_path / "dump" / f) for f in files) <= 64e6
+    assert all(np.array_equal(np.load(tmp_path / "dump" / (k + ".npy")).view(np.int32), v.view(np.int32)) for k, v in a.items())
+    # a batch that fits is dumped whole; every rank of a multi-GPU run writes its own share under its own names
+    small = bench.sample_outputs(torch, insts(1, 2, 1000), 2, 1)
+    assert sorted(small) == ["rank1_pcm_stream0_batch0", "rank1_pcm_stream0_batch1"]
+    assert np.array_equal(small["rank1_pcm_stream0_batch1"].view(np.int32), np.arange(1000, 2000, dtype=np.int32))
+    two = bench.sample_outputs(torch, big, 2, 0)
+    assert sum(v.nbytes for v in two.values()) * 2 <= 64e6

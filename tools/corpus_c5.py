@@ -11,7 +11,6 @@ tests/c5_corpus.py (lengths log-uniform 5-300 s x scale, seed = file 
 import argparse
 import json
 import os
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")  # before the HIP runtime initialises (nvorbis_amd.configure_process says why)
 os.environ.setdefault("NVH_CORPUS_MALLOPT", "1")  # this process is a corpus job: the allocator settings of nvorbis_amd.corpus._tune_malloc (opt-in)
 import sys
 import time

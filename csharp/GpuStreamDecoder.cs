@@ -26,6 +26,8 @@ namespace NVorbis.Hip
         int _channels, _sampleRate, _block0, _block1;
         readonly int _batchPackets;
         float[] _ring = Array.Empty<float>();
+        short[] _ring16 = Array.Empty<short>();   // pcm16: the ring holds 16-bit samples (nvh_stream_synth_pcm, NVH_PCM_S16)
+        readonly bool _pcm16;
         int _ringPos, _ringLen;
         bool _ended, _clip = true;
         long _skip;   // floats to drop in front of the next samples: SeekTo's roll-forward
@@ -40,8 +42,12 @@ namespace NVorbis.Hip
         /// <param name="poolParseLanes">0 for a lone decoder.  A host that runs many decoders at once (one per worker thread: a
         /// corpus transcoder) passes 32 -- nvh_ctx_set_parse_lanes: the GPU parser then puts up to 32 packets on a wavefront, every
         /// lane walking its own, so that the parses of all workers fit the chip side by side (INTEGRATION.md).  The PCM does not depend on it.</param>
-        public GpuStreamDecoder(Contracts.IPacketProvider packetProvider, int device = 0, int batchPackets = 1024, int poolParseLanes = 0)
+        /// <param name="pcm16">true: the decoder delivers 16-bit PCM through Read(Span&lt;short&gt;, ...) -- libvorbis ov_read's conversion,
+        /// done in the kernels, half the bytes over PCIe -- and Read(Span&lt;float&gt;, ...) throws; false: float PCM, as the reference.</param>
+        public GpuStreamDecoder(Contracts.IPacketProvider packetProvider, int device = 0, int batchPackets = 1024, int poolParseLanes = 0,
+                                bool pcm16 = false)
         {
+            _pcm16 = pcm16;
             _packetProvider = packetProvider ?? throw new ArgumentNullException(nameof(packetProvider));
             _batchPackets = batchPackets;
             NativeMethods.Check(NativeMethods.nvh_ctx_create(device, out _ctx));
@@ -161,10 +167,19 @@ namespace NVorbis.Hip
                 if (frames != 0)
                 {
                     long need = samples * _channels;
-                    if (_ring.Length < need) _ring = new float[need];
                     int rc;
-                    fixed (float* dst = _ring)
-                        rc = NativeMethods.nvh_stream_synth(_stream, dst, IntPtr.Zero, _ring.Length, out written);
+                    if (_pcm16)
+                    {
+                        if (_ring16.Length < need) _ring16 = new short[need];
+                        fixed (short* dst = _ring16)
+                            rc = NativeMethods.nvh_stream_synth_pcm(_stream, NativeMethods.NVH_PCM_S16, dst, IntPtr.Zero, _ring16.Length, out written);
+                    }
+                    else
+                    {
+                        if (_ring.Length < need) _ring = new float[need];
+                        fixed (float* dst = _ring)
+                            rc = NativeMethods.nvh_stream_synth(_stream, dst, IntPtr.Zero, _ring.Length, out written);
+                    }
                     _ringPos = 0; _ringLen = (int)written;
                     if (rc != 0)
                     {
@@ -194,6 +209,19 @@ namespace NVorbis.Hip
         // StreamDecoder.Read (StreamDecoder.cs:320-389): same argument checks, partial reads, 0 at end of stream.
         public int Read(Span<float> buffer, int offset, int count)
         {
+            if (_pcm16) throw new InvalidOperationException("this decoder delivers 16-bit PCM: Read(Span<short>, ...)");
+            return ReadRing(buffer, _ring, offset, count);
+        }
+
+        // the same for a decoder constructed with pcm16: true
+        public int Read(Span<short> buffer, int offset, int count)
+        {
+            if (!_pcm16) throw new InvalidOperationException("this decoder delivers float PCM: Read(Span<float>, ...)");
+            return ReadRing(buffer, _ring16, offset, count);
+        }
+
+        int ReadRing<T>(Span<T> buffer, T[] ring, int offset, int count)
+        {
             if (offset < 0 || offset + count > buffer.Length) throw new ArgumentOutOfRangeException(nameof(offset));
             if (count % _channels != 0) throw new ArgumentOutOfRangeException(nameof(count), "Must be a multiple of Channels!");
             if (_stream == IntPtr.Zero) throw new ObjectDisposedException(nameof(GpuStreamDecoder));
@@ -203,10 +231,11 @@ namespace NVorbis.Hip
                 // an exception of the packet that follows this ring position: the samples before it have been delivered
                 if (_pendingErrors.Count > 0 && _ringPos >= _pendingErrors.Peek().Value) throw _pendingErrors.Dequeue().Key;
                 if (_ringPos >= _ringLen && !Refill()) break;
+                ring = _pcm16 ? (T[])(object)_ring16 : (T[])(object)_ring;  // (Refill may have grown it)
                 if (_skip > 0) { int drop = (int)Math.Min(_skip, _ringLen - _ringPos); _ringPos += drop; _skip -= drop; continue; }
                 int take = Math.Min(tgt - idx, _ringLen - _ringPos);
                 if (_pendingErrors.Count > 0) take = Math.Min(take, _pendingErrors.Peek().Value - _ringPos);
-                new Span<float>(_ring, _ringPos, take).CopyTo(buffer.Slice(idx, take));
+                new Span<T>(ring, _ringPos, take).CopyTo(buffer.Slice(idx, take));
                 _ringPos += take; idx += take;
             }
             return idx - offset;

@@ -95,6 +95,11 @@ namespace NVorbis.Hip
         /// <summary>Pipelined form (pinned destination): the transfer of one batch overlaps the pushes, parse and kernels of the next.</summary>
         [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_begin(IntPtr stream, float* pcmHost, long capacity, out long expected);
         [DllImport(Lib)] public static extern int nvh_stream_synth_end(IntPtr stream, out long written);
+        /// <summary>Output formats of the *_pcm synthesis calls: NVH_PCM_S16 is ov_read's 16-bit conversion, done in the kernels.</summary>
+        public const int NVH_PCM_F32 = 0, NVH_PCM_S16 = 1;
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_pcm(IntPtr stream, int format, void* pcmHost, IntPtr dPcm, long capacity, out long written);
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_begin_pcm(IntPtr stream, int format, void* pcmHost, long capacity, out long expected);
+        [DllImport(Lib)] public static extern int nvh_batch_synth_pcm(IntPtr batch, int format, IntPtr dPcm, long capacity);
 
         /// <summary>The corpus gather (include/nvorbis_hip.h, "multi-GPU"): RCCL over xGMI through the library, one process per GPU (GpuCorpusGather.cs).</summary>
         public const int NVH_COMM_ID_BYTES = 128;

@@ -274,6 +274,16 @@ int nvh_stream_synth(nvh_stream *s, float *pcm_host, float *d_pcm, int64_t capac
  * reference (its Read is synchronous); nvh_stream_synth must not be mixed in while batches are outstanding (NVH_ERR_ARGUMENT). */
 int nvh_stream_synth_begin(nvh_stream *s, float *pcm_host, int64_t capacity, int64_t *expected);
 int nvh_stream_synth_end(nvh_stream *s, int64_t *written);
+/* Output formats of the *_pcm forms of the synthesis calls.  NVH_PCM_S16 is libvorbis ov_read's conversion, done inside the
+ * kernels on the float the float path emits (after ClipSamples' clip): s16 = clamp(rint(x * 32768), -32768, 32767), ties to even,
+ * NaN -> 0; out-of-range values saturate without touching HasClipped.  No counterpart in the reference.  The format belongs to
+ * the call, not the stream (batches of one stream may alternate).  Capacities, *written and *expected count samples; a 16-bit
+ * d_pcm must be 16-byte aligned.  An unknown format, or a misaligned 16-bit d_pcm: NVH_ERR_ARGUMENT.  The float forms above are
+ * these with NVH_PCM_F32; nvh_stream_synth_end serves both. */
+#define NVH_PCM_F32 0
+#define NVH_PCM_S16 1
+int nvh_stream_synth_pcm(nvh_stream *s, int format, void *pcm_host, void *d_pcm, int64_t capacity, int64_t *written);
+int nvh_stream_synth_begin_pcm(nvh_stream *s, int format, void *pcm_host, int64_t capacity, int64_t *expected);
 /* After nvh_stream_synth returned an error code together with *written > 0 (GPU-parse mode: packets of the batch made
  * the parser fail -- with the codes nvh_stream_push_packet returns for them in host-parse mode -- and the batch was
  * parsed again on the host without them): every such packet in stream order, codes[i] and samples_before[i] = the
@@ -305,6 +315,8 @@ int nvh_stream_kernels(const nvh_stream *s, char *buf, int cap);
 /* Launch the synthesis kernels for a resident batch (asynchronous on the context's stream);
  * may be repeated, results are identical each time.  d_pcm holds samples*channels floats. */
 int nvh_batch_synth(nvh_batch *b, float *d_pcm, int64_t capacity);
+/* The same in an output format (NVH_PCM_*; see nvh_stream_synth_pcm). */
+int nvh_batch_synth_pcm(nvh_batch *b, int format, void *d_pcm, int64_t capacity);
 /* Time `iters` repetitions with hipEvents on the launch stream: total milliseconds for the whole
  * pipeline, and per timing slot (spectrum: residue | couple+floor, or fused in slot 1; imdct+window; overlap+emit;
  * see nvh_batch_kernels).  A slot brackets its launches with event records, which costs ~2 us per slot. */

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_common.h"
+#include <type_traits>
 
 #define NVH_THREADS 256
 
@@ -584,9 +585,11 @@ k_couple_floor(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, int* __r
 
 // Parallel form: valid when no overlap region reaches into a tail (FrameBatch::sequential_ola == false),
 // i.e. every tail read here is an untouched windowed block.  One workgroup per frame.
-extern "C" __global__ void __launch_bounds__(NVH_THREADS)
-k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
-           float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
+// (PCM: float, or int16_t for the _s16 twin -- kernels_common.h: pcm_s16_value -- here and in every emitting kernel below)
+template <typename PCM>
+__device__ __forceinline__ void ola_emit_body(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work,
+                                              const float* __restrict__ carry, PCM* __restrict__ pcm, int clip,
+                                              int* __restrict__ clipped_flag) {
   const int f = blockIdx.x;
   const NvhFrame fr = Bt.frames[f];
   const int ch = S.channels;
@@ -595,7 +598,7 @@ k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const 
   const float* cur = work + (long long)f * ch * S.block1;
   const float* prev = nullptr;
   if (fr.ov_len > 0) prev = (fr.ov_frame == -2) ? carry : (fr.ov_frame >= 0 ? work + (long long)fr.ov_frame * ch * S.block1 : nullptr);
-  float* out = pcm + fr.out_pos * ch;
+  PCM* out = pcm + fr.out_pos * ch;
   int clipped = 0;
   for (int o = threadIdx.x; o < total; o += NVH_THREADS) {
     int t = o / ch, c = o - t * ch;
@@ -613,13 +616,24 @@ k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const 
   }
   report_clipped(clipped, clipped_flag);
 }
+extern "C" __global__ void __launch_bounds__(NVH_THREADS)
+k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
+           float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
+  ola_emit_body<float>(S, Bt, work, carry, pcm, clip, clipped_flag);
+}
+extern "C" __global__ void __launch_bounds__(NVH_THREADS)
+k_ola_emit_s16(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
+               int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
+  ola_emit_body<int16_t>(S, Bt, work, carry, pcm, clip, clipped_flag);
+}
 
 // Sequential form: one workgroup walks the frames in order and performs the adds in place, exactly
 // like the reference's ping-pong buffers (needed only for streams whose window flags disagree with
 // their neighbours so that an overlap reaches a block's own tail).
-extern "C" __global__ void __launch_bounds__(NVH_THREADS)
-k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry,
-               float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
+template <typename PCM>
+__device__ __forceinline__ void ola_emit_seq_body(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work,
+                                                  const float* __restrict__ carry, PCM* __restrict__ pcm, int clip,
+                                                  int* __restrict__ clipped_flag) {
   const int ch = S.channels;
   int clipped = 0;
   for (int f = 0; f < Bt.nframes; ++f) {
@@ -635,7 +649,7 @@ k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const fl
       }
     }
     __syncthreads();
-    float* out = pcm + fr.out_pos * ch;
+    PCM* out = pcm + fr.out_pos * ch;
     const int total = fr.emit_count * ch;
     for (int o = threadIdx.x; o < total; o += NVH_THREADS) {
       int t = o / ch, c = o - t * ch;
@@ -646,6 +660,16 @@ k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const fl
     __syncthreads();
   }
   report_clipped(clipped, clipped_flag);
+}
+extern "C" __global__ void __launch_bounds__(NVH_THREADS)
+k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry,
+               float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
+  ola_emit_seq_body<float>(S, Bt, work, carry, pcm, clip, clipped_flag);
+}
+extern "C" __global__ void __launch_bounds__(NVH_THREADS)
+k_ola_emit_seq_s16(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry,
+                   int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
+  ola_emit_seq_body<int16_t>(S, Bt, work, carry, pcm, clip, clipped_flag);
 }
 
 
@@ -674,9 +698,9 @@ __device__ __forceinline__ float compact_value(const float* __restrict__ plane, 
 
 // Overlap-add of one frame, CH channels, everything in units of four samples: a lane produces four consecutive
 // sample times of every channel and writes them as CH 16-byte stores (its 4*CH interleaved floats are contiguous).
-template <int CH>
+template <int CH, typename PCM>
 __device__ __forceinline__ int ola_vec(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev, bool prev_full,
-                                       const float* __restrict__ w, const float* __restrict__ wp, float* out, int clip, int tid, int threads) {
+                                       const float* __restrict__ w, const float* __restrict__ wp, PCM* out, int clip, int tid, int threads) {
   int clipped = 0;
   const int groups = fr.emit_count >> 2;
   for (int g = tid; g < groups; g += threads) {
@@ -703,9 +727,13 @@ __device__ __forceinline__ int ola_vec(const NvhDevSetup& S, const NvhFrame& fr,
       flat[2 * CH + c] = v.z;
       flat[3 * CH + c] = v.w;
     }
-    float4* o4 = reinterpret_cast<float4*>(out) + (long long)g * CH;
+    pcm4_t<PCM>* o4 = reinterpret_cast<pcm4_t<PCM>*>(out) + (long long)g * CH;
+    if constexpr (CH == 2 && std::is_same<PCM, int16_t>::value) {  // (float: the stores as they were)
+      pcm_store4x2(o4, flat);
+    } else {
 #pragma unroll
-    for (int k = 0; k < CH; ++k) pcm_store4(o4 + k, flat[4 * k], flat[4 * k + 1], flat[4 * k + 2], flat[4 * k + 3]);
+      for (int k = 0; k < CH; ++k) pcm_store4(o4 + k, flat[4 * k], flat[4 * k + 1], flat[4 * k + 2], flat[4 * k + 3]);
+    }
   }
   return clipped;
 }
@@ -717,9 +745,9 @@ __device__ __forceinline__ int ola_vec(const NvhDevSetup& S, const NvhFrame& fr,
 // sample times (i, n/2-1-i) needs exactly A[i] and B[i].  A lane takes four consecutive i: two 16-byte loads per channel,
 // two groups of four sample times out (ola_vec reads every value twice: once for i, once, reversed, for n/2-1-i).
 // Same products, same additions, same order as ola_vec / the reference (Mode.cs:160-166, StreamDecoder.cs:532-541).
-template <int CH>
+template <int CH, typename PCM>
 __device__ __forceinline__ int ola_sym(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev,
-                                       const float* __restrict__ w, const float* __restrict__ wp, float* out, int clip, int tid, int threads) {
+                                       const float* __restrict__ w, const float* __restrict__ wp, PCM* out, int clip, int tid, int threads) {
   int clipped = 0;
   const int n = fr.n, n2 = n >> 1;
   const int groups = n >> 4;  // n/4 compact values per quarter, four per lane
@@ -751,12 +779,17 @@ __device__ __forceinline__ int ola_sym(const NvhDevSetup& S, const NvhFrame& fr,
       fwd[0 * CH + c] = v.x; fwd[1 * CH + c] = v.y; fwd[2 * CH + c] = v.z; fwd[3 * CH + c] = v.w;
       mir[0 * CH + c] = u.x; mir[1 * CH + c] = u.y; mir[2 * CH + c] = u.z; mir[3 * CH + c] = u.w;
     }
-    float4* of = reinterpret_cast<float4*>(out) + (long long)g * CH;
-    float4* om = reinterpret_cast<float4*>(out) + (long long)((n >> 3) - 1 - g) * CH;
+    pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + (long long)g * CH;
+    pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + (long long)((n >> 3) - 1 - g) * CH;
+    if constexpr (CH == 2 && std::is_same<PCM, int16_t>::value) {  // (float: the stores as they were)
+      pcm_store4x2(of, fwd);
+      pcm_store4x2(om, mir);
+    } else {
 #pragma unroll
-    for (int k = 0; k < CH; ++k) {
-      pcm_store4(of + k, fwd[4 * k], fwd[4 * k + 1], fwd[4 * k + 2], fwd[4 * k + 3]);
-      pcm_store4(om + k, mir[4 * k], mir[4 * k + 1], mir[4 * k + 2], mir[4 * k + 3]);
+      for (int k = 0; k < CH; ++k) {
+        pcm_store4(of + k, fwd[4 * k], fwd[4 * k + 1], fwd[4 * k + 2], fwd[4 * k + 3]);
+        pcm_store4(om + k, mir[4 * k], mir[4 * k + 1], mir[4 * k + 2], mir[4 * k + 3]);
+      }
     }
   }
   return clipped;
@@ -767,9 +800,9 @@ __device__ __forceinline__ int ola_sym(const NvhDevSetup& S, const NvhFrame& fr,
 // through LDS: a lane's eight results go to channel-planar rows of the workgroup's two runs of sample times (the forward run
 // [4 g0, 4 g0 + 4 GW) and the mirrored run [n/2 - 4 (g0 + GW), n/2 - 4 g0)), and after one barrier the runs leave as whole
 // 16-byte vectors of interleaved, clipped PCM.  Workgroup blockIdx.y owns groups [GW y, GW y + GW).
-template <int CH>
+template <int CH, typename PCM>
 __device__ __forceinline__ int ola_sym_lds(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev,
-                                           const float* __restrict__ w, const float* __restrict__ wp, float* out, int clip,
+                                           const float* __restrict__ w, const float* __restrict__ wp, PCM* out, int clip,
                                            float* s_run /* [2][CH][4 * NVH_OLA_GW] */) {
   constexpr int GW = NVH_OLA_GW, RUN = 4 * GW;
   const int n = fr.n, n2 = n >> 1;
@@ -800,8 +833,8 @@ __device__ __forceinline__ int ola_sym_lds(const NvhDevSetup& S, const NvhFrame&
   __syncthreads();
   int clipped = 0;
   const int nvec = gw * CH;  // 16-byte vectors per run: 4 gw sample times x CH channels
-  float4* oF = reinterpret_cast<float4*>(out + (long long)(4 * g0) * CH);
-  float4* oM = reinterpret_cast<float4*>(out + (long long)(n2 - 4 * (g0 + gw)) * CH);
+  pcm4_t<PCM>* oF = reinterpret_cast<pcm4_t<PCM>*>(out + (long long)(4 * g0) * CH);
+  pcm4_t<PCM>* oM = reinterpret_cast<pcm4_t<PCM>*>(out + (long long)(n2 - 4 * (g0 + gw)) * CH);
   for (int j = threadIdx.x; j < 2 * nvec; j += blockDim.x) {
     const bool mir = j >= nvec;
     const int jj = mir ? j - nvec : j;
@@ -828,108 +861,15 @@ extern "C" __global__ void __launch_bounds__(256)
 k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
               float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out, int last_decoded,
               int nosym, const int* __restrict__ list, int emitted) {
-  // list: the frames paired emission left to this kernel (nvh_launch.hip); emitted: k_synth wrote the PCM of every frame with
-  // NVH_EMIT_DONE (such a frame is on the list only as the block that becomes the carried tail)
-  const int f = list ? list[blockIdx.x] : (int)blockIdx.x;
-  const NvhFrame fr = Bt.frames[f];
-  const int ch = S.channels;
-  if (f == last_decoded && carry_out) {
-    // this block becomes the carried tail of the next batch (StreamDecoder's _prevPacketBuf), stored fully windowed
-    const float* __restrict__ wl = S.windows + fr.window_off;
-    for (int o = NVH_OLA_TID; o < (fr.n >> 2) * ch; o += NVH_OLA_THREADS) {
-      int c = o / (fr.n >> 2), g = o - c * (fr.n >> 2);
-      const float* plane = work + ((long long)f * ch + c) * S.block1;
-      *reinterpret_cast<float4*>(carry_out + (long long)c * S.block1 + 4 * g) =
-          compact_value4(plane, wl, fr.n, Bt.chans[fr.chan_off + c].exec, 4 * g);
-    }
-  }
-  const int total = fr.emit_count * ch;
-  if (total <= 0) return;
-  if (emitted && (fr.emit_flags & NVH_EMIT_DONE)) return;
-  const float* cur = work + (long long)f * ch * S.block1;
-  const float* prev = nullptr;
-  if (fr.ov_len > 0) prev = (fr.ov_frame == -2) ? carry : (fr.ov_frame >= 0 ? work + (long long)fr.ov_frame * ch * S.block1 : nullptr);
-  const float* __restrict__ w = S.windows + fr.window_off;
-  const float* __restrict__ wp = S.windows + fr.ov_window_off;
-  const NvhChan* chans = Bt.chans + fr.chan_off;
-  float* out = pcm + fr.out_pos * ch;
-  int clipped = 0;
-  // the carried block (ov_frame == -2) is always stored fully windowed (k_expand_carry); blocks of this batch are compact
-  const bool prev_full = fr.ov_frame == -2;
-
-  // fast path: everything in units of four samples (true for every frame of a well-formed stream except an
-  // EOS-trimmed last one), up to 8 channels
-  const bool vec = fr.n != 0 && ch <= 8 && ((fr.emit_start | fr.emit_count | fr.start | fr.ov_src | fr.ov_len) & 3) == 0 &&
-                   ((fr.out_pos * ch) & 3) == 0;
-  // steady state: whole first half over the whole second half of an executing predecessor of the same size
-  const unsigned all_ch = ch >= 32 ? 0xFFFFFFFFu : ((1u << ch) - 1u);
-  const bool sym = vec && prev && !prev_full && fr.ov_n == fr.n && fr.start == 0 && fr.emit_start == 0 && fr.emit_count == (fr.n >> 1) &&
-                   fr.ov_src == (fr.n >> 1) && fr.ov_len == (fr.n >> 1) && (fr.exec_mask & all_ch) == all_ch &&
-                   (fr.ov_exec_mask & all_ch) == all_ch && !nosym;
-  if (sym && ch > 2 && gridDim.y * NVH_OLA_GW >= (unsigned)(fr.n >> 4)) {
-    // more than two channels: per-(group, channel) lanes, interleave through LDS (the launch gives every frame gridDim.y
-    // workgroups of NVH_OLA_GW groups each: nvh_launch.hip)
-    __shared__ __attribute__((aligned(16))) float s_run[2 * 8 * 4 * NVH_OLA_GW];
-    switch (ch) {
-      case 3: clipped = ola_sym_lds<3>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
-      case 4: clipped = ola_sym_lds<4>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
-      case 5: clipped = ola_sym_lds<5>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
-      case 6: clipped = ola_sym_lds<6>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
-      case 7: clipped = ola_sym_lds<7>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
-      default: clipped = ola_sym_lds<8>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
-    }
-    report_clipped(clipped, clipped_flag);
-    return;
-  }
-  if (sym) {
-    switch (ch) {
-      case 1: clipped = ola_sym<1>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 2: clipped = ola_sym<2>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 3: clipped = ola_sym<3>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 4: clipped = ola_sym<4>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 5: clipped = ola_sym<5>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 6: clipped = ola_sym<6>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 7: clipped = ola_sym<7>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      default: clipped = ola_sym<8>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-    }
-    report_clipped(clipped, clipped_flag);
-    return;
-  }
-  if (vec) {
-    switch (ch) {
-      case 1: clipped = ola_vec<1>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 2: clipped = ola_vec<2>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 3: clipped = ola_vec<3>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 4: clipped = ola_vec<4>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 5: clipped = ola_vec<5>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 6: clipped = ola_vec<6>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      case 7: clipped = ola_vec<7>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-      default: clipped = ola_vec<8>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
-    }
-    report_clipped(clipped, clipped_flag);
-    return;
-  }
-
-  for (int o = NVH_OLA_TID; o < total; o += NVH_OLA_THREADS) {
-    int t = o / ch, c = o - t * ch;
-    int idx = fr.emit_start + t;
-    const NvhChan cn = chans[c];
-    float v;
-    if (fr.n == 0) {
-      // drained carried tail (StreamDecoder.cs:352-356): the previous block's windowed samples as they are
-      v = prev[(long long)c * S.block1 + fr.ov_src + t];
-    } else {
-      v = compact_value(cur + (long long)c * S.block1, w, fr.n, cn.exec, idx);
-      int j = idx - fr.start;
-      if (prev && j >= 0 && j < fr.ov_len) {  // OverlapBuffers: next[start + j] += previous[prevStart + j]
-        const float* pp = prev + (long long)c * S.block1;
-        v = v + (prev_full ? pp[fr.ov_src + j] : compact_value(pp, wp, fr.ov_n, cn.ov_exec, fr.ov_src + j));
-      }
-    }
-    if (clip) v = clip_value(v, &clipped);
-    pcm_store1(out + o, v);
-  }
-  report_clipped(clipped, clipped_flag);
+  typedef float PCM;
+#include "ola_compact_body.inc"
+}
+extern "C" __global__ void __launch_bounds__(256)
+k_ola_compact_s16(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
+                  int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out, int last_decoded,
+                  int nosym, const int* __restrict__ list, int emitted) {
+  typedef int16_t PCM;
+#include "ola_compact_body.inc"
 }
 
 // Expands the compact planes of one frame into the fully windowed block (the carried tail format shared by all

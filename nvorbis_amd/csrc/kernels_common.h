@@ -84,7 +84,7 @@ struct NvhSynthArgs {
   int prefetch_prev;        // paired emission, odd launch: workgroup b touches the slab of frame f - 1, which workgroup b of the even
                             // launch fetches next -- on the same XCD (workgroups go round the XCDs by index), so from that XCD's L2
   // paired emission (nvh_format.h: NVH_EMIT_*); pcm == nullptr: off, every frame leaves its plane for k_ola_compact
-  float* pcm;
+  float* pcm;               // (the _s16 twins: int16_t samples)
   const float* windows;
   int clip;
   int* clipped_flag;
@@ -108,6 +108,61 @@ __device__ __forceinline__ void pcm_store4(float4* p, float a, float b, float c,
 #endif
 }
 __device__ __forceinline__ void pcm_store1(float* p, float v) { __builtin_nontemporal_store(v, p); }
+
+// ---- 16-bit PCM (NVH_PCM_S16): the emitting kernels' twins (<name>_s16) are the same bodies instantiated with int16_t
+// samples; only these helpers differ.  The rule is ov_read's: s16 = clamp(rint(x * 32768), -32768, 32767), on the float the
+// float path would have stored (after the clip).  x * 32768 is exact; v_rndne_f32 rounds ties to even; v_cvt_i32_f32
+// saturates out-of-range values and maps NaN to 0 -- written as asm because a C conversion of NaN is undefined (a float clamp
+// in front of it would turn NaN into -32768).
+__device__ __forceinline__ int pcm_s16_value(float x) {
+  const float r = __builtin_rintf(x * 32768.0f);
+  int i;
+  asm("v_cvt_i32_f32 %0, %1" : "=v"(i) : "v"(r));
+  return i < -32768 ? -32768 : (i > 32767 ? 32767 : i);
+}
+__device__ __forceinline__ unsigned pcm_s16_pair(float lo, float hi) {
+  return ((unsigned)pcm_s16_value(lo) & 0xFFFFu) | ((unsigned)pcm_s16_value(hi) << 16);
+}
+
+// four consecutive 16-bit samples: what a float4 of float PCM becomes (8 bytes)
+struct __attribute__((aligned(8))) nvh_s16x4 { int16_t v[4]; };
+template <typename T> struct PcmVec4;
+template <> struct PcmVec4<float> { typedef float4 type; };
+template <> struct PcmVec4<int16_t> { typedef nvh_s16x4 type; };
+template <typename T> using pcm4_t = typename PcmVec4<T>::type;
+
+__device__ __forceinline__ void pcm_store4(nvh_s16x4* p, float a, float b, float c, float d) {
+  typedef unsigned nvh_v2u __attribute__((ext_vector_type(2)));
+  const nvh_v2u v = {pcm_s16_pair(a, b), pcm_s16_pair(c, d)};
+#ifdef NVH_PCM_POLICY
+  asm volatile("global_store_dwordx2 %0, %1, off " NVH_STR(NVH_PCM_POLICY) : : "v"(p), "v"(v) : "memory");
+#else
+  __builtin_nontemporal_store(v, reinterpret_cast<nvh_v2u*>(p));
+#endif
+}
+__device__ __forceinline__ void pcm_store1(int16_t* p, float v) { __builtin_nontemporal_store((int16_t)pcm_s16_value(v), p); }
+// Two groups of four stereo sample times (p[0], p[1]) from eight interleaved values -- two 16-byte stores of float PCM -- as one
+// 16-byte store of 16-bit PCM where p is 16-byte aligned.  The vector paths only guarantee an element offset that is a multiple of 4
+// (8 bytes of s16), so the other frames take two 8-byte stores (uniform per frame: p moves by 16 bytes per lane).  (The float
+// kernels keep their own two calls of pcm_store4: through this helper their code comes out differently.)
+__device__ __forceinline__ void pcm_store4x2(nvh_s16x4* p, const float (&v)[8]) {
+  if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+    typedef unsigned nvh_v4u __attribute__((ext_vector_type(4)));
+    const nvh_v4u u = {pcm_s16_pair(v[0], v[1]), pcm_s16_pair(v[2], v[3]), pcm_s16_pair(v[4], v[5]), pcm_s16_pair(v[6], v[7])};
+#ifdef NVH_PCM_POLICY
+    asm volatile("global_store_dwordx4 %0, %1, off " NVH_STR(NVH_PCM_POLICY) : : "v"(p), "v"(u) : "memory");
+#else
+    __builtin_nontemporal_store(u, reinterpret_cast<nvh_v4u*>(p));
+#endif
+  } else {
+    pcm_store4(p, v[0], v[1], v[2], v[3]);
+    pcm_store4(p + 1, v[4], v[5], v[6], v[7]);
+  }
+}
+// plain (not streaming) store of four 16-bit samples: synth_emit8_direct's partial-line stores, which the L2 merges
+__device__ __forceinline__ void pcm_plain4(nvh_s16x4* p, float a, float b, float c, float d) {
+  *reinterpret_cast<uint2*>(p) = make_uint2(pcm_s16_pair(a, b), pcm_s16_pair(c, d));
+}
 // ... and the streaming load of 16 bytes that exactly one lane reads exactly once (a neighbour frame's quarter)
 __device__ __forceinline__ float4 stream_load4(const float* p) {
   typedef float nvh_v4f __attribute__((ext_vector_type(4)));

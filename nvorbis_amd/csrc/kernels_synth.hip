@@ -42,6 +42,8 @@
 #include "kernels_common.h"
 #include "spectrum_dev.h"
 
+#include <type_traits>
+
 namespace {
 
 // Ablation builds (tools/build_variant.py NAME -DNVH_ABL_...): one phase of the slab kernels left out, to read its marginal cost
@@ -689,13 +691,13 @@ __device__ __forceinline__ void synth_carry_out(const NvhSynthArgs& A, const flo
 // (k_ola_compact's prev_full case: no second window multiply, the tail in time order).  The frame's own first quarter A lies in
 // its channel's dead transform slice (synth_emit).  One workgroup per batch: out of line, so that the steady-state loop keeps
 // its registers.
-template <int NT>
+template <int NT, typename PCM = float>
 __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const float* spec, int n, int nch, unsigned window_off,
                                               unsigned out_pos, int tid, int cstride = 0) {
   const int half = n >> 1;
   if (cstride == 0) cstride = half;  // floats between the channels' first quarters
   const float* __restrict__ w = A.windows + window_off;
-  float* out = A.pcm + (long long)out_pos * nch;
+  PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)out_pos * nch;
   int clipped = 0;
   for (int g = tid; g < (n >> 4); g += NT) {
     const int i0 = 4 * g;
@@ -727,15 +729,20 @@ __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const fl
     // kernel's emission does, was tried: 202 -> 167 M frames/s -- nine spilled registers and four more wavefront syncs cost more than
     // half-line streaming stores do)
     if (nch == 2) {
-      float4* of = reinterpret_cast<float4*>(out) + 2 * (long long)g;
-      float4* om = reinterpret_cast<float4*>(out) + 2 * (long long)((n >> 3) - 1 - g);
-      pcm_store4(of, fwd[0], fwd[1], fwd[2], fwd[3]);
-      pcm_store4(of + 1, fwd[4], fwd[5], fwd[6], fwd[7]);
-      pcm_store4(om, mir[0], mir[1], mir[2], mir[3]);
-      pcm_store4(om + 1, mir[4], mir[5], mir[6], mir[7]);
+      pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
+      pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
+      if constexpr (std::is_same<PCM, int16_t>::value) {  // four stereo sample times: one 16-byte store where aligned
+        pcm_store4x2(of, fwd);
+        pcm_store4x2(om, mir);
+      } else {
+        pcm_store4(of, fwd[0], fwd[1], fwd[2], fwd[3]);
+        pcm_store4(of + 1, fwd[4], fwd[5], fwd[6], fwd[7]);
+        pcm_store4(om, mir[0], mir[1], mir[2], mir[3]);
+        pcm_store4(om + 1, mir[4], mir[5], mir[6], mir[7]);
+      }
     } else {
-      pcm_store4(reinterpret_cast<float4*>(out) + g, fwd[0], fwd[2], fwd[4], fwd[6]);
-      pcm_store4(reinterpret_cast<float4*>(out) + ((n >> 3) - 1 - g), mir[0], mir[2], mir[4], mir[6]);
+      pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + g, fwd[0], fwd[2], fwd[4], fwd[6]);
+      pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + ((n >> 3) - 1 - g), mir[0], mir[2], mir[4], mir[6]);
     }
   }
   if (A.clip) report_clipped(clipped, A.clipped_flag);
@@ -753,7 +760,7 @@ __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const fl
 // registers into the channel's dead transform slice, and every lane of the workgroup then overlap-adds, clips and interleaves
 // one group of sample times of one overlap, straight into 16-byte vectors of PCM.
 // The frame's own plane is written only when k_ola_compact still needs it (not both overlaps emitted here).
-template <int NT>
+template <int NT, typename PCM = float>
 __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, float* spec, const uint32_t* s_chan, int n, int nch,
                                            unsigned frame, int sl, bool emit_self, bool emit_next, bool self_carry, bool carry_out,
                                            unsigned exec_mask, float* planes,
@@ -834,7 +841,7 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
   __syncthreads();  // drains the staging DMA (vmcnt(0) in front of the barrier): all four quarters of every channel are in LDS
   EM_T(17);
   if (carry_out) synth_carry_out<NT>(A, planes, n, nch, exec_mask, w_self, tid);  // (such a frame has no NEXT: its plane was written)
-  if (self_carry) synth_self_carry<NT>(A, spec, n, nch, w_self, out_self, tid);    // the batch's first frame
+  if (self_carry) synth_self_carry<NT, PCM>(A, spec, n, nch, w_self, out_self, tid);    // the batch's first frame
   // ---- overlap-add + interleave + clip, every lane of the workgroup: lane task = (overlap, group of four compact indices i0);
   // it produces sample times i0 .. i0 + 3 and n/2 - 4 - i0 .. n/2 - 1 - i0 of every channel (kernels.hip: ola_sym) ----
   int clipped = 0;
@@ -885,23 +892,28 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
         mir[c] = u.x; mir[2 + c] = u.y; mir[4 + c] = u.z; mir[6 + c] = u.w;
       }
     }
-    float* out = A.pcm + (long long)(nx ? out_next : out_self) * nch;
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)(nx ? out_next : out_self) * nch;
 #ifdef NVH_ABL_PCM_SMALL
-    out = A.pcm + (long long)((nx ? out_next : out_self) & 0x7FFF) * nch;  // (ablation build: every frame's PCM into the same 256 KB)
+    out = reinterpret_cast<PCM*>(A.pcm) + (long long)((nx ? out_next : out_self) & 0x7FFF) * nch;  // (ablation build: every frame's PCM into the same 256 KB)
 #endif
 #ifdef NVH_ABL_NO_PCM_STORE
     if (fwd[0] != 1.2345e-30f) return;  // (ablation build: the arithmetic kept alive, the stores left out)
 #endif
     if (nch == 2) {
-      float4* of = reinterpret_cast<float4*>(out) + 2 * (long long)g;
-      float4* om = reinterpret_cast<float4*>(out) + 2 * (long long)((n >> 3) - 1 - g);
-      pcm_store4(of, fwd[0], fwd[1], fwd[2], fwd[3]);
-      pcm_store4(of + 1, fwd[4], fwd[5], fwd[6], fwd[7]);
-      pcm_store4(om, mir[0], mir[1], mir[2], mir[3]);
-      pcm_store4(om + 1, mir[4], mir[5], mir[6], mir[7]);
+      pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
+      pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
+      if constexpr (std::is_same<PCM, int16_t>::value) {  // four stereo sample times: one 16-byte store where aligned
+        pcm_store4x2(of, fwd);
+        pcm_store4x2(om, mir);
+      } else {
+        pcm_store4(of, fwd[0], fwd[1], fwd[2], fwd[3]);
+        pcm_store4(of + 1, fwd[4], fwd[5], fwd[6], fwd[7]);
+        pcm_store4(om, mir[0], mir[1], mir[2], mir[3]);
+        pcm_store4(om + 1, mir[4], mir[5], mir[6], mir[7]);
+      }
     } else {
-      pcm_store4(reinterpret_cast<float4*>(out) + g, fwd[0], fwd[2], fwd[4], fwd[6]);
-      pcm_store4(reinterpret_cast<float4*>(out) + ((n >> 3) - 1 - g), mir[0], mir[2], mir[4], mir[6]);
+      pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + g, fwd[0], fwd[2], fwd[4], fwd[6]);
+      pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + ((n >> 3) - 1 - g), mir[0], mir[2], mir[4], mir[6]);
     }
   };
   const bool do_self = emit_self && !self_carry;
@@ -934,7 +946,7 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
 // and puts its eight results into channel-planar LDS rows; behind a barrier the rows leave as 16-byte vectors of interleaved,
 // clipped PCM.  The overlap-add's memory phase then runs inside the synthesis kernel, next to other workgroups' arithmetic,
 // instead of as a launch of its own (k_ola_compact: 42 us per 2048 six-channel frames), and half the planes are read from L2.
-template <int NT>
+template <int NT, typename PCM = float>
 __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run, int n, int nch, unsigned frame, unsigned ef,
                                             unsigned exec_mask, int tid) {
   // One round per overlap: the rows of ALL groups fit the dead slices (2 x nch x n/4 floats: 48 KB for six channels at 4096),
@@ -954,7 +966,7 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
     const float* prev = from_carry ? A.carry : A.work + (long long)(frame + ov - 1) * nch * A.block1;  // the earlier block
     const float* __restrict__ w = A.windows + fr->window_off;
     const float* __restrict__ wp = A.windows + fr->ov_window_off;
-    float* out = A.pcm + fr->out_pos * nch;
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + fr->out_pos * nch;
     float* sF = s_run;
     float* sM = s_run + nch * RUN;
     for (int t0 = tid; t0 < total; t0 += K * NT) {
@@ -998,8 +1010,8 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
     __syncthreads();
     // the forward rows hold sample times [0, n/4), the mirrored rows [n/4, n/2): together the frame's n/2 samples in time order
     const int nvec = total;  // 16-byte vectors per half: n/4 sample times x nch channels / 4
-    float4* oF = reinterpret_cast<float4*>(out);
-    float4* oM = reinterpret_cast<float4*>(out + (long long)(half >> 1) * nch);
+    pcm4_t<PCM>* oF = reinterpret_cast<pcm4_t<PCM>*>(out);
+    pcm4_t<PCM>* oM = reinterpret_cast<pcm4_t<PCM>*>(out + (long long)(half >> 1) * nch);
     for (int j = tid; j < 2 * nvec; j += NT) {
       const bool mir = j >= nvec;
       const int jj = mir ? j - nvec : j;
@@ -1072,7 +1084,7 @@ __device__ __forceinline__ void imdct_keep_quarters(const float* X, float* slice
   }
 }
 
-template <int NT, int CH>
+template <int NT, int CH, typename PCM = float>
 __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float* smem, int n, unsigned frame, int tid) {
   const int half = n >> 1, groups = n >> 4, slice = half + (n >> 4);
   const NvhFrame* fs = A.frames + frame;
@@ -1113,9 +1125,9 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
       fwd[0 * CH + c] = v.x; fwd[1 * CH + c] = v.y; fwd[2 * CH + c] = v.z; fwd[3 * CH + c] = v.w;
       mir[0 * CH + c] = u.x; mir[1 * CH + c] = u.y; mir[2 * CH + c] = u.z; mir[3 * CH + c] = u.w;
     }
-    float4* out = reinterpret_cast<float4*>(A.pcm + (nx ? o_next : o_self) * CH);
-    float4* of = out + (long long)g * CH;
-    float4* om = out + (long long)((n >> 3) - 1 - g) * CH;
+    pcm4_t<PCM>* out = reinterpret_cast<pcm4_t<PCM>*>(reinterpret_cast<PCM*>(A.pcm) + (nx ? o_next : o_self) * CH);
+    pcm4_t<PCM>* of = out + (long long)g * CH;
+    pcm4_t<PCM>* om = out + (long long)((n >> 3) - 1 - g) * CH;
     if (whole_wave) {
       // A lane's CH vectors are consecutive in memory, a store instruction's 64 vectors would lie 16 CH bytes apart.  The 64
       // tasks of this wavefront cover ONE contiguous 1024 CH bytes per half, so the vectors go through a 64 x CH transposition
@@ -1123,8 +1135,8 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
       // leave as CH fully coalesced streaming stores per half.
       const int l = tid & 63, g0 = g - l;
       float* piece0 = smem + (nx ? (half >> 1) : 0) + 4 * g0;
-      float4* rf = out + (long long)g0 * CH;                         // the forward half: groups g0 .. g0 + 63 ascending
-      float4* rm = out + (long long)((n >> 3) - 1 - (g0 + 63)) * CH;  // the mirrored half: the same groups, descending
+      pcm4_t<PCM>* rf = out + (long long)g0 * CH;                         // the forward half: groups g0 .. g0 + 63 ascending
+      pcm4_t<PCM>* rm = out + (long long)((n >> 3) - 1 - (g0 + 63)) * CH;  // the mirrored half: the same groups, descending
       wave_sync();  // every lane's own-quarter reads are through
 #pragma unroll
       for (int k = 0; k < CH; ++k) {
@@ -1159,8 +1171,13 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
 #else
       // (a lane's CH vectors are consecutive, a store instruction's 64 vectors are 16 CH bytes apart: plain stores, which the
       // L2 merges into whole lines -- streamed, such partial lines cost 273 us per C4 pass instead of 110)
-      of[k] = make_float4(fwd[4 * k], fwd[4 * k + 1], fwd[4 * k + 2], fwd[4 * k + 3]);
-      om[k] = make_float4(mir[4 * k], mir[4 * k + 1], mir[4 * k + 2], mir[4 * k + 3]);
+      if constexpr (std::is_same<PCM, int16_t>::value) {
+        pcm_plain4(of + k, fwd[4 * k], fwd[4 * k + 1], fwd[4 * k + 2], fwd[4 * k + 3]);
+        pcm_plain4(om + k, mir[4 * k], mir[4 * k + 1], mir[4 * k + 2], mir[4 * k + 3]);
+      } else {
+        of[k] = make_float4(fwd[4 * k], fwd[4 * k + 1], fwd[4 * k + 2], fwd[4 * k + 3]);
+        om[k] = make_float4(mir[4 * k], mir[4 * k + 1], mir[4 * k + 2], mir[4 * k + 3]);
+      }
 #endif
     }
   };
@@ -1332,7 +1349,7 @@ __device__ __forceinline__ void synth_frame_spectrum(const NvhSynthArgs& A, cons
 // MODE (k_synth only): 0 = synthesis alone, 1 = + the carried tail written by the last decoded block's workgroup, 2 = + paired
 // emission.  Three instantiations, so that the launches that never emit keep the registers of the kernel that cannot (62 instead
 // of 64 VGPRs at the 64-VGPR cap: 24.4 against 25.1 us for 4096 frames).
-template <int NT, int MAXCH, int MODE = 0, bool GENERAL = false>
+template <int NT, int MAXCH, int MODE = 0, bool GENERAL = false, typename PCM = float>
 __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NVH_DBG_PARAMS) {
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
 #ifdef NVH_ABL_EMPTY0
@@ -1450,10 +1467,10 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
   if (MAXCH <= 2 && MODE >= 2 && (emit_self || emit_next)) {
     if constexpr (MAXCH <= 2 && MODE >= 2)
 #ifdef NVH_DEBUG
-      synth_emit<NT>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
+      synth_emit<NT, PCM>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
                      Aa, Bb, Cc, TW, tid, dbg ? dbg + (long long)f * 24 : nullptr);
 #else
-      synth_emit<NT>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
+      synth_emit<NT, PCM>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
                      Aa, Bb, Cc, TW, tid);
 #endif
   } else
@@ -1536,21 +1553,21 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
     if (direct8) {
       __syncthreads();  // every channel's own quarters are in its slice
       switch (nch) {
-        case 1: synth_emit8_direct<NT, 1>(A, smem, n, frame, tid); break;  // (mono / stereo land here with blocks beyond 2048)
-        case 2: synth_emit8_direct<NT, 2>(A, smem, n, frame, tid); break;
-        case 3: synth_emit8_direct<NT, 3>(A, smem, n, frame, tid); break;
-        case 4: synth_emit8_direct<NT, 4>(A, smem, n, frame, tid); break;
-        case 5: synth_emit8_direct<NT, 5>(A, smem, n, frame, tid); break;
-        case 6: synth_emit8_direct<NT, 6>(A, smem, n, frame, tid); break;
-        case 7: synth_emit8_direct<NT, 7>(A, smem, n, frame, tid); break;
-        case 8: synth_emit8_direct<NT, 8>(A, smem, n, frame, tid); break;
+        case 1: synth_emit8_direct<NT, 1, PCM>(A, smem, n, frame, tid); break;  // (mono / stereo land here with blocks beyond 2048)
+        case 2: synth_emit8_direct<NT, 2, PCM>(A, smem, n, frame, tid); break;
+        case 3: synth_emit8_direct<NT, 3, PCM>(A, smem, n, frame, tid); break;
+        case 4: synth_emit8_direct<NT, 4, PCM>(A, smem, n, frame, tid); break;
+        case 5: synth_emit8_direct<NT, 5, PCM>(A, smem, n, frame, tid); break;
+        case 6: synth_emit8_direct<NT, 6, PCM>(A, smem, n, frame, tid); break;
+        case 7: synth_emit8_direct<NT, 7, PCM>(A, smem, n, frame, tid); break;
+        case 8: synth_emit8_direct<NT, 8, PCM>(A, smem, n, frame, tid); break;
         default: __builtin_trap();
       }
     } else
     if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT | NVH_EMIT_CARRY_OUT)) {
       __syncthreads();
       if ((ef & NVH_EMIT_CARRY_OUT) && A.carry_out) synth_carry_out8<NT>(A, planes, n, nch, exec_mask, A.frames[frame].window_off, tid);
-      if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT)) synth_emit8<NT>(A, smem, n, nch, frame, ef, exec_mask, tid);
+      if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT)) synth_emit8<NT, PCM>(A, smem, n, nch, frame, ef, exec_mask, tid);
     }
   }
   if constexpr (MAXCH > 2 && MODE < 2) {
@@ -1600,7 +1617,7 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
 // (Tried and removed, round 6: two frames per workgroup of EIGHT wavefronts, every 256 threads walking their own frame side by side --
 // k_synth's per-frame parallelism, 4 workgroups = 32 wavefronts per CU at 64 VGPRs: 171 M frames/s over three streams against 202 M for
 // this form, 124 M against 123 M on one.)
-template <int NT, int FPW>
+template <int NT, int FPW, typename PCM = float>
 __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* smem NVH_DBG_PARAMS) {
   static_assert(NT / 64 >= 2 * FPW, "one wavefront per (frame, channel) in the transform");
   // (the wavefront's index through readfirstlane: what depends on it alone -- which frame and channel it transforms, where its
@@ -1905,7 +1922,7 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
     if (cout_k[k])  // the block that becomes the next batch's carried tail (its whole plane was written above)
       synth_carry_out<NT>(A, A.work + (long long)(fa + k) * nch * A.block1, nn[k], nch, (w0[k] >> 16) & 0xFFu, cwin[k], tid);
   if (self_carry)  // the batch's first frame
-    synth_self_carry<NT>(A, slice0, nn[0], nch, __builtin_amdgcn_readfirstlane(otab[0]), __builtin_amdgcn_readfirstlane(otab[2]), tid, slice_words);
+    synth_self_carry<NT, PCM>(A, slice0, nn[0], nch, __builtin_amdgcn_readfirstlane(otab[0]), __builtin_amdgcn_readfirstlane(otab[2]), tid, slice_words);
 
   // ---- overlap-add + interleave + clip: lane task = (overlap j, group of four compact indices i0); it produces sample times
   // i0 .. i0 + 3 and n/2 - 4 - i0 .. n/2 - 1 - i0 of every channel (kernels.hip: ola_sym) ----
@@ -1951,17 +1968,22 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
         mir[c] = u.x; mir[2 + c] = u.y; mir[4 + c] = u.z; mir[6 + c] = u.w;
       }
     }
-    float* out = A.pcm + (long long)r0.z * nch;
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)r0.z * nch;
     if (nch == 2) {
-      float4* of = reinterpret_cast<float4*>(out) + 2 * (long long)g;
-      float4* om = reinterpret_cast<float4*>(out) + 2 * (long long)((n >> 3) - 1 - g);
-      pcm_store4(of, fwd[0], fwd[1], fwd[2], fwd[3]);
-      pcm_store4(of + 1, fwd[4], fwd[5], fwd[6], fwd[7]);
-      pcm_store4(om, mir[0], mir[1], mir[2], mir[3]);
-      pcm_store4(om + 1, mir[4], mir[5], mir[6], mir[7]);
+      pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
+      pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
+      if constexpr (std::is_same<PCM, int16_t>::value) {  // four stereo sample times: one 16-byte store where aligned
+        pcm_store4x2(of, fwd);
+        pcm_store4x2(om, mir);
+      } else {
+        pcm_store4(of, fwd[0], fwd[1], fwd[2], fwd[3]);
+        pcm_store4(of + 1, fwd[4], fwd[5], fwd[6], fwd[7]);
+        pcm_store4(om, mir[0], mir[1], mir[2], mir[3]);
+        pcm_store4(om + 1, mir[4], mir[5], mir[6], mir[7]);
+      }
     } else {
-      pcm_store4(reinterpret_cast<float4*>(out) + g, fwd[0], fwd[2], fwd[4], fwd[6]);
-      pcm_store4(reinterpret_cast<float4*>(out) + ((n >> 3) - 1 - g), mir[0], mir[2], mir[4], mir[6]);
+      pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + g, fwd[0], fwd[2], fwd[4], fwd[6]);
+      pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + ((n >> 3) - 1 - g), mir[0], mir[2], mir[4], mir[6]);
     }
   }
   // ---- what a frame emits alone: lane task = four consecutive sample times of R1 or R2 of one frame (window multiply of
@@ -1998,12 +2020,16 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
         o[c] = v.x; o[2 + c] = v.y; o[4 + c] = v.z; o[6 + c] = v.w;
       }
     }
-    float* out = A.pcm + ((long long)r0.y + (idx0 - (int)r1.w)) * nch;
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + ((long long)r0.y + (idx0 - (int)r1.w)) * nch;
     if (nch == 2) {
-      pcm_store4(reinterpret_cast<float4*>(out), o[0], o[1], o[2], o[3]);
-      pcm_store4(reinterpret_cast<float4*>(out) + 1, o[4], o[5], o[6], o[7]);
+      if constexpr (std::is_same<PCM, int16_t>::value) {
+        pcm_store4x2(reinterpret_cast<pcm4_t<PCM>*>(out), o);
+      } else {
+        pcm_store4(reinterpret_cast<float4*>(out), o[0], o[1], o[2], o[3]);
+        pcm_store4(reinterpret_cast<float4*>(out) + 1, o[4], o[5], o[6], o[7]);
+      }
     } else {
-      pcm_store4(reinterpret_cast<float4*>(out), o[0], o[2], o[4], o[6]);
+      pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out), o[0], o[2], o[4], o[6]);
     }
   }
   if (A.clip && emit) report_clipped(clipped, A.clipped_flag);
@@ -2036,6 +2062,14 @@ k_synth_emit(NvhSynthArgs A NVH_DBG_PARAMS) {
   synth_body<NVH_SYNTH_NT, 2, 2>(A, smem NVH_DBG_ARGS);
 }
 
+// The 16-bit twins of the kernels that write PCM (NVH_PCM_S16; A.pcm then points at int16_t samples: kernels_common.h,
+// pcm_s16_value).  k_synth, k_synth_tail and k_synth8 never store PCM (A.pcm is only tested in the emitting modes).
+extern "C" __global__ void __launch_bounds__(NVH_SYNTH_NT) __attribute__((amdgpu_waves_per_eu(NVH_SYNTH_WPE)))
+k_synth_emit_s16(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_body<NVH_SYNTH_NT, 2, 2, false, int16_t>(A, smem NVH_DBG_ARGS);
+}
+
 // mono / stereo streams some of whose frames need the general bin walk (never with paired emission)
 extern "C" __global__ void __launch_bounds__(SP_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_synth_g(NvhSynthArgs A NVH_DBG_PARAMS) {
@@ -2063,6 +2097,11 @@ k_synth8_emit(NvhSynthArgs A NVH_DBG_PARAMS) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   synth_body<512, NVH_SLAB_MAX_CH, 2>(A, smem NVH_DBG_ARGS);
 }
+extern "C" __global__ void __launch_bounds__(512)
+k_synth8_emit_s16(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_body<512, NVH_SLAB_MAX_CH, 2, false, int16_t>(A, smem NVH_DBG_ARGS);
+}
 
 // frame groups: two frames per workgroup (four wavefronts: one per (frame, channel)); LDS, not registers, decides the residency
 extern "C" __global__ void __launch_bounds__(256)
@@ -2076,4 +2115,15 @@ extern "C" __global__ void __launch_bounds__(512)
 k_synth_group4(NvhSynthArgs A NVH_DBG_PARAMS) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   synth_group_body<512, 4>(A, smem NVH_DBG_ARGS);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_synth_group2_s16(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_group_body<256, 2, int16_t>(A, smem NVH_DBG_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(512)
+k_synth_group4_s16(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_group_body<512, 4, int16_t>(A, smem NVH_DBG_ARGS);
 }

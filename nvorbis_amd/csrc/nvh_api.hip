@@ -574,9 +574,20 @@ extern "C" int nvh_stream_pending(const nvh_stream* s, int* frames, int64_t* pcm
   });
 }
 
+// The output formats of the synthesis entry points (NVH_PCM_*); a 16-bit device destination must be 16-byte aligned (the
+// stereo twins store eight samples at a time).
+static bool pcm_format_ok(int format) { return format == NVH_PCM_F32 || format == NVH_PCM_S16; }
+static bool pcm_dest_ok(int format, const void* d_pcm) {
+  return format != NVH_PCM_S16 || ((uintptr_t)d_pcm & 15u) == 0;
+}
+
 extern "C" int nvh_stream_synth(nvh_stream* s, float* pcm_host, float* d_pcm, int64_t capacity, int64_t* written) {
+  return nvh_stream_synth_pcm(s, NVH_PCM_F32, pcm_host, d_pcm, capacity, written);
+}
+
+extern "C" int nvh_stream_synth_pcm(nvh_stream* s, int format, void* pcm_host, void* d_pcm, int64_t capacity, int64_t* written) {
   return nvh_guard([&]() -> int {
-    if (!s || (pcm_host && d_pcm)) return NVH_ERR_ARGUMENT;
+    if (!s || (pcm_host && d_pcm) || !pcm_format_ok(format) || !pcm_dest_ok(format, d_pcm)) return NVH_ERR_ARGUMENT;
     if (written) *written = 0;
     if (!s->ctx) return NVH_ERR_NO_GPU;
     if (s->flight[0].on || s->flight[1].on) return NVH_ERR_ARGUMENT;  // pipelined batches outstanding: end them first
@@ -595,17 +606,19 @@ extern "C" int nvh_stream_synth(nvh_stream* s, float* pcm_host, float* d_pcm, in
     // throwing packet contributes nothing, so the batch may emit less than the look-ahead said
     need = b->pcm_samples * ch;
     if (capacity < need) return NVH_ERR_ARGUMENT;
-    float* dst = d_pcm;
+    const size_t sample_bytes = pcm_sample_bytes(format);
+    void* dst = d_pcm;
     if (!dst) {
-      if ((rc = s->pcm.reserve((size_t)(need > 0 ? need : 1) * sizeof(float))) != NVH_OK) return rc;
-      dst = (float*)s->pcm.p;
+      if ((rc = s->pcm.reserve((size_t)(need > 0 ? need : 1) * sample_bytes)) != NVH_OK) return rc;
+      dst = s->pcm.p;
     }
-    rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr);
+    rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
+                      format);
     if (rc != NVH_OK) return rc;
     hipStream_t st = s->ctx->stream;
     if (b->last_decoded >= 0) s->carry_cur ^= 1;  // the batch wrote its last block's tail into the other buffer
     // one read-back, one synchronisation: PCM and the two flag words land in a pinned bounce buffer
-    size_t pcm_bytes = pcm_host ? (size_t)need * sizeof(float) : 0;
+    size_t pcm_bytes = pcm_host ? (size_t)need * sample_bytes : 0;
     // a destination in pinned host memory (nvh_pinned_alloc, hipHostMalloc, hipHostRegister) is written by the copy
     // engine directly; anything else goes through the bounce buffer and one memcpy on this thread
     bool direct = false;
@@ -636,8 +649,14 @@ extern "C" int nvh_stream_synth(nvh_stream* s, float* pcm_host, float* d_pcm, in
 // transfer of batch i (8 KB per stereo long frame over PCIe: the longest step of the end-to-end path) then runs while the host
 // pushes batch i+1 and the GPU parses and synthesises it.
 extern "C" int nvh_stream_synth_begin(nvh_stream* s, float* pcm_host, int64_t capacity, int64_t* expected) {
+  return nvh_stream_synth_begin_pcm(s, NVH_PCM_F32, pcm_host, capacity, expected);
+}
+
+// (the format is the call's, not the stream's: the carried tail between batches is float planes either way, and
+// nvh_stream_synth_end only waits for the copy this call queued)
+extern "C" int nvh_stream_synth_begin_pcm(nvh_stream* s, int format, void* pcm_host, int64_t capacity, int64_t* expected) {
   return nvh_guard([&]() -> int {
-    if (!s || !pcm_host) return NVH_ERR_ARGUMENT;
+    if (!s || !pcm_host || !pcm_format_ok(format)) return NVH_ERR_ARGUMENT;
     if (expected) *expected = 0;
     if (!s->ctx) return NVH_ERR_NO_GPU;
     HIP_TRY(hipSetDevice(s->ctx->device));
@@ -675,10 +694,12 @@ extern "C" int nvh_stream_synth_begin(nvh_stream* s, float* pcm_host, int64_t ca
     if (rc != NVH_OK) return rc;
     const int64_t need = b->pcm_samples * ch;
     if (capacity < need) return NVH_ERR_ARGUMENT;
-    if ((rc = s->pcm2[slot].reserve((size_t)(need > 0 ? need : 1) * sizeof(float))) != NVH_OK) return rc;
+    const size_t sample_bytes = pcm_sample_bytes(format);
+    if ((rc = s->pcm2[slot].reserve((size_t)(need > 0 ? need : 1) * sample_bytes)) != NVH_OK) return rc;
     if ((rc = s->h_flags2.reserve(4 * sizeof(int))) != NVH_OK) return rc;
-    float* dst = (float*)s->pcm2[slot].p;
-    rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr);
+    void* dst = s->pcm2[slot].p;
+    rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
+                      format);
     if (rc != NVH_OK) return rc;
     if (b->last_decoded >= 0) s->carry_cur ^= 1;
     // this batch's flag words, then a clean pair for the next one (all on the launch stream, in order)
@@ -686,7 +707,7 @@ extern "C" int nvh_stream_synth_begin(nvh_stream* s, float* pcm_host, int64_t ca
     HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), st));
     HIP_TRY(hipEventRecord(F.kernels, st));
     HIP_TRY(hipStreamWaitEvent(s->copy_stream, F.kernels, 0));
-    if (need > 0) HIP_TRY(hipMemcpyAsync(pcm_host, dst, (size_t)need * sizeof(float), hipMemcpyDeviceToHost, s->copy_stream));
+    if (need > 0) HIP_TRY(hipMemcpyAsync(pcm_host, dst, (size_t)need * sample_bytes, hipMemcpyDeviceToHost, s->copy_stream));
     HIP_TRY(hipEventRecord(F.done, s->copy_stream));
     F.need = need;
     F.replay_error = s->replay_error;
@@ -803,14 +824,18 @@ extern "C" int nvh_stream_kernels(const nvh_stream* s, char* buf, int cap) {
 }
 
 extern "C" int nvh_batch_synth(nvh_batch* b, float* d_pcm, int64_t capacity) {
+  return nvh_batch_synth_pcm(b, NVH_PCM_F32, d_pcm, capacity);
+}
+
+extern "C" int nvh_batch_synth_pcm(nvh_batch* b, int format, void* d_pcm, int64_t capacity) {
   return nvh_guard([&]() -> int {
-    if (!b || !b->s) return NVH_ERR_ARGUMENT;
+    if (!b || !b->s || !pcm_format_ok(format) || !pcm_dest_ok(format, d_pcm)) return NVH_ERR_ARGUMENT;
     nvh_stream* s = b->s;
     if (capacity < b->pcm_samples * s->setup.channels) return NVH_ERR_ARGUMENT;
     if (b->pcm_samples > 0 && !d_pcm) return NVH_ERR_ARGUMENT;
     HIP_TRY(hipSetDevice(s->ctx->device));
     // the stream keeps the tail of the newest batch (written to its current carry buffer; the batch reads its own snapshot)
-    return batch_launch(b, (const float*)b->carry_in.p, (float*)s->carry[s->carry_cur].p, d_pcm, false, nullptr);
+    return batch_launch(b, (const float*)b->carry_in.p, (float*)s->carry[s->carry_cur].p, d_pcm, false, nullptr, nullptr, format);
   });
 }
 

@@ -74,6 +74,17 @@ __global__ void k_synth_group4(NvhSynthArgs A NVH_DBG_PARAMS);
 __global__ void k_synth8(NvhSynthArgs A NVH_DBG_PARAMS);
 __global__ void k_synth8_g(NvhSynthArgs A NVH_DBG_PARAMS);    // + the general bin walk
 __global__ void k_synth8_emit(NvhSynthArgs A NVH_DBG_PARAMS);  // wide frames + paired emission through LDS (synth_emit8)
+// the 16-bit twins of the kernels that write PCM (NVH_PCM_S16: A.pcm / pcm point at int16_t samples)
+__global__ void k_synth_emit_s16(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_synth8_emit_s16(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_synth_group2_s16(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_synth_group4_s16(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_ola_compact_s16(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, int16_t* pcm, int clip,
+                                  int* clipped_flag, float* carry_out, int last_decoded, int nosym, const int* list, int emitted);
+__global__ void k_ola_emit_s16(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, int16_t* pcm, int clip,
+                               int* clipped_flag);
+__global__ void k_ola_emit_seq_s16(NvhDevSetup S, NvhDevBatch Bt, float* work, const float* carry, int16_t* pcm, int clip,
+                                   int* clipped_flag);
 __global__ void k_window_apply(float* buf, const float* window, int n, long long stride, int batch);
 __global__ void k_overlap_buffers(const float* previous, float* next, int prev_start, int len, int next_start, int channels,
                                   long long plane_stride);
@@ -435,7 +446,9 @@ int get_mdct(nvh_ctx* c, int n, MdctDev** out);                 // nvh_ops.hip
 int upload_setup(nvh_stream* s);                                 // nvh_setup.hip
 int upload_parse_tables(nvh_stream* s);                          // nvh_setup.hip
 int batch_upload(nvh_stream* s, nvh_batch* b);                   // nvh_launch.hip
-int batch_launch(nvh_batch* b, const float* carry, float* carry_out, float* d_pcm, bool timing, float* kernel_ms,
-                 hipEvent_t* ext_ev = nullptr);  // nvh_launch.hip
+// d_pcm: float samples, or int16_t with pcm_format NVH_PCM_S16 (the kernels' _s16 twins)
+int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms,
+                 hipEvent_t* ext_ev = nullptr, int pcm_format = NVH_PCM_F32);  // nvh_launch.hip
+static inline size_t pcm_sample_bytes(int pcm_format) { return pcm_format == NVH_PCM_S16 ? sizeof(int16_t) : sizeof(float); }
 int collect_flags(nvh_stream* s);                                // nvh_launch.hip
 void replay_note(nvh_stream* s, int kind, const uint8_t* data, int len, int64_t granule, int flags);  // nvh_launch.hip

@@ -721,8 +721,10 @@ static bool slab_size_ok(const nvh_batch* b) {
 
 static bool slab_path(const nvh_batch* b) { return slab_shape_ok(b) && slab_size_ok(b); }
 
-int batch_launch(nvh_batch* b, const float* carry, float* carry_out, float* d_pcm, bool timing, float* kernel_ms, hipEvent_t* ext_ev) {
+int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms, hipEvent_t* ext_ev,
+                 int pcm_format) {
   nvh_stream* s = b->s;
+  const bool s16 = pcm_format == NVH_PCM_S16;  // the emitting kernels' 16-bit twins (kernels_common.h: pcm_s16_value)
   hipStream_t st = s->ctx->stream;
   if (b->nframes == 0) return NVH_OK;
   const int ch = s->setup.channels;
@@ -783,7 +785,7 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, float* d_pc
     // paired emission (nvh_format.h: NVH_EMIT_*): the host marked the frames at upload; it needs the PCM buffer and the slabs
     // in frame order
     emitted = b->emit_frames > 0 && d_pcm != nullptr && !b->block_only && !T.no_emit && !s->shared->slab_general;
-    A.pcm = emitted ? d_pcm : nullptr;
+    A.pcm = emitted ? (float*)d_pcm : nullptr;  // (int16_t samples for the _s16 twins)
     A.windows = s->dev.windows;
     A.clip = s->clip;
     A.clipped_flag = flags + 1;
@@ -795,6 +797,7 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, float* d_pc
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_emit, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_g, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_emit_s16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       s->ctx->synth_lds_attr_set = true;
     }
     if (timing) HIP_TRY(hipEventRecord(ev[1], st));  // slot 0 stays empty: slot 1 = the synthesis kernel
@@ -808,7 +811,8 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, float* d_pc
       A.f0 = 1;
       if (b->nframes > 1) hipLaunchKernelGGL(k_synth8, dim3((unsigned)(b->nframes / 2)), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
       A.f0 = 0;
-      hipLaunchKernelGGL(k_synth8_emit, dim3((unsigned)((b->nframes + 1) / 2)), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
+      hipLaunchKernelGGL(s16 ? k_synth8_emit_s16 : k_synth8_emit, dim3((unsigned)((b->nframes + 1) / 2)), dim3(512), synth_lds, st,
+                         A NVH_DBG_LAUNCH);
     } else if (wide_general) hipLaunchKernelGGL(k_synth8_g, dim3((unsigned)b->nframes), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
     else if (wide) hipLaunchKernelGGL(k_synth8, dim3((unsigned)b->nframes), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
     else if (narrow_general) hipLaunchKernelGGL(k_synth_g, dim3((unsigned)b->nframes), dim3(256), synth_lds, st, A NVH_DBG_LAUNCH);
@@ -821,9 +825,11 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, float* d_pc
       if (synth_lds > 64 * 1024 && !s->ctx->group_lds_attr_set) {
         HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group4, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group2_s16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group4_s16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         s->ctx->group_lds_attr_set = true;
       }
-      auto kern = gw == 2 ? k_synth_group2 : k_synth_group4;
+      auto kern = gw == 2 ? (s16 ? k_synth_group2_s16 : k_synth_group2) : (s16 ? k_synth_group4_s16 : k_synth_group4);
       const unsigned nt = gw == 2 ? 256u : 512u;
       if (T.debug_occ) {
         int nb = -1;
@@ -856,9 +862,12 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, float* d_pc
       }
       A.f0 = 0;
       A.prefetch_prev = 0;
-      hipLaunchKernelGGL(k_synth_emit, dim3((unsigned)((b->nframes + 1) / 2)), dim3(NVH_SYNTH_NT), synth_lds, st, A NVH_DBG_LAUNCH);
+      hipLaunchKernelGGL(s16 ? k_synth_emit_s16 : k_synth_emit, dim3((unsigned)((b->nframes + 1) / 2)), dim3(NVH_SYNTH_NT), synth_lds, st,
+                         A NVH_DBG_LAUNCH);
     }
-    if (emitted) b->slot_name[1] = wide ? "k_synth8+k_synth8_emit" : (b->fpw == 2 ? "k_synth_group2" : b->fpw == 4 ? "k_synth_group4" : "k_synth+k_synth_emit");  // odd frames, then the emitting even frames
+    if (emitted && !s16) b->slot_name[1] = wide ? "k_synth8+k_synth8_emit" : (b->fpw == 2 ? "k_synth_group2" : b->fpw == 4 ? "k_synth_group4" : "k_synth+k_synth_emit");  // odd frames, then the emitting even frames
+    if (emitted && s16)
+      b->slot_name[1] = wide ? "k_synth8+k_synth8_emit_s16" : (b->fpw == 2 ? "k_synth_group2_s16" : b->fpw == 4 ? "k_synth_group4_s16" : "k_synth+k_synth_emit_s16");
     slab_done = true;
     fuse_gen8 = true;  // the inverse MDCT is inside: no transform kernel behind it
   }
@@ -961,7 +970,8 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, float* d_pc
   const size_t plane_bytes = (size_t)ch * (size_t)s->setup.block1 * sizeof(float);
   {
     b->slot_name[2] = (fuse_imdct || fuse_gen8) ? "-" : compact ? "k_imdct_compact" : (s->setup.block0 >= 256 ? "k_imdct_wave" : "k_imdct_window");
-    b->slot_name[3] = compact ? "k_ola_compact" : (!b->sequential_ola ? "k_ola_emit" : "k_ola_emit_seq");
+    if (!s16) b->slot_name[3] = compact ? "k_ola_compact" : (!b->sequential_ola ? "k_ola_emit" : "k_ola_emit_seq");
+    else b->slot_name[3] = compact ? "k_ola_compact_s16" : (!b->sequential_ola ? "k_ola_emit_s16" : "k_ola_emit_seq_s16");
     if (fuse_imdct || fuse_gen8)
       ;  // done inside k_spectrum_imdct / k_spectrum_gen8_imdct
     else if (compact)
@@ -990,25 +1000,37 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, float* d_pc
       // more than two channels: the steady-state path splits a frame into runs of NVH_OLA_GW groups of four sample times, one
       // workgroup each, and interleaves through LDS (ola_sym_lds)
       if (ch > 2 && !T.no_ola_sym && T.ola_segs <= 0) segs = ((s->setup.block1 / 16) + NVH_OLA_GW - 1) / NVH_OLA_GW;
+      // k_ola_compact, or its 16-bit twin
+      auto ola_compact = [&](unsigned nwg, float* c_out, const int* list, int emitted_frames) {
+        if (s16)
+          hipLaunchKernelGGL(k_ola_compact_s16, dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
+                             (const float*)work, carry, (int16_t*)d_pcm, s->clip, flags + 1, c_out, b->last_decoded,
+                             T.no_ola_sym ? 1 : 0, list, emitted_frames);
+        else
+          hipLaunchKernelGGL(k_ola_compact, dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
+                             (const float*)work, carry, (float*)d_pcm, s->clip, flags + 1, c_out, b->last_decoded,
+                             T.no_ola_sym ? 1 : 0, list, emitted_frames);
+      };
       if (!emitted)
-        hipLaunchKernelGGL(k_ola_compact, dim3((unsigned)b->nframes, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
-                           (const float*)work, carry, d_pcm, s->clip, flags + 1, carry_out, b->last_decoded, T.no_ola_sym ? 1 : 0,
-                           (const int*)nullptr, 0);
+        ola_compact((unsigned)b->nframes, carry_out, (const int*)nullptr, 0);
       else if (b->ola_all)  // GPU-parsed batch, some candidate withdrawn on the device: every frame, the emitted ones return at once
-        hipLaunchKernelGGL(k_ola_compact, dim3((unsigned)b->nframes, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
-                           (const float*)work, carry, d_pcm, s->clip, flags + 1, (float*)nullptr /* k_synth wrote the carried tail */,
-                           b->last_decoded, T.no_ola_sym ? 1 : 0, (const int*)nullptr, 1);
+        ola_compact((unsigned)b->nframes, (float*)nullptr /* k_synth wrote the carried tail */, (const int*)nullptr, 1);
       else if (b->ola_count == 0)
         b->slot_name[3] = "-";  // paired emission covered every frame, the carried tail included: no launch
       else  // paired emission: only the frames k_synth left over
-        hipLaunchKernelGGL(k_ola_compact, dim3((unsigned)b->ola_count, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
-                           (const float*)work, carry, d_pcm, s->clip, flags + 1, (float*)nullptr /* k_synth wrote the carried tail */,
-                           b->last_decoded, T.no_ola_sym ? 1 : 0, b->d_ola_list, 1);
-    } else if (!b->sequential_ola)
-      hipLaunchKernelGGL(k_ola_emit, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, (const float*)work, carry,
-                         d_pcm, s->clip, flags + 1);
-    else
-      hipLaunchKernelGGL(k_ola_emit_seq, dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry, d_pcm, s->clip, flags + 1);
+        ola_compact((unsigned)b->ola_count, (float*)nullptr /* k_synth wrote the carried tail */, b->d_ola_list, 1);
+    } else if (!b->sequential_ola) {
+      if (s16)
+        hipLaunchKernelGGL(k_ola_emit_s16, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, (const float*)work, carry,
+                           (int16_t*)d_pcm, s->clip, flags + 1);
+      else
+        hipLaunchKernelGGL(k_ola_emit, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, (const float*)work, carry,
+                           (float*)d_pcm, s->clip, flags + 1);
+    } else if (s16) {
+      hipLaunchKernelGGL(k_ola_emit_seq_s16, dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry, (int16_t*)d_pcm, s->clip, flags + 1);
+    } else {
+      hipLaunchKernelGGL(k_ola_emit_seq, dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry, (float*)d_pcm, s->clip, flags + 1);
+    }
     // the last decoded block becomes the carried tail (StreamDecoder's _prevPacketBuf), always fully windowed
     if (!compact && !b->block_only && b->last_decoded >= 0 && carry_out)
       HIP_TRY(hipMemcpyAsync(carry_out, (const uint8_t*)b->work.p + (size_t)b->last_decoded * plane_bytes, plane_bytes,

@@ -13,6 +13,7 @@ OK = 0
 ERR_INVALID_DATA, ERR_ARGUMENT, ERR_RUNTIME, ERR_NOMEM = -1, -2, -3, -4
 ERR_NOT_VORBIS, ERR_DEVICE, ERR_UNSUPPORTED, ERR_NO_GPU = -5, -6, -7, -8
 PKT_EOS, PKT_RESYNC = 1, 2
+PCM_F32, PCM_S16 = 0, 1  # output formats of the *_pcm synthesis calls (NVH_PCM_*)
 
 _ERRNAMES = {
     ERR_INVALID_DATA: "InvalidDataException", ERR_ARGUMENT: "ArgumentOutOfRangeException",
@@ -91,6 +92,8 @@ SIGNATURES = {
     "nvh_stream_synth_begin": (C.c_int, [_vp, _vp, C.c_int64, _i64p]),
     "nvh_stream_synth_end": (C.c_int, [_vp, _i64p]),
     "nvh_stream_synth": (C.c_int, [_vp, _vp, _vp, C.c_int64, _i64p]),
+    "nvh_stream_synth_pcm": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, _i64p]),
+    "nvh_stream_synth_begin_pcm": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _i64p]),
     "nvh_stream_parse_errors": (C.c_int, [_vp, _i32p, _i64p, C.c_int, _ip]),
     "nvh_batch_upload": (C.c_int, [_vp, _vpp]),
     "nvh_batch_info": (C.c_int, [_vp, _ip, _ip, _i64p, _i64p]),
@@ -98,6 +101,7 @@ SIGNATURES = {
     "nvh_batch_kernels": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "nvh_stream_kernels": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "nvh_batch_synth": (C.c_int, [_vp, _vp, C.c_int64]),
+    "nvh_batch_synth_pcm": (C.c_int, [_vp, C.c_int, _vp, C.c_int64]),
     "nvh_batch_time": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _f32p, _f32p]),
     "nvh_batch_free": (None, [_vp]),
     "nvh_ogg_demux": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int64, _vp, _vp, _vp, C.c_int, _ip, _i64p]),

@@ -15,6 +15,26 @@ from . import native
 from .native import check, lib
 
 
+# output formats of the synthesis calls: numpy dtype -> NVH_PCM_* (int16: libvorbis ov_read's conversion inside the kernels)
+_PCM_FORMATS = {np.dtype(np.float32): native.PCM_F32, np.dtype(np.int16): native.PCM_S16}
+# ... and the names StreamDecoder / VorbisReader take
+_SAMPLE_FORMATS = {"f32": np.float32, "s16": np.int16}
+
+
+def _pcm_format(dtype):
+    """(NVH_PCM_* code, numpy dtype) of a sample dtype; ValueError for anything but float32 / int16."""
+    dt = np.dtype(dtype)
+    if dt not in _PCM_FORMATS:
+        raise ValueError("PCM dtype must be float32 or int16, not %s" % dt)
+    return _PCM_FORMATS[dt], dt
+
+
+def _sample_format(name):
+    if name not in _SAMPLE_FORMATS:
+        raise ValueError("sample_format must be 'f32' or 's16', not %r" % (name,))
+    return np.dtype(_SAMPLE_FORMATS[name])
+
+
 class PacketArray:
     """Packets of one logical stream in one contiguous buffer (what nvh_ogg_demux produces): packet i is
     bytes[offsets[i]:offsets[i+1]].  Feeds nvh_stream_push_packets without one FFI call per packet."""
@@ -263,8 +283,10 @@ class Batch:
         check(lib().nvh_batch_kernels(self._h, buf, 256), "nvh_batch_kernels")
         return buf.value.decode().split(",")
 
-    def synth(self, d_pcm_ptr, capacity):
-        check(lib().nvh_batch_synth(self._h, C.c_void_p(d_pcm_ptr), int(capacity)), "nvh_batch_synth")
+    def synth(self, d_pcm_ptr, capacity, dtype=np.float32):
+        """Launch the synthesis into d_pcm_ptr (capacity in samples) as float32 or int16 PCM (a 16-byte aligned int16 destination)."""
+        fmt, _ = _pcm_format(dtype)
+        check(lib().nvh_batch_synth_pcm(self._h, fmt, C.c_void_p(d_pcm_ptr), int(capacity)), "nvh_batch_synth_pcm")
 
     def time(self, d_pcm_ptr, capacity, iters, per_kernel=True):
         total = C.c_float(0)
@@ -500,65 +522,71 @@ class Stream:
         check(lib().nvh_stream_has_clipped(self._h, C.byref(v)), "nvh_stream_has_clipped")
         return bool(v.value)
 
-    def synth_host(self, pinned=False, out=None):
-        """Synthesise the pending batch; returns interleaved float32 PCM (numpy).
+    def synth_host(self, pinned=False, out=None, dtype=np.float32):
+        """Synthesise the pending batch; returns interleaved PCM (numpy) of `dtype`: float32, or int16 (ov_read's conversion,
+        done in the kernels: half the bytes over PCIe).
 
-        out: a contiguous float32 array to write into (must hold the batch); the written prefix is returned.
+        out: a contiguous array of that dtype to write into (must hold the batch); the written prefix is returned.
 
         pinned=True: the result is a view of a page-locked buffer owned by this stream (written by the copy engine
         directly, no extra copy) and stays valid until the next call."""
+        fmt, dt = _pcm_format(dtype)
         _, smp = self.pending()
         n = max(smp * self.channels, 1)
         wr = C.c_int64(0)
         if out is not None:
-            if out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"] or out.size < smp * self.channels:
-                raise ValueError("out must be a contiguous float32 array that holds the pending batch")
+            if out.dtype != dt or not out.flags["C_CONTIGUOUS"] or out.size < smp * self.channels:
+                raise ValueError("out must be a contiguous %s array that holds the pending batch" % dt)
             if out.size == 0:
-                out = np.empty(1, dtype=np.float32)
+                out = np.empty(1, dtype=dt)
             n = out.size
         elif pinned:
-            if getattr(self, "_pin_cap", 0) < n:
+            nbytes = n * dt.itemsize
+            if getattr(self, "_pin_cap", 0) < nbytes:  # (capacity in bytes: float and int16 batches share the buffer)
                 if getattr(self, "_pin_ptr", None):
                     lib().nvh_pinned_free(self._pin_ptr)
                 p = C.c_void_p()
-                cap = max(n, 2 * getattr(self, "_pin_cap", 0))
-                check(lib().nvh_pinned_alloc(cap * 4, C.byref(p)), "nvh_pinned_alloc")
+                cap = max(nbytes, 2 * getattr(self, "_pin_cap", 0))
+                check(lib().nvh_pinned_alloc(cap, C.byref(p)), "nvh_pinned_alloc")
                 self._pin_ptr, self._pin_cap = p, cap
-                self._pin_arr = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(cap,))
-            out = self._pin_arr
+                self._pin_arr = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(cap,))
+            out = self._pin_arr[:nbytes].view(dt)
         else:
-            out = np.empty(n, dtype=np.float32)
-        rc = lib().nvh_stream_synth(self._h, out.ctypes.data, None, n, C.byref(wr))
-        self._note_parse_error(rc, wr.value, "nvh_stream_synth")
+            out = np.empty(n, dtype=dt)
+        rc = lib().nvh_stream_synth_pcm(self._h, fmt, out.ctypes.data, None, n, C.byref(wr))
+        self._note_parse_error(rc, wr.value, "nvh_stream_synth_pcm")
         return out[:wr.value]
 
     # ---- pipelined read-back (nvh_stream_synth_begin / _end) ----
-    def _pipe_buffer(self, k, n):
+    def _pipe_buffer(self, k, n, dt):
         bufs = getattr(self, "_pipe", None)
         if bufs is None:
-            bufs = self._pipe = [[None, 0, None], [None, 0, None]]  # [pointer, capacity in floats, numpy view]
-        ptr, cap, arr = bufs[k]
-        if cap < n:
+            bufs = self._pipe = [[None, 0, None, None], [None, 0, None, None]]  # [pointer, capacity in bytes, byte view, dtype]
+        ptr, cap, arr, _ = bufs[k]
+        nbytes = n * dt.itemsize
+        if cap < nbytes:
             if ptr:
                 lib().nvh_pinned_free(ptr)
             p = C.c_void_p()
-            cap = max(n, 2 * cap)
-            check(lib().nvh_pinned_alloc(cap * 4, C.byref(p)), "nvh_pinned_alloc")
-            bufs[k] = [p, cap, np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(cap,))]
-        return bufs[k][2]
+            cap = max(nbytes, 2 * cap)
+            check(lib().nvh_pinned_alloc(cap, C.byref(p)), "nvh_pinned_alloc")
+            bufs[k] = [p, cap, np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(cap,)), None]
+        bufs[k][3] = dt
+        return bufs[k][2][:cap - cap % dt.itemsize].view(dt)
 
-    def synth_begin(self):
+    def synth_begin(self, dtype=np.float32):
         """Queue the pending batch (upload, GPU parse, synthesis, transfer of the PCM on a copy stream) and return at once.
-        Two batches may be outstanding; synth_end() hands them back in order."""
+        Two batches may be outstanding; synth_end() hands them back in order, each in the dtype of its begin (float32 / int16)."""
+        fmt, dt = _pcm_format(dtype)
         if getattr(self, "_pipe_out", 0) >= 2:
             # refuse before touching a buffer: slot k is still the DMA destination of the oldest outstanding batch
             raise native.NvhError(native.ERR_ARGUMENT, "nvh_stream_synth_begin (two batches are outstanding: call synth_end first)")
         _, smp = self.pending()
         n = max(smp * self.channels, 1)
         k = getattr(self, "_pipe_next", 0)
-        out = self._pipe_buffer(k, n)
+        out = self._pipe_buffer(k, n, dt)
         exp = C.c_int64(0)
-        check(lib().nvh_stream_synth_begin(self._h, out.ctypes.data, out.size, C.byref(exp)), "nvh_stream_synth_begin")
+        check(lib().nvh_stream_synth_begin_pcm(self._h, fmt, out.ctypes.data, out.size, C.byref(exp)), "nvh_stream_synth_begin_pcm")
         # only a begin that succeeded occupies a slot
         self._pipe_next = k ^ 1
         self._pipe_out = getattr(self, "_pipe_out", 0) + 1
@@ -579,12 +607,15 @@ class Stream:
         self._pipe_first = k ^ 1
         self._pipe_out -= 1
         self._note_parse_error(rc, wr.value, "nvh_stream_synth_end")
-        return self._pipe[k][2][:wr.value]
+        _, cap, arr, dt = self._pipe[k]
+        return arr[:cap - cap % dt.itemsize].view(dt)[:wr.value]
 
-    def synth_device(self, d_ptr, capacity):
+    def synth_device(self, d_ptr, capacity, dtype=np.float32):
+        """Synthesise the pending batch into device memory (capacity in samples; int16: 16-byte aligned); returns the samples written."""
+        fmt, _ = _pcm_format(dtype)
         wr = C.c_int64(0)
-        rc = lib().nvh_stream_synth(self._h, None, C.c_void_p(d_ptr), int(capacity), C.byref(wr))
-        self._note_parse_error(rc, wr.value, "nvh_stream_synth")
+        rc = lib().nvh_stream_synth_pcm(self._h, fmt, None, C.c_void_p(d_ptr), int(capacity), C.byref(wr))
+        self._note_parse_error(rc, wr.value, "nvh_stream_synth_pcm")
         return wr.value
 
     def _note_parse_error(self, rc, written, where):
@@ -633,7 +664,9 @@ class Stream:
 class StreamDecoder:
     """IStreamDecoder-shaped object (Contracts/IStreamDecoder.cs:9-105) over a packet list."""
 
-    def __init__(self, ctx, packets, granules=None, flags=None, batch_frames=1024, gpu_parse=False):
+    def __init__(self, ctx, packets, granules=None, flags=None, batch_frames=1024, gpu_parse=False, sample_format="f32"):
+        # sample_format "s16": the ring is decoded as int16 (ov_read's conversion, in the kernels); Read then takes int16 buffers
+        self._dtype = _sample_format(sample_format)
         if len(packets) < 3:
             raise native.NvhError(native.ERR_NOT_VORBIS, "StreamDecoder")
         self._stream = Stream(ctx, packets[0], packets[1], packets[2])
@@ -656,7 +689,7 @@ class StreamDecoder:
             self._flags = flags if flags is not None else [0] * len(packets)
         self._next = 3
         self._batch_frames = int(batch_frames)
-        self._ring = np.zeros(0, dtype=np.float32)
+        self._ring = np.zeros(0, dtype=self._dtype)
         self._ring_pos = 0
         self._ended = False
         self._position = 0
@@ -735,7 +768,7 @@ class StreamDecoder:
             pcm = None
             if frames:
                 # the ring is only replaced once it has been read out, so the stream's pinned buffer can be it
-                pcm = self._stream.synth_host(pinned=True)
+                pcm = self._stream.synth_host(pinned=True, dtype=self._dtype)
             got = pcm is not None and pcm.size > 0
             if got:
                 self._ring = pcm
@@ -759,6 +792,8 @@ class StreamDecoder:
             raise IndexError("offset")  # ArgumentOutOfRangeException
         if count % ch != 0:
             raise ValueError("count must be a multiple of Channels")
+        if getattr(buffer, "dtype", None) != self._dtype:
+            raise TypeError("this decoder delivers %s samples: the buffer must be a numpy %s array" % (self._dtype, self._dtype))
         idx, tgt = offset, offset + count
         while idx < tgt:
             if self._pending_errors and self._ring_pos >= self._pending_errors[0][1]:
@@ -895,7 +930,7 @@ class StreamDecoder:
             k, pos = self._provider_seek(s, 1)
             roll = s - pos
         self._stream.reset()
-        self._ring = np.zeros(0, dtype=np.float32)
+        self._ring = np.zeros(0, dtype=self._dtype)
         self._ring_pos = 0
         self._pending_errors = []
         self._ended = False
@@ -935,7 +970,10 @@ class StreamDecoder:
 class VorbisReader:
     """VorbisReader-shaped facade (VorbisReader.cs): first logical stream of an .ogg file or byte string."""
 
-    def __init__(self, source, ctx=None, device=0, batch_frames=8192, gpu_parse=True, forward_only=False):
+    def __init__(self, source, ctx=None, device=0, batch_frames=8192, gpu_parse=True, forward_only=False, sample_format="f32"):
+        # sample_format: "f32" (float32 PCM, the reference's) or "s16" (int16, libvorbis ov_read's conversion in the kernels)
+        self._dtype = _sample_format(sample_format)
+        self._sample_format = sample_format
         # gpu_parse: parse the packets on the GPU too when the stream shape allows it (StreamDecoder falls back silently)
         # forward_only: read the container the way the reference reads a source that cannot seek (ContainerReader picks
         # ForwardOnlyPageReader for !stream.CanSeek, Ogg/ContainerReader.cs); SeekTo then raises as IPacketProvider.CanSeek is false
@@ -959,7 +997,8 @@ class VorbisReader:
                 self._ctx.close()
             raise native.NvhError(native.ERR_NOT_VORBIS, "VorbisReader")  # ArgumentException: could not load the container
         self._stream_index = 0
-        self._dec = StreamDecoder(self._ctx, demux_ogg_array(data, self._stream_ids[0], self._forward_only), None, None, batch_frames, gpu_parse)
+        self._dec = StreamDecoder(self._ctx, demux_ogg_array(data, self._stream_ids[0], self._forward_only), None, None, batch_frames, gpu_parse,
+                                  sample_format)
         if self._forward_only:
             self._dec.can_seek = False
         else:
@@ -990,7 +1029,7 @@ class VorbisReader:
         clip = self.ClipSamples
         if index not in self._decs:
             self._decs[index] = StreamDecoder(self._ctx, demux_ogg_array(self._data, self._stream_ids[index], self._forward_only), None,
-                                              None, self._batch_frames, self._gpu_parse)
+                                              None, self._batch_frames, self._gpu_parse, self._sample_format)
             if self._forward_only:
                 self._decs[index].can_seek = False
             else:
@@ -1036,6 +1075,8 @@ class VorbisReader:
 
     def ReadSamples(self, buffer, offset=0, count=None):
         """VorbisReader.ReadSamples(float[], int, int) (VorbisReader.cs:336-345)."""
+        if getattr(buffer, "dtype", None) != self._dtype:
+            raise TypeError("this reader delivers %s samples: the buffer must be a numpy %s array" % (self._dtype, self._dtype))
         if count is None:
             count = len(buffer) - offset
         count -= count % self.Channels
@@ -1045,13 +1086,13 @@ class VorbisReader:
 
     def read_all(self):
         chunks = []
-        buf = np.empty(65536 * self.Channels, dtype=np.float32)
+        buf = np.empty(65536 * self.Channels, dtype=self._dtype)
         while True:
             n = self.ReadSamples(buf, 0, buf.size)
             if n <= 0:
                 break
             chunks.append(buf[:n].copy())
-        return np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.float32)
+        return np.concatenate(chunks) if chunks else np.zeros(0, dtype=self._dtype)
 
     def close(self):
         for d in self._decs.values():

@@ -355,7 +355,7 @@ def config(name):
         c.update(channels=2, block0=256, block1=1024,
                  floors=[lambda w: write_floor0(w, 8, 22050, 64, 5, 40, [10]),
                          lambda w: write_floor0(w, 7, 22050, 128, 6, 30, [10])],
-                 residues=[lambda w: write_residue(w, 1, 0, 120, 8, 2, [1, 1, 3, 0], [8, 3, 3, 4])],
+                 residues=[lambda w: write_residue(w, 1, 0, 128, 8, 2, [1, 1, 3, 0], [8, 3, 3, 4])],  # (short blocks: up to n/2)
                  mappings=[lambda w: write_mapping(w, 2, 1, [(0, 1)], None, [(0, 0)]),
                            lambda w: write_mapping(w, 2, 1, [], None, [(1, 0)])],
                  modes=[(0, 0), (1, 1)])
@@ -475,6 +475,37 @@ def config(name):
                  mappings=[lambda w: write_mapping(w, nch, 1, couple, None, [(0, 0)]),
                            lambda w: write_mapping(w, nch, 1, couple[::-1], None, [(1, 1)])],
                  modes=[(0, 0), (1, 1)])
+    elif name == "ch9_res2":                  # nine channels: 4-bit coupling fields, a step that names channel 8; Residue2 with
+        # partitions that are whole multiples of the channel count (18 / 36: no quirk B-1), books of dimension 1 / 2 / 4
+        cpl = [(0, 8), (3, 4), (8, 5)]
+        c.update(channels=9, block0=256, block1=2048,
+                 floors=[_floor1_small(0, 1), _floor1_long(0, 1, 10)],
+                 residues=[lambda w: write_residue(w, 2, 0, 9 * 96, 18, 2, [1, 2, 7, 0], [3, 8, 7, 3, 8]),
+                           lambda w: write_residue(w, 2, 0, 9 * 480, 36, 2, [3, 1, 4, 6], [3, 4, 3, 4, 4, 3])],
+                 mappings=[lambda w: write_mapping(w, 9, 1, cpl, None, [(0, 0)]),
+                           lambda w: write_mapping(w, 9, 1, cpl[::-1], None, [(1, 1)])],
+                 modes=[(0, 0), (1, 1)])
+    elif name == "ch16_res1_4096":            # sixteen channels at n = 4096: 128 KiB of spectra per frame.  The long residue has a
+        # dimension-3 book in 16-value partitions (vector overrun: nvh_setup.hip marks the residue sequential), so the spectra may
+        # not take the 152 KB LDS window either and the frame goes to the global-memory kernels k_residue + k_couple_floor
+        cpl = [(0, 15), (1, 14), (7, 8), (12, 3)]
+        c.update(channels=16, block0=512, block1=4096, rate=48000,
+                 floors=[_floor1_small(0, 1), _floor1_long(0, 1, 11, n_parts=8)],
+                 residues=[lambda w: write_residue(w, 1, 0, 200, 16, 2, [1, 2, 7, 0], [3, 8, 7, 3, 8]),
+                           lambda w: write_residue(w, 1, 8, 520, 16, 2, [3, 1, 4, 6], [3, 6, 4, 3, 6, 4])],
+                 mappings=[lambda w: write_mapping(w, 16, 1, cpl, None, [(0, 0)]),
+                           lambda w: write_mapping(w, 16, 1, cpl[::-1], None, [(1, 1)])],
+                 modes=[(0, 0), (1, 1)])
+    elif name == "ch40_res1":                 # forty channels: 6-bit coupling fields, steps across channel 32 (the frame's 32-bit
+        # execute masks do not reach there: nvh_format.h NvhFrame), modest residue ends
+        cpl = [(0, 39), (31, 32), (33, 5), (20, 35), (36, 37)]
+        c.update(channels=40, block0=256, block1=512,
+                 floors=[_floor1_small(0, 1), _floor1_long(0, 1, 8, n_parts=3)],
+                 residues=[lambda w: write_residue(w, 1, 0, 64, 16, 2, [1, 2, 7, 0], [3, 8, 7, 3, 8]),
+                           lambda w: write_residue(w, 1, 0, 160, 16, 2, [3, 1, 4, 6], [3, 4, 3, 4, 4, 3])],
+                 mappings=[lambda w: write_mapping(w, 40, 1, cpl, None, [(0, 0)]),
+                           lambda w: write_mapping(w, 40, 1, cpl[::-1], None, [(1, 1)])],
+                 modes=[(0, 0), (1, 1)])
     else:
         raise KeyError(name)
     return c
@@ -483,7 +514,7 @@ def config(name):
 CONFIG_NAMES = ["mono_res0_small_blocks", "stereo_res1_coupled", "three_ch_res2_misaligned", "six_ch_res2_4096",
                 "floor0_stereo", "floor0_slab", "two_submaps", "equal_blocks_overrun", "mono_8192", "stereo_8192", "ch4_res1", "ch5_res2", "ch7_res1", "ch8_res2", "mono_res1_2048",
                 "res0_slab", "odd_dims_slab", "res2_alias_stereo", "two_pass_slab", "res0_3ch",
-                "table_books_pair", "table_books_general", "table_books_b1"]
+                "table_books_pair", "table_books_general", "table_books_b1", "ch9_res2", "ch16_res1_4096", "ch40_res1"]
 
 
 def filtered_stream(oracle, name, npackets, seed, consistent_windows=True):

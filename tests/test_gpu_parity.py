@@ -247,13 +247,15 @@ def _decode_gpu(nv, ctx, pk, gr, fl, clip, batch_frames):
 
 
 @pytest.mark.parametrize("name", ["mono_res0_small_blocks", "stereo_res1_coupled", "three_ch_res2_misaligned", "six_ch_res2_4096",
-                                  "two_submaps", "equal_blocks_overrun", "mono_8192", "stereo_8192", "mono_res1_2048", "floor0_slab"])
+                                  "two_submaps", "equal_blocks_overrun", "mono_8192", "stereo_8192", "mono_res1_2048", "floor0_slab",
+                                  "ch9_res2", "ch16_res1_4096", "ch40_res1"])
 @pytest.mark.parametrize("consistent", [True, False])
 def test_synthetic_configs_bit_exact(oracle, gpu_ctx, name, consistent):
     """Paths no shipped file reaches -- Residue0, Residue1 with coupling, 3 and 6 channels (incl. the Residue2
     offset quirk B-1 and BASELINE config C4's shape), several submaps (quirk B-3), block sizes 64/128 and 8192,
     codebook dimensions that do not divide the partition size, inconsistent window flags (sequential overlap
-    path) -- bit-exact against the oracle on random-bit packets."""
+    path), 9 / 16 / 40 channels (the descriptor kernels and k_ola_compact's scalar loop; execute flags of channels
+    32 and beyond) -- bit-exact against the oracle on random-bit packets."""
     import nvorbis_amd as nv
     from tests import synth_stream as ss
     pk, gr, fl = ss.filtered_stream(oracle, name, 150, 11 + int(consistent), consistent_windows=consistent)
@@ -384,6 +386,91 @@ def test_channel_counts_4_5_7_8_bit_exact(oracle, gpu_ctx, name):
             got = _decode_gpu(nv, gpu_ctx, pk, gr, fl, clip, bf)
             assert got.size == ref.size, (name, clip, bf)
             assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (name, clip, bf, float(np.abs(got - ref).max()))
+
+
+_KERNEL_TOGGLES = ("NVH_EMIT_ALWAYS", "NVH_UNFUSED", "NVH_NO_FUSED_IMDCT", "NVH_NO_COMPACT", "NVH_GPU_PARSE", "NVH_COPY_UPLOAD",
+                   "NVH_NO_EMIT", "NVH_NO_EMIT8", "NVH_NO_SLAB", "NVH_POISON_PLANES")
+
+
+@pytest.mark.parametrize("name", ["ch9_res2", "ch16_res1_4096", "ch40_res1"])
+def test_wide_configs_take_the_descriptor_kernels(oracle, gpu_ctx, name):
+    """More than eight channels are outside the slab contract (NVH_SLAB_MAX_CH) and the GPU parser's: the descriptor kernels
+    and k_ola_compact's scalar loop (ola_compact_body.inc) decode them.  Sixteen channels at n = 4096 (128 KiB of spectra, a
+    residue with vector overrun: no 152 KB LDS window) take the global-memory pair k_residue + k_couple_floor, nine and forty
+    channels the LDS-resident k_spectrum_gen8.  Bit-exact against the oracle on the structured stream of tests/spec_pin.py,
+    whose silent channels include channels beyond 31."""
+    import os
+    import nvorbis_amd as nv
+    from tests import spec_pin
+    torch = _torch()
+    pk, gr = (list(x) for x in spec_pin.stream(name))
+    fl = [0] * len(pk)
+    ref, _ = oracle.decode_packets(pk, gr, fl, clip=False)
+    for bf in (1024, 5):
+        got = _decode_gpu(nv, gpu_ctx, pk, gr, fl, False, bf)
+        assert got.size == ref.size and np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (bf, float(np.abs(got - ref).max()))
+    st = nv.Stream(gpu_ctx, pk[0], pk[1], pk[2])
+    for p in pk[3:]:
+        st.push_packet(p, -1, 0)
+    b = st.upload_batch()
+    pcm = torch.empty(max(b.samples * st.channels, 1), dtype=torch.float32, device="cuda")
+    b.synth(pcm.data_ptr(), pcm.numel())
+    names = [k for k in b.kernels() if k != "-"]
+    b.free()
+    st.close()
+    assert not any(k.startswith("k_synth") for k in names), names
+    if not any(os.environ.get(t) for t in _KERNEL_TOGGLES):
+        assert "k_ola_compact" in names, names
+        if name == "ch16_res1_4096":
+            assert "k_residue" in names and "k_couple_floor" in names, names
+        else:
+            assert "k_spectrum_gen8" in names, names
+
+
+@pytest.mark.parametrize("name", ["ch9_res2", "ch16_res1_4096", "ch40_res1"])
+def test_gpu_parser_refuses_wide_streams(oracle, gpu_ctx, name):
+    """The GPU packet parser takes at most NVH_PARSE_MAX_CH channels: set_gpu_parse raises ERR_UNSUPPORTED (as for Floor0), and
+    VorbisReader(gpu_parse=True) -- whose StreamDecoder asks for it -- keeps the host parser and returns the oracle's PCM."""
+    import nvorbis_amd as nv
+    from nvorbis_amd import native
+    from tests import ogg_py, spec_pin
+    pk, gr = (list(x) for x in spec_pin.stream(name))
+    st = nv.Stream(gpu_ctx, pk[0], pk[1], pk[2])
+    try:
+        with pytest.raises(native.NvhError) as e:
+            st.set_gpu_parse(True)
+        assert e.value.code == native.ERR_UNSUPPORTED
+    finally:
+        st.close()
+    data = ogg_py.write_ogg(pk, gr)
+    ref, info = oracle.decode_ogg(data, clip=False)
+    rd = nv.VorbisReader(data, ctx=gpu_ctx, batch_frames=7, gpu_parse=True)
+    rd.ClipSamples = False
+    got = rd.read_all()
+    assert rd.Channels == info["channels"]
+    rd.close()
+    assert got.size == ref.size > 0
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+
+
+@pytest.mark.parametrize("name", ["stereo_res1_coupled", "three_ch_res2_misaligned", "six_ch_res2_4096", "floor0_stereo", "floor0_slab",
+                                  "two_submaps", "equal_blocks_overrun", "mono_8192", "stereo_8192", "ch4_res1", "ch5_res2", "ch7_res1",
+                                  "ch8_res2", "mono_res1_2048", "res0_slab", "odd_dims_slab", "res2_alias_stereo", "two_pass_slab",
+                                  "res0_3ch", "table_books_pair", "table_books_general", "table_books_b1", "ch9_res2", "ch16_res1_4096",
+                                  "ch40_res1"])
+def test_gpu_matches_the_spec_decoder(gpu_ctx, name):
+    """The product's PCM (clip off) on every pinned configuration's structured stream against the spec-derived decoder with the
+    configuration's quirk set (tests/spec_pin.py), within the CPU pin's bound (1e-6 x peak; Floor0 spec_pin.FLOOR0_BOUND): no
+    oracle in between.  In the replays that force the descriptor kernels this is the high-precision check of k_spectrum_f0's
+    device cos / sqrt / exp.  The spec decode is cached per process (spec_pin.spec_pcm)."""
+    import nvorbis_amd as nv
+    from tests import spec_pin
+    pk, gr = (list(x) for x in spec_pin.stream(name))
+    want = spec_pin.spec_pcm(name, tuple(sorted(spec_pin.QUIRKS[name])))
+    got = _decode_gpu(nv, gpu_ctx, pk, gr, [0] * len(pk), False, 1024).astype(np.float64)
+    assert got.size == want.size
+    peak = float(np.abs(want).max())
+    assert float(np.abs(got - want).max()) <= spec_pin.bound(name) * peak, (name, float(np.abs(got - want).max()) / peak)
 
 
 def test_floor0_within_tolerance(oracle, gpu_ctx):

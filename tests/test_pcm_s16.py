@@ -149,7 +149,8 @@ def _decode(nv, ctx, pk, gr, fl, clip, batch_frames, fmt):
 CONFIGS = ["mono_res0_small_blocks", "stereo_res1_coupled", "three_ch_res2_misaligned", "six_ch_res2_4096", "two_submaps",
            "equal_blocks_overrun", "mono_8192", "stereo_8192", "mono_res1_2048", "floor0_slab", "floor0_stereo",
            "res0_slab", "odd_dims_slab", "res2_alias_stereo", "two_pass_slab", "res0_3ch",
-           "table_books_pair", "table_books_general", "table_books_b1", "ch4_res1", "ch5_res2", "ch7_res1", "ch8_res2"]
+           "table_books_pair", "table_books_general", "table_books_b1", "ch4_res1", "ch5_res2", "ch7_res1", "ch8_res2",
+           "ch9_res2", "ch16_res1_4096", "ch40_res1"]
 
 
 @pytest.mark.gpu

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from tests import ogg_py, vorbis_encode as ve, vorbis_spec
+from tests import ogg_py, spec_pin, synth_stream as ss, vorbis_encode as ve, vorbis_spec
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -35,6 +35,111 @@ def test_spec_decoder_agrees_with_oracle_on_shipped_files(oracle, ogg_bytes, nam
         assert ref.size == pcm.size + (S.block1 // 2) * S.channels
     else:
         assert pcm.size == ref.size == last * S.channels
+
+
+def _oracle_pcm(oracle, name):
+    pk, gr = spec_pin.stream(name)
+    ref, info = oracle.decode_packets(list(pk), list(gr), [0] * len(pk), clip=False)
+    return ref.astype(np.float64), info
+
+
+@pytest.mark.parametrize("name", [n for n in ss.CONFIG_NAMES if n not in spec_pin.UNPINNED])
+def test_synthetic_config_pinned_to_the_spec_decoder(oracle, name):
+    """Every synthetic configuration, on a structured stream (long x 4 / short x 3 / long x 5, full-depth side information,
+    a quarter of the channels of every packet silent): the oracle (clip off) and the spec-derived decoder with the
+    configuration's declared quirk set (tests/spec_pin.py: QUIRKS, with the measured errors) agree within 1e-6 x peak on
+    Floor1 setups and spec_pin.FLOOR0_BOUND x peak on Floor0 ones.  Switching off any one declared quirk raises the error above
+    1e-3 x peak: a declared quirk the stream does not exercise fails here.  mono_res0_small_blocks stays unpinned: quirk B10
+    (spec_pin.UNPINNED).  Sample counts: the spec's count is the last granule; the reference hands out the windowed right half
+    of the last (long) block after it (the tail spec_pin.spec_pcm appends), one half long block per channel more."""
+    pk, gr = spec_pin.stream(name)
+    S = ve.setup_of(pk[:3])
+    ref, info = _oracle_pcm(oracle, name)
+    assert info["channels"] == S.channels
+    quirks = tuple(sorted(spec_pin.QUIRKS[name]))
+    pcm = spec_pin.spec_pcm(name, quirks)
+    assert ref.size == pcm.size == (gr[-1] + S.block1 // 2) * S.channels
+    peak = float(np.abs(ref).max())
+    assert peak > 1e-3 and np.isfinite(ref).all()
+    err = float(np.abs(ref - pcm).max())
+    assert err <= spec_pin.bound(name) * peak, (name, quirks, err / peak)
+    for q in quirks:
+        off = tuple(x for x in quirks if x != q)
+        e_off = float(np.abs(ref - spec_pin.spec_pcm(name, off)).max())
+        assert e_off > 1e-3 * peak, (name, q, e_off / peak)
+
+
+def test_every_config_is_pinned_or_says_why():
+    assert set(spec_pin.QUIRKS) | set(spec_pin.UNPINNED) == set(ss.CONFIG_NAMES)
+    assert not set(spec_pin.QUIRKS) & set(spec_pin.UNPINNED)
+    assert all(set(q) <= set(vorbis_spec.QUIRKS) for q in spec_pin.QUIRKS.values())
+
+
+def test_structured_streams_silence_channels_and_name_them(oracle):
+    """The structured encoder on the wide setups: coupling fields of 4 (9 channels) and 6 bits (16, 40) read back as written,
+    and the silent channels of packet() -- channels 32 and beyond included -- come back as unused floors, the others as used."""
+    for name, cpl in (("ch9_res2", [(0, 8), (3, 4), (8, 5)]), ("ch16_res1_4096", [(0, 15), (1, 14), (7, 8), (12, 3)]),
+                      ("ch40_res1", [(0, 39), (31, 32), (33, 5), (20, 35), (36, 37)])):
+        hdr = list(spec_pin.headers(name))
+        S = ve.setup_of(hdr)
+        assert S.mappings[0].coupling == cpl and S.mappings[1].coupling == cpl[::-1]
+        enc = ve.PacketEncoder(S)
+        rng = np.random.default_rng(5)
+        for mode in (0, 1):
+            silent = {0, 3, S.channels - 1} | ({32, 34} if S.channels > 34 else set())
+            dec = vorbis_spec.SpecDecoder(hdr[0], hdr[2])
+            assert dec.block(enc.packet(rng, mode, silent=silent)) is not None
+            assert dec.last_floor_used == [c not in silent for c in range(S.channels)]
+    pk, _ = spec_pin.stream("ch40_res1")
+    dec = vorbis_spec.SpecDecoder(pk[0], pk[2])
+    unused_high = 0
+    for p in pk[3:]:
+        dec.block(p)
+        unused_high += sum(not u for u in dec.last_floor_used[32:])
+    assert unused_high > 0  # the pinned stream has silent channels beyond 31
+
+
+def test_floor0_packets_round_trip():
+    """put_floor0 writes what the spec's Floor0 packet decode (6.2.2) reads: amplitude, book number, and entries until `order`
+    coefficients exist; an amplitude of 0 is an unused floor and nothing follows it."""
+    for name in ("floor0_stereo", "floor0_slab"):
+        hdr = list(spec_pin.headers(name))
+        S = ve.setup_of(hdr)
+        enc = ve.PacketEncoder(S)
+        rng = np.random.default_rng(9)
+        for fl in (f for f in S.floors if f.type == 0):
+            for _ in range(20):
+                amp, book, entries = enc.random_floor0(rng, fl)
+                w = ss.BitWriter()
+                enc.put_floor0(w, fl, amp, book, entries)
+                enc.put_floor0(w, fl, 0)
+                w.write(1, 1)
+                r = vorbis_spec.BitReader(w.bytes())
+                got = fl.decode(r, S.books)
+                b = S.books[fl.book_list[book]]
+                want, last = [], 0.0
+                for e in entries:
+                    want.extend(v + last for v in b.vector(e))
+                    last = want[-1]
+                assert got[0] == amp and got[1] == want[:fl.order]
+                assert fl.decode(r, S.books) is None and r.read(1) == 1
+                assert np.isfinite(fl.curve(got, S.block1 // 2)).all()
+
+
+@pytest.mark.parametrize("n", [512, 2048, 4096, 8192])
+def test_spec_imdct_chunked_equals_the_matrix(n):
+    """The spec-derived decoder's inverse MDCT above n = 4096 is the cosine sum evaluated in row chunks: against the matrix form
+    (every row at n <= 4096; 96 random rows of the full matrix at 8192, where it is not kept), on random spectra, several at once
+    and one alone."""
+    rng = np.random.default_rng(n)
+    X = rng.standard_normal((n // 2, 3))
+    got = vorbis_spec.imdct_chunked(X)
+    rows = np.arange(n) if n <= 4096 else np.sort(rng.choice(n, 96, replace=False))
+    want = vorbis_spec.imdct_matrix(n, rows) @ X
+    assert float(np.abs(got[rows] - want).max()) <= 1e-9 * float(np.abs(want).max())
+    S = vorbis_spec.Setup(*spec_pin.headers("mono_8192")[0::2])
+    one = S.imdct(X[:, 1])
+    assert one.shape == (n,) and float(np.abs(one - got[:, 1]).max()) <= 1e-9 * float(np.abs(got[:, 1]).max())
 
 
 def test_inverse_db_closed_form_matches_the_table(oracle):
@@ -131,6 +236,10 @@ def test_c4_six_channel_full_depth(oracle, ogg_bytes, psize):
     else:
         assert err > 1e-3 * peak  # the reference's write positions are not the specification's here
         assert min(fracs) >= 0.60, fracs  # rows of adjacent partitions overlap, some rows are never written
+        # ... and they are quirk B1's: with it, the spec-derived decoder agrees
+        pcm_b1, _ = vorbis_spec.decode_ogg_packets(pk, quirks=("B1",))
+        assert pcm_b1.size == pcm.size
+        assert float(np.abs(ref[:n] - pcm_b1[:n]).max()) <= 1e-6 * peak
     assert min(len(p) for p, k in zip(pk[3:], kinds) if k) > 3000
 
 

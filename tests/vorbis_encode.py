@@ -107,6 +107,39 @@ class PacketEncoder:
                     assert ys[k] == 0
                 k += 1
 
+    # ---- floor 0 -----------------------------------------------------------------------------------
+    def random_floor0(self, rng, fl, max_db=20.0):
+        """Floor0 side information of one channel: (amplitude > 0, book number, one entry per vector until `order`
+        coefficients exist).  Coefficient sets whose curve (6.2.3) rises above exp(.11512925 * max_db) at some Bark
+        section -- p + q near 0, where float32 and double part ways, or an overflow -- are drawn again."""
+        cos_w = np.cos(np.pi * np.arange(fl.bark_map_size) / fl.bark_map_size)
+        for _attempt in range(256):
+            amp = int(rng.integers(1, 1 << fl.amp_bits))
+            book = int(rng.integers(0, fl.nbooks))
+            be = self.enc[fl.book_list[book]]
+            entries = be.used[rng.integers(0, be.used.size, -(-fl.order // be.book.dims))].tolist()
+            coefficients, last = [], 0.0
+            for e in entries:
+                vec = [v + last for v in be.book.vector(e)]
+                last = vec[-1]
+                coefficients.extend(vec)
+            with np.errstate(all="ignore"):
+                top = float(np.max(fl.curve_at((amp, coefficients[:fl.order]), cos_w)))
+            if np.isfinite(top) and top <= np.exp(.11512925 * max_db):
+                return amp, book, entries
+        raise AssertionError("no Floor0 coefficient set with a bounded curve")
+
+    def put_floor0(self, w, fl, amp, book=0, entries=()):
+        """Floor0 packet data (spec 6.2.2): the amplitude (0 = unused floor), then the book number and the entries."""
+        w.write(amp, fl.amp_bits)
+        if amp == 0:
+            return
+        w.write(book, ilog(fl.nbooks))
+        be = self.enc[fl.book_list[book]]
+        assert len(entries) * be.book.dims >= fl.order
+        for e in entries:
+            be.put(w, e)
+
     # ---- residue -----------------------------------------------------------------------------------
     def put_residue(self, w, rng, res, block_size, class_weights=None, stats=None):
         """Residue0.Decode's read order (Residue0.cs:119-178) with random classifications / entries."""
@@ -187,7 +220,9 @@ class PacketEncoder:
         m = S.mappings[mapping_idx]
         for c in range(S.channels):
             fl = S.floors[m.submap_floor[m.mux[c]]]
-            if c in silent:
+            if fl.type == 0:
+                self.put_floor0(w, fl, *((0,) if c in silent else self.random_floor0(rng, fl)))
+            elif c in silent:
                 self.put_floor(w, fl, None, None)
             else:
                 ys, subs = self.random_floor(rng, fl, **(floor_kw or {}))
@@ -224,9 +259,12 @@ def granules_for(setup, kinds):
     return out
 
 
-def encode_stream(setup, headers, kinds, seed, long_mode=None, short_mode=None, **kw):
-    """Full-depth audio packets for a block-kind sequence with consistent window flags.  Returns (packets, granules)."""
+def encode_stream(setup, headers, kinds, seed, long_mode=None, short_mode=None, p_silent=0.0, **kw):
+    """Full-depth audio packets for a block-kind sequence with consistent window flags.  Returns (packets, granules).
+    p_silent > 0: every channel of every packet gets an unused floor with that probability (drawn from a generator of
+    its own, so that the side information of the other channels is what p_silent = 0 writes)."""
     rng = np.random.default_rng(seed)
+    srng = np.random.default_rng(seed + 7777) if p_silent > 0 else None
     enc = PacketEncoder(setup)
     if long_mode is None:
         long_mode = next(i for i, (f, _) in enumerate(setup.modes) if f)
@@ -235,6 +273,8 @@ def encode_stream(setup, headers, kinds, seed, long_mode=None, short_mode=None, 
     packets = list(headers)
     n = len(kinds)
     for i in range(n):
+        if srng is not None:
+            kw["silent"] = {c for c in range(setup.channels) if srng.random() < p_silent}
         if kinds[i]:
             prev_flag = 1 if (i == 0 or kinds[i - 1]) else 0
             next_flag = 1 if (i + 1 >= n or kinds[i + 1]) else 0

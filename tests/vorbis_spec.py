@@ -10,8 +10,27 @@ file on the shipped .ogg files (tests/test_spec_pin.py: <= 1e-6 absolute).
 It also provides what tests/vorbis_encode.py needs: parsed setup structures (with the bit extents of every header
 section, so that sections can be copied verbatim into new setup headers) and the codeword tables.
 
-Deliberately NOT mirrored here (spec behaviour kept): residue decode honours the per-channel "do not decode" flags,
-floor curves are rendered toward the post and truncated, the final granule trims the output.
+By default nothing of the reference is mirrored (spec behaviour kept): residue decode honours the per-channel "do not
+decode" flags, floor curves are rendered toward the post and truncated, the final granule trims the output.  The
+reference's departures from the specification are opt-in switches of SpecDecoder, each named by
+its Appendix B number and written in this decoder's own terms from the appendix's text:
+
+  B1  Residue2: every partition's first value goes to channel 0 at interleaved position begin + p * psize rounded down
+      to a multiple of the channel count (the spec's position is begin + p * psize itself).
+  B2  Residue decode covers all of the stream's channels for every submap (their vectors are added onto the spectra),
+      and is skipped only when no channel of the packet has a used floor; the per-channel flags are not consulted.
+  B3  With submaps whose (floor, residue) pairs differ, a channel whose own pair differs from any submap's does not
+      execute: its floor is not applied and no inverse MDCT is run for it (the mapping's channels become "silenced").
+  B4  A channel that does not execute keeps its residue values in the first half of the block and zeros in the
+      second, windowed and overlap-added as if they were time samples (the spec's output is zero); an inverse
+      coupling step whose two channels both do not execute is skipped.
+  B6  Floor1: a line segment whose end post lies beyond n/2 is drawn to x = n/2 with that post's Y (the spec draws it
+      toward the post and truncates at n/2).
+  B9  Floor0: the Bark map is filled for i < n - 1 only, so map[n - 1] = 0 (the last bin takes Bark section 0).
+
+B5 (execute flags for the residue decode taken before coupling propagation) has no effect once B2 is on -- only "some
+channel has a used floor" is asked then, and propagation cannot change that -- and B10 (the reference's inverse MDCT
+for n < 256 is not a transform) is not modelled.
 """
 import math
 
@@ -214,6 +233,82 @@ class Codebook:
         return out
 
 
+def bark(x):
+    """Spec 6.2.3: bark(x) = 13.1 atan(.00074 x) + 2.24 atan(.0000000185 x^2) + .0001 x."""
+    return 13.1 * np.arctan(.00074 * x) + 2.24 * np.arctan(.0000000185 * x * x) + .0001 * x
+
+
+class Undecodable(Exception):
+    pass
+
+
+class Floor0:
+    type = 0
+
+    @staticmethod
+    def parse(r):
+        """Spec 6.2.1."""
+        f = Floor0()
+        f.order = r.read(8)
+        f.rate = r.read(16)
+        f.bark_map_size = r.read(16)
+        f.amp_bits = r.read(6)
+        f.amp_offset = r.read(8)
+        f.nbooks = r.read(4) + 1
+        f.book_list = [r.read(8) for _ in range(f.nbooks)]
+        return f
+
+    def decode(self, r, books):
+        """Packet decode (6.2.2): (amplitude, coefficients) or None ('unused').  A book number beyond the list makes the
+        packet undecodable (step 4)."""
+        try:
+            amplitude = r.read(self.amp_bits)
+            if amplitude == 0:
+                return None
+            booknumber = r.read(ilog(self.nbooks))
+            if booknumber >= self.nbooks:
+                raise Undecodable()
+            book = books[self.book_list[booknumber]]
+            coefficients = []
+            last = 0.0
+            while len(coefficients) < self.order:
+                vec = [v + last for v in book.vector(book.decode_scalar(r))]
+                last = vec[-1]
+                coefficients.extend(vec)
+            return amplitude, coefficients[:self.order]
+        except EndOfPacket:
+            return None
+
+    def bark_map(self, n, quirks=()):
+        """map[i], i < n (6.2.3); with quirk B9 the last entry stays 0."""
+        i = np.arange(n, dtype=np.float64)
+        foobar = np.floor(bark(self.rate * i / (2.0 * n)) * self.bark_map_size / bark(.5 * self.rate)).astype(np.int64)
+        m = np.minimum(self.bark_map_size - 1, foobar)
+        if "B9" in quirks:
+            m[n - 1] = 0
+        return m
+
+    def curve(self, data, n, quirks=()):
+        """Curve computation (6.2.3): n linear floor values, double precision."""
+        return self.curve_at(data, np.cos(np.pi * self.bark_map(n, quirks) / self.bark_map_size))
+
+    def curve_at(self, data, cos_w):
+        """The linear floor value at the given cos(omega) values."""
+        amplitude, coefficients = data
+        n = cos_w.size
+        cc = np.cos(np.asarray(coefficients, dtype=np.float64))
+        odd = np.prod([4.0 * (cc[j] - cos_w) ** 2 for j in range(1, self.order, 2)] or [np.ones(n)], axis=0)
+        even = np.prod([4.0 * (cc[j] - cos_w) ** 2 for j in range(0, self.order, 2)], axis=0)
+        if self.order & 1:
+            p = (1.0 - cos_w * cos_w) * odd
+            q = 0.25 * even
+        else:
+            p = (1.0 - cos_w) / 2.0 * odd
+            q = (1.0 + cos_w) / 2.0 * even
+        lin = amplitude * self.amp_offset / ((2 ** self.amp_bits - 1) * np.sqrt(p + q)) - self.amp_offset
+        return np.exp(.11512925 * lin)
+
+
 class Floor1:
     type = 1
 
@@ -290,8 +385,9 @@ class Floor1:
                 final[i] = pred
         return final, flag
 
-    def curve(self, ys, n2):
-        """Curve synthesis (7.2.4 step 2): n2 integer floor values (dB table indices)."""
+    def curve(self, ys, n2, quirks=()):
+        """Curve synthesis (7.2.4 step 2): n2 integer floor values (dB table indices).  Quirk B6: a segment whose end post
+        lies beyond n2 is drawn to (n2, its Y) instead."""
         final, flag = self.unwrap(ys)
         out = [0] * max(n2, self.xs[1] + 1)
         hx = lx = 0
@@ -301,7 +397,11 @@ class Floor1:
             if flag[k]:
                 hy = final[k] * self.multiplier
                 hx = self.xs[k]
-                render_line(lx, ly, hx, hy, out)
+                if "B6" in quirks:
+                    if lx < n2:
+                        render_line(lx, ly, min(hx, n2), hy, out)
+                else:
+                    render_line(lx, ly, hx, hy, out)
                 lx, ly = hx, hy
         if hx < n2:
             render_line(hx, hy, n2, hy, out)
@@ -417,9 +517,9 @@ class Setup:
         self.floors = []
         for _ in range(r.read(6) + 1):
             t = r.read(16)
-            if t != 1:
-                raise ValueError("only floor 1 is implemented in the spec-derived decoder (floor type %d)" % t)
-            self.floors.append(Floor1.parse(r))
+            if t > 1:
+                raise ValueError("floor type %d" % t)
+            self.floors.append(Floor1.parse(r) if t == 1 else Floor0.parse(r))
         self.residues = []
         for _ in range(r.read(6) + 1):
             t = r.read(16)
@@ -474,39 +574,50 @@ class Setup:
         return w
 
     def imdct(self, X):
-        """y[i] = sum_k X[k] cos(2 pi / n (i + 1/2 + n/4)(k + 1/2)), i < n (unnormalised, as Vorbis uses it)."""
-        n2 = len(X)
-        n = 2 * n2
+        """y[i] = sum_k X[k] cos(2 pi / n (i + 1/2 + n/4)(k + 1/2)), i < n (unnormalised, as Vorbis uses it).  X: n/2 values,
+        or an (n/2, m) array of m spectra.  The cosine matrix is kept for n <= 4096; above, it is evaluated in row chunks."""
+        n = 2 * X.shape[0]
         M = self._imdct.get(n)
-        if M is None:
-            i = np.arange(n)[:, None] + 0.5 + n / 4.0
-            k = np.arange(n2)[None, :] + 0.5
-            M = np.cos(2.0 * np.pi / n * i * k) if n <= 4096 else None
-            self._imdct[n] = M
+        if M is None and n <= 4096:
+            M = self._imdct[n] = imdct_matrix(n)
         if M is not None:
             return M @ X
-        out = np.zeros(n)
-        k = np.arange(n2) + 0.5
-        for i0 in range(0, n, 256):
-            i = np.arange(i0, i0 + 256)[:, None] + 0.5 + n / 4.0
-            out[i0:i0 + 256] = np.cos(2.0 * np.pi / n * i * k[None, :]) @ X
-        return out
+        return imdct_chunked(X)
 
 
-def decode_residue(setup, res, r, do_not_decode, n2, nch):
-    """Spec 8.6.2 .. 8.6.5.  Returns nch vectors of n2 doubles (the channels of this submap, in order)."""
+def imdct_matrix(n, rows=None):
+    """The inverse MDCT's cosine matrix (rows i of `rows`, all n by default), doubles."""
+    i = (np.arange(n) if rows is None else np.asarray(rows))[:, None] + 0.5 + n / 4.0
+    k = np.arange(n // 2)[None, :] + 0.5
+    return np.cos(2.0 * np.pi / n * i * k)
+
+
+def imdct_chunked(X, chunk=256):
+    """The same sum as imdct_matrix(n) @ X, the matrix built and applied `chunk` rows at a time."""
+    n = 2 * X.shape[0]
+    out = np.zeros((n,) + X.shape[1:])
+    for i0 in range(0, n, chunk):
+        out[i0:i0 + chunk] = imdct_matrix(n, range(i0, min(n, i0 + chunk))) @ X
+    return out
+
+
+def decode_residue(setup, res, r, do_not_decode, n2, nch, quirks=()):
+    """Spec 8.6.2 .. 8.6.5.  Returns nch vectors of n2 doubles (the channels of this submap, in order).  Quirk B1: the
+    Residue2 partitions' write positions (module docstring)."""
     books = setup.books
     if res.type == 2:
         if all(do_not_decode):
             return [np.zeros(n2) for _ in range(nch)]
-        vec = _decode_residue_01(setup, res, r, [False], n2 * nch, 1, 1)[0]
-        return [vec[c::nch].copy() for c in range(nch)]
-    return _decode_residue_01(setup, res, r, do_not_decode, n2, nch, res.type)
+        vec = _decode_residue_01(setup, res, r, [False], n2 * nch, 1, 1, nch if "B1" in quirks else 1)[0]
+        return [vec[c:n2 * nch:nch].copy() for c in range(nch)]
+    return [v[:n2] for v in _decode_residue_01(setup, res, r, do_not_decode, n2, nch, res.type)]
 
 
-def _decode_residue_01(setup, res, r, do_not_decode, size, nch, fmt):
+def _decode_residue_01(setup, res, r, do_not_decode, size, nch, fmt, align=1):
+    """Vectors of `size` values (+ room for the last vector of a partition to run over its end: 8.6.3 adds whole
+    vectors); partition p starts at begin + p * psize, rounded down to a multiple of `align`."""
     books = setup.books
-    out = [np.zeros(size) for _ in range(nch)]
+    out = [np.zeros(size + max(b.dims for b in books)) for _ in range(nch)]
     begin = min(res.begin, size)
     end = min(res.end, size)
     cb = books[res.classbook]
@@ -534,7 +645,7 @@ def _decode_residue_01(setup, res, r, do_not_decode, size, nch, fmt):
                             bk = res.books[cls[j][p]][stage]
                             if bk >= 0:
                                 book = books[bk]
-                                off = begin + p * res.psize
+                                off = (begin + p * res.psize) // align * align
                                 v = out[j]
                                 if fmt == 0:
                                     step = res.psize // book.dims
@@ -556,18 +667,28 @@ def _decode_residue_01(setup, res, r, do_not_decode, size, nch, fmt):
     return out
 
 
-class SpecDecoder:
-    """Audio packet decode (4.3) + overlap-add; feed packets in order with packet()."""
+QUIRKS = ("B1", "B2", "B3", "B4", "B6", "B9")
 
-    def __init__(self, id_pkt, setup_pkt):
+
+class SpecDecoder:
+    """Audio packet decode (4.3) + overlap-add; feed packets in order with packet().  quirks: a subset of QUIRKS, the
+    reference departures to apply (module docstring); empty = the specification."""
+
+    def __init__(self, id_pkt, setup_pkt, quirks=()):
         self.setup = Setup(id_pkt, setup_pkt)
+        self.quirks = frozenset(quirks)
+        unknown = self.quirks - set(QUIRKS)
+        if unknown:
+            raise ValueError("unknown quirks %s" % sorted(unknown))
         self.prev_tail = None  # right half of the previous windowed block, per channel
         self.prev_n = 0
         self._db = np.array([inverse_db(i) for i in range(256)])
+        self.last_floor_used = None  # per channel of the last decoded packet: the floor was used (test aid)
 
     def block(self, pkt):
         """One audio packet -> (n, windowed block [channels][n]) or None if the packet is to be discarded."""
         S = self.setup
+        Q = self.quirks
         r = BitReader(pkt)
         try:
             if r.read(1) != 0:
@@ -586,34 +707,60 @@ class SpecDecoder:
         ch = S.channels
         floors = []
         no_residue = []
-        for c in range(ch):
-            fl = S.floors[m.submap_floor[m.mux[c]]]
-            ys = fl.decode(r, S.books)
-            floors.append((fl, ys))
-            no_residue.append(ys is None)
+        try:
+            for c in range(ch):
+                fl = S.floors[m.submap_floor[m.mux[c]]]
+                ys = fl.decode(r, S.books)
+                floors.append((fl, ys))
+                no_residue.append(ys is None)
+        except Undecodable:
+            return None
+        used = [ys is not None for _, ys in floors]
+        self.last_floor_used = used
         for mag, ang in m.coupling:  # nonzero vector propagate (4.3.3)
             if not (no_residue[mag] and no_residue[ang]):
                 no_residue[mag] = no_residue[ang] = False
-        spectra = [None] * ch
+        execute = [not f for f in no_residue]
+        if "B3" in Q and len(set(zip(m.submap_floor, m.submap_residue))) > 1:
+            execute = [False] * ch  # every channel's pair differs from some submap's
+        spectra = [np.zeros(n2) for _ in range(ch)]
         for sm in range(m.submaps):
-            chans = [c for c in range(ch) if m.mux[c] == sm]
             res = S.residues[m.submap_residue[sm]]
-            vecs = decode_residue(S, res, r, [no_residue[c] for c in chans], n2, len(chans))
+            if "B2" in Q:
+                chans = list(range(ch))
+                flags = [not any(used)] * ch
+            else:
+                chans = [c for c in range(ch) if m.mux[c] == sm]
+                flags = [no_residue[c] for c in chans]
+            vecs = decode_residue(S, res, r, flags, n2, len(chans), Q)
             for c, v in zip(chans, vecs):
-                spectra[c] = v
+                spectra[c] = spectra[c] + v
         for mag, ang in reversed(m.coupling):  # inverse coupling (4.3.5)
+            if "B4" in Q and not (execute[mag] or execute[ang]):
+                continue
             M, A = spectra[mag], spectra[ang]
             newM = np.where(M > 0, np.where(A > 0, M, M + A), np.where(A > 0, M, M - A))
             newA = np.where(M > 0, np.where(A > 0, M - A, M), np.where(A > 0, M + A, M))
             spectra[mag], spectra[ang] = newM, newA
         w = S.window(n, bool(long_block), prev_flag, next_flag)
         out = np.zeros((ch, n))
+        live = []
         for c in range(ch):
             fl, ys = floors[c]
+            if not execute[c]:
+                if "B4" in Q:
+                    out[c, :n2] = spectra[c] * w[:n2]
+                continue
             if ys is None:
                 continue  # unused floor: the channel's spectrum is zero (4.3.6)
-            curve = self._db[np.asarray(fl.curve(ys, n2), dtype=np.int64)]
-            out[c] = S.imdct(spectra[c] * curve) * w
+            if fl.type == 1:
+                curve = self._db[np.asarray(fl.curve(ys, n2, Q), dtype=np.int64)]
+            else:
+                curve = fl.curve(ys, n2, Q)
+            spectra[c] = spectra[c] * curve
+            live.append(c)
+        if live:
+            out[live] = S.imdct(np.stack([spectra[c] for c in live], axis=1)).T * w
         return n, out
 
     def packet(self, pkt):
@@ -641,9 +788,10 @@ class SpecDecoder:
         return out
 
 
-def decode_ogg_packets(packets, final_granule=None):
-    """packets: all packets of one logical stream (3 headers first).  Interleaved float64 PCM, spec semantics."""
-    dec = SpecDecoder(packets[0], packets[2])
+def decode_ogg_packets(packets, final_granule=None, quirks=()):
+    """packets: all packets of one logical stream (3 headers first).  Interleaved float64 PCM, spec semantics (plus the
+    reference departures named in `quirks`)."""
+    dec = SpecDecoder(packets[0], packets[2], quirks)
     outs = [dec.packet(p) for p in packets[3:]]
     pcm = np.concatenate(outs, axis=1) if outs else np.zeros((dec.setup.channels, 0))
     if final_granule is not None and final_granule >= 0:

@@ -501,7 +501,8 @@ def test_floor0_within_tolerance(oracle, gpu_ctx):
 
 @pytest.mark.parametrize("toggle", ["NVH_EMIT_ALWAYS", "NVH_UNFUSED", "NVH_NO_FUSED_IMDCT", "NVH_NO_COMPACT", "NVH_GPU_PARSE",
                                     "NVH_EMIT_ALWAYS+NVH_GPU_PARSE", "NVH_COPY_UPLOAD+NVH_GPU_PARSE", "NVH_NO_EMIT", "NVH_NO_EMIT8", "NVH_NO_SLAB",
-                                    "NVH_POISON_PLANES", "NVH_POISON_PLANES+NVH_GPU_PARSE"])
+                                    "NVH_POISON_PLANES", "NVH_POISON_PLANES+NVH_GPU_PARSE", "NVH_FPW=1", "NVH_FPW=4",
+                                    "NVH_FPW=1+NVH_GPU_PARSE", "NVH_FPW=4+NVH_GPU_PARSE", "NVH_FPW=4+NVH_POISON_PLANES"])
 def test_fallback_kernel_paths_bit_exact(toggle):
     """The library picks kernel variants by stream shape.  The default path of every stream the slab
     kernels take is host-written (or GPU-parsed) slabs -> k_synth / k_synth8 with paired emission; each environment toggle
@@ -516,7 +517,11 @@ def test_fallback_kernel_paths_bit_exact(toggle):
     NVH_POISON_PLANES -> every batch's work planes start out as NaN bit patterns (hipMemsetAsync at upload): device blocks are
     recycled through a pool and never cleared, so a kernel that read a plane region nothing wrote in this batch would get by on
     what an earlier decode left there -- the replay turns that into NaN PCM (round 5: the library has no such read; what
-    round 4 saw with planes in hipDeviceMallocUncached memory was the platform, tools/ubench/uncached_handoff.hip)."""
+    round 4 saw with planes in hipDeviceMallocUncached memory was the platform, tools/ubench/uncached_handoff.hip);
+    NVH_FPW=1 -> paired emission with one frame per workgroup (k_synth + k_synth_emit, k_synth_tail when a batch's last decoded
+    frame is odd) instead of the default frame groups of two (k_synth_group2), NVH_FPW=4 -> frame groups of four (k_synth_group4;
+    k_synth + k_synth_emit for batches whose slabs leave no room for four frames' LDS) -- these two replays take
+    tests/test_full_depth.py and tests/test_frame_groups.py along.  A part KEY=VALUE sets KEY to VALUE, a bare KEY sets it to 1."""
     import os
     import subprocess
     import sys
@@ -524,12 +529,16 @@ def test_fallback_kernel_paths_bit_exact(toggle):
         pytest.skip("already inside a fallback-path run")
     env = dict(os.environ)
     for t in toggle.split("+"):  # "A+B": both switches (slab kernels fed by the GPU packet parser)
-        env[t] = "1"
+        key, _, val = t.partition("=")
+        env[key] = val or "1"
     env["NVH_TEST_CHILD"] = "1"
     from tests.replay import run_children
     children = [(["test_gpu_parity.py"], env, [])]
     if toggle in ("NVH_EMIT_ALWAYS", "NVH_NO_EMIT", "NVH_NO_EMIT8", "NVH_NO_SLAB"):
         children.append((["test_full_depth.py"], env, []))  # (a second child beside the first)
+    if toggle in ("NVH_FPW=1", "NVH_FPW=4"):
+        children.append((["test_full_depth.py"], env, []))  # (three children beside this process: four with the GPU open)
+        children.append((["test_frame_groups.py"], env, []))
     run_children(children, timeout=900)
 
 

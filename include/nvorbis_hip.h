@@ -284,6 +284,17 @@ int nvh_stream_synth_end(nvh_stream *s, int64_t *written);
 #define NVH_PCM_S16 1
 int nvh_stream_synth_pcm(nvh_stream *s, int format, void *pcm_host, void *d_pcm, int64_t capacity, int64_t *written);
 int nvh_stream_synth_begin_pcm(nvh_stream *s, int format, void *pcm_host, int64_t capacity, int64_t *expected);
+/* Planar forms of nvh_stream_synth_pcm / nvh_stream_synth_begin_pcm / nvh_batch_synth_pcm: channel c's samples go to
+ * base + c * plane_stride (in samples of the format); plane_stride >= the batch's samples per channel; *written and
+ * *expected count samples PER CHANNEL.  Nothing outside [c*plane_stride, c*plane_stride + written) is written.  The emitting
+ * kernels' _planar twins write the planes themselves (a device base aligned to its sample size; the vector stores run where the
+ * base is 16-byte aligned and plane_stride a multiple of 4).  A host destination is read back as one 2-D copy (one plain copy
+ * when plane_stride equals the batch's length); pinned memory takes it without a bounce.  nvh_stream_synth_end retires planar
+ * flights too; planar and interleaved batches of one stream may alternate.  NVH_ERR_ARGUMENT: an unknown format, both
+ * destinations or neither (with PCM to write), plane_stride too small, a misaligned device base, batches outstanding.
+ * No counterpart in the reference (libvorbis' ov_read_float hands out planes). */
+int nvh_stream_synth_planar(nvh_stream *s, int format, void *pcm_host, void *d_pcm, int64_t plane_stride, int64_t *written);
+int nvh_stream_synth_begin_planar(nvh_stream *s, int format, void *pcm_host, int64_t plane_stride, int64_t *expected);
 /* After nvh_stream_synth returned an error code together with *written > 0 (GPU-parse mode: packets of the batch made
  * the parser fail -- with the codes nvh_stream_push_packet returns for them in host-parse mode -- and the batch was
  * parsed again on the host without them): every such packet in stream order, codes[i] and samples_before[i] = the
@@ -317,6 +328,8 @@ int nvh_stream_kernels(const nvh_stream *s, char *buf, int cap);
 int nvh_batch_synth(nvh_batch *b, float *d_pcm, int64_t capacity);
 /* The same in an output format (NVH_PCM_*; see nvh_stream_synth_pcm). */
 int nvh_batch_synth_pcm(nvh_batch *b, int format, void *d_pcm, int64_t capacity);
+/* ... and channel-planar (see nvh_stream_synth_planar). */
+int nvh_batch_synth_planar(nvh_batch *b, int format, void *d_pcm, int64_t plane_stride);
 /* Time `iters` repetitions with hipEvents on the launch stream: total milliseconds for the whole
  * pipeline, and per timing slot (spectrum: residue | couple+floor, or fused in slot 1; imdct+window; overlap+emit;
  * see nvh_batch_kernels).  A slot brackets its launches with event records, which costs ~2 us per slot. */

@@ -41,6 +41,7 @@ def gather_pcm(local, nfiles, rank, world, dist=None, device="cpu", to_host=True
     link to the root, so the root receives from all of them at once; a ring collective would be the wrong shape)."""
     # (a process group of one rank still goes through the backend: the counts' all_gather and the barrier are then the whole
     # exchange -- tests/test_multi_rank_gpu.py initialises RCCL that way on a one-GPU box)
+    _refuse_planar(local)
     import_torch = dist is not None
     if not import_torch:
         vals = [local.get(i) for i in range(nfiles)]
@@ -110,6 +111,7 @@ def gather_pcm_native(local, nfiles, comm, root=0, flags=0):
     `root`.  `local`: {file index -> float32 torch tensor on this process's GPU}.  Returns, on the root, a list of nfiles
     device tensors (views of the receive buffer, files that produced nothing: empty), None elsewhere."""
     import torch
+    _refuse_planar(local)
     mine = [0] * nfiles
     for i, a in local.items():
         mine[i] = int(a.numel())
@@ -144,6 +146,13 @@ def _to_numpy(v):
     return v.detach().cpu().numpy()
 
 
+def _refuse_planar(local):
+    """The gathers move interleaved PCM: a (channels, T) view from decode_files_to_device(layout="planar") is refused."""
+    for a in local.values():
+        if a is not None and getattr(a, "ndim", 1) != 1:
+            raise ValueError("the PCM gathers take interleaved (1-D) PCM, not the planar layout's (channels, T) views")
+
+
 def _flat_payload(parts, torch, dev):
     """One contiguous tensor holding `parts` back to back; no copy when they already are (slices of one arena)."""
     parts = [p for p in parts if p.numel() > 0]
@@ -166,12 +175,15 @@ def _flat_payload(parts, torch, dev):
     return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
-def transcode(files, decode_fn=None, rank=0, world=1, dist=None, device="cpu", gpu=0, workers=16, to_host=True):
+def transcode(files, decode_fn=None, rank=0, world=1, dist=None, device="cpu", gpu=0, workers=16, to_host=True, layout="interleaved"):
     """Decode `files` (list of bytes) file-parallel; rank 0 returns the list of PCM arrays in file order.
 
     decode_fn(bytes) -> float32 numpy PCM decodes one file; None = this package's GPU path with a pool of `workers`
     host threads on HIP device `gpu`, every file's PCM written by the synthesis kernels straight into one device arena
-    (decode_files_to_device) and gathered from there.  Gathered PCM is byte-identical to a single-rank run."""
+    (decode_files_to_device) and gathered from there.  Gathered PCM is byte-identical to a single-rank run.  Interleaved only:
+    layout="planar" raises ValueError."""
+    if layout != "interleaved":
+        raise ValueError("transcode gathers interleaved PCM only (layout %r)" % (layout,))
     shards = lpt_shards([len(f) for f in files], world)
     mine = shards[rank]
     if decode_fn is None:
@@ -525,9 +537,14 @@ def _index_pass(files, workers, full_index=False):
     return shape, totals, chans, errors
 
 
-def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_parse=False, keep_contexts=False, timings=None, tune_process=False):
+def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_parse=False, keep_contexts=False, timings=None, tune_process=False,
+                           layout="interleaved"):
     """Decode .ogg byte strings on ONE GPU into ONE device arena: returns (arena, views) with views[i] the interleaved
     float32 PCM of files[i] as a slice of `arena` (torch tensors on cuda:<device>), files back to back in list order.
+
+    layout="planar": views[i] has shape (C_i, T_i), channel-planar, written so by the synthesis kernels' _planar twins.  A
+    file's slot holds its C_i planes with the plane stride padded to a multiple of 4 samples (so that the kernels' vector stores
+    run): views[i] is then a STRIDED view of the arena (strides (S_i, 1), S_i >= T_i); .contiguous() makes a packed copy.
 
     Two passes over the worker pool: a geometry-only index of every stream (nvh_stream_index_packets: packet type, mode
     number, window flags -- how many samples the serial decoder emits), which sizes the arena; then the decode, whose
@@ -536,6 +553,7 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
     import torch
 
     from .reader import Context, Stream, demux_ogg_array, index_ogg_array
+    planar = _layout_planar(layout)
     n = len(files)
     full_index = bool(os.environ.get("NVH_CORPUS_FULL_INDEX"))  # A/B aid: the round-5 index (checksums + a copy of every packet)
 
@@ -575,8 +593,11 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
                     c.close()
         raise RuntimeError("index failed for files %s: %r" % ([i for i, _ in errors], errors[0][1]))
     t_index = time.perf_counter()
+    # planar: per file C planes of S = T rounded up to whole groups of four samples
+    per_ch = [int(totals[i]) // max(int(chans[i]), 1) for i in range(n)]
+    strides = [(t + 3) & ~3 for t in per_ch]
     offs = np.zeros(n + 1, np.int64)
-    offs[1:] = np.cumsum(totals)
+    offs[1:] = np.cumsum([int(chans[i]) * strides[i] for i in range(n)] if planar else totals)
     total = int(offs[-1])
     if arena_box[0] is not None and total >= 1 and total <= int(arena_box[0].numel()) <= total + max(total // 50, 1 << 20):
         # allocated during the index pass from an upper bound (two maximal blocks per file beyond its last granule position): taken
@@ -617,6 +638,12 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
 
             def sink(s):
                 ts = time.perf_counter()
+                if planar:  # pos[0]: samples per channel written so far; plane c at offs[i] + c * strides[i]
+                    if s.pending()[1] > per_ch[i] - pos[0]:
+                        raise RuntimeError("file %d produces more than the %d samples per channel its index says" % (i, per_ch[i]))
+                    pos[0] += s.synth_device(base + 4 * (int(offs[i]) + pos[0]), 0, plane_stride=strides[i])
+                    in_sink[0] += time.perf_counter() - ts
+                    return
                 room = int(offs[i + 1]) - pos[0]
                 need = s.pending()[1] * s.channels
                 if need > room:
@@ -624,8 +651,12 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
                 pos[0] += s.synth_device(base + 4 * pos[0], room)
                 in_sink[0] += time.perf_counter() - ts
 
+            if planar:
+                pos[0] = 0
             _decode_file_packets(st, pa, batch_frames, sink)
-            if pos[0] != int(offs[i + 1]):
+            if planar and pos[0] != per_ch[i]:
+                raise RuntimeError("file %d produced %d samples per channel, its index says %d" % (i, pos[0], per_ch[i]))
+            if not planar and pos[0] != int(offs[i + 1]):
                 raise RuntimeError("file %d produced %d floats, its index says %d" % (i, pos[0] - int(offs[i]), totals[i]))
         finally:
             t2 = time.perf_counter()
@@ -654,7 +685,10 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
         sys.stderr.write("decode_files_to_device: waited %.3f s for the warmed contexts; summed over the workers: stream open %.3f s, "
                          "push (+ upload and parse on the GPU in GPU-parse mode) %.3f s, synthesis %.3f s, close %.3f s\n" % (
                              t_warm - t_alloc, phase["open"], phase["push"], phase["synth"], phase["close"]))
-    views = [arena[int(offs[i]):int(offs[i + 1])] for i in range(n)]
+    if planar:
+        views = [arena[int(offs[i]):int(offs[i + 1])].view(int(chans[i]), strides[i])[:, :per_ch[i]] for i in range(n)]
+    else:
+        views = [arena[int(offs[i]):int(offs[i + 1])] for i in range(n)]
     if redo:
         # A page the index took at its word failed its checksum: the reference's reader drops it and resynchronises, the file's
         # packet list -- and with it its length -- is another.  Such a file gets a tensor of its own (views[i] is then not a slice
@@ -665,10 +699,13 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
                 pa = demux_ogg_array(files[i])
                 st = Stream(None, pa[0], pa[1], pa[2])
                 try:
-                    tot = int(st.index_total(pa, 3)) * st.channels
+                    per = int(st.index_total(pa, 3))
+                    nch = st.channels
+                    tot = per * nch
                 finally:
                     st.close()
-                own = torch.empty(max(tot, 1), dtype=torch.float32, device="cuda:%d" % device)
+                stride = (per + 3) & ~3
+                own = torch.empty(max(nch * stride if planar else tot, 1), dtype=torch.float32, device="cuda:%d" % device)
                 torch.cuda.synchronize(device)
                 st = Stream(ctx, pa[0], pa[1], pa[2])
                 try:
@@ -680,20 +717,29 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
                     pos = [0]
 
                     def sink(s_):
-                        pos[0] += s_.synth_device(own.data_ptr() + 4 * pos[0], tot - pos[0])
+                        if planar:
+                            pos[0] += s_.synth_device(own.data_ptr() + 4 * pos[0], 0, plane_stride=stride)
+                        else:
+                            pos[0] += s_.synth_device(own.data_ptr() + 4 * pos[0], tot - pos[0])
 
                     _decode_file_packets(st, pa, batch_frames, sink)
-                    if pos[0] != tot:
-                        raise RuntimeError("file %d produced %d floats, its checked index says %d" % (i, pos[0], tot))
+                    if pos[0] != (per if planar else tot):
+                        raise RuntimeError("file %d produced %d samples, its checked index says %d" % (i, pos[0], per if planar else tot))
                 finally:
                     st.close()
                 ctx.synchronize()
-                views[i] = own[:tot]
+                views[i] = own[:nch * stride].view(nch, stride)[:, :per] if planar else own[:tot]
         finally:
             ctx.close()
         if timings is not None:
             timings["files_reindexed"] = sorted(redo)
     return arena, views
+
+
+def _layout_planar(layout):
+    if layout not in ("interleaved", "planar"):
+        raise ValueError("layout must be 'interleaved' or 'planar', not %r" % (layout,))
+    return layout == "planar"
 
 
 def decode_files_threaded(files, device=0, workers=16, batch_frames=4096, gpu_parse=False):

@@ -586,10 +586,12 @@ k_couple_floor(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, int* __r
 // Parallel form: valid when no overlap region reaches into a tail (FrameBatch::sequential_ola == false),
 // i.e. every tail read here is an untouched windowed block.  One workgroup per frame.
 // (PCM: float, or int16_t for the _s16 twin -- kernels_common.h: pcm_s16_value -- here and in every emitting kernel below)
-template <typename PCM>
+// PLANAR: the channel-planar twins -- sample time t of channel c at pcm + c * plane_stride + t; the per-sample index runs plane-major
+// (o -> channel o / emit_count, time o % emit_count), so consecutive lanes write consecutive addresses of one plane.
+template <typename PCM, bool PLANAR = false>
 __device__ __forceinline__ void ola_emit_body(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work,
                                               const float* __restrict__ carry, PCM* __restrict__ pcm, int clip,
-                                              int* __restrict__ clipped_flag) {
+                                              int* __restrict__ clipped_flag, long long plane_stride = 0) {
   const int f = blockIdx.x;
   const NvhFrame fr = Bt.frames[f];
   const int ch = S.channels;
@@ -598,10 +600,11 @@ __device__ __forceinline__ void ola_emit_body(NvhDevSetup S, NvhDevBatch Bt, con
   const float* cur = work + (long long)f * ch * S.block1;
   const float* prev = nullptr;
   if (fr.ov_len > 0) prev = (fr.ov_frame == -2) ? carry : (fr.ov_frame >= 0 ? work + (long long)fr.ov_frame * ch * S.block1 : nullptr);
-  PCM* out = pcm + fr.out_pos * ch;
+  PCM* out = pcm + fr.out_pos * (PLANAR ? 1 : ch);
   int clipped = 0;
   for (int o = threadIdx.x; o < total; o += NVH_THREADS) {
     int t = o / ch, c = o - t * ch;
+    if constexpr (PLANAR) c = o / fr.emit_count, t = o - c * fr.emit_count;
     int idx = fr.emit_start + t;
     float v;
     if (fr.n == 0) {
@@ -612,7 +615,8 @@ __device__ __forceinline__ void ola_emit_body(NvhDevSetup S, NvhDevBatch Bt, con
       if (prev && j >= 0 && j < fr.ov_len) v = v + prev[(long long)c * S.block1 + fr.ov_src + j];  // OverlapBuffers
     }
     if (clip) v = clip_value(v, &clipped);
-    pcm_store1(out + o, v);
+    if constexpr (PLANAR) pcm_store1(out + c * plane_stride + t, v);
+    else pcm_store1(out + o, v);
   }
   report_clipped(clipped, clipped_flag);
 }
@@ -626,14 +630,24 @@ k_ola_emit_s16(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, co
                int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
   ola_emit_body<int16_t>(S, Bt, work, carry, pcm, clip, clipped_flag);
 }
+extern "C" __global__ void __launch_bounds__(NVH_THREADS)
+k_ola_emit_planar(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
+                  float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, long long plane_stride) {
+  ola_emit_body<float, true>(S, Bt, work, carry, pcm, clip, clipped_flag, plane_stride);
+}
+extern "C" __global__ void __launch_bounds__(NVH_THREADS)
+k_ola_emit_s16_planar(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
+                      int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, long long plane_stride) {
+  ola_emit_body<int16_t, true>(S, Bt, work, carry, pcm, clip, clipped_flag, plane_stride);
+}
 
 // Sequential form: one workgroup walks the frames in order and performs the adds in place, exactly
 // like the reference's ping-pong buffers (needed only for streams whose window flags disagree with
 // their neighbours so that an overlap reaches a block's own tail).
-template <typename PCM>
+template <typename PCM, bool PLANAR = false>  // (PLANAR: as ola_emit_body)
 __device__ __forceinline__ void ola_emit_seq_body(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work,
                                                   const float* __restrict__ carry, PCM* __restrict__ pcm, int clip,
-                                                  int* __restrict__ clipped_flag) {
+                                                  int* __restrict__ clipped_flag, long long plane_stride = 0) {
   const int ch = S.channels;
   int clipped = 0;
   for (int f = 0; f < Bt.nframes; ++f) {
@@ -649,13 +663,15 @@ __device__ __forceinline__ void ola_emit_seq_body(NvhDevSetup S, NvhDevBatch Bt,
       }
     }
     __syncthreads();
-    PCM* out = pcm + fr.out_pos * ch;
+    PCM* out = pcm + fr.out_pos * (PLANAR ? 1 : ch);
     const int total = fr.emit_count * ch;
     for (int o = threadIdx.x; o < total; o += NVH_THREADS) {
       int t = o / ch, c = o - t * ch;
+      if constexpr (PLANAR) c = o / fr.emit_count, t = o - c * fr.emit_count;
       float v = (fr.n == 0) ? prev[(long long)c * S.block1 + fr.ov_src + t] : cur[(long long)c * S.block1 + fr.emit_start + t];
       if (clip) v = clip_value(v, &clipped);
-      pcm_store1(out + o, v);
+      if constexpr (PLANAR) pcm_store1(out + c * plane_stride + t, v);
+      else pcm_store1(out + o, v);
     }
     __syncthreads();
   }
@@ -670,6 +686,16 @@ extern "C" __global__ void __launch_bounds__(NVH_THREADS)
 k_ola_emit_seq_s16(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry,
                    int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
   ola_emit_seq_body<int16_t>(S, Bt, work, carry, pcm, clip, clipped_flag);
+}
+extern "C" __global__ void __launch_bounds__(NVH_THREADS)
+k_ola_emit_seq_planar(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry,
+                      float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, long long plane_stride) {
+  ola_emit_seq_body<float, true>(S, Bt, work, carry, pcm, clip, clipped_flag, plane_stride);
+}
+extern "C" __global__ void __launch_bounds__(NVH_THREADS)
+k_ola_emit_seq_s16_planar(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry,
+                          int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, long long plane_stride) {
+  ola_emit_seq_body<int16_t, true>(S, Bt, work, carry, pcm, clip, clipped_flag, plane_stride);
 }
 
 
@@ -853,6 +879,71 @@ __device__ __forceinline__ int ola_sym_lds(const NvhDevSetup& S, const NvhFrame&
   return clipped;
 }
 
+// The channel-planar forms of ola_vec and ola_sym (k_ola_compact's _planar twins): the same arithmetic, one lane per (channel,
+// group of four sample times), plane-major -- consecutive lanes take consecutive groups of one plane, and every vector leaves
+// as one store (16 bytes of float, 8 of int16_t) to its channel's plane: no interleave, no LDS.  `out` points at the frame's
+// first sample of plane 0, 16-byte aligned with the plane stride a multiple of four (nvh_launch.hip).
+template <typename PCM>
+__device__ __forceinline__ int ola_vec_planar(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev,
+                                              bool prev_full, const float* __restrict__ w, const float* __restrict__ wp, PCM* out,
+                                              long long plane_stride, int ch, int clip, int tid, int threads) {
+  int clipped = 0;
+  const int groups = fr.emit_count >> 2;
+  for (int task = tid; task < groups * ch; task += threads) {
+    const int c = task / groups, g = task - c * groups;
+    const int idx0 = fr.emit_start + 4 * g;
+    const int j0 = idx0 - fr.start;
+    const bool ov = prev && j0 >= 0 && j0 < fr.ov_len;
+    float4 v = compact_value4(cur + (long long)c * S.block1, w, fr.n, (fr.exec_mask >> c) & 1, idx0);
+    if (ov) {
+      const float* pp = prev + (long long)c * S.block1;
+      const float4 t4 = prev_full ? *reinterpret_cast<const float4*>(pp + fr.ov_src + j0)
+                                  : compact_value4(pp, wp, fr.ov_n, (fr.ov_exec_mask >> c) & 1, fr.ov_src + j0);
+      v.x = v.x + t4.x; v.y = v.y + t4.y; v.z = v.z + t4.z; v.w = v.w + t4.w;
+    }
+    if (clip) {
+      v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
+      v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
+    }
+    pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out + (long long)c * plane_stride) + g, v.x, v.y, v.z, v.w);
+  }
+  return clipped;
+}
+template <typename PCM>
+__device__ __forceinline__ int ola_sym_planar(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev,
+                                              const float* __restrict__ w, const float* __restrict__ wp, PCM* out,
+                                              long long plane_stride, int ch, int clip, int tid, int threads) {
+  int clipped = 0;
+  const int n = fr.n, n2 = n >> 1;
+  const int groups = n >> 4;
+  for (int task = tid; task < groups * ch; task += threads) {
+    const int c = task / groups, g = task - c * groups;
+    const int i0 = 4 * g;
+    const float4 wf = *reinterpret_cast<const float4*>(w + i0);
+    const float4 wm = *reinterpret_cast<const float4*>(w + (n2 - 4 - i0));
+    const float4 pf = *reinterpret_cast<const float4*>(wp + (n2 + i0));
+    const float4 pm = *reinterpret_cast<const float4*>(wp + (n - 4 - i0));
+    const float4 a = *reinterpret_cast<const float4*>(cur + (long long)c * S.block1 + i0);
+    const float4 b = *reinterpret_cast<const float4*>(prev + (long long)c * S.block1 + n2 + i0);
+    float4 v = make_float4(a.x * wf.x, a.y * wf.y, a.z * wf.z, a.w * wf.w);
+    const float4 t = make_float4(b.x * pf.x, b.y * pf.y, b.z * pf.z, b.w * pf.w);
+    v.x = v.x + t.x; v.y = v.y + t.y; v.z = v.z + t.z; v.w = v.w + t.w;
+    float4 u = make_float4(-a.w * wm.x, -a.z * wm.y, -a.y * wm.z, -a.x * wm.w);
+    const float4 r = make_float4(b.w * pm.x, b.z * pm.y, b.y * pm.z, b.x * pm.w);
+    u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
+    if (clip) {
+      v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
+      v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
+      u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
+      u.z = clip_value(u.z, &clipped); u.w = clip_value(u.w, &clipped);
+    }
+    pcm4_t<PCM>* p = reinterpret_cast<pcm4_t<PCM>*>(out + (long long)c * plane_stride);
+    pcm_store4(p + g, v.x, v.y, v.z, v.w);                   // sample times i0 .. i0 + 3
+    pcm_store4(p + ((n >> 3) - 1 - g), u.x, u.y, u.z, u.w);  // sample times n/2 - 4 - i0 .. n/2 - 1 - i0
+  }
+  return clipped;
+}
+
 // A frame may be shared by gridDim.y workgroups (large frames: six channels at n = 4096 are 48 KB of PCM, and 128 lanes
 // per frame leave the CUs with four wavefronts each): lane `OLA_TID` of `NVH_OLA_THREADS`.
 #define NVH_OLA_THREADS ((int)(blockDim.x * gridDim.y))
@@ -862,6 +953,8 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
               float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out, int last_decoded,
               int nosym, const int* __restrict__ list, int emitted) {
   typedef float PCM;
+  constexpr bool PLANAR = false;
+  constexpr long long plane_stride = 0;
 #include "ola_compact_body.inc"
 }
 extern "C" __global__ void __launch_bounds__(256)
@@ -869,6 +962,25 @@ k_ola_compact_s16(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work,
                   int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out, int last_decoded,
                   int nosym, const int* __restrict__ list, int emitted) {
   typedef int16_t PCM;
+  constexpr bool PLANAR = false;
+  constexpr long long plane_stride = 0;
+#include "ola_compact_body.inc"
+}
+// the channel-planar twins: plane_stride samples between the channels' planes
+extern "C" __global__ void __launch_bounds__(256)
+k_ola_compact_planar(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
+                     float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out, int last_decoded,
+                     int nosym, const int* __restrict__ list, int emitted, long long plane_stride) {
+  typedef float PCM;
+  constexpr bool PLANAR = true;
+#include "ola_compact_body.inc"
+}
+extern "C" __global__ void __launch_bounds__(256)
+k_ola_compact_s16_planar(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
+                         int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out,
+                         int last_decoded, int nosym, const int* __restrict__ list, int emitted, long long plane_stride) {
+  typedef int16_t PCM;
+  constexpr bool PLANAR = true;
 #include "ola_compact_body.inc"
 }
 

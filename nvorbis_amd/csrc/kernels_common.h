@@ -87,6 +87,9 @@ struct NvhSynthArgs {
   float* pcm;               // (the _s16 twins: int16_t samples)
   const float* windows;
   int clip;
+  int plane_stride;         // the _planar twins: samples between the channels' planes (time t of channel c at pcm + c * plane_stride + t).
+                            // (In the padding in front of clipped_flag, not at the end: a larger struct moves the implicit kernel
+                            // arguments behind it, which changes an s_load offset in every kernel that takes NvhSynthArgs.)
   int* clipped_flag;
   const float* carry;       // the carried tail this batch's first frame overlaps with (fully windowed), NVH_EMIT_SELF_CARRY
   float* carry_out;         // receives the last decoded block, fully windowed (NVH_EMIT_CARRY_OUT); nullptr: k_ola_compact writes it
@@ -162,6 +165,16 @@ __device__ __forceinline__ void pcm_store4x2(nvh_s16x4* p, const float (&v)[8]) 
 // plain (not streaming) store of four 16-bit samples: synth_emit8_direct's partial-line stores, which the L2 merges
 __device__ __forceinline__ void pcm_plain4(nvh_s16x4* p, float a, float b, float c, float d) {
   *reinterpret_cast<uint2*>(p) = make_uint2(pcm_s16_pair(a, b), pcm_s16_pair(c, d));
+}
+// ---- channel-planar PCM (the _planar twins: sample time t of channel c at pcm + c * plane_stride + out_pos + t).  The narrow
+// emission's lane computes four forward sample times i0 .. i0 + 3 (v) and four mirrored ones n/2 - 4 - i0 .. n/2 - 1 - i0 (u, already
+// in time order) of one channel: they leave as one vector each (16 bytes of float, 8 of int16_t) as soon as the channel is done.
+// `plane`: the frame's first sample in the channel's plane; g / gm: the two vectors' indices in units of four samples.
+template <typename PCM>
+__device__ __forceinline__ void pcm_store_plane(PCM* plane, long long g, long long gm, const float4& v, const float4& u) {
+  pcm4_t<PCM>* p = reinterpret_cast<pcm4_t<PCM>*>(plane);
+  pcm_store4(p + g, v.x, v.y, v.z, v.w);
+  pcm_store4(p + gm, u.x, u.y, u.z, u.w);
 }
 // ... and the streaming load of 16 bytes that exactly one lane reads exactly once (a neighbour frame's quarter)
 __device__ __forceinline__ float4 stream_load4(const float* p) {

@@ -691,13 +691,13 @@ __device__ __forceinline__ void synth_carry_out(const NvhSynthArgs& A, const flo
 // (k_ola_compact's prev_full case: no second window multiply, the tail in time order).  The frame's own first quarter A lies in
 // its channel's dead transform slice (synth_emit).  One workgroup per batch: out of line, so that the steady-state loop keeps
 // its registers.
-template <int NT, typename PCM = float>
+template <int NT, typename PCM = float, bool PLANAR = false>
 __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const float* spec, int n, int nch, unsigned window_off,
                                               unsigned out_pos, int tid, int cstride = 0) {
   const int half = n >> 1;
   if (cstride == 0) cstride = half;  // floats between the channels' first quarters
   const float* __restrict__ w = A.windows + window_off;
-  PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)out_pos * nch;
+  PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)out_pos * (PLANAR ? 1 : nch);
   int clipped = 0;
   for (int g = tid; g < (n >> 4); g += NT) {
     const int i0 = 4 * g;
@@ -721,14 +721,20 @@ __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const fl
           u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
           u.z = clip_value(u.z, &clipped); u.w = clip_value(u.w, &clipped);
         }
-        fwd[c] = v.x; fwd[2 + c] = v.y; fwd[4 + c] = v.z; fwd[6 + c] = v.w;
-        mir[c] = u.x; mir[2 + c] = u.y; mir[4 + c] = u.z; mir[6 + c] = u.w;
+        if constexpr (PLANAR) {  // channel-planar: the channel leaves at once (nothing is held for an interleave)
+          pcm_store_plane(out + (long long)c * A.plane_stride, g, (n >> 3) - 1 - g, v, u);
+        } else {
+          fwd[c] = v.x; fwd[2 + c] = v.y; fwd[4 + c] = v.z; fwd[6 + c] = v.w;
+            mir[c] = u.x; mir[2 + c] = u.y; mir[4 + c] = u.z; mir[6 + c] = u.w;
+        }
       }
     }
     // (a 64 x 2 transposition through LDS in front of these stores, so that every instruction writes whole lines the way the wide
     // kernel's emission does, was tried: 202 -> 167 M frames/s -- nine spilled registers and four more wavefront syncs cost more than
     // half-line streaming stores do)
-    if (nch == 2) {
+    if constexpr (PLANAR) {
+      // (stored per channel above)
+    } else if (nch == 2) {
       pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
       pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
       if constexpr (std::is_same<PCM, int16_t>::value) {  // four stereo sample times: one 16-byte store where aligned
@@ -760,7 +766,7 @@ __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const fl
 // registers into the channel's dead transform slice, and every lane of the workgroup then overlap-adds, clips and interleaves
 // one group of sample times of one overlap, straight into 16-byte vectors of PCM.
 // The frame's own plane is written only when k_ola_compact still needs it (not both overlaps emitted here).
-template <int NT, typename PCM = float>
+template <int NT, typename PCM = float, bool PLANAR = false>
 __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, float* spec, const uint32_t* s_chan, int n, int nch,
                                            unsigned frame, int sl, bool emit_self, bool emit_next, bool self_carry, bool carry_out,
                                            unsigned exec_mask, float* planes,
@@ -841,7 +847,7 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
   __syncthreads();  // drains the staging DMA (vmcnt(0) in front of the barrier): all four quarters of every channel are in LDS
   EM_T(17);
   if (carry_out) synth_carry_out<NT>(A, planes, n, nch, exec_mask, w_self, tid);  // (such a frame has no NEXT: its plane was written)
-  if (self_carry) synth_self_carry<NT, PCM>(A, spec, n, nch, w_self, out_self, tid);    // the batch's first frame
+  if (self_carry) synth_self_carry<NT, PCM, PLANAR>(A, spec, n, nch, w_self, out_self, tid);    // the batch's first frame
   // ---- overlap-add + interleave + clip, every lane of the workgroup: lane task = (overlap, group of four compact indices i0);
   // it produces sample times i0 .. i0 + 3 and n/2 - 4 - i0 .. n/2 - 1 - i0 of every channel (kernels.hip: ola_sym) ----
   int clipped = 0;
@@ -888,18 +894,24 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
           u.z = clip_value(u.z, &clipped); u.w = clip_value(u.w, &clipped);
         }
 #endif
-        fwd[c] = v.x; fwd[2 + c] = v.y; fwd[4 + c] = v.z; fwd[6 + c] = v.w;
-        mir[c] = u.x; mir[2 + c] = u.y; mir[4 + c] = u.z; mir[6 + c] = u.w;
+        if constexpr (PLANAR) {  // channel-planar: the channel leaves at once (nothing is held for an interleave)
+          pcm_store_plane(reinterpret_cast<PCM*>(A.pcm) + (long long)(nx ? out_next : out_self) + (long long)c * A.plane_stride, g, (n >> 3) - 1 - g, v, u);
+        } else {
+          fwd[c] = v.x; fwd[2 + c] = v.y; fwd[4 + c] = v.z; fwd[6 + c] = v.w;
+            mir[c] = u.x; mir[2 + c] = u.y; mir[4 + c] = u.z; mir[6 + c] = u.w;
+        }
       }
     }
-    PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)(nx ? out_next : out_self) * nch;
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)(nx ? out_next : out_self) * (PLANAR ? 1 : nch);
 #ifdef NVH_ABL_PCM_SMALL
     out = reinterpret_cast<PCM*>(A.pcm) + (long long)((nx ? out_next : out_self) & 0x7FFF) * nch;  // (ablation build: every frame's PCM into the same 256 KB)
 #endif
 #ifdef NVH_ABL_NO_PCM_STORE
     if (fwd[0] != 1.2345e-30f) return;  // (ablation build: the arithmetic kept alive, the stores left out)
 #endif
-    if (nch == 2) {
+    if constexpr (PLANAR) {
+      // (stored per channel above)
+    } else if (nch == 2) {
       pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
       pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
       if constexpr (std::is_same<PCM, int16_t>::value) {  // four stereo sample times: one 16-byte store where aligned
@@ -946,7 +958,7 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
 // and puts its eight results into channel-planar LDS rows; behind a barrier the rows leave as 16-byte vectors of interleaved,
 // clipped PCM.  The overlap-add's memory phase then runs inside the synthesis kernel, next to other workgroups' arithmetic,
 // instead of as a launch of its own (k_ola_compact: 42 us per 2048 six-channel frames), and half the planes are read from L2.
-template <int NT, typename PCM = float>
+template <int NT, typename PCM = float, bool PLANAR = false>
 __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run, int n, int nch, unsigned frame, unsigned ef,
                                             unsigned exec_mask, int tid) {
   // One round per overlap: the rows of ALL groups fit the dead slices (2 x nch x n/4 floats: 48 KB for six channels at 4096),
@@ -966,7 +978,7 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
     const float* prev = from_carry ? A.carry : A.work + (long long)(frame + ov - 1) * nch * A.block1;  // the earlier block
     const float* __restrict__ w = A.windows + fr->window_off;
     const float* __restrict__ wp = A.windows + fr->ov_window_off;
-    PCM* out = reinterpret_cast<PCM*>(A.pcm) + fr->out_pos * nch;
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + fr->out_pos * (PLANAR ? 1 : nch);
     float* sF = s_run;
     float* sM = s_run + nch * RUN;
     for (int t0 = tid; t0 < total; t0 += K * NT) {
@@ -1003,10 +1015,24 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
           const float4 r = make_float4(b[k].w * pm[k].x, b[k].z * pm[k].y, b[k].y * pm[k].z, b[k].x * pm[k].w);
           u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
         }
-        *reinterpret_cast<float4*>(sF + cc[k] * RUN + 4 * gl[k]) = v;                 // sample times 4 gl ..
-        *reinterpret_cast<float4*>(sM + cc[k] * RUN + 4 * (groups - 1 - gl[k])) = u;  // sample times n/2 - 4 - 4 gl ..
+        if constexpr (PLANAR) {
+          // channel-planar: straight from the lane to the channel's plane (consecutive lanes, consecutive groups of one plane)
+          if (A.clip) {
+            v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
+            v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
+            u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
+            u.z = clip_value(u.z, &clipped); u.w = clip_value(u.w, &clipped);
+          }
+          pcm4_t<PCM>* pc = reinterpret_cast<pcm4_t<PCM>*>(out + (long long)cc[k] * A.plane_stride);
+          pcm_store4(pc + gl[k], v.x, v.y, v.z, v.w);
+          pcm_store4(pc + ((n >> 3) - 1 - gl[k]), u.x, u.y, u.z, u.w);
+        } else {
+          *reinterpret_cast<float4*>(sF + cc[k] * RUN + 4 * gl[k]) = v;                 // sample times 4 gl ..
+          *reinterpret_cast<float4*>(sM + cc[k] * RUN + 4 * (groups - 1 - gl[k])) = u;  // sample times n/2 - 4 - 4 gl ..
+        }
       }
     }
+    if constexpr (PLANAR) continue;  // (no LDS rows, no barriers: every value has left already)
     __syncthreads();
     // the forward rows hold sample times [0, n/4), the mirrored rows [n/4, n/2): together the frame's n/2 samples in time order
     const int nvec = total;  // 16-byte vectors per half: n/4 sample times x nch channels / 4
@@ -1084,7 +1110,7 @@ __device__ __forceinline__ void imdct_keep_quarters(const float* X, float* slice
   }
 }
 
-template <int NT, int CH, typename PCM = float>
+template <int NT, int CH, typename PCM = float, bool PLANAR = false>
 __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float* smem, int n, unsigned frame, int tid) {
   const int half = n >> 1, groups = n >> 4, slice = half + (n >> 4);
   const NvhFrame* fs = A.frames + frame;
@@ -1124,6 +1150,18 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
       }
       fwd[0 * CH + c] = v.x; fwd[1 * CH + c] = v.y; fwd[2 * CH + c] = v.z; fwd[3 * CH + c] = v.w;
       mir[0 * CH + c] = u.x; mir[1 * CH + c] = u.y; mir[2 * CH + c] = u.z; mir[3 * CH + c] = u.w;
+    }
+    if constexpr (PLANAR) {
+      // channel-planar: per channel one vector of the four forward and one of the four mirrored sample times; the 64 lanes of a
+      // store instruction (consecutive groups) write consecutive vectors of one plane -- whole lines without the transposition
+      PCM* base = reinterpret_cast<PCM*>(A.pcm) + (nx ? o_next : o_self);
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        pcm4_t<PCM>* p = reinterpret_cast<pcm4_t<PCM>*>(base + (long long)c * A.plane_stride);
+        pcm_store4(p + g, fwd[c], fwd[CH + c], fwd[2 * CH + c], fwd[3 * CH + c]);
+        pcm_store4(p + ((n >> 3) - 1 - g), mir[c], mir[CH + c], mir[2 * CH + c], mir[3 * CH + c]);
+      }
+      return;
     }
     pcm4_t<PCM>* out = reinterpret_cast<pcm4_t<PCM>*>(reinterpret_cast<PCM*>(A.pcm) + (nx ? o_next : o_self) * CH);
     pcm4_t<PCM>* of = out + (long long)g * CH;
@@ -1349,7 +1387,7 @@ __device__ __forceinline__ void synth_frame_spectrum(const NvhSynthArgs& A, cons
 // MODE (k_synth only): 0 = synthesis alone, 1 = + the carried tail written by the last decoded block's workgroup, 2 = + paired
 // emission.  Three instantiations, so that the launches that never emit keep the registers of the kernel that cannot (62 instead
 // of 64 VGPRs at the 64-VGPR cap: 24.4 against 25.1 us for 4096 frames).
-template <int NT, int MAXCH, int MODE = 0, bool GENERAL = false, typename PCM = float>
+template <int NT, int MAXCH, int MODE = 0, bool GENERAL = false, typename PCM = float, bool PLANAR = false>
 __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NVH_DBG_PARAMS) {
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
 #ifdef NVH_ABL_EMPTY0
@@ -1467,10 +1505,10 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
   if (MAXCH <= 2 && MODE >= 2 && (emit_self || emit_next)) {
     if constexpr (MAXCH <= 2 && MODE >= 2)
 #ifdef NVH_DEBUG
-      synth_emit<NT, PCM>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
+      synth_emit<NT, PCM, PLANAR>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
                      Aa, Bb, Cc, TW, tid, dbg ? dbg + (long long)f * 24 : nullptr);
 #else
-      synth_emit<NT, PCM>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
+      synth_emit<NT, PCM, PLANAR>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
                      Aa, Bb, Cc, TW, tid);
 #endif
   } else
@@ -1553,21 +1591,21 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
     if (direct8) {
       __syncthreads();  // every channel's own quarters are in its slice
       switch (nch) {
-        case 1: synth_emit8_direct<NT, 1, PCM>(A, smem, n, frame, tid); break;  // (mono / stereo land here with blocks beyond 2048)
-        case 2: synth_emit8_direct<NT, 2, PCM>(A, smem, n, frame, tid); break;
-        case 3: synth_emit8_direct<NT, 3, PCM>(A, smem, n, frame, tid); break;
-        case 4: synth_emit8_direct<NT, 4, PCM>(A, smem, n, frame, tid); break;
-        case 5: synth_emit8_direct<NT, 5, PCM>(A, smem, n, frame, tid); break;
-        case 6: synth_emit8_direct<NT, 6, PCM>(A, smem, n, frame, tid); break;
-        case 7: synth_emit8_direct<NT, 7, PCM>(A, smem, n, frame, tid); break;
-        case 8: synth_emit8_direct<NT, 8, PCM>(A, smem, n, frame, tid); break;
+        case 1: synth_emit8_direct<NT, 1, PCM, PLANAR>(A, smem, n, frame, tid); break;  // (mono / stereo land here with blocks beyond 2048)
+        case 2: synth_emit8_direct<NT, 2, PCM, PLANAR>(A, smem, n, frame, tid); break;
+        case 3: synth_emit8_direct<NT, 3, PCM, PLANAR>(A, smem, n, frame, tid); break;
+        case 4: synth_emit8_direct<NT, 4, PCM, PLANAR>(A, smem, n, frame, tid); break;
+        case 5: synth_emit8_direct<NT, 5, PCM, PLANAR>(A, smem, n, frame, tid); break;
+        case 6: synth_emit8_direct<NT, 6, PCM, PLANAR>(A, smem, n, frame, tid); break;
+        case 7: synth_emit8_direct<NT, 7, PCM, PLANAR>(A, smem, n, frame, tid); break;
+        case 8: synth_emit8_direct<NT, 8, PCM, PLANAR>(A, smem, n, frame, tid); break;
         default: __builtin_trap();
       }
     } else
     if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT | NVH_EMIT_CARRY_OUT)) {
       __syncthreads();
       if ((ef & NVH_EMIT_CARRY_OUT) && A.carry_out) synth_carry_out8<NT>(A, planes, n, nch, exec_mask, A.frames[frame].window_off, tid);
-      if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT)) synth_emit8<NT, PCM>(A, smem, n, nch, frame, ef, exec_mask, tid);
+      if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT)) synth_emit8<NT, PCM, PLANAR>(A, smem, n, nch, frame, ef, exec_mask, tid);
     }
   }
   if constexpr (MAXCH > 2 && MODE < 2) {
@@ -1617,7 +1655,7 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
 // (Tried and removed, round 6: two frames per workgroup of EIGHT wavefronts, every 256 threads walking their own frame side by side --
 // k_synth's per-frame parallelism, 4 workgroups = 32 wavefronts per CU at 64 VGPRs: 171 M frames/s over three streams against 202 M for
 // this form, 124 M against 123 M on one.)
-template <int NT, int FPW, typename PCM = float>
+template <int NT, int FPW, typename PCM = float, bool PLANAR = false>
 __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* smem NVH_DBG_PARAMS) {
   static_assert(NT / 64 >= 2 * FPW, "one wavefront per (frame, channel) in the transform");
   // (the wavefront's index through readfirstlane: what depends on it alone -- which frame and channel it transforms, where its
@@ -1922,7 +1960,7 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
     if (cout_k[k])  // the block that becomes the next batch's carried tail (its whole plane was written above)
       synth_carry_out<NT>(A, A.work + (long long)(fa + k) * nch * A.block1, nn[k], nch, (w0[k] >> 16) & 0xFFu, cwin[k], tid);
   if (self_carry)  // the batch's first frame
-    synth_self_carry<NT, PCM>(A, slice0, nn[0], nch, __builtin_amdgcn_readfirstlane(otab[0]), __builtin_amdgcn_readfirstlane(otab[2]), tid, slice_words);
+    synth_self_carry<NT, PCM, PLANAR>(A, slice0, nn[0], nch, __builtin_amdgcn_readfirstlane(otab[0]), __builtin_amdgcn_readfirstlane(otab[2]), tid, slice_words);
 
   // ---- overlap-add + interleave + clip: lane task = (overlap j, group of four compact indices i0); it produces sample times
   // i0 .. i0 + 3 and n/2 - 4 - i0 .. n/2 - 1 - i0 of every channel (kernels.hip: ola_sym) ----
@@ -1964,12 +2002,18 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
           u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
           u.z = clip_value(u.z, &clipped); u.w = clip_value(u.w, &clipped);
         }
-        fwd[c] = v.x; fwd[2 + c] = v.y; fwd[4 + c] = v.z; fwd[6 + c] = v.w;
-        mir[c] = u.x; mir[2 + c] = u.y; mir[4 + c] = u.z; mir[6 + c] = u.w;
+        if constexpr (PLANAR) {  // channel-planar: the channel leaves at once (nothing is held for an interleave)
+          pcm_store_plane(reinterpret_cast<PCM*>(A.pcm) + (long long)r0.z + (long long)c * A.plane_stride, g, (n >> 3) - 1 - g, v, u);
+        } else {
+          fwd[c] = v.x; fwd[2 + c] = v.y; fwd[4 + c] = v.z; fwd[6 + c] = v.w;
+            mir[c] = u.x; mir[2 + c] = u.y; mir[4 + c] = u.z; mir[6 + c] = u.w;
+        }
       }
     }
-    PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)r0.z * nch;
-    if (nch == 2) {
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)r0.z * (PLANAR ? 1 : nch);
+    if constexpr (PLANAR) {
+      // (stored per channel above)
+    } else if (nch == 2) {
       pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
       pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
       if constexpr (std::is_same<PCM, int16_t>::value) {  // four stereo sample times: one 16-byte store where aligned
@@ -2017,11 +2061,18 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
           v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
           v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
         }
-        o[c] = v.x; o[2 + c] = v.y; o[4 + c] = v.z; o[6 + c] = v.w;
+        if constexpr (PLANAR)
+          pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(reinterpret_cast<PCM*>(A.pcm) + ((long long)r0.y + (idx0 - (int)r1.w)) +
+                                                    (long long)c * A.plane_stride), v.x, v.y, v.z, v.w);
+        else {
+          o[c] = v.x; o[2 + c] = v.y; o[4 + c] = v.z; o[6 + c] = v.w;
+        }
       }
     }
-    PCM* out = reinterpret_cast<PCM*>(A.pcm) + ((long long)r0.y + (idx0 - (int)r1.w)) * nch;
-    if (nch == 2) {
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + ((long long)r0.y + (idx0 - (int)r1.w)) * (PLANAR ? 1 : nch);
+    if constexpr (PLANAR) {
+      // (stored per channel above)
+    } else if (nch == 2) {
       if constexpr (std::is_same<PCM, int16_t>::value) {
         pcm_store4x2(reinterpret_cast<pcm4_t<PCM>*>(out), o);
       } else {
@@ -2070,6 +2121,19 @@ k_synth_emit_s16(NvhSynthArgs A NVH_DBG_PARAMS) {
   synth_body<NVH_SYNTH_NT, 2, 2, false, int16_t>(A, smem NVH_DBG_ARGS);
 }
 
+// The channel-planar twins (A.plane_stride: sample time t of channel c at pcm + c * plane_stride + t; kernels_common.h,
+// pcm_store_planes), float and 16-bit.
+extern "C" __global__ void __launch_bounds__(NVH_SYNTH_NT) __attribute__((amdgpu_waves_per_eu(NVH_SYNTH_WPE)))
+k_synth_emit_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_body<NVH_SYNTH_NT, 2, 2, false, float, true>(A, smem NVH_DBG_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(NVH_SYNTH_NT) __attribute__((amdgpu_waves_per_eu(NVH_SYNTH_WPE)))
+k_synth_emit_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_body<NVH_SYNTH_NT, 2, 2, false, int16_t, true>(A, smem NVH_DBG_ARGS);
+}
+
 // mono / stereo streams some of whose frames need the general bin walk (never with paired emission)
 extern "C" __global__ void __launch_bounds__(SP_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_synth_g(NvhSynthArgs A NVH_DBG_PARAMS) {
@@ -2102,6 +2166,16 @@ k_synth8_emit_s16(NvhSynthArgs A NVH_DBG_PARAMS) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   synth_body<512, NVH_SLAB_MAX_CH, 2, false, int16_t>(A, smem NVH_DBG_ARGS);
 }
+extern "C" __global__ void __launch_bounds__(512)
+k_synth8_emit_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_body<512, NVH_SLAB_MAX_CH, 2, false, float, true>(A, smem NVH_DBG_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(512)
+k_synth8_emit_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_body<512, NVH_SLAB_MAX_CH, 2, false, int16_t, true>(A, smem NVH_DBG_ARGS);
+}
 
 // frame groups: two frames per workgroup (four wavefronts: one per (frame, channel)); LDS, not registers, decides the residency
 extern "C" __global__ void __launch_bounds__(256)
@@ -2126,4 +2200,24 @@ extern "C" __global__ void __launch_bounds__(512)
 k_synth_group4_s16(NvhSynthArgs A NVH_DBG_PARAMS) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   synth_group_body<512, 4, int16_t>(A, smem NVH_DBG_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(256)
+k_synth_group2_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_group_body<256, 2, float, true>(A, smem NVH_DBG_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(512)
+k_synth_group4_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_group_body<512, 4, float, true>(A, smem NVH_DBG_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(256)
+k_synth_group2_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_group_body<256, 2, int16_t, true>(A, smem NVH_DBG_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(512)
+k_synth_group4_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  synth_group_body<512, 4, int16_t, true>(A, smem NVH_DBG_ARGS);
 }

@@ -743,6 +743,141 @@ extern "C" int nvh_stream_synth_end(nvh_stream* s, int64_t* written) {
   });
 }
 
+// ---- channel-planar PCM (the _planar twins): channel c's samples at base + c * plane_stride, counts per channel ----
+// A host destination is staged on the device as [C, n4] planes (n4: the batch's samples per channel rounded up to whole groups of
+// four, so that the emission's vector stores run) and read back as one 2-D copy; one plain copy when the planes are contiguous.
+static int64_t planar_stage_stride(int64_t n) { return (n + 3) & ~(int64_t)3; }
+static int64_t planar_launch_stride(int64_t plane_stride) { return plane_stride > 0 ? plane_stride : 4; }  // (0 only with no samples)
+static bool planar_dest_ok(int format, const void* d_pcm) { return ((uintptr_t)d_pcm % pcm_sample_bytes(format)) == 0; }
+
+// `n` samples per channel of `ch` planes from device planes at stride `src_stride` to host planes at stride `dst_stride`
+static hipError_t planar_readback(void* dst, int64_t dst_stride, const void* src, int64_t src_stride, int64_t n, int ch, size_t sb,
+                                  hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (dst_stride == n && src_stride == n) return hipMemcpyAsync(dst, src, (size_t)n * (size_t)ch * sb, hipMemcpyDeviceToHost, st);
+  return hipMemcpy2DAsync(dst, (size_t)dst_stride * sb, src, (size_t)src_stride * sb, (size_t)n * sb, (size_t)ch, hipMemcpyDeviceToHost, st);
+}
+
+extern "C" int nvh_stream_synth_planar(nvh_stream* s, int format, void* pcm_host, void* d_pcm, int64_t plane_stride, int64_t* written) {
+  return nvh_guard([&]() -> int {
+    if (!s || (pcm_host && d_pcm) || !pcm_format_ok(format) || !planar_dest_ok(format, d_pcm)) return NVH_ERR_ARGUMENT;
+    if (written) *written = 0;
+    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
+    if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
+    if (!s->ctx) return NVH_ERR_NO_GPU;
+    if (s->flight[0].on || s->flight[1].on) return NVH_ERR_ARGUMENT;  // pipelined batches outstanding: end them first
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    const int ch = s->setup.channels;
+    if (s->pending.frames.empty()) return NVH_OK;
+    nvh_batch* b = &s->scratch;
+    s->replay_error = NVH_OK;
+    s->replay_errors.clear();
+    int rc = batch_upload(s, b);
+    if (rc != NVH_OK) return rc;
+    const int64_t n = b->pcm_samples;  // (GPU-parse mode: at most the look-ahead's count, nvh_stream_synth_pcm)
+    if (plane_stride < n) return NVH_ERR_ARGUMENT;
+    const size_t sb = pcm_sample_bytes(format);
+    const int64_t n4 = planar_stage_stride(n);
+    void* dst = d_pcm;
+    if (!dst) {
+      if ((rc = s->pcm.reserve((size_t)(n4 > 0 ? n4 : 1) * (size_t)ch * sb)) != NVH_OK) return rc;
+      dst = s->pcm.p;
+    }
+    rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
+                      format, planar_launch_stride(d_pcm ? plane_stride : n4));
+    if (rc != NVH_OK) return rc;
+    hipStream_t st = s->ctx->stream;
+    if (b->last_decoded >= 0) s->carry_cur ^= 1;
+    // pinned host planes are written by the copy engine directly; anything else through the bounce buffer ([C, n]) and one
+    // memcpy per plane on this thread
+    bool direct = false;
+    if (pcm_host && n > 0) {
+      hipPointerAttribute_t attr;
+      if (hipPointerGetAttributes(&attr, pcm_host) == hipSuccess) direct = attr.type == hipMemoryTypeHost;
+      else (void)hipGetLastError();
+    }
+    const size_t bounce = (pcm_host && !direct) ? (size_t)n * (size_t)ch * sb : 0;
+    if ((rc = s->h_pcm.reserve(bounce + 2 * sizeof(int))) != NVH_OK) return rc;
+    int* h_flags = (int*)((uint8_t*)s->h_pcm.p + bounce);
+    if (pcm_host) HIP_TRY(planar_readback(direct ? pcm_host : s->h_pcm.p, direct ? plane_stride : n, dst, n4, n, ch, sb, st));
+    HIP_TRY(hipMemcpyAsync(h_flags, s->flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(nvh_wait_stream(s->ctx, st));
+    if (bounce)
+      for (int c = 0; c < ch; c++)
+        std::memcpy((uint8_t*)pcm_host + (size_t)c * (size_t)plane_stride * sb, (const uint8_t*)s->h_pcm.p + (size_t)c * (size_t)n * sb,
+                    (size_t)n * sb);
+    if (h_flags[0] || h_flags[1]) HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), st));
+    if (h_flags[1]) s->has_clipped = 1;
+    if (h_flags[0]) return NVH_ERR_RUNTIME;
+    if (written) *written = n;
+    return s->replay_error;
+  });
+}
+
+extern "C" int nvh_stream_synth_begin_planar(nvh_stream* s, int format, void* pcm_host, int64_t plane_stride, int64_t* expected) {
+  return nvh_guard([&]() -> int {
+    if (!s || !pcm_host || !pcm_format_ok(format)) return NVH_ERR_ARGUMENT;
+    if (expected) *expected = 0;
+    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
+    if (!s->ctx) return NVH_ERR_NO_GPU;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    const int slot = s->flight_next;
+    nvh_stream::Flight& F = s->flight[slot];
+    if (F.on) return NVH_ERR_ARGUMENT;  // two batches outstanding already
+    {
+      hipPointerAttribute_t attr;
+      if (hipPointerGetAttributes(&attr, pcm_host) != hipSuccess || attr.type != hipMemoryTypeHost) {
+        (void)hipGetLastError();
+        return NVH_ERR_ARGUMENT;  // the copy engine needs page-locked memory (nvh_pinned_alloc)
+      }
+    }
+    const int ch = s->setup.channels;
+    hipStream_t st = s->ctx->stream;
+    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+    if (!F.kernels) HIP_TRY(hipEventCreateWithFlags(&F.kernels, hipEventDisableTiming));
+    if (!F.done) HIP_TRY(hipEventCreateWithFlags(&F.done, hipEventDisableTiming));
+    HIP_TRY(hipStreamSynchronize(st));  // (nvh_stream_synth_begin_pcm: the previous batch's staging image)
+    F.need = 0;
+    F.replay_error = NVH_OK;
+    F.replay_errors.clear();
+    if (s->pending.frames.empty()) {
+      HIP_TRY(hipEventRecord(F.done, st));
+      F.on = true;
+      s->flight_next ^= 1;
+      return NVH_OK;
+    }
+    nvh_batch* b = &s->scratch;
+    s->replay_error = NVH_OK;
+    s->replay_errors.clear();
+    int rc = batch_upload(s, b);
+    if (rc != NVH_OK) return rc;
+    const int64_t n = b->pcm_samples;
+    if (plane_stride < n) return NVH_ERR_ARGUMENT;
+    const size_t sb = pcm_sample_bytes(format);
+    const int64_t n4 = planar_stage_stride(n);
+    if ((rc = s->pcm2[slot].reserve((size_t)(n4 > 0 ? n4 : 1) * (size_t)ch * sb)) != NVH_OK) return rc;
+    if ((rc = s->h_flags2.reserve(4 * sizeof(int))) != NVH_OK) return rc;
+    void* dst = s->pcm2[slot].p;
+    rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
+                      format, planar_launch_stride(n4));
+    if (rc != NVH_OK) return rc;
+    if (b->last_decoded >= 0) s->carry_cur ^= 1;
+    HIP_TRY(hipMemcpyAsync((int*)s->h_flags2.p + 2 * slot, s->flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), st));
+    HIP_TRY(hipEventRecord(F.kernels, st));
+    HIP_TRY(hipStreamWaitEvent(s->copy_stream, F.kernels, 0));
+    HIP_TRY(planar_readback(pcm_host, plane_stride, dst, n4, n, ch, sb, s->copy_stream));
+    HIP_TRY(hipEventRecord(F.done, s->copy_stream));
+    F.need = n;  // (nvh_stream_synth_end reports it: samples per channel for a planar flight)
+    F.replay_error = s->replay_error;
+    F.replay_errors = s->replay_errors;
+    F.on = true;
+    s->flight_next ^= 1;
+    if (expected) *expected = n;
+    return NVH_OK;
+  });
+}
+
 extern "C" int nvh_stream_parse_errors(const nvh_stream* s, int32_t* codes, int64_t* samples_before, int cap, int* count) {
   return nvh_guard([&]() -> int {
     if (!s || !count || cap < 0 || (cap > 0 && (!codes || !samples_before))) return NVH_ERR_ARGUMENT;
@@ -836,6 +971,18 @@ extern "C" int nvh_batch_synth_pcm(nvh_batch* b, int format, void* d_pcm, int64_
     HIP_TRY(hipSetDevice(s->ctx->device));
     // the stream keeps the tail of the newest batch (written to its current carry buffer; the batch reads its own snapshot)
     return batch_launch(b, (const float*)b->carry_in.p, (float*)s->carry[s->carry_cur].p, d_pcm, false, nullptr, nullptr, format);
+  });
+}
+
+extern "C" int nvh_batch_synth_planar(nvh_batch* b, int format, void* d_pcm, int64_t plane_stride) {
+  return nvh_guard([&]() -> int {
+    if (!b || !b->s || !pcm_format_ok(format) || !planar_dest_ok(format, d_pcm)) return NVH_ERR_ARGUMENT;
+    nvh_stream* s = b->s;
+    if (plane_stride < b->pcm_samples) return NVH_ERR_ARGUMENT;
+    if (b->pcm_samples > 0 && !d_pcm) return NVH_ERR_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    return batch_launch(b, (const float*)b->carry_in.p, (float*)s->carry[s->carry_cur].p, d_pcm, false, nullptr, nullptr, format,
+                        planar_launch_stride(plane_stride));
   });
 }
 

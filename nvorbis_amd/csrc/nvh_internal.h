@@ -85,6 +85,29 @@ __global__ void k_ola_emit_s16(NvhDevSetup S, NvhDevBatch Bt, const float* work,
                                int* clipped_flag);
 __global__ void k_ola_emit_seq_s16(NvhDevSetup S, NvhDevBatch Bt, float* work, const float* carry, int16_t* pcm, int clip,
                                    int* clipped_flag);
+// the channel-planar twins (plane_stride: samples between the channels' planes; NvhSynthArgs::plane_stride for the slab kernels)
+__global__ void k_synth_emit_planar(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_synth_emit_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_synth8_emit_planar(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_synth8_emit_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_synth_group2_planar(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_synth_group2_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_synth_group4_planar(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_synth_group4_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS);
+__global__ void k_ola_compact_planar(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, float* pcm, int clip,
+                                     int* clipped_flag, float* carry_out, int last_decoded, int nosym, const int* list, int emitted,
+                                     long long plane_stride);
+__global__ void k_ola_compact_s16_planar(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, int16_t* pcm, int clip,
+                                         int* clipped_flag, float* carry_out, int last_decoded, int nosym, const int* list, int emitted,
+                                         long long plane_stride);
+__global__ void k_ola_emit_planar(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, float* pcm, int clip,
+                                  int* clipped_flag, long long plane_stride);
+__global__ void k_ola_emit_s16_planar(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, int16_t* pcm, int clip,
+                                      int* clipped_flag, long long plane_stride);
+__global__ void k_ola_emit_seq_planar(NvhDevSetup S, NvhDevBatch Bt, float* work, const float* carry, float* pcm, int clip,
+                                      int* clipped_flag, long long plane_stride);
+__global__ void k_ola_emit_seq_s16_planar(NvhDevSetup S, NvhDevBatch Bt, float* work, const float* carry, int16_t* pcm, int clip,
+                                          int* clipped_flag, long long plane_stride);
 __global__ void k_window_apply(float* buf, const float* window, int n, long long stride, int batch);
 __global__ void k_overlap_buffers(const float* previous, float* next, int prev_start, int len, int next_start, int channels,
                                   long long plane_stride);
@@ -313,6 +336,7 @@ struct nvh_batch {
   bool sequential_ola = false;
   int last_decoded = -1;  // last frame with n != 0 (its block becomes the next carried tail)
   const char* slot_name[4] = {"-", "-", "-", "-"};  // kernels behind the four timing slots of the last launch
+  std::string slot_name_buf[4];  // storage of the names built with a twin's suffix (_s16, _planar, _s16_planar)
   bool links_ok = false;  // op_link chains usable (every frame has < 32767 ops): k_spectrum's chain walk
   int max_ops = 0, max_ent = 0, max_pass = 0;  // largest per-frame op / entry / pass slice (LDS staging capacity of k_spectrum)
   int max_vecs = 0;     // GPU-parsed batch in slab mode: its largest slab, as k_parse reported it
@@ -330,6 +354,7 @@ struct nvh_batch {
   const uint4* d_slabs = nullptr;  // ... here
   // paired emission (nvh_format.h: NVH_EMIT_*): frames whose PCM k_synth writes itself, and the frames left to k_ola_compact
   int emit_frames = 0;           // frames with NVH_EMIT_DONE
+  bool emit_planar_ok = true;    // every frame the emission covers starts on a whole group of four samples (the _planar twins' vectors)
   int fpw = 1;                   // frames per workgroup the emission flags were laid out for (1: odd / even frames; 2, 4: frame groups)
   bool ola_all = false;          // GPU-parsed batch in which k_parse_links withdrew an emission candidate: k_ola_compact over every frame
   int ola_count = 0;             // entries of d_ola_list
@@ -448,7 +473,8 @@ int upload_parse_tables(nvh_stream* s);                          // nvh_setup.hi
 int batch_upload(nvh_stream* s, nvh_batch* b);                   // nvh_launch.hip
 // d_pcm: float samples, or int16_t with pcm_format NVH_PCM_S16 (the kernels' _s16 twins)
 int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms,
-                 hipEvent_t* ext_ev = nullptr, int pcm_format = NVH_PCM_F32);  // nvh_launch.hip
+                 hipEvent_t* ext_ev = nullptr, int pcm_format = NVH_PCM_F32,
+                 int64_t plane_stride = 0);  // nvh_launch.hip; plane_stride > 0: channel-planar PCM (the _planar twins)
 static inline size_t pcm_sample_bytes(int pcm_format) { return pcm_format == NVH_PCM_S16 ? sizeof(int16_t) : sizeof(float); }
 int collect_flags(nvh_stream* s);                                // nvh_launch.hip
 void replay_note(nvh_stream* s, int kind, const uint8_t* data, int len, int64_t granule, int flags);  // nvh_launch.hip

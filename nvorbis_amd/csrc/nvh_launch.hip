@@ -458,6 +458,12 @@ static void assign_emission(nvh_stream* s, nvh_batch* b, nvh::FrameBatch& P, int
     for (int i = nf - 1; i >= 0; --i)
       if (P.frames[(size_t)i].n != 0) { last = i; break; }
     if (b->emit_frames > 0 && last >= 0 && P.frames[(size_t)last].n >= 256) P.frames[(size_t)last].emit_flags |= NVH_EMIT_CARRY_OUT;
+    // channel-planar output (the _planar twins) needs every emitted frame's first sample of a plane on a whole group of four
+    // samples -- the tests above only ask that of the interleaved position out_pos * ch; a batch where one does not is synthesised
+    // without paired emission when the call is planar (batch_launch)
+    b->emit_planar_ok = true;
+    for (const NvhFrame& fr : P.frames)
+      if ((fr.emit_flags & NVH_EMIT_DONE) && (fr.out_pos & 3) != 0) b->emit_planar_ok = false;
     for (int g = 0; g < nf; g++) {
       const NvhFrame& fr = P.frames[(size_t)g];
       if ((fr.emit_count > 0 && !(fr.emit_flags & NVH_EMIT_DONE)) || (g == last && !(fr.emit_flags & NVH_EMIT_CARRY_OUT))) ola_list.push_back(g);
@@ -722,12 +728,21 @@ static bool slab_size_ok(const nvh_batch* b) {
 static bool slab_path(const nvh_batch* b) { return slab_shape_ok(b) && slab_size_ok(b); }
 
 int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms, hipEvent_t* ext_ev,
-                 int pcm_format) {
+                 int pcm_format, int64_t plane_stride) {
   nvh_stream* s = b->s;
   const bool s16 = pcm_format == NVH_PCM_S16;  // the emitting kernels' 16-bit twins (kernels_common.h: pcm_s16_value)
   hipStream_t st = s->ctx->stream;
   if (b->nframes == 0) return NVH_OK;
   const int ch = s->setup.channels;
+  // Channel-planar output: the _planar twins.  One channel is the same bytes either way: mono takes the interleaved kernels.
+  // The twins' vector stores need every plane's first sample of a frame on a 16-byte boundary: an aligned base, a plane stride in
+  // whole groups of four samples (below 2^31: NvhSynthArgs::plane_stride) and a frame position in whole groups of four
+  // (batch_upload: emit_planar_ok); otherwise the batch runs without paired emission and k_ola_compact_*planar takes each frame
+  // by its vector form where that frame's own position allows it, else sample by sample.
+  const bool planar = plane_stride > 0 && ch > 1;
+  const bool planar_emit = !planar || (((uintptr_t)d_pcm & 15u) == 0 && (plane_stride & 3) == 0 && plane_stride <= 0x7FFFFFFFll &&
+                                       b->emit_planar_ok);
+  const char* sfx = planar ? (s16 ? "_s16_planar" : "_planar") : (s16 ? "_s16" : "");
   float* work = (float*)b->work.p;
   int* flags = (int*)s->flags.p;
   const size_t lds = (size_t)s->setup.block1 * sizeof(float);
@@ -784,10 +799,11 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
     const bool wide = slab_wide(s);
     // paired emission (nvh_format.h: NVH_EMIT_*): the host marked the frames at upload; it needs the PCM buffer and the slabs
     // in frame order
-    emitted = b->emit_frames > 0 && d_pcm != nullptr && !b->block_only && !T.no_emit && !s->shared->slab_general;
+    emitted = b->emit_frames > 0 && d_pcm != nullptr && !b->block_only && !T.no_emit && !s->shared->slab_general && planar_emit;
     A.pcm = emitted ? (float*)d_pcm : nullptr;  // (int16_t samples for the _s16 twins)
     A.windows = s->dev.windows;
     A.clip = s->clip;
+    A.plane_stride = planar && planar_emit ? (int)plane_stride : 0;
     A.clipped_flag = flags + 1;
     A.carry = carry;
     A.carry_out = emitted ? carry_out : nullptr;
@@ -798,6 +814,8 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_emit, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_g, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_emit_s16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_emit_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_emit_s16_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       s->ctx->synth_lds_attr_set = true;
     }
     if (timing) HIP_TRY(hipEventRecord(ev[1], st));  // slot 0 stays empty: slot 1 = the synthesis kernel
@@ -811,8 +829,8 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       A.f0 = 1;
       if (b->nframes > 1) hipLaunchKernelGGL(k_synth8, dim3((unsigned)(b->nframes / 2)), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
       A.f0 = 0;
-      hipLaunchKernelGGL(s16 ? k_synth8_emit_s16 : k_synth8_emit, dim3((unsigned)((b->nframes + 1) / 2)), dim3(512), synth_lds, st,
-                         A NVH_DBG_LAUNCH);
+      auto kern8 = planar ? (s16 ? k_synth8_emit_s16_planar : k_synth8_emit_planar) : (s16 ? k_synth8_emit_s16 : k_synth8_emit);
+      hipLaunchKernelGGL(kern8, dim3((unsigned)((b->nframes + 1) / 2)), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
     } else if (wide_general) hipLaunchKernelGGL(k_synth8_g, dim3((unsigned)b->nframes), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
     else if (wide) hipLaunchKernelGGL(k_synth8, dim3((unsigned)b->nframes), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
     else if (narrow_general) hipLaunchKernelGGL(k_synth_g, dim3((unsigned)b->nframes), dim3(256), synth_lds, st, A NVH_DBG_LAUNCH);
@@ -827,9 +845,14 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
         HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group4, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group2_s16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group4_s16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group2_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group4_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group2_s16_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group4_s16_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         s->ctx->group_lds_attr_set = true;
       }
-      auto kern = gw == 2 ? (s16 ? k_synth_group2_s16 : k_synth_group2) : (s16 ? k_synth_group4_s16 : k_synth_group4);
+      auto kern = planar ? (gw == 2 ? (s16 ? k_synth_group2_s16_planar : k_synth_group2_planar) : (s16 ? k_synth_group4_s16_planar : k_synth_group4_planar))
+                         : (gw == 2 ? (s16 ? k_synth_group2_s16 : k_synth_group2) : (s16 ? k_synth_group4_s16 : k_synth_group4));
       const unsigned nt = gw == 2 ? 256u : 512u;
       if (T.debug_occ) {
         int nb = -1;
@@ -862,12 +885,13 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       }
       A.f0 = 0;
       A.prefetch_prev = 0;
-      hipLaunchKernelGGL(s16 ? k_synth_emit_s16 : k_synth_emit, dim3((unsigned)((b->nframes + 1) / 2)), dim3(NVH_SYNTH_NT), synth_lds, st,
-                         A NVH_DBG_LAUNCH);
+      auto kern = planar ? (s16 ? k_synth_emit_s16_planar : k_synth_emit_planar) : (s16 ? k_synth_emit_s16 : k_synth_emit);
+      hipLaunchKernelGGL(kern, dim3((unsigned)((b->nframes + 1) / 2)), dim3(NVH_SYNTH_NT), synth_lds, st, A NVH_DBG_LAUNCH);
     }
-    if (emitted && !s16) b->slot_name[1] = wide ? "k_synth8+k_synth8_emit" : (b->fpw == 2 ? "k_synth_group2" : b->fpw == 4 ? "k_synth_group4" : "k_synth+k_synth_emit");  // odd frames, then the emitting even frames
-    if (emitted && s16)
-      b->slot_name[1] = wide ? "k_synth8+k_synth8_emit_s16" : (b->fpw == 2 ? "k_synth_group2_s16" : b->fpw == 4 ? "k_synth_group4_s16" : "k_synth+k_synth_emit_s16");
+    if (emitted) {  // odd frames, then the emitting even frames; the twins' names carry the format's / layout's suffix
+      b->slot_name_buf[1] = std::string(wide ? "k_synth8+k_synth8_emit" : (b->fpw == 2 ? "k_synth_group2" : b->fpw == 4 ? "k_synth_group4" : "k_synth+k_synth_emit")) + sfx;
+      b->slot_name[1] = b->slot_name_buf[1].c_str();
+    }
     slab_done = true;
     fuse_gen8 = true;  // the inverse MDCT is inside: no transform kernel behind it
   }
@@ -970,8 +994,8 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
   const size_t plane_bytes = (size_t)ch * (size_t)s->setup.block1 * sizeof(float);
   {
     b->slot_name[2] = (fuse_imdct || fuse_gen8) ? "-" : compact ? "k_imdct_compact" : (s->setup.block0 >= 256 ? "k_imdct_wave" : "k_imdct_window");
-    if (!s16) b->slot_name[3] = compact ? "k_ola_compact" : (!b->sequential_ola ? "k_ola_emit" : "k_ola_emit_seq");
-    else b->slot_name[3] = compact ? "k_ola_compact_s16" : (!b->sequential_ola ? "k_ola_emit_s16" : "k_ola_emit_seq_s16");
+    b->slot_name_buf[3] = std::string(compact ? "k_ola_compact" : (!b->sequential_ola ? "k_ola_emit" : "k_ola_emit_seq")) + sfx;
+    b->slot_name[3] = b->slot_name_buf[3].c_str();
     if (fuse_imdct || fuse_gen8)
       ;  // done inside k_spectrum_imdct / k_spectrum_gen8_imdct
     else if (compact)
@@ -1002,7 +1026,15 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       if (ch > 2 && !T.no_ola_sym && T.ola_segs <= 0) segs = ((s->setup.block1 / 16) + NVH_OLA_GW - 1) / NVH_OLA_GW;
       // k_ola_compact, or its 16-bit twin
       auto ola_compact = [&](unsigned nwg, float* c_out, const int* list, int emitted_frames) {
-        if (s16)
+        if (planar && s16)
+          hipLaunchKernelGGL(k_ola_compact_s16_planar, dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
+                             (const float*)work, carry, (int16_t*)d_pcm, s->clip, flags + 1, c_out, b->last_decoded,
+                             T.no_ola_sym ? 1 : 0, list, emitted_frames, (long long)plane_stride);
+        else if (planar)
+          hipLaunchKernelGGL(k_ola_compact_planar, dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
+                             (const float*)work, carry, (float*)d_pcm, s->clip, flags + 1, c_out, b->last_decoded,
+                             T.no_ola_sym ? 1 : 0, list, emitted_frames, (long long)plane_stride);
+        else if (s16)
           hipLaunchKernelGGL(k_ola_compact_s16, dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
                              (const float*)work, carry, (int16_t*)d_pcm, s->clip, flags + 1, c_out, b->last_decoded,
                              T.no_ola_sym ? 1 : 0, list, emitted_frames);
@@ -1020,12 +1052,24 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       else  // paired emission: only the frames k_synth left over
         ola_compact((unsigned)b->ola_count, (float*)nullptr /* k_synth wrote the carried tail */, b->d_ola_list, 1);
     } else if (!b->sequential_ola) {
-      if (s16)
+      if (planar && s16)
+        hipLaunchKernelGGL(k_ola_emit_s16_planar, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, (const float*)work, carry,
+                           (int16_t*)d_pcm, s->clip, flags + 1, (long long)plane_stride);
+      else if (planar)
+        hipLaunchKernelGGL(k_ola_emit_planar, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, (const float*)work, carry,
+                           (float*)d_pcm, s->clip, flags + 1, (long long)plane_stride);
+      else if (s16)
         hipLaunchKernelGGL(k_ola_emit_s16, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, (const float*)work, carry,
                            (int16_t*)d_pcm, s->clip, flags + 1);
       else
         hipLaunchKernelGGL(k_ola_emit, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, (const float*)work, carry,
                            (float*)d_pcm, s->clip, flags + 1);
+    } else if (planar && s16) {
+      hipLaunchKernelGGL(k_ola_emit_seq_s16_planar, dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry, (int16_t*)d_pcm, s->clip,
+                         flags + 1, (long long)plane_stride);
+    } else if (planar) {
+      hipLaunchKernelGGL(k_ola_emit_seq_planar, dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry, (float*)d_pcm, s->clip,
+                         flags + 1, (long long)plane_stride);
     } else if (s16) {
       hipLaunchKernelGGL(k_ola_emit_seq_s16, dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry, (int16_t*)d_pcm, s->clip, flags + 1);
     } else {

@@ -1,6 +1,7 @@
-// ola_compact_body.inc -- the body of k_ola_compact and k_ola_compact_s16 (kernels.hip), included inside both kernels with
-// `PCM` (float / int16_t) typedef'd in front: the float kernel's code is exactly what it was before the 16-bit twin existed
-// (the same body as an inlined template function compiles to a different register allocation).
+// ola_compact_body.inc -- the body of k_ola_compact, k_ola_compact_s16 and their _planar twins (kernels.hip), included inside
+// each kernel with `PCM` (float / int16_t) typedef'd and `PLANAR` (and, interleaved, a zero `plane_stride`) declared in front:
+// the float kernel's code is exactly what it was before the 16-bit twin existed (the same body as an inlined template function
+// compiles to a different register allocation).
   // list: the frames paired emission left to this kernel (nvh_launch.hip); emitted: k_synth wrote the PCM of every frame with
   // NVH_EMIT_DONE (such a frame is on the list only as the block that becomes the carried tail)
   const int f = list ? list[blockIdx.x] : (int)blockIdx.x;
@@ -25,17 +26,34 @@
   const float* __restrict__ w = S.windows + fr.window_off;
   const float* __restrict__ wp = S.windows + fr.ov_window_off;
   const NvhChan* chans = Bt.chans + fr.chan_off;
-  PCM* out = pcm + fr.out_pos * ch;
+  PCM* out = pcm + fr.out_pos * (PLANAR ? 1 : ch);
   int clipped = 0;
   // the carried block (ov_frame == -2) is always stored fully windowed (k_expand_carry); blocks of this batch are compact
   const bool prev_full = fr.ov_frame == -2;
 
   // fast path: everything in units of four samples (true for every frame of a well-formed stream except an
   // EOS-trimmed last one), up to 8 channels
-  const bool vec = fr.n != 0 && ch <= 8 && ((fr.emit_start | fr.emit_count | fr.start | fr.ov_src | fr.ov_len) & 3) == 0 &&
+  const bool vec = !PLANAR && fr.n != 0 && ch <= 8 && ((fr.emit_start | fr.emit_count | fr.start | fr.ov_src | fr.ov_len) & 3) == 0 &&
                    ((fr.out_pos * ch) & 3) == 0;
   // steady state: whole first half over the whole second half of an executing predecessor of the same size
   const unsigned all_ch = ch >= 32 ? 0xFFFFFFFFu : ((1u << ch) - 1u);
+  if constexpr (PLANAR) {
+    // channel-planar: every plane's first sample of the frame on a 16-byte boundary (an aligned base, a plane stride and an
+    // output position in whole groups of four), up to 32 channels (the execute flags of the frame record's masks); else the
+    // per-sample form below
+    const bool pvec = fr.n != 0 && ch <= 32 && ((fr.emit_start | fr.emit_count | fr.start | fr.ov_src | fr.ov_len) & 3) == 0 &&
+                      ((fr.out_pos | plane_stride) & 3) == 0 && (reinterpret_cast<uintptr_t>(pcm) & 15u) == 0;
+    const unsigned pall = ch >= 32 ? 0xFFFFFFFFu : ((1u << ch) - 1u);
+    const bool psym = pvec && prev && !prev_full && fr.ov_n == fr.n && fr.start == 0 && fr.emit_start == 0 &&
+                      fr.emit_count == (fr.n >> 1) && fr.ov_src == (fr.n >> 1) && fr.ov_len == (fr.n >> 1) &&
+                      (fr.exec_mask & pall) == pall && (fr.ov_exec_mask & pall) == pall && !nosym;
+    if (psym || pvec) {
+      clipped = psym ? ola_sym_planar<PCM>(S, fr, cur, prev, w, wp, out, plane_stride, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS)
+                     : ola_vec_planar<PCM>(S, fr, cur, prev, prev_full, w, wp, out, plane_stride, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS);
+      report_clipped(clipped, clipped_flag);
+      return;
+    }
+  }
   const bool sym = vec && prev && !prev_full && fr.ov_n == fr.n && fr.start == 0 && fr.emit_start == 0 && fr.emit_count == (fr.n >> 1) &&
                    fr.ov_src == (fr.n >> 1) && fr.ov_len == (fr.n >> 1) && (fr.exec_mask & all_ch) == all_ch &&
                    (fr.ov_exec_mask & all_ch) == all_ch && !nosym;
@@ -85,6 +103,7 @@
 
   for (int o = NVH_OLA_TID; o < total; o += NVH_OLA_THREADS) {
     int t = o / ch, c = o - t * ch;
+    if constexpr (PLANAR) c = o / fr.emit_count, t = o - c * fr.emit_count;  // plane-major: consecutive lanes, one plane
     int idx = fr.emit_start + t;
     const NvhChan cn = chans[c];
     float v;
@@ -100,6 +119,7 @@
       }
     }
     if (clip) v = clip_value(v, &clipped);
-    pcm_store1(out + o, v);
+    if constexpr (PLANAR) pcm_store1(out + c * plane_stride + t, v);
+    else pcm_store1(out + o, v);
   }
   report_clipped(clipped, clipped_flag);

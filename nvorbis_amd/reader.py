@@ -29,6 +29,16 @@ def _pcm_format(dtype):
     return _PCM_FORMATS[dt], dt
 
 
+_LAYOUTS = ("interleaved", "planar")
+
+
+def _layout(name):
+    """True for "planar" (channel-planar PCM, [channels, samples]), False for "interleaved"; ValueError for anything else."""
+    if not isinstance(name, str) or name not in _LAYOUTS:
+        raise ValueError("layout must be 'interleaved' or 'planar', not %r" % (name,))
+    return name == "planar"
+
+
 def _sample_format(name):
     if name not in _SAMPLE_FORMATS:
         raise ValueError("sample_format must be 'f32' or 's16', not %r" % (name,))
@@ -283,9 +293,14 @@ class Batch:
         check(lib().nvh_batch_kernels(self._h, buf, 256), "nvh_batch_kernels")
         return buf.value.decode().split(",")
 
-    def synth(self, d_pcm_ptr, capacity, dtype=np.float32):
-        """Launch the synthesis into d_pcm_ptr (capacity in samples) as float32 or int16 PCM (a 16-byte aligned int16 destination)."""
+    def synth(self, d_pcm_ptr, capacity, dtype=np.float32, plane_stride=None):
+        """Launch the synthesis into d_pcm_ptr (capacity in samples) as float32 or int16 PCM (a 16-byte aligned int16 destination).
+        plane_stride (samples, >= self.samples): channel-planar PCM instead, channel c at d_pcm_ptr + c * plane_stride samples
+        (capacity is then not used)."""
         fmt, _ = _pcm_format(dtype)
+        if plane_stride is not None:
+            check(lib().nvh_batch_synth_planar(self._h, fmt, C.c_void_p(d_pcm_ptr), int(plane_stride)), "nvh_batch_synth_planar")
+            return
         check(lib().nvh_batch_synth_pcm(self._h, fmt, C.c_void_p(d_pcm_ptr), int(capacity)), "nvh_batch_synth_pcm")
 
     def time(self, d_pcm_ptr, capacity, iters, per_kernel=True):
@@ -522,15 +537,20 @@ class Stream:
         check(lib().nvh_stream_has_clipped(self._h, C.byref(v)), "nvh_stream_has_clipped")
         return bool(v.value)
 
-    def synth_host(self, pinned=False, out=None, dtype=np.float32):
+    def synth_host(self, pinned=False, out=None, dtype=np.float32, planar=False):
         """Synthesise the pending batch; returns interleaved PCM (numpy) of `dtype`: float32, or int16 (ov_read's conversion,
         done in the kernels: half the bytes over PCIe).
 
         out: a contiguous array of that dtype to write into (must hold the batch); the written prefix is returned.
 
         pinned=True: the result is a view of a page-locked buffer owned by this stream (written by the copy engine
-        directly, no extra copy) and stays valid until the next call."""
+        directly, no extra copy) and stays valid until the next call.
+
+        planar=True: channel-planar PCM, a (channels, n) array (n samples per channel); `out` is then a C-contiguous
+        (channels, m) array of the dtype with m >= the pending samples per channel, and the result is out[:, :n]."""
         fmt, dt = _pcm_format(dtype)
+        if planar:
+            return self._synth_host_planar(pinned, out, fmt, dt)
         _, smp = self.pending()
         n = max(smp * self.channels, 1)
         wr = C.c_int64(0)
@@ -557,12 +577,38 @@ class Stream:
         self._note_parse_error(rc, wr.value, "nvh_stream_synth_pcm")
         return out[:wr.value]
 
+    def _synth_host_planar(self, pinned, out, fmt, dt):
+        _, smp = self.pending()
+        ch = self.channels
+        if out is not None:
+            if (not isinstance(out, np.ndarray) or out.dtype != dt or out.ndim != 2 or out.shape[0] != ch or
+                    not out.flags["C_CONTIGUOUS"] or out.shape[1] < smp):
+                raise ValueError("out must be a C-contiguous (%d, >= %d) %s array" % (ch, smp, dt))
+            arr = out
+        elif pinned:
+            nbytes = max(smp, 1) * ch * dt.itemsize
+            if getattr(self, "_pin_cap", 0) < nbytes:
+                if getattr(self, "_pin_ptr", None):
+                    lib().nvh_pinned_free(self._pin_ptr)
+                p = C.c_void_p()
+                cap = max(nbytes, 2 * getattr(self, "_pin_cap", 0))
+                check(lib().nvh_pinned_alloc(cap, C.byref(p)), "nvh_pinned_alloc")
+                self._pin_ptr, self._pin_cap = p, cap
+                self._pin_arr = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(cap,))
+            arr = self._pin_arr[:nbytes].view(dt).reshape(ch, max(smp, 1))
+        else:
+            arr = np.empty((ch, max(smp, 1)), dtype=dt)
+        wr = C.c_int64(0)
+        rc = lib().nvh_stream_synth_planar(self._h, fmt, arr.ctypes.data, None, arr.shape[1], C.byref(wr))
+        self._note_parse_error(rc, wr.value, "nvh_stream_synth_planar", planar=True)
+        return arr[:, :wr.value]
+
     # ---- pipelined read-back (nvh_stream_synth_begin / _end) ----
     def _pipe_buffer(self, k, n, dt):
         bufs = getattr(self, "_pipe", None)
         if bufs is None:
-            bufs = self._pipe = [[None, 0, None, None], [None, 0, None, None]]  # [pointer, capacity in bytes, byte view, dtype]
-        ptr, cap, arr, _ = bufs[k]
+            bufs = self._pipe = [[None, 0, None, None, 0], [None, 0, None, None, 0]]  # [pointer, capacity in bytes, byte view, dtype, planes' stride]
+        ptr, cap, arr, _, _ = bufs[k]
         nbytes = n * dt.itemsize
         if cap < nbytes:
             if ptr:
@@ -570,13 +616,15 @@ class Stream:
             p = C.c_void_p()
             cap = max(nbytes, 2 * cap)
             check(lib().nvh_pinned_alloc(cap, C.byref(p)), "nvh_pinned_alloc")
-            bufs[k] = [p, cap, np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(cap,)), None]
+            bufs[k] = [p, cap, np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(cap,)), None, 0]
         bufs[k][3] = dt
+        bufs[k][4] = 0
         return bufs[k][2][:cap - cap % dt.itemsize].view(dt)
 
-    def synth_begin(self, dtype=np.float32):
+    def synth_begin(self, dtype=np.float32, planar=False):
         """Queue the pending batch (upload, GPU parse, synthesis, transfer of the PCM on a copy stream) and return at once.
-        Two batches may be outstanding; synth_end() hands them back in order, each in the dtype of its begin (float32 / int16)."""
+        Two batches may be outstanding; synth_end() hands them back in order, each in the dtype of its begin (float32 / int16),
+        and -- planar=True -- as a (channels, n) view of channel-planar PCM (the return value is then per channel too)."""
         fmt, dt = _pcm_format(dtype)
         if getattr(self, "_pipe_out", 0) >= 2:
             # refuse before touching a buffer: slot k is still the DMA destination of the oldest outstanding batch
@@ -586,7 +634,12 @@ class Stream:
         k = getattr(self, "_pipe_next", 0)
         out = self._pipe_buffer(k, n, dt)
         exp = C.c_int64(0)
-        check(lib().nvh_stream_synth_begin_pcm(self._h, fmt, out.ctypes.data, out.size, C.byref(exp)), "nvh_stream_synth_begin_pcm")
+        if planar:
+            stride = max(smp, 1)
+            check(lib().nvh_stream_synth_begin_planar(self._h, fmt, out.ctypes.data, stride, C.byref(exp)), "nvh_stream_synth_begin_planar")
+            self._pipe[k][4] = stride
+        else:
+            check(lib().nvh_stream_synth_begin_pcm(self._h, fmt, out.ctypes.data, out.size, C.byref(exp)), "nvh_stream_synth_begin_pcm")
         # only a begin that succeeded occupies a slot
         self._pipe_next = k ^ 1
         self._pipe_out = getattr(self, "_pipe_out", 0) + 1
@@ -606,23 +659,32 @@ class Stream:
         # any other outcome has retired the native flight (nvh_api.hip pops the slot before it reports a runtime or parse error)
         self._pipe_first = k ^ 1
         self._pipe_out -= 1
-        self._note_parse_error(rc, wr.value, "nvh_stream_synth_end")
-        _, cap, arr, dt = self._pipe[k]
+        _, cap, arr, dt, stride = self._pipe[k]
+        self._note_parse_error(rc, wr.value, "nvh_stream_synth_end", planar=bool(stride))
+        if stride:  # a planar flight: the planes lie `stride` samples apart
+            return arr[:stride * self.channels * dt.itemsize].view(dt).reshape(self.channels, stride)[:, :wr.value]
         return arr[:cap - cap % dt.itemsize].view(dt)[:wr.value]
 
-    def synth_device(self, d_ptr, capacity, dtype=np.float32):
-        """Synthesise the pending batch into device memory (capacity in samples; int16: 16-byte aligned); returns the samples written."""
+    def synth_device(self, d_ptr, capacity, dtype=np.float32, plane_stride=None):
+        """Synthesise the pending batch into device memory (capacity in samples; int16: 16-byte aligned); returns the samples written.
+        plane_stride (samples): channel-planar PCM instead, channel c at d_ptr + c * plane_stride samples; returns the samples
+        written per channel (capacity is then not used)."""
         fmt, _ = _pcm_format(dtype)
         wr = C.c_int64(0)
+        if plane_stride is not None:
+            rc = lib().nvh_stream_synth_planar(self._h, fmt, None, C.c_void_p(d_ptr), int(plane_stride), C.byref(wr))
+            self._note_parse_error(rc, wr.value, "nvh_stream_synth_planar", planar=True)
+            return wr.value
         rc = lib().nvh_stream_synth_pcm(self._h, fmt, None, C.c_void_p(d_ptr), int(capacity), C.byref(wr))
         self._note_parse_error(rc, wr.value, "nvh_stream_synth_pcm")
         return wr.value
 
-    def _note_parse_error(self, rc, written, where):
+    def _note_parse_error(self, rc, written, where, planar=False):
         """A synthesis call that returns an error code together with PCM (GPU-parse mode: a packet of the batch made the
         parser fail and the batch was parsed again without them): the PCM is complete; the errors are kept in
         `parse_errors` = [(NvhError, floats of this batch's PCM that precede the failing packet), ...] in stream order for
-        the caller to raise where the reference would have thrown.  Any other failure raises here."""
+        the caller to raise where the reference would have thrown (planar calls: samples per channel that precede it).  Any
+        other failure raises here."""
         self.parse_errors = []
         if rc == native.OK:
             return
@@ -633,7 +695,8 @@ class Stream:
         codes, before = np.zeros(n.value, np.int32), np.zeros(n.value, np.int64)
         check(lib().nvh_stream_parse_errors(self._h, codes.ctypes.data_as(C.POINTER(C.c_int32)), before.ctypes.data_as(C.POINTER(C.c_int64)),
                                             n.value, C.byref(n)), "nvh_stream_parse_errors")
-        self.parse_errors = [(native.NvhError(int(c), where), int(b) * self.channels) for c, b in zip(codes, before)]
+        per = 1 if planar else self.channels
+        self.parse_errors = [(native.NvhError(int(c), where), int(b) * per) for c, b in zip(codes, before)]
 
     def upload_batch(self):
         h = C.c_void_p()
@@ -664,9 +727,14 @@ class Stream:
 class StreamDecoder:
     """IStreamDecoder-shaped object (Contracts/IStreamDecoder.cs:9-105) over a packet list."""
 
-    def __init__(self, ctx, packets, granules=None, flags=None, batch_frames=1024, gpu_parse=False, sample_format="f32"):
+    def __init__(self, ctx, packets, granules=None, flags=None, batch_frames=1024, gpu_parse=False, sample_format="f32",
+                 layout="interleaved"):
         # sample_format "s16": the ring is decoded as int16 (ov_read's conversion, in the kernels); Read then takes int16 buffers
         self._dtype = _sample_format(sample_format)
+        # layout "planar": the ring is channel-planar PCM (the kernels' _planar twins); Read then takes (Channels, m) buffers and
+        # counts samples per channel.  The bookkeeping below (ring position, roll-forward, error positions) stays in interleaved
+        # units -- whole multiples of Channels -- either way.
+        self._planar = _layout(layout)
         if len(packets) < 3:
             raise native.NvhError(native.ERR_NOT_VORBIS, "StreamDecoder")
         self._stream = Stream(ctx, packets[0], packets[1], packets[2])
@@ -768,14 +836,15 @@ class StreamDecoder:
             pcm = None
             if frames:
                 # the ring is only replaced once it has been read out, so the stream's pinned buffer can be it
-                pcm = self._stream.synth_host(pinned=True, dtype=self._dtype)
+                pcm = self._stream.synth_host(pinned=True, dtype=self._dtype, planar=self._planar)
             got = pcm is not None and pcm.size > 0
             if got:
                 self._ring = pcm
                 self._ring_pos = 0
             size = pcm.size if got else 0
             if self._stream.parse_errors:  # GPU-parse mode: packets inside the batch failed
-                self._pending_errors = [(e, min(at, size)) for e, at in self._stream.parse_errors]
+                per = self.Channels if self._planar else 1  # (planar calls report samples per channel)
+                self._pending_errors = [(e, min(at * per, size)) for e, at in self._stream.parse_errors]
                 self._stream.parse_errors = []
             if push_error is not None:  # host-parse mode: everything parsed before the packet comes first
                 self._pending_errors.append((push_error, size))
@@ -786,8 +855,11 @@ class StreamDecoder:
         return False
 
     def Read(self, buffer, offset, count):
-        """StreamDecoder.Read (StreamDecoder.cs:320-389)."""
+        """StreamDecoder.Read (StreamDecoder.cs:320-389).  Planar layout: buffer is a (Channels, m) array, offset and count are
+        samples per channel, and so is the return value."""
         ch = self.Channels
+        if self._planar:
+            return self._read_planar(buffer, offset, count)
         if offset < 0 or offset + count > len(buffer):
             raise IndexError("offset")  # ArgumentOutOfRangeException
         if count % ch != 0:
@@ -815,6 +887,35 @@ class StreamDecoder:
             self._ring_pos += take
             idx += take
         return idx - offset
+
+    def _read_planar(self, buffer, offset, count):
+        ch = self.Channels
+        if getattr(buffer, "dtype", None) != self._dtype:
+            raise TypeError("this decoder delivers %s samples: the buffer must be a numpy %s array" % (self._dtype, self._dtype))
+        if buffer.ndim != 2 or buffer.shape[0] != ch:
+            raise ValueError("planar layout: the buffer must have shape (%d, m), not %s" % (ch, buffer.shape))
+        if offset < 0 or count < 0 or offset + count > buffer.shape[1]:
+            raise IndexError("offset")  # ArgumentOutOfRangeException
+        idx, tgt = offset * ch, (offset + count) * ch  # interleaved units, as the ring's bookkeeping
+        while idx < tgt:
+            if self._pending_errors and self._ring_pos >= self._pending_errors[0][1]:
+                raise self._pending_errors.pop(0)[0]
+            if self._ring_pos >= self._ring.size:
+                if not self._refill():
+                    break
+            if self._skip:
+                drop = min(self._skip, self._ring.size - self._ring_pos)
+                self._ring_pos += drop
+                self._skip -= drop
+                continue
+            take = min(tgt - idx, self._ring.size - self._ring_pos)
+            if self._pending_errors:
+                take = min(take, self._pending_errors[0][1] - self._ring_pos)
+            r, b, k = self._ring_pos // ch, idx // ch, take // ch
+            buffer[:, b:b + k] = self._ring[:, r:r + k]
+            self._ring_pos += take
+            idx += take
+        return idx // ch - offset
 
     # ---- seeking (StreamDecoder.cs:562-628) ----
     def _granule_index(self):
@@ -970,10 +1071,14 @@ class StreamDecoder:
 class VorbisReader:
     """VorbisReader-shaped facade (VorbisReader.cs): first logical stream of an .ogg file or byte string."""
 
-    def __init__(self, source, ctx=None, device=0, batch_frames=8192, gpu_parse=True, forward_only=False, sample_format="f32"):
+    def __init__(self, source, ctx=None, device=0, batch_frames=8192, gpu_parse=True, forward_only=False, sample_format="f32",
+                 layout="interleaved"):
         # sample_format: "f32" (float32 PCM, the reference's) or "s16" (int16, libvorbis ov_read's conversion in the kernels)
         self._dtype = _sample_format(sample_format)
         self._sample_format = sample_format
+        # layout: "interleaved" (the reference's) or "planar" (ReadSamples takes (Channels, m) arrays, counts per channel)
+        self._planar = _layout(layout)
+        self._layout = layout
         # gpu_parse: parse the packets on the GPU too when the stream shape allows it (StreamDecoder falls back silently)
         # forward_only: read the container the way the reference reads a source that cannot seek (ContainerReader picks
         # ForwardOnlyPageReader for !stream.CanSeek, Ogg/ContainerReader.cs); SeekTo then raises as IPacketProvider.CanSeek is false
@@ -998,7 +1103,7 @@ class VorbisReader:
             raise native.NvhError(native.ERR_NOT_VORBIS, "VorbisReader")  # ArgumentException: could not load the container
         self._stream_index = 0
         self._dec = StreamDecoder(self._ctx, demux_ogg_array(data, self._stream_ids[0], self._forward_only), None, None, batch_frames, gpu_parse,
-                                  sample_format)
+                                  sample_format, layout)
         if self._forward_only:
             self._dec.can_seek = False
         else:
@@ -1029,7 +1134,7 @@ class VorbisReader:
         clip = self.ClipSamples
         if index not in self._decs:
             self._decs[index] = StreamDecoder(self._ctx, demux_ogg_array(self._data, self._stream_ids[index], self._forward_only), None,
-                                              None, self._batch_frames, self._gpu_parse, self._sample_format)
+                                              None, self._batch_frames, self._gpu_parse, self._sample_format, self._layout)
             if self._forward_only:
                 self._decs[index].can_seek = False
             else:
@@ -1074,9 +1179,16 @@ class VorbisReader:
         self._dec.ClipSamples = on
 
     def ReadSamples(self, buffer, offset=0, count=None):
-        """VorbisReader.ReadSamples(float[], int, int) (VorbisReader.cs:336-345)."""
+        """VorbisReader.ReadSamples(float[], int, int) (VorbisReader.cs:336-345).  Planar layout: a (Channels, m) buffer,
+        offset and count in samples per channel."""
         if getattr(buffer, "dtype", None) != self._dtype:
             raise TypeError("this reader delivers %s samples: the buffer must be a numpy %s array" % (self._dtype, self._dtype))
+        if self._planar:
+            if buffer.ndim != 2 or buffer.shape[0] != self.Channels:
+                raise ValueError("planar layout: the buffer must have shape (%d, m), not %s" % (self.Channels, buffer.shape))
+            if count is None:
+                count = buffer.shape[1] - offset
+            return self._dec.Read(buffer, offset, count) if count > 0 else 0
         if count is None:
             count = len(buffer) - offset
         count -= count % self.Channels
@@ -1085,7 +1197,16 @@ class VorbisReader:
         return 0
 
     def read_all(self):
+        """Everything from the current position: interleaved, or (Channels, T) in the planar layout."""
         chunks = []
+        if self._planar:
+            buf = np.empty((self.Channels, 65536), dtype=self._dtype)
+            while True:
+                n = self.ReadSamples(buf, 0, buf.shape[1])
+                if n <= 0:
+                    break
+                chunks.append(buf[:, :n].copy())
+            return np.concatenate(chunks, axis=1) if chunks else np.zeros((self.Channels, 0), dtype=self._dtype)
         buf = np.empty(65536 * self.Channels, dtype=self._dtype)
         while True:
             n = self.ReadSamples(buf, 0, buf.size)

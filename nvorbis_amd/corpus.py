@@ -552,8 +552,8 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
     PCM crosses PCIe.  tune_process: see _tune_malloc (process-wide, opt-in)."""
     import torch
 
-    from .reader import Context, Stream, demux_ogg_array, index_ogg_array
-    planar = _layout_planar(layout)
+    from .reader import Context, Stream, _layout, demux_ogg_array, index_ogg_array
+    planar = _layout(layout)
     n = len(files)
     full_index = bool(os.environ.get("NVH_CORPUS_FULL_INDEX"))  # A/B aid: the round-5 index (checksums + a copy of every packet)
 
@@ -734,12 +734,6 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
         if timings is not None:
             timings["files_reindexed"] = sorted(redo)
     return arena, views
-
-
-def _layout_planar(layout):
-    if layout not in ("interleaved", "planar"):
-        raise ValueError("layout must be 'interleaved' or 'planar', not %r" % (layout,))
-    return layout == "planar"
 
 
 def decode_files_threaded(files, device=0, workers=16, batch_frames=4096, gpu_parse=False):

@@ -574,11 +574,154 @@ extern "C" int nvh_stream_pending(const nvh_stream* s, int* frames, int64_t* pcm
   });
 }
 
-// The output formats of the synthesis entry points (NVH_PCM_*); a 16-bit device destination must be 16-byte aligned (the
-// stereo twins store eight samples at a time).
-static bool pcm_format_ok(int format) { return format == NVH_PCM_F32 || format == NVH_PCM_S16; }
-static bool pcm_dest_ok(int format, const void* d_pcm) {
-  return format != NVH_PCM_S16 || ((uintptr_t)d_pcm & 15u) == 0;
+// ---- synthesis into PCM (PcmOut: format x layout) ----
+// A host destination is staged on the device and read back in one copy.  Interleaved PCM is one plane of n * channels samples.
+// Channel-planar PCM (the _planar calls: channel c's samples at base + c * plane_stride, counts per channel) is staged as
+// [C, n4] planes (n4: the batch's samples per channel rounded up to whole groups of four, so that the emission's vector stores
+// run) and read back as one 2-D copy; one plain copy when the planes are contiguous.
+static int64_t planar_stage_stride(int64_t n) { return (n + 3) & ~(int64_t)3; }
+static int64_t planar_launch_stride(int64_t plane_stride) { return plane_stride > 0 ? plane_stride : 4; }  // (0 only with no samples)
+
+// One batch's PCM in the layout of `out`: `len` samples in each of `planes` planes (the unit of *written), staged at `stage`
+// samples per plane on the device, at `stride` samples per plane in the caller's host destination
+struct PcmShape {
+  int64_t len, stage, stride;
+  int planes;
+  PcmShape(const PcmOut& out, int64_t n, int ch)
+      : len(out.planar() ? n : n * ch), stage(out.planar() ? planar_stage_stride(n) : len),
+        stride(out.planar() ? out.plane_stride : len), planes(out.planar() ? ch : 1) {}
+  size_t stage_bytes(size_t sb) const { return (size_t)(stage > 0 ? stage : 1) * (size_t)planes * sb; }
+  PcmOut staged(const PcmOut& out) const { return {out.format, out.planar() ? planar_launch_stride(stage) : 0}; }
+};
+
+// `n` samples of each of `planes` planes from device planes at stride `src_stride` to host planes at stride `dst_stride`
+static hipError_t planar_readback(void* dst, int64_t dst_stride, const void* src, int64_t src_stride, int64_t n, int planes,
+                                  size_t sb, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (dst_stride == n && src_stride == n) return hipMemcpyAsync(dst, src, (size_t)n * (size_t)planes * sb, hipMemcpyDeviceToHost, st);
+  return hipMemcpy2DAsync(dst, (size_t)dst_stride * sb, src, (size_t)src_stride * sb, (size_t)n * sb, (size_t)planes,
+                          hipMemcpyDeviceToHost, st);
+}
+
+// Whether host memory is page-locked (nvh_pinned_alloc, hipHostMalloc, hipHostRegister): the copy engine writes it directly
+static bool host_pinned(const void* p) {
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) == hipSuccess) return attr.type == hipMemoryTypeHost;
+  (void)hipGetLastError();  // plain pageable memory: not an error
+  return false;
+}
+
+// nvh_stream_synth_pcm / _planar past their own argument checks; `capacity` in the unit of *written (samples, or samples per
+// channel for planar PCM)
+static int stream_synth(nvh_stream* s, const PcmOut& out, void* pcm_host, void* d_pcm, int64_t capacity, int64_t* written) {
+  if (!s->ctx) return NVH_ERR_NO_GPU;
+  if (s->flight[0].on || s->flight[1].on) return NVH_ERR_ARGUMENT;  // pipelined batches outstanding: end them first
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  const int ch = s->setup.channels;
+  if (s->pending.frames.empty()) return NVH_OK;
+  if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
+  if (capacity < PcmShape(out, s->pending.pcm_samples, ch).len) return NVH_ERR_ARGUMENT;
+  nvh_batch* b = &s->scratch;
+  s->replay_error = NVH_OK;
+  s->replay_errors.clear();
+  int rc = batch_upload(s, b);
+  if (rc != NVH_OK) return rc;
+  // GPU-parse mode: a batch with a throwing packet was parsed again on the host (nvh_launch.hip: replay_on_host); the
+  // throwing packet contributes nothing, so the batch may emit less than the look-ahead said
+  const PcmShape P(out, b->pcm_samples, ch);
+  if (capacity < P.len) return NVH_ERR_ARGUMENT;
+  const size_t sb = out.sample_bytes();
+  void* dst = d_pcm;
+  if (!dst) {
+    if ((rc = s->pcm.reserve(P.stage_bytes(sb))) != NVH_OK) return rc;
+    dst = s->pcm.p;
+  }
+  rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
+                    d_pcm ? out : P.staged(out));
+  if (rc != NVH_OK) return rc;
+  hipStream_t st = s->ctx->stream;
+  if (b->last_decoded >= 0) s->carry_cur ^= 1;  // the batch wrote its last block's tail into the other buffer
+  // one read-back, one synchronisation: PCM and the two flag words land in a pinned bounce buffer.  A destination in pinned
+  // host memory is written by the copy engine directly; anything else goes through the bounce buffer and one memcpy per plane
+  // on this thread.
+  const bool direct = pcm_host && P.len > 0 && host_pinned(pcm_host);
+  const size_t plane_bytes = (size_t)P.len * sb;
+  const size_t bounce = (pcm_host && !direct) ? plane_bytes * (size_t)P.planes : 0;
+  if ((rc = s->h_pcm.reserve(bounce + 2 * sizeof(int))) != NVH_OK) return rc;
+  int* h_flags = (int*)((uint8_t*)s->h_pcm.p + bounce);
+  if (pcm_host) HIP_TRY(planar_readback(direct ? pcm_host : s->h_pcm.p, direct ? P.stride : P.len, dst, P.stage, P.len, P.planes, sb, st));
+  HIP_TRY(hipMemcpyAsync(h_flags, s->flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(nvh_wait_stream(s->ctx, st));
+  if (bounce)
+    for (int c = 0; c < P.planes; c++)
+      std::memcpy((uint8_t*)pcm_host + (size_t)c * (size_t)P.stride * sb, (const uint8_t*)s->h_pcm.p + (size_t)c * plane_bytes, plane_bytes);
+  if (h_flags[0] || h_flags[1]) HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), st));
+  if (h_flags[1]) s->has_clipped = 1;
+  if (h_flags[0]) return NVH_ERR_RUNTIME;  // inverse_dB_table / wMap index out of range in the reference
+  if (written) *written = P.len;
+  // a packet of this batch made the parser fail (the code nvh_stream_push_packet returns in host-parse mode): the PCM of
+  // every other packet is complete and *written says so; nvh_stream_parse_errors tells where the exceptions belong
+  return s->replay_error;
+}
+
+// Pipelined form of stream_synth for a destination in page-locked host memory: begin queues upload, (GPU parse,) synthesis and
+// -- on a copy stream of its own -- the transfer of the PCM, and returns; end waits for the OLDEST outstanding batch.  The
+// transfer of batch i (8 KB per stereo long frame over PCIe: the longest step of the end-to-end path) then runs while the host
+// pushes batch i+1 and the GPU parses and synthesises it.  (The format and layout are the call's, not the stream's: the carried
+// tail between batches is float planes either way, and nvh_stream_synth_end only waits for the copy this call queued.)
+static int stream_synth_begin(nvh_stream* s, const PcmOut& out, void* pcm_host, int64_t capacity, int64_t* expected) {
+  if (!s->ctx) return NVH_ERR_NO_GPU;
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  const int slot = s->flight_next;
+  nvh_stream::Flight& F = s->flight[slot];
+  if (F.on) return NVH_ERR_ARGUMENT;                              // two batches outstanding already
+  if (!host_pinned(pcm_host)) return NVH_ERR_ARGUMENT;            // the copy engine needs page-locked memory (nvh_pinned_alloc)
+  const int ch = s->setup.channels;
+  hipStream_t st = s->ctx->stream;
+  if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+  if (!F.kernels) HIP_TRY(hipEventCreateWithFlags(&F.kernels, hipEventDisableTiming));
+  if (!F.done) HIP_TRY(hipEventCreateWithFlags(&F.done, hipEventDisableTiming));
+  // the staging image of the previous batch's descriptors is about to be overwritten: its upload (and kernels) must be through
+  HIP_TRY(hipStreamSynchronize(st));
+  F.need = 0;
+  F.replay_error = NVH_OK;
+  F.replay_errors.clear();
+  if (s->pending.frames.empty()) {  // nothing to do: an outstanding "batch" of zero samples keeps begin / end paired
+    HIP_TRY(hipEventRecord(F.done, st));
+    F.on = true;
+    s->flight_next ^= 1;
+    return NVH_OK;
+  }
+  if (capacity < PcmShape(out, s->pending.pcm_samples, ch).len) return NVH_ERR_ARGUMENT;
+  nvh_batch* b = &s->scratch;
+  s->replay_error = NVH_OK;
+  s->replay_errors.clear();
+  int rc = batch_upload(s, b);
+  if (rc != NVH_OK) return rc;
+  const PcmShape P(out, b->pcm_samples, ch);
+  if (capacity < P.len) return NVH_ERR_ARGUMENT;
+  const size_t sb = out.sample_bytes();
+  if ((rc = s->pcm2[slot].reserve(P.stage_bytes(sb))) != NVH_OK) return rc;
+  if ((rc = s->h_flags2.reserve(4 * sizeof(int))) != NVH_OK) return rc;
+  void* dst = s->pcm2[slot].p;
+  rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
+                    P.staged(out));
+  if (rc != NVH_OK) return rc;
+  if (b->last_decoded >= 0) s->carry_cur ^= 1;
+  // this batch's flag words, then a clean pair for the next one (all on the launch stream, in order)
+  HIP_TRY(hipMemcpyAsync((int*)s->h_flags2.p + 2 * slot, s->flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), st));
+  HIP_TRY(hipEventRecord(F.kernels, st));
+  HIP_TRY(hipStreamWaitEvent(s->copy_stream, F.kernels, 0));
+  HIP_TRY(planar_readback(pcm_host, P.stride, dst, P.stage, P.len, P.planes, sb, s->copy_stream));
+  HIP_TRY(hipEventRecord(F.done, s->copy_stream));
+  F.need = P.len;  // (nvh_stream_synth_end reports it: samples per channel for a planar flight)
+  F.replay_error = s->replay_error;
+  F.replay_errors = s->replay_errors;
+  F.on = true;
+  s->flight_next ^= 1;
+  if (expected) *expected = P.len;
+  return NVH_OK;
 }
 
 extern "C" int nvh_stream_synth(nvh_stream* s, float* pcm_host, float* d_pcm, int64_t capacity, int64_t* written) {
@@ -587,135 +730,42 @@ extern "C" int nvh_stream_synth(nvh_stream* s, float* pcm_host, float* d_pcm, in
 
 extern "C" int nvh_stream_synth_pcm(nvh_stream* s, int format, void* pcm_host, void* d_pcm, int64_t capacity, int64_t* written) {
   return nvh_guard([&]() -> int {
-    if (!s || (pcm_host && d_pcm) || !pcm_format_ok(format) || !pcm_dest_ok(format, d_pcm)) return NVH_ERR_ARGUMENT;
+    const PcmOut out{format, 0};
+    if (!s || (pcm_host && d_pcm) || !PcmOut::format_ok(format) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
     if (written) *written = 0;
-    if (!s->ctx) return NVH_ERR_NO_GPU;
-    if (s->flight[0].on || s->flight[1].on) return NVH_ERR_ARGUMENT;  // pipelined batches outstanding: end them first
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    const int ch = s->setup.channels;
-    int64_t need = s->pending.pcm_samples * ch;
-    if (s->pending.frames.empty()) return NVH_OK;
-    if (need > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
-    if (capacity < need) return NVH_ERR_ARGUMENT;
-    nvh_batch* b = &s->scratch;
-    s->replay_error = NVH_OK;
-    s->replay_errors.clear();
-    int rc = batch_upload(s, b);
-    if (rc != NVH_OK) return rc;
-    // GPU-parse mode: a batch with a throwing packet was parsed again on the host (nvh_launch.hip: replay_on_host); the
-    // throwing packet contributes nothing, so the batch may emit less than the look-ahead said
-    need = b->pcm_samples * ch;
-    if (capacity < need) return NVH_ERR_ARGUMENT;
-    const size_t sample_bytes = pcm_sample_bytes(format);
-    void* dst = d_pcm;
-    if (!dst) {
-      if ((rc = s->pcm.reserve((size_t)(need > 0 ? need : 1) * sample_bytes)) != NVH_OK) return rc;
-      dst = s->pcm.p;
-    }
-    rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
-                      format);
-    if (rc != NVH_OK) return rc;
-    hipStream_t st = s->ctx->stream;
-    if (b->last_decoded >= 0) s->carry_cur ^= 1;  // the batch wrote its last block's tail into the other buffer
-    // one read-back, one synchronisation: PCM and the two flag words land in a pinned bounce buffer
-    size_t pcm_bytes = pcm_host ? (size_t)need * sample_bytes : 0;
-    // a destination in pinned host memory (nvh_pinned_alloc, hipHostMalloc, hipHostRegister) is written by the copy
-    // engine directly; anything else goes through the bounce buffer and one memcpy on this thread
-    bool direct = false;
-    if (pcm_bytes) {
-      hipPointerAttribute_t attr;
-      if (hipPointerGetAttributes(&attr, pcm_host) == hipSuccess) direct = attr.type == hipMemoryTypeHost;
-      else (void)hipGetLastError();  // plain pageable memory: not an error
-    }
-    const size_t bounce = direct ? 0 : pcm_bytes;
-    if ((rc = s->h_pcm.reserve(bounce + 2 * sizeof(int))) != NVH_OK) return rc;
-    int* h_flags = (int*)((uint8_t*)s->h_pcm.p + bounce);
-    if (pcm_bytes) HIP_TRY(hipMemcpyAsync(direct ? (void*)pcm_host : s->h_pcm.p, dst, pcm_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_flags, s->flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(nvh_wait_stream(s->ctx, st));
-    if (bounce) std::memcpy(pcm_host, s->h_pcm.p, bounce);
-    if (h_flags[0] || h_flags[1]) HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), st));
-    if (h_flags[1]) s->has_clipped = 1;
-    if (h_flags[0]) return NVH_ERR_RUNTIME;  // inverse_dB_table / wMap index out of range in the reference
-    if (written) *written = need;
-    // a packet of this batch made the parser fail (the code nvh_stream_push_packet returns in host-parse mode): the PCM of
-    // every other packet is complete and *written says so; nvh_stream_parse_errors tells where the exceptions belong
-    return s->replay_error;
+    return stream_synth(s, out, pcm_host, d_pcm, capacity, written);
   });
 }
 
-// Pipelined form of nvh_stream_synth for a destination in page-locked host memory: begin queues upload, (GPU parse,) synthesis and
-// -- on a copy stream of its own -- the transfer of the PCM, and returns; end waits for the OLDEST outstanding batch.  The
-// transfer of batch i (8 KB per stereo long frame over PCIe: the longest step of the end-to-end path) then runs while the host
-// pushes batch i+1 and the GPU parses and synthesises it.
+extern "C" int nvh_stream_synth_planar(nvh_stream* s, int format, void* pcm_host, void* d_pcm, int64_t plane_stride, int64_t* written) {
+  return nvh_guard([&]() -> int {
+    const PcmOut out{format, planar_launch_stride(plane_stride)};
+    if (!s || (pcm_host && d_pcm) || !PcmOut::format_ok(format) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
+    if (written) *written = 0;
+    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
+    if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
+    return stream_synth(s, out, pcm_host, d_pcm, plane_stride, written);
+  });
+}
+
 extern "C" int nvh_stream_synth_begin(nvh_stream* s, float* pcm_host, int64_t capacity, int64_t* expected) {
   return nvh_stream_synth_begin_pcm(s, NVH_PCM_F32, pcm_host, capacity, expected);
 }
 
-// (the format is the call's, not the stream's: the carried tail between batches is float planes either way, and
-// nvh_stream_synth_end only waits for the copy this call queued)
 extern "C" int nvh_stream_synth_begin_pcm(nvh_stream* s, int format, void* pcm_host, int64_t capacity, int64_t* expected) {
   return nvh_guard([&]() -> int {
-    if (!s || !pcm_host || !pcm_format_ok(format)) return NVH_ERR_ARGUMENT;
+    if (!s || !pcm_host || !PcmOut::format_ok(format)) return NVH_ERR_ARGUMENT;
     if (expected) *expected = 0;
-    if (!s->ctx) return NVH_ERR_NO_GPU;
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    const int slot = s->flight_next;
-    nvh_stream::Flight& F = s->flight[slot];
-    if (F.on) return NVH_ERR_ARGUMENT;  // two batches outstanding already
-    {
-      hipPointerAttribute_t attr;
-      if (hipPointerGetAttributes(&attr, pcm_host) != hipSuccess || attr.type != hipMemoryTypeHost) {
-        (void)hipGetLastError();
-        return NVH_ERR_ARGUMENT;  // the copy engine needs page-locked memory (nvh_pinned_alloc)
-      }
-    }
-    const int ch = s->setup.channels;
-    hipStream_t st = s->ctx->stream;
-    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-    if (!F.kernels) HIP_TRY(hipEventCreateWithFlags(&F.kernels, hipEventDisableTiming));
-    if (!F.done) HIP_TRY(hipEventCreateWithFlags(&F.done, hipEventDisableTiming));
-    // the staging image of the previous batch's descriptors is about to be overwritten: its upload (and kernels) must be through
-    HIP_TRY(hipStreamSynchronize(st));
-    F.need = 0;
-    F.replay_error = NVH_OK;
-    F.replay_errors.clear();
-    if (s->pending.frames.empty()) {  // nothing to do: an outstanding "batch" of zero samples keeps begin / end paired
-      HIP_TRY(hipEventRecord(F.done, st));
-      F.on = true;
-      s->flight_next ^= 1;
-      return NVH_OK;
-    }
-    if (capacity < s->pending.pcm_samples * ch) return NVH_ERR_ARGUMENT;
-    nvh_batch* b = &s->scratch;
-    s->replay_error = NVH_OK;
-    s->replay_errors.clear();
-    int rc = batch_upload(s, b);
-    if (rc != NVH_OK) return rc;
-    const int64_t need = b->pcm_samples * ch;
-    if (capacity < need) return NVH_ERR_ARGUMENT;
-    const size_t sample_bytes = pcm_sample_bytes(format);
-    if ((rc = s->pcm2[slot].reserve((size_t)(need > 0 ? need : 1) * sample_bytes)) != NVH_OK) return rc;
-    if ((rc = s->h_flags2.reserve(4 * sizeof(int))) != NVH_OK) return rc;
-    void* dst = s->pcm2[slot].p;
-    rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
-                      format);
-    if (rc != NVH_OK) return rc;
-    if (b->last_decoded >= 0) s->carry_cur ^= 1;
-    // this batch's flag words, then a clean pair for the next one (all on the launch stream, in order)
-    HIP_TRY(hipMemcpyAsync((int*)s->h_flags2.p + 2 * slot, s->flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), st));
-    HIP_TRY(hipEventRecord(F.kernels, st));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, F.kernels, 0));
-    if (need > 0) HIP_TRY(hipMemcpyAsync(pcm_host, dst, (size_t)need * sample_bytes, hipMemcpyDeviceToHost, s->copy_stream));
-    HIP_TRY(hipEventRecord(F.done, s->copy_stream));
-    F.need = need;
-    F.replay_error = s->replay_error;
-    F.replay_errors = s->replay_errors;
-    F.on = true;
-    s->flight_next ^= 1;
-    if (expected) *expected = need;
-    return NVH_OK;
+    return stream_synth_begin(s, PcmOut{format, 0}, pcm_host, capacity, expected);
+  });
+}
+
+extern "C" int nvh_stream_synth_begin_planar(nvh_stream* s, int format, void* pcm_host, int64_t plane_stride, int64_t* expected) {
+  return nvh_guard([&]() -> int {
+    if (!s || !pcm_host || !PcmOut::format_ok(format)) return NVH_ERR_ARGUMENT;
+    if (expected) *expected = 0;
+    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
+    return stream_synth_begin(s, PcmOut{format, planar_launch_stride(plane_stride)}, pcm_host, plane_stride, expected);
   });
 }
 
@@ -740,141 +790,6 @@ extern "C" int nvh_stream_synth_end(nvh_stream* s, int64_t* written) {
     }
     if (written) *written = F.need;
     return F.replay_error;
-  });
-}
-
-// ---- channel-planar PCM (the _planar twins): channel c's samples at base + c * plane_stride, counts per channel ----
-// A host destination is staged on the device as [C, n4] planes (n4: the batch's samples per channel rounded up to whole groups of
-// four, so that the emission's vector stores run) and read back as one 2-D copy; one plain copy when the planes are contiguous.
-static int64_t planar_stage_stride(int64_t n) { return (n + 3) & ~(int64_t)3; }
-static int64_t planar_launch_stride(int64_t plane_stride) { return plane_stride > 0 ? plane_stride : 4; }  // (0 only with no samples)
-static bool planar_dest_ok(int format, const void* d_pcm) { return ((uintptr_t)d_pcm % pcm_sample_bytes(format)) == 0; }
-
-// `n` samples per channel of `ch` planes from device planes at stride `src_stride` to host planes at stride `dst_stride`
-static hipError_t planar_readback(void* dst, int64_t dst_stride, const void* src, int64_t src_stride, int64_t n, int ch, size_t sb,
-                                  hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  if (dst_stride == n && src_stride == n) return hipMemcpyAsync(dst, src, (size_t)n * (size_t)ch * sb, hipMemcpyDeviceToHost, st);
-  return hipMemcpy2DAsync(dst, (size_t)dst_stride * sb, src, (size_t)src_stride * sb, (size_t)n * sb, (size_t)ch, hipMemcpyDeviceToHost, st);
-}
-
-extern "C" int nvh_stream_synth_planar(nvh_stream* s, int format, void* pcm_host, void* d_pcm, int64_t plane_stride, int64_t* written) {
-  return nvh_guard([&]() -> int {
-    if (!s || (pcm_host && d_pcm) || !pcm_format_ok(format) || !planar_dest_ok(format, d_pcm)) return NVH_ERR_ARGUMENT;
-    if (written) *written = 0;
-    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
-    if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
-    if (!s->ctx) return NVH_ERR_NO_GPU;
-    if (s->flight[0].on || s->flight[1].on) return NVH_ERR_ARGUMENT;  // pipelined batches outstanding: end them first
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    const int ch = s->setup.channels;
-    if (s->pending.frames.empty()) return NVH_OK;
-    nvh_batch* b = &s->scratch;
-    s->replay_error = NVH_OK;
-    s->replay_errors.clear();
-    int rc = batch_upload(s, b);
-    if (rc != NVH_OK) return rc;
-    const int64_t n = b->pcm_samples;  // (GPU-parse mode: at most the look-ahead's count, nvh_stream_synth_pcm)
-    if (plane_stride < n) return NVH_ERR_ARGUMENT;
-    const size_t sb = pcm_sample_bytes(format);
-    const int64_t n4 = planar_stage_stride(n);
-    void* dst = d_pcm;
-    if (!dst) {
-      if ((rc = s->pcm.reserve((size_t)(n4 > 0 ? n4 : 1) * (size_t)ch * sb)) != NVH_OK) return rc;
-      dst = s->pcm.p;
-    }
-    rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
-                      format, planar_launch_stride(d_pcm ? plane_stride : n4));
-    if (rc != NVH_OK) return rc;
-    hipStream_t st = s->ctx->stream;
-    if (b->last_decoded >= 0) s->carry_cur ^= 1;
-    // pinned host planes are written by the copy engine directly; anything else through the bounce buffer ([C, n]) and one
-    // memcpy per plane on this thread
-    bool direct = false;
-    if (pcm_host && n > 0) {
-      hipPointerAttribute_t attr;
-      if (hipPointerGetAttributes(&attr, pcm_host) == hipSuccess) direct = attr.type == hipMemoryTypeHost;
-      else (void)hipGetLastError();
-    }
-    const size_t bounce = (pcm_host && !direct) ? (size_t)n * (size_t)ch * sb : 0;
-    if ((rc = s->h_pcm.reserve(bounce + 2 * sizeof(int))) != NVH_OK) return rc;
-    int* h_flags = (int*)((uint8_t*)s->h_pcm.p + bounce);
-    if (pcm_host) HIP_TRY(planar_readback(direct ? pcm_host : s->h_pcm.p, direct ? plane_stride : n, dst, n4, n, ch, sb, st));
-    HIP_TRY(hipMemcpyAsync(h_flags, s->flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(nvh_wait_stream(s->ctx, st));
-    if (bounce)
-      for (int c = 0; c < ch; c++)
-        std::memcpy((uint8_t*)pcm_host + (size_t)c * (size_t)plane_stride * sb, (const uint8_t*)s->h_pcm.p + (size_t)c * (size_t)n * sb,
-                    (size_t)n * sb);
-    if (h_flags[0] || h_flags[1]) HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), st));
-    if (h_flags[1]) s->has_clipped = 1;
-    if (h_flags[0]) return NVH_ERR_RUNTIME;
-    if (written) *written = n;
-    return s->replay_error;
-  });
-}
-
-extern "C" int nvh_stream_synth_begin_planar(nvh_stream* s, int format, void* pcm_host, int64_t plane_stride, int64_t* expected) {
-  return nvh_guard([&]() -> int {
-    if (!s || !pcm_host || !pcm_format_ok(format)) return NVH_ERR_ARGUMENT;
-    if (expected) *expected = 0;
-    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
-    if (!s->ctx) return NVH_ERR_NO_GPU;
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    const int slot = s->flight_next;
-    nvh_stream::Flight& F = s->flight[slot];
-    if (F.on) return NVH_ERR_ARGUMENT;  // two batches outstanding already
-    {
-      hipPointerAttribute_t attr;
-      if (hipPointerGetAttributes(&attr, pcm_host) != hipSuccess || attr.type != hipMemoryTypeHost) {
-        (void)hipGetLastError();
-        return NVH_ERR_ARGUMENT;  // the copy engine needs page-locked memory (nvh_pinned_alloc)
-      }
-    }
-    const int ch = s->setup.channels;
-    hipStream_t st = s->ctx->stream;
-    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-    if (!F.kernels) HIP_TRY(hipEventCreateWithFlags(&F.kernels, hipEventDisableTiming));
-    if (!F.done) HIP_TRY(hipEventCreateWithFlags(&F.done, hipEventDisableTiming));
-    HIP_TRY(hipStreamSynchronize(st));  // (nvh_stream_synth_begin_pcm: the previous batch's staging image)
-    F.need = 0;
-    F.replay_error = NVH_OK;
-    F.replay_errors.clear();
-    if (s->pending.frames.empty()) {
-      HIP_TRY(hipEventRecord(F.done, st));
-      F.on = true;
-      s->flight_next ^= 1;
-      return NVH_OK;
-    }
-    nvh_batch* b = &s->scratch;
-    s->replay_error = NVH_OK;
-    s->replay_errors.clear();
-    int rc = batch_upload(s, b);
-    if (rc != NVH_OK) return rc;
-    const int64_t n = b->pcm_samples;
-    if (plane_stride < n) return NVH_ERR_ARGUMENT;
-    const size_t sb = pcm_sample_bytes(format);
-    const int64_t n4 = planar_stage_stride(n);
-    if ((rc = s->pcm2[slot].reserve((size_t)(n4 > 0 ? n4 : 1) * (size_t)ch * sb)) != NVH_OK) return rc;
-    if ((rc = s->h_flags2.reserve(4 * sizeof(int))) != NVH_OK) return rc;
-    void* dst = s->pcm2[slot].p;
-    rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
-                      format, planar_launch_stride(n4));
-    if (rc != NVH_OK) return rc;
-    if (b->last_decoded >= 0) s->carry_cur ^= 1;
-    HIP_TRY(hipMemcpyAsync((int*)s->h_flags2.p + 2 * slot, s->flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), st));
-    HIP_TRY(hipEventRecord(F.kernels, st));
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, F.kernels, 0));
-    HIP_TRY(planar_readback(pcm_host, plane_stride, dst, n4, n, ch, sb, s->copy_stream));
-    HIP_TRY(hipEventRecord(F.done, s->copy_stream));
-    F.need = n;  // (nvh_stream_synth_end reports it: samples per channel for a planar flight)
-    F.replay_error = s->replay_error;
-    F.replay_errors = s->replay_errors;
-    F.on = true;
-    s->flight_next ^= 1;
-    if (expected) *expected = n;
-    return NVH_OK;
   });
 }
 
@@ -962,28 +877,25 @@ extern "C" int nvh_batch_synth(nvh_batch* b, float* d_pcm, int64_t capacity) {
   return nvh_batch_synth_pcm(b, NVH_PCM_F32, d_pcm, capacity);
 }
 
-extern "C" int nvh_batch_synth_pcm(nvh_batch* b, int format, void* d_pcm, int64_t capacity) {
+// nvh_batch_synth_pcm / _planar: `capacity` in the unit of the batch's PCM in `out` (samples per channel for planar PCM)
+static int batch_synth(nvh_batch* b, const PcmOut& out, void* d_pcm, int64_t capacity) {
   return nvh_guard([&]() -> int {
-    if (!b || !b->s || !pcm_format_ok(format) || !pcm_dest_ok(format, d_pcm)) return NVH_ERR_ARGUMENT;
+    if (!b || !b->s || !PcmOut::format_ok(out.format) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
     nvh_stream* s = b->s;
-    if (capacity < b->pcm_samples * s->setup.channels) return NVH_ERR_ARGUMENT;
+    if (capacity < PcmShape(out, b->pcm_samples, s->setup.channels).len) return NVH_ERR_ARGUMENT;
     if (b->pcm_samples > 0 && !d_pcm) return NVH_ERR_ARGUMENT;
     HIP_TRY(hipSetDevice(s->ctx->device));
     // the stream keeps the tail of the newest batch (written to its current carry buffer; the batch reads its own snapshot)
-    return batch_launch(b, (const float*)b->carry_in.p, (float*)s->carry[s->carry_cur].p, d_pcm, false, nullptr, nullptr, format);
+    return batch_launch(b, (const float*)b->carry_in.p, (float*)s->carry[s->carry_cur].p, d_pcm, false, nullptr, nullptr, out);
   });
 }
 
+extern "C" int nvh_batch_synth_pcm(nvh_batch* b, int format, void* d_pcm, int64_t capacity) {
+  return batch_synth(b, PcmOut{format, 0}, d_pcm, capacity);
+}
+
 extern "C" int nvh_batch_synth_planar(nvh_batch* b, int format, void* d_pcm, int64_t plane_stride) {
-  return nvh_guard([&]() -> int {
-    if (!b || !b->s || !pcm_format_ok(format) || !planar_dest_ok(format, d_pcm)) return NVH_ERR_ARGUMENT;
-    nvh_stream* s = b->s;
-    if (plane_stride < b->pcm_samples) return NVH_ERR_ARGUMENT;
-    if (b->pcm_samples > 0 && !d_pcm) return NVH_ERR_ARGUMENT;
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    return batch_launch(b, (const float*)b->carry_in.p, (float*)s->carry[s->carry_cur].p, d_pcm, false, nullptr, nullptr, format,
-                        planar_launch_stride(plane_stride));
-  });
+  return batch_synth(b, PcmOut{format, planar_launch_stride(plane_stride)}, d_pcm, plane_stride);
 }
 
 extern "C" int nvh_batch_time(nvh_batch* b, float* d_pcm, int64_t capacity, int iters, float* total_ms,

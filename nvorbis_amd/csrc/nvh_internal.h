@@ -471,10 +471,22 @@ int get_mdct(nvh_ctx* c, int n, MdctDev** out);                 // nvh_ops.hip
 int upload_setup(nvh_stream* s);                                 // nvh_setup.hip
 int upload_parse_tables(nvh_stream* s);                          // nvh_setup.hip
 int batch_upload(nvh_stream* s, nvh_batch* b);                   // nvh_launch.hip
-// d_pcm: float samples, or int16_t with pcm_format NVH_PCM_S16 (the kernels' _s16 twins)
+// A PCM destination: the sample format (NVH_PCM_*: float, or int16_t for the kernels' _s16 twins) and the layout -- interleaved
+// (plane_stride == 0), or channel-planar with channel c's samples at base + c * plane_stride (the _planar twins)
+struct PcmOut {
+  int format = NVH_PCM_F32;
+  int64_t plane_stride = 0;
+  static bool format_ok(int format) { return format == NVH_PCM_F32 || format == NVH_PCM_S16; }
+  bool s16() const { return format == NVH_PCM_S16; }
+  bool planar() const { return plane_stride > 0; }
+  size_t sample_bytes() const { return s16() ? sizeof(int16_t) : sizeof(float); }
+  // a device destination: interleaved 16-bit PCM 16-byte aligned (the stereo twins store eight samples at a time), planar PCM
+  // aligned to its samples
+  bool dest_ok(const void* d_pcm) const {
+    return planar() ? ((uintptr_t)d_pcm % sample_bytes()) == 0 : (!s16() || ((uintptr_t)d_pcm & 15u) == 0);
+  }
+};
 int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms,
-                 hipEvent_t* ext_ev = nullptr, int pcm_format = NVH_PCM_F32,
-                 int64_t plane_stride = 0);  // nvh_launch.hip; plane_stride > 0: channel-planar PCM (the _planar twins)
-static inline size_t pcm_sample_bytes(int pcm_format) { return pcm_format == NVH_PCM_S16 ? sizeof(int16_t) : sizeof(float); }
+                 hipEvent_t* ext_ev = nullptr, PcmOut out = PcmOut());  // nvh_launch.hip
 int collect_flags(nvh_stream* s);                                // nvh_launch.hip
 void replay_note(nvh_stream* s, int kind, const uint8_t* data, int len, int64_t granule, int flags);  // nvh_launch.hip

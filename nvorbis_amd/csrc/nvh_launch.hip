@@ -1,4 +1,5 @@
 // nvh_launch.hip -- moving a parsed batch into HBM and the launch policy: which kernel variants a batch runs through.
+#include <array>
 #include <chrono>
 
 #include "nvh_internal.h"
@@ -727,10 +728,63 @@ static bool slab_size_ok(const nvh_batch* b) {
 
 static bool slab_path(const nvh_batch* b) { return slab_shape_ok(b) && slab_size_ok(b); }
 
+// ---- the kernels that write PCM, one set of twins per (sample type, layout) ----
+// The seven emitting kernels are template bodies instantiated per sample type (the _s16 twins: kernels_common.h pcm_s16_value)
+// and layout (the _planar twins, which take the planes' stride as one more argument); batch_launch picks a set here and nowhere
+// else.  `sfx` is the suffix of the set's kernel names.
+template <typename PCM, bool PLANAR>
+struct PcmTwins {
+  static constexpr bool planar = PLANAR;
+  static PCM* pcm(void* p) { return (PCM*)p; }
+};
+struct PcmF32 : PcmTwins<float, false> {
+  static constexpr const char* sfx = "";
+  static constexpr auto synth_emit = k_synth_emit, synth8_emit = k_synth8_emit, group2 = k_synth_group2, group4 = k_synth_group4;
+  static constexpr auto ola_compact = k_ola_compact;
+  static constexpr auto ola_emit = k_ola_emit;
+  static constexpr auto ola_emit_seq = k_ola_emit_seq;
+};
+struct PcmS16 : PcmTwins<int16_t, false> {
+  static constexpr const char* sfx = "_s16";
+  static constexpr auto synth_emit = k_synth_emit_s16, synth8_emit = k_synth8_emit_s16, group2 = k_synth_group2_s16,
+                        group4 = k_synth_group4_s16;
+  static constexpr auto ola_compact = k_ola_compact_s16;
+  static constexpr auto ola_emit = k_ola_emit_s16;
+  static constexpr auto ola_emit_seq = k_ola_emit_seq_s16;
+};
+struct PcmF32Planar : PcmTwins<float, true> {
+  static constexpr const char* sfx = "_planar";
+  static constexpr auto synth_emit = k_synth_emit_planar, synth8_emit = k_synth8_emit_planar, group2 = k_synth_group2_planar,
+                        group4 = k_synth_group4_planar;
+  static constexpr auto ola_compact = k_ola_compact_planar;
+  static constexpr auto ola_emit = k_ola_emit_planar;
+  static constexpr auto ola_emit_seq = k_ola_emit_seq_planar;
+};
+struct PcmS16Planar : PcmTwins<int16_t, true> {
+  static constexpr const char* sfx = "_s16_planar";
+  static constexpr auto synth_emit = k_synth_emit_s16_planar, synth8_emit = k_synth8_emit_s16_planar,
+                        group2 = k_synth_group2_s16_planar, group4 = k_synth_group4_s16_planar;
+  static constexpr auto ola_compact = k_ola_compact_s16_planar;
+  static constexpr auto ola_emit = k_ola_emit_s16_planar;
+  static constexpr auto ola_emit_seq = k_ola_emit_seq_s16_planar;
+};
+
+// f(twins) for the set that writes `out`
+template <typename F>
+static auto with_pcm_twins(const PcmOut& out, F&& f) {
+  if (out.planar()) return out.s16() ? f(PcmS16Planar()) : f(PcmF32Planar());
+  return out.s16() ? f(PcmS16()) : f(PcmF32());
+}
+
+// pick(twins) of every set (the kernels that need a launch attribute)
+template <typename F>
+static std::array<const void*, 4> pcm_twin_kernels(F pick) {
+  return {(const void*)pick(PcmF32()), (const void*)pick(PcmS16()), (const void*)pick(PcmF32Planar()), (const void*)pick(PcmS16Planar())};
+}
+
 int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms, hipEvent_t* ext_ev,
-                 int pcm_format, int64_t plane_stride) {
+                 PcmOut out) {
   nvh_stream* s = b->s;
-  const bool s16 = pcm_format == NVH_PCM_S16;  // the emitting kernels' 16-bit twins (kernels_common.h: pcm_s16_value)
   hipStream_t st = s->ctx->stream;
   if (b->nframes == 0) return NVH_OK;
   const int ch = s->setup.channels;
@@ -739,10 +793,17 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
   // whole groups of four samples (below 2^31: NvhSynthArgs::plane_stride) and a frame position in whole groups of four
   // (batch_upload: emit_planar_ok); otherwise the batch runs without paired emission and k_ola_compact_*planar takes each frame
   // by its vector form where that frame's own position allows it, else sample by sample.
-  const bool planar = plane_stride > 0 && ch > 1;
+  if (ch == 1) out.plane_stride = 0;
+  const bool planar = out.planar();
+  const int64_t plane_stride = out.plane_stride;
   const bool planar_emit = !planar || (((uintptr_t)d_pcm & 15u) == 0 && (plane_stride & 3) == 0 && plane_stride <= 0x7FFFFFFFll &&
                                        b->emit_planar_ok);
-  const char* sfx = planar ? (s16 ? "_s16_planar" : "_planar") : (s16 ? "_s16" : "");
+  const char* sfx = with_pcm_twins(out, [](auto t) { return t.sfx; });
+  // launches one of the set's k_ola_* kernels: the planar twins take the planes' stride as their last argument
+  auto launch_ola = [&](auto t, auto kern, dim3 grid, dim3 block, auto... args) {
+    if constexpr (decltype(t)::planar) hipLaunchKernelGGL(kern, grid, block, 0, st, args..., (long long)plane_stride);
+    else hipLaunchKernelGGL(kern, grid, block, 0, st, args...);
+  };
   float* work = (float*)b->work.p;
   int* flags = (int*)s->flags.p;
   const size_t lds = (size_t)s->setup.block1 * sizeof(float);
@@ -811,11 +872,9 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
     const size_t synth_lds = slab_lds_bytes(b) + (size_t)T.lds_pad;
     if (synth_lds > 64 * 1024 && !s->ctx->synth_lds_attr_set) {
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_emit, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_g, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_emit_s16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_emit_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_emit_s16_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      for (const void* k : pcm_twin_kernels([](auto t) { return t.synth8_emit; }))
+        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       s->ctx->synth_lds_attr_set = true;
     }
     if (timing) HIP_TRY(hipEventRecord(ev[1], st));  // slot 0 stays empty: slot 1 = the synthesis kernel
@@ -829,7 +888,7 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       A.f0 = 1;
       if (b->nframes > 1) hipLaunchKernelGGL(k_synth8, dim3((unsigned)(b->nframes / 2)), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
       A.f0 = 0;
-      auto kern8 = planar ? (s16 ? k_synth8_emit_s16_planar : k_synth8_emit_planar) : (s16 ? k_synth8_emit_s16 : k_synth8_emit);
+      auto kern8 = with_pcm_twins(out, [](auto t) { return t.synth8_emit; });
       hipLaunchKernelGGL(kern8, dim3((unsigned)((b->nframes + 1) / 2)), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
     } else if (wide_general) hipLaunchKernelGGL(k_synth8_g, dim3((unsigned)b->nframes), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
     else if (wide) hipLaunchKernelGGL(k_synth8, dim3((unsigned)b->nframes), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
@@ -841,18 +900,13 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       // between groups as well.
       const int gw = b->fpw, ngroups = (b->nframes + gw - 1) / gw;
       if (synth_lds > 64 * 1024 && !s->ctx->group_lds_attr_set) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group4, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group2_s16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group4_s16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group2_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group4_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group2_s16_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_synth_group4_s16_planar, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        for (const void* k : pcm_twin_kernels([](auto t) { return t.group2; }))
+          HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        for (const void* k : pcm_twin_kernels([](auto t) { return t.group4; }))
+          HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         s->ctx->group_lds_attr_set = true;
       }
-      auto kern = planar ? (gw == 2 ? (s16 ? k_synth_group2_s16_planar : k_synth_group2_planar) : (s16 ? k_synth_group4_s16_planar : k_synth_group4_planar))
-                         : (gw == 2 ? (s16 ? k_synth_group2_s16 : k_synth_group2) : (s16 ? k_synth_group4_s16 : k_synth_group4));
+      auto kern = with_pcm_twins(out, [gw](auto t) { return gw == 2 ? t.group2 : t.group4; });
       const unsigned nt = gw == 2 ? 256u : 512u;
       if (T.debug_occ) {
         int nb = -1;
@@ -885,7 +939,7 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       }
       A.f0 = 0;
       A.prefetch_prev = 0;
-      auto kern = planar ? (s16 ? k_synth_emit_s16_planar : k_synth_emit_planar) : (s16 ? k_synth_emit_s16 : k_synth_emit);
+      auto kern = with_pcm_twins(out, [](auto t) { return t.synth_emit; });
       hipLaunchKernelGGL(kern, dim3((unsigned)((b->nframes + 1) / 2)), dim3(NVH_SYNTH_NT), synth_lds, st, A NVH_DBG_LAUNCH);
     }
     if (emitted) {  // odd frames, then the emitting even frames; the twins' names carry the format's / layout's suffix
@@ -1024,24 +1078,11 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       // more than two channels: the steady-state path splits a frame into runs of NVH_OLA_GW groups of four sample times, one
       // workgroup each, and interleaves through LDS (ola_sym_lds)
       if (ch > 2 && !T.no_ola_sym && T.ola_segs <= 0) segs = ((s->setup.block1 / 16) + NVH_OLA_GW - 1) / NVH_OLA_GW;
-      // k_ola_compact, or its 16-bit twin
       auto ola_compact = [&](unsigned nwg, float* c_out, const int* list, int emitted_frames) {
-        if (planar && s16)
-          hipLaunchKernelGGL(k_ola_compact_s16_planar, dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
-                             (const float*)work, carry, (int16_t*)d_pcm, s->clip, flags + 1, c_out, b->last_decoded,
-                             T.no_ola_sym ? 1 : 0, list, emitted_frames, (long long)plane_stride);
-        else if (planar)
-          hipLaunchKernelGGL(k_ola_compact_planar, dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
-                             (const float*)work, carry, (float*)d_pcm, s->clip, flags + 1, c_out, b->last_decoded,
-                             T.no_ola_sym ? 1 : 0, list, emitted_frames, (long long)plane_stride);
-        else if (s16)
-          hipLaunchKernelGGL(k_ola_compact_s16, dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
-                             (const float*)work, carry, (int16_t*)d_pcm, s->clip, flags + 1, c_out, b->last_decoded,
-                             T.no_ola_sym ? 1 : 0, list, emitted_frames);
-        else
-          hipLaunchKernelGGL(k_ola_compact, dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st, s->dev, b->dev,
-                             (const float*)work, carry, (float*)d_pcm, s->clip, flags + 1, c_out, b->last_decoded,
-                             T.no_ola_sym ? 1 : 0, list, emitted_frames);
+        with_pcm_twins(out, [&](auto t) {
+          launch_ola(t, t.ola_compact, dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), s->dev, b->dev, (const float*)work, carry,
+                     t.pcm(d_pcm), s->clip, flags + 1, c_out, b->last_decoded, T.no_ola_sym ? 1 : 0, list, emitted_frames);
+        });
       };
       if (!emitted)
         ola_compact((unsigned)b->nframes, carry_out, (const int*)nullptr, 0);
@@ -1052,28 +1093,14 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       else  // paired emission: only the frames k_synth left over
         ola_compact((unsigned)b->ola_count, (float*)nullptr /* k_synth wrote the carried tail */, b->d_ola_list, 1);
     } else if (!b->sequential_ola) {
-      if (planar && s16)
-        hipLaunchKernelGGL(k_ola_emit_s16_planar, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, (const float*)work, carry,
-                           (int16_t*)d_pcm, s->clip, flags + 1, (long long)plane_stride);
-      else if (planar)
-        hipLaunchKernelGGL(k_ola_emit_planar, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, (const float*)work, carry,
-                           (float*)d_pcm, s->clip, flags + 1, (long long)plane_stride);
-      else if (s16)
-        hipLaunchKernelGGL(k_ola_emit_s16, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, (const float*)work, carry,
-                           (int16_t*)d_pcm, s->clip, flags + 1);
-      else
-        hipLaunchKernelGGL(k_ola_emit, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, (const float*)work, carry,
-                           (float*)d_pcm, s->clip, flags + 1);
-    } else if (planar && s16) {
-      hipLaunchKernelGGL(k_ola_emit_seq_s16_planar, dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry, (int16_t*)d_pcm, s->clip,
-                         flags + 1, (long long)plane_stride);
-    } else if (planar) {
-      hipLaunchKernelGGL(k_ola_emit_seq_planar, dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry, (float*)d_pcm, s->clip,
-                         flags + 1, (long long)plane_stride);
-    } else if (s16) {
-      hipLaunchKernelGGL(k_ola_emit_seq_s16, dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry, (int16_t*)d_pcm, s->clip, flags + 1);
+      with_pcm_twins(out, [&](auto t) {
+        launch_ola(t, t.ola_emit, dim3((unsigned)b->nframes), dim3(256), s->dev, b->dev, (const float*)work, carry, t.pcm(d_pcm), s->clip,
+                   flags + 1);
+      });
     } else {
-      hipLaunchKernelGGL(k_ola_emit_seq, dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry, (float*)d_pcm, s->clip, flags + 1);
+      with_pcm_twins(out, [&](auto t) {
+        launch_ola(t, t.ola_emit_seq, dim3(1), dim3(256), s->dev, b->dev, work, carry, t.pcm(d_pcm), s->clip, flags + 1);
+      });
     }
     // the last decoded block becomes the carried tail (StreamDecoder's _prevPacketBuf), always fully windowed
     if (!compact && !b->block_only && b->last_decoded >= 0 && carry_out)

@@ -39,6 +39,11 @@ def _layout(name):
     return name == "planar"
 
 
+def _host_shape(samples, channels, planar):
+    """A host array for `samples` per channel, never empty: (channels, m) planes, or (m,) interleaved."""
+    return (channels, max(samples, 1)) if planar else (max(samples * channels, 1),)
+
+
 def _sample_format(name):
     if name not in _SAMPLE_FORMATS:
         raise ValueError("sample_format must be 'f32' or 's16', not %r" % (name,))
@@ -322,11 +327,41 @@ class Batch:
             pass
 
 
+class _PinnedBuffer:
+    """A page-locked host buffer (nvh_pinned_alloc) that grows to max(need, 2 x capacity) bytes."""
+
+    def __init__(self):
+        self._ptr, self._cap, self._bytes = None, 0, None
+
+    def get(self, n, dt):
+        """The whole buffer, at least n samples of dtype dt, as a flat array of them (the capacity is in bytes: dtypes share it)."""
+        nbytes = n * dt.itemsize
+        if self._cap < nbytes:
+            cap = max(nbytes, 2 * self._cap)
+            self.free()
+            p = C.c_void_p()
+            check(lib().nvh_pinned_alloc(cap, C.byref(p)), "nvh_pinned_alloc")
+            self._ptr, self._cap = p, cap
+            self._bytes = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(cap,))
+        return self._bytes[:self._cap - self._cap % dt.itemsize].view(dt)
+
+    def free(self):
+        if self._ptr:
+            self._bytes = None
+            lib().nvh_pinned_free(self._ptr)
+            self._ptr, self._cap = None, 0
+
+
 class Stream:
     """nvh_stream: setup tables in HBM + host parser + overlap state.  ctx=None -> host-only (parse, no synthesis)."""
 
     def __init__(self, ctx, id_pkt, comment_pkt, setup_pkt):
         self._ctx = ctx
+        self._pinned = _PinnedBuffer()  # synth_host(pinned=True)
+        # pipelined read-back (synth_begin / synth_end): one buffer per native flight slot, the array each flight fills
+        self._flight_bufs = (_PinnedBuffer(), _PinnedBuffer())
+        self._flight_out = [None, None]
+        self._pipe_next = self._pipe_first = self._pipe_out = 0
         self._h = C.c_void_p()
         check(lib().nvh_stream_open(ctx._h if ctx is not None else None, id_pkt, len(id_pkt), comment_pkt,
                                     len(comment_pkt) if comment_pkt is not None else 0, setup_pkt, len(setup_pkt),
@@ -549,107 +584,61 @@ class Stream:
         planar=True: channel-planar PCM, a (channels, n) array (n samples per channel); `out` is then a C-contiguous
         (channels, m) array of the dtype with m >= the pending samples per channel, and the result is out[:, :n]."""
         fmt, dt = _pcm_format(dtype)
-        if planar:
-            return self._synth_host_planar(pinned, out, fmt, dt)
-        _, smp = self.pending()
-        n = max(smp * self.channels, 1)
-        wr = C.c_int64(0)
-        if out is not None:
-            if out.dtype != dt or not out.flags["C_CONTIGUOUS"] or out.size < smp * self.channels:
-                raise ValueError("out must be a contiguous %s array that holds the pending batch" % dt)
-            if out.size == 0:
-                out = np.empty(1, dtype=dt)
-            n = out.size
-        elif pinned:
-            nbytes = n * dt.itemsize
-            if getattr(self, "_pin_cap", 0) < nbytes:  # (capacity in bytes: float and int16 batches share the buffer)
-                if getattr(self, "_pin_ptr", None):
-                    lib().nvh_pinned_free(self._pin_ptr)
-                p = C.c_void_p()
-                cap = max(nbytes, 2 * getattr(self, "_pin_cap", 0))
-                check(lib().nvh_pinned_alloc(cap, C.byref(p)), "nvh_pinned_alloc")
-                self._pin_ptr, self._pin_cap = p, cap
-                self._pin_arr = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(cap,))
-            out = self._pin_arr[:nbytes].view(dt)
-        else:
-            out = np.empty(n, dtype=dt)
-        rc = lib().nvh_stream_synth_pcm(self._h, fmt, out.ctypes.data, None, n, C.byref(wr))
-        self._note_parse_error(rc, wr.value, "nvh_stream_synth_pcm")
-        return out[:wr.value]
-
-    def _synth_host_planar(self, pinned, out, fmt, dt):
         _, smp = self.pending()
         ch = self.channels
-        if out is not None:
+        if out is None:
+            shape = _host_shape(smp, ch, planar)
+            n = int(np.prod(shape))
+            out = self._pinned.get(n, dt)[:n].reshape(shape) if pinned else np.empty(shape, dtype=dt)
+        elif planar:
             if (not isinstance(out, np.ndarray) or out.dtype != dt or out.ndim != 2 or out.shape[0] != ch or
                     not out.flags["C_CONTIGUOUS"] or out.shape[1] < smp):
                 raise ValueError("out must be a C-contiguous (%d, >= %d) %s array" % (ch, smp, dt))
-            arr = out
-        elif pinned:
-            nbytes = max(smp, 1) * ch * dt.itemsize
-            if getattr(self, "_pin_cap", 0) < nbytes:
-                if getattr(self, "_pin_ptr", None):
-                    lib().nvh_pinned_free(self._pin_ptr)
-                p = C.c_void_p()
-                cap = max(nbytes, 2 * getattr(self, "_pin_cap", 0))
-                check(lib().nvh_pinned_alloc(cap, C.byref(p)), "nvh_pinned_alloc")
-                self._pin_ptr, self._pin_cap = p, cap
-                self._pin_arr = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(cap,))
-            arr = self._pin_arr[:nbytes].view(dt).reshape(ch, max(smp, 1))
         else:
-            arr = np.empty((ch, max(smp, 1)), dtype=dt)
+            if out.dtype != dt or not out.flags["C_CONTIGUOUS"] or out.size < smp * ch:
+                raise ValueError("out must be a contiguous %s array that holds the pending batch" % dt)
+            if out.size == 0:
+                out = np.empty(1, dtype=dt)
         wr = C.c_int64(0)
-        rc = lib().nvh_stream_synth_planar(self._h, fmt, arr.ctypes.data, None, arr.shape[1], C.byref(wr))
-        self._note_parse_error(rc, wr.value, "nvh_stream_synth_planar", planar=True)
-        return arr[:, :wr.value]
+        if planar:
+            where = "nvh_stream_synth_planar"
+            rc = lib().nvh_stream_synth_planar(self._h, fmt, out.ctypes.data, None, out.shape[1], C.byref(wr))
+        else:
+            where = "nvh_stream_synth_pcm"
+            rc = lib().nvh_stream_synth_pcm(self._h, fmt, out.ctypes.data, None, out.size, C.byref(wr))
+        self._note_parse_error(rc, wr.value, where, planar=planar)
+        return out[:, :wr.value] if planar else out[:wr.value]
 
     # ---- pipelined read-back (nvh_stream_synth_begin / _end) ----
-    def _pipe_buffer(self, k, n, dt):
-        bufs = getattr(self, "_pipe", None)
-        if bufs is None:
-            bufs = self._pipe = [[None, 0, None, None, 0], [None, 0, None, None, 0]]  # [pointer, capacity in bytes, byte view, dtype, planes' stride]
-        ptr, cap, arr, _, _ = bufs[k]
-        nbytes = n * dt.itemsize
-        if cap < nbytes:
-            if ptr:
-                lib().nvh_pinned_free(ptr)
-            p = C.c_void_p()
-            cap = max(nbytes, 2 * cap)
-            check(lib().nvh_pinned_alloc(cap, C.byref(p)), "nvh_pinned_alloc")
-            bufs[k] = [p, cap, np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(cap,)), None, 0]
-        bufs[k][3] = dt
-        bufs[k][4] = 0
-        return bufs[k][2][:cap - cap % dt.itemsize].view(dt)
-
     def synth_begin(self, dtype=np.float32, planar=False):
         """Queue the pending batch (upload, GPU parse, synthesis, transfer of the PCM on a copy stream) and return at once.
         Two batches may be outstanding; synth_end() hands them back in order, each in the dtype of its begin (float32 / int16),
         and -- planar=True -- as a (channels, n) view of channel-planar PCM (the return value is then per channel too)."""
         fmt, dt = _pcm_format(dtype)
-        if getattr(self, "_pipe_out", 0) >= 2:
+        if self._pipe_out >= 2:
             # refuse before touching a buffer: slot k is still the DMA destination of the oldest outstanding batch
             raise native.NvhError(native.ERR_ARGUMENT, "nvh_stream_synth_begin (two batches are outstanding: call synth_end first)")
-        _, smp = self.pending()
-        n = max(smp * self.channels, 1)
-        k = getattr(self, "_pipe_next", 0)
-        out = self._pipe_buffer(k, n, dt)
+        shape = _host_shape(self.pending()[1], self.channels, planar)
+        n = int(np.prod(shape))
+        k = self._pipe_next
+        out = self._flight_bufs[k].get(n, dt)
         exp = C.c_int64(0)
         if planar:
-            stride = max(smp, 1)
-            check(lib().nvh_stream_synth_begin_planar(self._h, fmt, out.ctypes.data, stride, C.byref(exp)), "nvh_stream_synth_begin_planar")
-            self._pipe[k][4] = stride
+            check(lib().nvh_stream_synth_begin_planar(self._h, fmt, out.ctypes.data, shape[1], C.byref(exp)), "nvh_stream_synth_begin_planar")
+            out = out[:n].reshape(shape)
         else:
             check(lib().nvh_stream_synth_begin_pcm(self._h, fmt, out.ctypes.data, out.size, C.byref(exp)), "nvh_stream_synth_begin_pcm")
         # only a begin that succeeded occupies a slot
+        self._flight_out[k] = out
         self._pipe_next = k ^ 1
-        self._pipe_out = getattr(self, "_pipe_out", 0) + 1
+        self._pipe_out += 1
         return exp.value
 
     def synth_end(self):
         """PCM of the oldest outstanding batch: a view of a page-locked buffer that stays valid until the begin after next."""
-        if getattr(self, "_pipe_out", 0) <= 0:
+        if self._pipe_out <= 0:
             raise native.NvhError(native.ERR_ARGUMENT, "nvh_stream_synth_end (nothing is outstanding)")
-        k = getattr(self, "_pipe_first", 0)
+        k = self._pipe_first
         wr = C.c_int64(0)
         rc = lib().nvh_stream_synth_end(self._h, C.byref(wr))
         if rc in (native.ERR_ARGUMENT, native.ERR_DEVICE, native.ERR_NO_GPU):
@@ -659,11 +648,10 @@ class Stream:
         # any other outcome has retired the native flight (nvh_api.hip pops the slot before it reports a runtime or parse error)
         self._pipe_first = k ^ 1
         self._pipe_out -= 1
-        _, cap, arr, dt, stride = self._pipe[k]
-        self._note_parse_error(rc, wr.value, "nvh_stream_synth_end", planar=bool(stride))
-        if stride:  # a planar flight: the planes lie `stride` samples apart
-            return arr[:stride * self.channels * dt.itemsize].view(dt).reshape(self.channels, stride)[:, :wr.value]
-        return arr[:cap - cap % dt.itemsize].view(dt)[:wr.value]
+        out = self._flight_out[k]
+        planar = out.ndim == 2
+        self._note_parse_error(rc, wr.value, "nvh_stream_synth_end", planar=planar)
+        return out[:, :wr.value] if planar else out[:wr.value]
 
     def synth_device(self, d_ptr, capacity, dtype=np.float32, plane_stride=None):
         """Synthesise the pending batch into device memory (capacity in samples; int16: 16-byte aligned); returns the samples written.
@@ -707,15 +695,9 @@ class Stream:
         if self._h:
             lib().nvh_stream_close(self._h)
             self._h = C.c_void_p()
-        if getattr(self, "_pin_ptr", None):
-            self._pin_arr = None
-            lib().nvh_pinned_free(self._pin_ptr)
-            self._pin_ptr, self._pin_cap = None, 0
-        for b in getattr(self, "_pipe", None) or []:
-            if b[0]:
-                b[2] = None
-                lib().nvh_pinned_free(b[0])
-                b[0], b[1] = None, 0
+        self._flight_out = [None, None]
+        for b in (self._pinned,) + self._flight_bufs:
+            b.free()
 
     def __del__(self):
         try:
@@ -859,14 +841,21 @@ class StreamDecoder:
         samples per channel, and so is the return value."""
         ch = self.Channels
         if self._planar:
-            return self._read_planar(buffer, offset, count)
-        if offset < 0 or offset + count > len(buffer):
-            raise IndexError("offset")  # ArgumentOutOfRangeException
-        if count % ch != 0:
-            raise ValueError("count must be a multiple of Channels")
-        if getattr(buffer, "dtype", None) != self._dtype:
-            raise TypeError("this decoder delivers %s samples: the buffer must be a numpy %s array" % (self._dtype, self._dtype))
-        idx, tgt = offset, offset + count
+            if getattr(buffer, "dtype", None) != self._dtype:
+                raise TypeError("this decoder delivers %s samples: the buffer must be a numpy %s array" % (self._dtype, self._dtype))
+            if buffer.ndim != 2 or buffer.shape[0] != ch:
+                raise ValueError("planar layout: the buffer must have shape (%d, m), not %s" % (ch, buffer.shape))
+            if offset < 0 or count < 0 or offset + count > buffer.shape[1]:
+                raise IndexError("offset")  # ArgumentOutOfRangeException
+        else:
+            if offset < 0 or offset + count > len(buffer):
+                raise IndexError("offset")  # ArgumentOutOfRangeException
+            if count % ch != 0:
+                raise ValueError("count must be a multiple of Channels")
+            if getattr(buffer, "dtype", None) != self._dtype:
+                raise TypeError("this decoder delivers %s samples: the buffer must be a numpy %s array" % (self._dtype, self._dtype))
+        per = ch if self._planar else 1  # the ring's bookkeeping is in interleaved units
+        idx, tgt = offset * per, (offset + count) * per
         while idx < tgt:
             if self._pending_errors and self._ring_pos >= self._pending_errors[0][1]:
                 # the packet that follows here made the decoder throw; the samples before it have been delivered.  (The
@@ -883,39 +872,14 @@ class StreamDecoder:
             take = min(tgt - idx, self._ring.size - self._ring_pos)
             if self._pending_errors:
                 take = min(take, self._pending_errors[0][1] - self._ring_pos)
-            buffer[idx:idx + take] = self._ring[self._ring_pos:self._ring_pos + take]
+            if self._planar:
+                r, b, k = self._ring_pos // ch, idx // ch, take // ch
+                buffer[:, b:b + k] = self._ring[:, r:r + k]
+            else:
+                buffer[idx:idx + take] = self._ring[self._ring_pos:self._ring_pos + take]
             self._ring_pos += take
             idx += take
-        return idx - offset
-
-    def _read_planar(self, buffer, offset, count):
-        ch = self.Channels
-        if getattr(buffer, "dtype", None) != self._dtype:
-            raise TypeError("this decoder delivers %s samples: the buffer must be a numpy %s array" % (self._dtype, self._dtype))
-        if buffer.ndim != 2 or buffer.shape[0] != ch:
-            raise ValueError("planar layout: the buffer must have shape (%d, m), not %s" % (ch, buffer.shape))
-        if offset < 0 or count < 0 or offset + count > buffer.shape[1]:
-            raise IndexError("offset")  # ArgumentOutOfRangeException
-        idx, tgt = offset * ch, (offset + count) * ch  # interleaved units, as the ring's bookkeeping
-        while idx < tgt:
-            if self._pending_errors and self._ring_pos >= self._pending_errors[0][1]:
-                raise self._pending_errors.pop(0)[0]
-            if self._ring_pos >= self._ring.size:
-                if not self._refill():
-                    break
-            if self._skip:
-                drop = min(self._skip, self._ring.size - self._ring_pos)
-                self._ring_pos += drop
-                self._skip -= drop
-                continue
-            take = min(tgt - idx, self._ring.size - self._ring_pos)
-            if self._pending_errors:
-                take = min(take, self._pending_errors[0][1] - self._ring_pos)
-            r, b, k = self._ring_pos // ch, idx // ch, take // ch
-            buffer[:, b:b + k] = self._ring[:, r:r + k]
-            self._ring_pos += take
-            idx += take
-        return idx // ch - offset
+        return idx // per - offset
 
     # ---- seeking (StreamDecoder.cs:562-628) ----
     def _granule_index(self):
@@ -1199,21 +1163,13 @@ class VorbisReader:
     def read_all(self):
         """Everything from the current position: interleaved, or (Channels, T) in the planar layout."""
         chunks = []
-        if self._planar:
-            buf = np.empty((self.Channels, 65536), dtype=self._dtype)
-            while True:
-                n = self.ReadSamples(buf, 0, buf.shape[1])
-                if n <= 0:
-                    break
-                chunks.append(buf[:, :n].copy())
-            return np.concatenate(chunks, axis=1) if chunks else np.zeros((self.Channels, 0), dtype=self._dtype)
-        buf = np.empty(65536 * self.Channels, dtype=self._dtype)
+        buf = np.empty((self.Channels, 65536) if self._planar else (65536 * self.Channels,), dtype=self._dtype)
         while True:
-            n = self.ReadSamples(buf, 0, buf.size)
+            n = self.ReadSamples(buf, 0, buf.shape[-1])
             if n <= 0:
                 break
-            chunks.append(buf[:n].copy())
-        return np.concatenate(chunks) if chunks else np.zeros(0, dtype=self._dtype)
+            chunks.append(buf[..., :n].copy())
+        return np.concatenate(chunks, axis=-1) if chunks else np.zeros(buf.shape[:-1] + (0,), dtype=self._dtype)
 
     def close(self):
         for d in self._decs.values():

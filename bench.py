@@ -14,11 +14,16 @@ slabs the synthesis kernels fetch (nvorbis_amd/csrc/host_slab.cpp: Floor1 unwrap
 records), so a pass is ALL the GPU work a once-synthesised batch needs -- the same launches the streaming reader runs for every
 look-ahead batch (k_synth over the odd frames, k_synth_emit over the even ones); nothing is converted or prepared outside the
 timed region.  After the timed region the PCM of every resident batch is hashed and compared with the digest the CPU oracle
-produced for the same packets (tests/golden/bench_pcm_digests.json, tools/gen_bench_digests.py): `pcm_digest_ok`.
+produced for the same packets (tests/golden/bench_pcm_digests.json, tools/gen_bench_digests.py): `pcm_digest_ok` (--full).
 
-Launch: python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR].  For N > 1 the script starts its own ranks (a child
-torch.distributed.run, one rank per GPU over RCCL; the launching process never touches the GPU) unless it already runs as a rank
-(WORLD_SIZE set).
+Launch: python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full].  For N > 1 the script starts its own ranks (a
+child torch.distributed.run, one rank per GPU over RCCL; the launching process never touches the GPU) unless it already runs as a
+rank (WORLD_SIZE set).
+
+A plain run does only what the headline needs: it sets up the resident batches, runs the W + K steps, writes --dump-outputs and
+prints the line (`value`, `ms_per_step`, `config`).  Everything else below -- the L3-resident loop, `kernels_ms` and `roofline`
+(with the copy ceiling and the unfused child run), the PCM digest check, the `c5` corpus block, `configs`, `end_to_end` and
+`cpu_baseline` -- runs only with --full, after the timed region, and is never part of `value`.
 
 A step is one pass over every resident batch (`passes_per_step` = streams x resident batches per stream, fixed by --streams and
 --working-set-mib, never by the clock): W untimed steps, then exactly K timed steps.  `ms_per_step` is what one timed step took, so
@@ -32,12 +37,12 @@ work planes + PCM, ~57 MB per batch) exceeds `--working-set-mib` (default 512 Mi
 and `roofline` are the HBM-resident regime.  The same loop over one batch per stream (working set ~170 MB, L3-resident -- what
 rounds 1 and 2 reported) is in `roofline.l3_resident`.
 
-`roofline`: the dominant kernel per LAUNCH by hipEvents on its own stream (one stream, outside the overlapped loop), algorithmic
+`roofline` (--full): the dominant kernel per LAUNCH by hipEvents on its own stream (one stream, outside the overlapped loop), algorithmic
 bytes of that launch, HBM traffic from the committed PMC passes; `roofline.unfused`: the same loop in a child process with
 NVH_NO_EMIT=1 (the overlap-add in k_ola_compact instead of inside k_synth).  `end_to_end`: the PCIe-inclusive rate of the
 boundary, never `value`.
 
-`configs`: the other BASELINE.json workloads on full-depth packets (C2 G-rand, C3 Markov 256/2048, C4 six channels n = 4096
+`configs` (--full): the other BASELINE.json workloads on full-depth packets (C2 G-rand, C3 Markov 256/2048, C4 six channels n = 4096
 psize 48), kernel-only: one stream by hipEvents, and the sustained rate over three streams -- parity-test cases timed for the
 record, not the headline.
 """
@@ -538,21 +543,26 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C2 G-rand / C3 / C4 kernel-only lines")
-    ap.add_argument("--no-check", action="store_true", help="profiling builds with phases masked out produce garbage PCM")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also everything else the line can report: the L3-resident loop, per-kernel and roofline "
+                         "figures, the unfused run, the PCM digest check, the corpus block, the other configurations, the end-to-end rate "
+                         "and the CPU baseline (the options below marked --full select among them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the end-to-end rate and the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the C2 G-rand / C3 / C4 kernel-only lines")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the PCM checks (profiling builds with phases masked out produce garbage PCM)")
     ap.add_argument("--c5-scale", type=float, default=1.0,
-                    help="length scale of the corpus block (1.0 = BASELINE's stated size, the default: 3.3 GB of Ogg -> 21.6 GB of PCM, about "
-                         "half a minute with its generation and SHA-256 check; 0.1: a tenth; 0: no block)")
-    ap.add_argument("--c5-workers", type=int, default=0, help="parser threads per rank for the corpus block (0: twice the CPUs this rank may use, at most 32)")
+                    help="--full: length scale of the corpus block (1.0 = BASELINE's stated size, the default: 3.3 GB of Ogg -> 21.6 GB of PCM, "
+                         "about half a minute with its generation and SHA-256 check; 0.1: a tenth; 0: no block)")
+    ap.add_argument("--c5-workers", type=int, default=0,
+                    help="--full: parser threads per rank for the corpus block (0: twice the CPUs this rank may use, at most 32)")
     ap.add_argument("--streams", type=int, default=3,
                     help="independent decoder instances (own nvh_ctx / HIP stream) the passes rotate over")
     ap.add_argument("--working-set-mib", type=float, default=512.0,
                     help="lower bound of what the rotating passes touch (resident batches per stream follow from it)")
     ap.add_argument("--min-timed-ms", type=float, default=2000.0,
-                    help="four times the length of the L3-resident comparison loop (roofline.l3_resident); the headline times --steps steps")
+                    help="--full: four times the length of the L3-resident comparison loop (roofline.l3_resident); the headline times --steps steps")
     ap.add_argument("--no-unfused", action="store_true",
-                    help="skip the short NVH_NO_EMIT=1 run (overlap-add in k_ola_compact) that roofline.unfused reports beside the fused kernels")
+                    help="--full: skip the short NVH_NO_EMIT=1 run (overlap-add in k_ola_compact) that roofline.unfused reports beside the fused kernels")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the PCM of the last timed step (a fixed, seeded sample, at most 64 MB) as DIR/<name>.npy, float32")
     args = ap.parse_args()
@@ -670,120 +680,61 @@ def main():
     total_passes = args.steps * passes_per_step
     if args.dump_outputs:
         write_outputs(args.dump_outputs, sample_outputs(torch, insts, world, rank))
-    # the same loop over one batch per stream (L3-resident, the regime of the round-1 / round-2 lines), about a quarter of
-    # --min-timed-ms long at the headline's rate (the same count on every rank: `elapsed` is the slowest rank's)
-    order_l3 = make_order(1)
-    steps_l3 = max(1, int(args.min_timed_ms / 4 / (elapsed / total_passes * 1e3 * len(order_l3)) + 0.5))
-    el_l3 = timed(order_l3, steps_l3, max(args.warmup // 4, 1))
-    passes_l3 = steps_l3 * len(order_l3)
 
-    # per-kernel durations, hipEvents on the launch stream (rank 0 reports): rotating over instance 0's batches one launch
-    # at a time (HBM-resident when reps > 1) and repeated on one batch (L3-resident)
-    names = None
-    km = [0.0] * 4
-    total_ms, rounds = 0.0, max(1, 48 // len(batches0))
-    for b, p in batches0:
-        b.time(p.data_ptr(), cap, 1)
-    for _ in range(rounds):
+    # ---- --full: everything else the line reports, after the headline's timed region and never part of `value` ----
+    if args.full:
+        # the same loop over one batch per stream (L3-resident, the regime of the round-1 / round-2 lines), about a quarter of
+        # --min-timed-ms long at the headline's rate (the same count on every rank: `elapsed` is the slowest rank's)
+        order_l3 = make_order(1)
+        steps_l3 = max(1, int(args.min_timed_ms / 4 / (elapsed / total_passes * 1e3 * len(order_l3)) + 0.5))
+        el_l3 = timed(order_l3, steps_l3, max(args.warmup // 4, 1))
+        passes_l3 = steps_l3 * len(order_l3)
+
+        # per-kernel durations, hipEvents on the launch stream (rank 0 reports): rotating over instance 0's batches one launch
+        # at a time (HBM-resident when reps > 1) and repeated on one batch (L3-resident)
+        names = None
+        km = [0.0] * 4
+        total_ms, rounds = 0.0, max(1, 48 // len(batches0))
         for b, p in batches0:
-            t, k4 = b.time(p.data_ptr(), cap, 1)
-            total_ms += t
-            km = [x + y for x, y in zip(km, k4)]
-    n_ev = rounds * len(batches0)
-    km = [x / n_ev for x in km]
-    total_ms /= n_ev
-    total_l3, km_l3 = batch.time(pcm.data_ptr(), cap, 50)
-    checksum = float(pcm.double().abs().sum().item())
-    assert args.no_check or (checksum > 0 and bool(torch.isfinite(pcm).all().item()))
-    # every resident batch's PCM against the CPU oracle's digest of the same packets: a line cannot come from kernels that write
-    # wrong samples (every rank checks its own; rank 0 reports the AND)
-    torch.cuda.synchronize()
-    digest_ok, digest_n, digest_total = check_digests(insts, seeds)
-    if dist is not None:
-        t = torch.tensor([1.0 if digest_ok else 0.0], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MIN)
-        digest_ok = bool(t.item() > 0.5)
-    if not (digest_ok and digest_n > 0) and not args.no_check:
-        raise SystemExit("bench.py: the PCM of the timed batches does not match the oracle's digests -- no line")
+            b.time(p.data_ptr(), cap, 1)
+        for _ in range(rounds):
+            for b, p in batches0:
+                t, k4 = b.time(p.data_ptr(), cap, 1)
+                total_ms += t
+                km = [x + y for x, y in zip(km, k4)]
+        n_ev = rounds * len(batches0)
+        km = [x / n_ev for x in km]
+        total_ms /= n_ev
+        total_l3, km_l3 = batch.time(pcm.data_ptr(), cap, 50)
+        checksum = float(pcm.double().abs().sum().item())
+        assert args.no_check or (checksum > 0 and bool(torch.isfinite(pcm).all().item()))
+        # every resident batch's PCM against the CPU oracle's digest of the same packets: a line cannot come from kernels that write
+        # wrong samples (every rank checks its own; rank 0 reports the AND)
+        torch.cuda.synchronize()
+        digest_ok, digest_n, digest_total = check_digests(insts, seeds)
+        if dist is not None:
+            t = torch.tensor([1.0 if digest_ok else 0.0], dtype=torch.float64, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+            digest_ok = bool(t.item() > 0.5)
+        if not (digest_ok and digest_n > 0) and not args.no_check:
+            raise SystemExit("bench.py: the PCM of the timed batches does not match the oracle's digests -- no line")
 
-    # ---- BASELINE configs[4] beside the headline: the file-parallel corpus shard and the ONE collective of the north star, the
-    # gather of the PCM (every rank takes part; rank 0 reports).  Never part of `value`.
-    c5 = None
-    if args.c5_scale > 0:
-        # (GPU-parse workers wait for the GPU most of the time: twice the 16 cores a box's container has -- decode pass 0.48 -> 0.38 s)
-        workers = args.c5_workers or max(1, min(32, 2 * len(os.sched_getaffinity(0))))
-        try:
-            c5 = c5_block(nv, torch, dist, rank, world, local_rank, args.c5_scale, workers, share_gpu)
-            if c5 is not None:
-                c5["cpu_pinning"] = pinned
-        except Exception as e:  # never fatal for the headline, which is measured and verified above: the block says what failed
-            sys.stderr.write("bench.py: corpus block failed on rank %d: %r\n" % (rank, e))
-            c5 = {"error": repr(e)[:300], "rank": rank}
+        # ---- BASELINE configs[4] beside the headline: the file-parallel corpus shard and the ONE collective of the north star, the
+        # gather of the PCM (every rank takes part; rank 0 reports).  Never part of `value`.
+        c5 = None
+        if args.c5_scale > 0:
+            # (GPU-parse workers wait for the GPU most of the time: twice the 16 cores a box's container has -- decode pass 0.48 -> 0.38 s)
+            workers = args.c5_workers or max(1, min(32, 2 * len(os.sched_getaffinity(0))))
+            try:
+                c5 = c5_block(nv, torch, dist, rank, world, local_rank, args.c5_scale, workers, share_gpu)
+                if c5 is not None:
+                    c5["cpu_pinning"] = pinned
+            except Exception as e:  # never fatal for the headline, which is measured and verified above: the block says what failed
+                sys.stderr.write("bench.py: corpus block failed on rank %d: %r\n" % (rank, e))
+                c5 = {"error": repr(e)[:300], "rank": rank}
 
     if rank == 0:
-        # the library says which kernel variant sits behind each timing slot ("-" = empty: only event overhead)
-        names = batch.kernels()
-        live = [k for k in range(4) if names[k] != "-"]
-        dom = max(live, key=lambda k: km[k])
-        # SURVEY 8d / DESIGN.md: algorithmic bytes of one ch-frame = n/2*4 B spectrum in + n/2*4 B PCM out = 4n B ... per
-        # pipeline stage that means: every kernel of the chain moves one n/2-float vector in and one out per ch-frame
-        alg_bytes = FRAMES * ch * 4 * BLOCK
-        # paired emission: k_synth runs twice per pass, each launch over half of the batch's frames (the library times the two
-        # together); per LAUNCH, like rocprofv3's average and the PMC traffic: half the bytes, half the duration
-        launches = 2 if names[dom] in ("k_synth+k_synth_emit", "k_synth_group2", "k_synth_group4") else 1
-        dom_ms = km[dom]
-        achieved = alg_bytes / (dom_ms * 1e-3) / 1e9
-        # HBM bytes per launch of that kernel from the committed rocprofv3 PMC passes (tools/profile_round.sh);
-        # null when the committed profile does not cover the kernel that ran
-        traffic, traffic_source, traffic_build, rocprof_us = None, None, None, None
-        tfile = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tfile):
-            try:
-                tj = json.load(open(tfile))
-                tk = tj.get("kernels", {})
-                if launches == 2:
-                    # paired emission: the pass is one launch over the odd frames (k_synth_tail when the last block is odd,
-                    # else k_synth) and one of k_synth_emit over the even frames; per launch = their mean
-                    if names[dom].startswith("k_synth_group"):
-                        # frame groups: both launches are the same kernel (rocprofv3's row is the mean over the two)
-                        traffic = tk.get(names[dom], {}).get("hbm_bytes")
-                    else:
-                        odd = tk.get("k_synth_tail") or tk.get("k_synth")
-                        even = tk.get("k_synth_emit")
-                        traffic = (odd["hbm_bytes"] + even["hbm_bytes"]) / 2 if odd and even else None
-                else:
-                    traffic = tk.get(names[dom], {}).get("hbm_bytes")
-                traffic_build = tj.get("build")
-                # per-kernel average durations of the committed rocprofv3 --kernel-trace pass (the same three-stream loop)
-                rocprof_us = {k: round(v["avg_us"], 3) for k, v in tk.items() if k.startswith("k_synth") and "avg_us" in v}
-                rocprof_us["source"] = tj.get("source")
-                if traffic is not None:
-                    traffic_source = "profiles/traffic.json: %s (committed rocprofv3 --pmc passes of this command, not measured in this run)" % tj.get("source", "?")
-            except Exception:
-                traffic = None
-        ceiling = copy_ceiling(torch, nv, ctx, insts[0][0])
-        # the same workload with the overlap-add left to k_ola_compact (NVH_NO_EMIT=1: the library reads its switches once, so
-        # a child process), short: per-kernel durations of the unfused chain next to the fused kernel's
-        unfused = None
-        if fused and world == 1 and not args.no_unfused:
-            import subprocess
-            env = dict(os.environ)
-            env["NVH_NO_EMIT"] = "1"
-            # (about 0.4 s of timed steps at the fused rate)
-            unfused_steps = max(40, int(400.0 / (elapsed / args.steps * 1e3) + 0.5))
-            try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(unfused_steps), "--warmup", "4", "--min-timed-ms", "400",
-                                    "--streams", str(nin), "--working-set-mib", str(args.working_set_mib), "--no-configs",
-                                    "--no-cpu-baseline", "--no-unfused", "--c5-scale", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
-                                   text=True, timeout=600)
-                uj = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-                unfused = {"what": "NVH_NO_EMIT=1: every overlap-add in k_ola_compact (the path of GPU-parsed batches and of more than two channels); same loop, %d steps" % unfused_steps,
-                           "frames_per_s": uj["value"], "ms_per_pass": uj["config"]["ms_per_pass"], "kernels_ms": uj["kernels_ms"],
-                           "frac": uj["roofline"]["frac"], "whole_pass_frac": uj["roofline"]["whole_pass_frac"]}
-            except Exception as e:  # the headline does not depend on it
-                unfused = {"error": repr(e)[:200]}
         step_ms = elapsed / total_passes * 1e3
-        l3_ms = el_l3 / passes_l3 * 1e3
         out = {
             "metric": "decoded Vorbis frames/sec (44.1 kHz stereo long-block)",
             "value": world * FRAMES * total_passes / elapsed,
@@ -796,6 +747,7 @@ def main():
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "f32",
+            "full": args.full,
             "data": "synthetic (3test.ogg long/long packets tiled to %d resident batches of 4096 frames per GPU)" % (nin * reps) +
                     (" -- NVH_BENCH_SHARE_GPU: all %d ranks on ONE GPU over gloo, a code-path check, not a scaling number" % world if share_gpu else ""),
             "config": {"workload": "C2: 4096 stereo long-block (n=2048) frames, Floor1+Residue2+coupling, IMDCT+window+OLA",
@@ -804,54 +756,119 @@ def main():
                        "passes_per_step": passes_per_step, "ms_per_pass": step_ms, "timed_region_s": elapsed,
                        "working_set_MiB": touched / (1 << 20),
                        "descriptor_bytes_per_frame": batch.descriptor_bytes / FRAMES},
-            "kernels_ms": {names[k]: km[k] for k in live},
-            "pipeline_ms_events": total_ms,
-            "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
-                         "traffic_build_matches": (traffic_build == nv.native.build_id()) if traffic is not None else None,
-                         "algorithmic_bytes_per_launch": alg_bytes // launches, "avg_launch_ms": dom_ms / launches,
-                         "launches_per_pass": launches,
-                         "kernel_scope": (("k_synth_group2 = residue + floor + inverse MDCT + window / overlap-add / clip / interleave of two consecutive frames per "
-                                           "workgroup (the overlap inside a group on chip), two launches per pass (the groups with an odd index, then the even ones, "
-                                           "which also emit the overlaps between groups), timed together by hipEvents on ONE stream"
-                                           if names[dom].startswith("k_synth_group") else
-                                           "k_synth+k_synth_emit = residue + floor + inverse MDCT + (paired emission) window / overlap-add / clip / interleave of the "
-                                           "steady-state frames, two launches per pass (odd frames, then the emitting even frames), timed together, one stream")
-                                          if fused else "k_synth = residue + floor + inverse MDCT; overlap-add in k_ola_compact"),
-                         # how to read the numbers: `frac` / `achieved` / `avg_launch_ms` are ONE decoder instance (what a ReadSamples caller's
-                         # kernels run at); `value` and `whole_pass_frac` are the timed loop over `streams` instances, whose launches overlap
-                         "one_stream": {"pass_us": dom_ms * 1e3, "frames_per_s": FRAMES / (dom_ms * 1e-3), "frac": achieved / HBM_PEAK_GBPS},
-                         "timed_loop": {"streams": nin, "pass_us": step_ms * 1e3, "frames_per_s": FRAMES / (step_ms * 1e-3),
-                                        "frac": alg_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
-                         "rocprof_avg_us": rocprof_us,
-                         "unfused": unfused,
-                         "working_set_MiB": touched / (1 << 20), "regime": "HBM-resident: a batch is revisited after %.0f MiB went by (Infinity Cache: 256 MiB)" % (touched / (1 << 20)),
-                         # the same bytes over one whole pass of the pipeline (all kernels, the batches of the streams overlapped)
-                         "whole_pass_GBps": alg_bytes / (step_ms * 1e-3) / 1e9, "whole_pass_frac": alg_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                         "l3_resident": {"working_set_MiB": nin * per_batch_bytes / (1 << 20), "frames_per_s": world * FRAMES * passes_l3 / el_l3,
-                                         "ms_per_pass": l3_ms, "kernels_ms": {names[k]: km_l3[k] for k in live},
-                                         "frac": alg_bytes / (km_l3[dom] * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                                         "whole_pass_frac": alg_bytes / (l3_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
-                         "copy_ceiling_GBps": ceiling},
-            "pcm_digest_ok": digest_ok, "pcm_digests_checked": digest_n, "pcm_batches_timed": digest_total,
             # what the ranks talked through: barriers / MAX of the timings in the headline, the PCM gather in `c5`
             "collective": ({"backend": dist.get_backend(), "world": dist.get_world_size(),
                             "library": "RCCL over xGMI (torch.distributed backend nccl)" if dist.get_backend() == "nccl" else "gloo (CPU): code-path check only"}
                            if dist is not None else {"backend": None, "world": 1}),
-            "c5": c5,
             "decode_path": "resident input = the host packet parser's output (per-frame slabs, host_slab.cpp); a pass = every kernel a "
                            "once-synthesised batch needs (the streaming reader runs the same launches per look-ahead batch); no prepare / "
                            "conversion kernel exists for host-parsed batches",
             "build": nv.native.build_id(),
         }
-        if world == 1 and not args.no_configs:
-            out["configs"] = config_lines(nv, torch, ctx, ROOT)
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                out["end_to_end"] = end_to_end(nv, ctx, headers, ll)
-            except Exception as e:  # reported beside the headline, never part of it
-                out["end_to_end"] = {"error": repr(e)[:200]}
-            out["cpu_baseline"] = cpu_baseline(headers, ll)
+        if args.full:
+            # the library says which kernel variant sits behind each timing slot ("-" = empty: only event overhead)
+            names = batch.kernels()
+            live = [k for k in range(4) if names[k] != "-"]
+            dom = max(live, key=lambda k: km[k])
+            # SURVEY 8d / DESIGN.md: algorithmic bytes of one ch-frame = n/2*4 B spectrum in + n/2*4 B PCM out = 4n B ... per
+            # pipeline stage that means: every kernel of the chain moves one n/2-float vector in and one out per ch-frame
+            alg_bytes = FRAMES * ch * 4 * BLOCK
+            # paired emission: k_synth runs twice per pass, each launch over half of the batch's frames (the library times the two
+            # together); per LAUNCH, like rocprofv3's average and the PMC traffic: half the bytes, half the duration
+            launches = 2 if names[dom] in ("k_synth+k_synth_emit", "k_synth_group2", "k_synth_group4") else 1
+            dom_ms = km[dom]
+            achieved = alg_bytes / (dom_ms * 1e-3) / 1e9
+            # HBM bytes per launch of that kernel from the committed rocprofv3 PMC passes (tools/profile_round.sh);
+            # null when the committed profile does not cover the kernel that ran
+            traffic, traffic_source, traffic_build, rocprof_us = None, None, None, None
+            tfile = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tfile):
+                try:
+                    tj = json.load(open(tfile))
+                    tk = tj.get("kernels", {})
+                    if launches == 2:
+                        # paired emission: the pass is one launch over the odd frames (k_synth_tail when the last block is odd,
+                        # else k_synth) and one of k_synth_emit over the even frames; per launch = their mean
+                        if names[dom].startswith("k_synth_group"):
+                            # frame groups: both launches are the same kernel (rocprofv3's row is the mean over the two)
+                            traffic = tk.get(names[dom], {}).get("hbm_bytes")
+                        else:
+                            odd = tk.get("k_synth_tail") or tk.get("k_synth")
+                            even = tk.get("k_synth_emit")
+                            traffic = (odd["hbm_bytes"] + even["hbm_bytes"]) / 2 if odd and even else None
+                    else:
+                        traffic = tk.get(names[dom], {}).get("hbm_bytes")
+                    traffic_build = tj.get("build")
+                    # per-kernel average durations of the committed rocprofv3 --kernel-trace pass (the same three-stream loop)
+                    rocprof_us = {k: round(v["avg_us"], 3) for k, v in tk.items() if k.startswith("k_synth") and "avg_us" in v}
+                    rocprof_us["source"] = tj.get("source")
+                    if traffic is not None:
+                        traffic_source = "profiles/traffic.json: %s (committed rocprofv3 --pmc passes of this command, not measured in this run)" % tj.get("source", "?")
+                except Exception:
+                    traffic = None
+            ceiling = copy_ceiling(torch, nv, ctx, insts[0][0])
+            # the same workload with the overlap-add left to k_ola_compact (NVH_NO_EMIT=1: the library reads its switches once, so
+            # a child process), short: per-kernel durations of the unfused chain next to the fused kernel's
+            unfused = None
+            if fused and world == 1 and not args.no_unfused:
+                import subprocess
+                env = dict(os.environ)
+                env["NVH_NO_EMIT"] = "1"
+                # (about 0.4 s of timed steps at the fused rate)
+                unfused_steps = max(40, int(400.0 / (elapsed / args.steps * 1e3) + 0.5))
+                try:
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(unfused_steps), "--warmup", "4", "--min-timed-ms", "400",
+                                        "--streams", str(nin), "--working-set-mib", str(args.working_set_mib), "--full",
+                                        "--no-configs", "--no-cpu-baseline", "--no-unfused", "--c5-scale", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
+                                       text=True, timeout=600)
+                    uj = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+                    unfused = {"what": "NVH_NO_EMIT=1: every overlap-add in k_ola_compact (the path of GPU-parsed batches and of more than two channels); same loop, %d steps" % unfused_steps,
+                               "frames_per_s": uj["value"], "ms_per_pass": uj["config"]["ms_per_pass"], "kernels_ms": uj["kernels_ms"],
+                               "frac": uj["roofline"]["frac"], "whole_pass_frac": uj["roofline"]["whole_pass_frac"]}
+                except Exception as e:  # the headline does not depend on it
+                    unfused = {"error": repr(e)[:200]}
+            l3_ms = el_l3 / passes_l3 * 1e3
+            out.update({
+                "kernels_ms": {names[k]: km[k] for k in live},
+                "pipeline_ms_events": total_ms,
+                "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
+                             "traffic_build_matches": (traffic_build == nv.native.build_id()) if traffic is not None else None,
+                             "algorithmic_bytes_per_launch": alg_bytes // launches, "avg_launch_ms": dom_ms / launches,
+                             "launches_per_pass": launches,
+                             "kernel_scope": (("k_synth_group2 = residue + floor + inverse MDCT + window / overlap-add / clip / interleave of two consecutive frames per "
+                                               "workgroup (the overlap inside a group on chip), two launches per pass (the groups with an odd index, then the even ones, "
+                                               "which also emit the overlaps between groups), timed together by hipEvents on ONE stream"
+                                               if names[dom].startswith("k_synth_group") else
+                                               "k_synth+k_synth_emit = residue + floor + inverse MDCT + (paired emission) window / overlap-add / clip / interleave of the "
+                                               "steady-state frames, two launches per pass (odd frames, then the emitting even frames), timed together, one stream")
+                                              if fused else "k_synth = residue + floor + inverse MDCT; overlap-add in k_ola_compact"),
+                             # how to read the numbers: `frac` / `achieved` / `avg_launch_ms` are ONE decoder instance (what a ReadSamples caller's
+                             # kernels run at); `value` and `whole_pass_frac` are the timed loop over `streams` instances, whose launches overlap
+                             "one_stream": {"pass_us": dom_ms * 1e3, "frames_per_s": FRAMES / (dom_ms * 1e-3), "frac": achieved / HBM_PEAK_GBPS},
+                             "timed_loop": {"streams": nin, "pass_us": step_ms * 1e3, "frames_per_s": FRAMES / (step_ms * 1e-3),
+                                            "frac": alg_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
+                             "rocprof_avg_us": rocprof_us,
+                             "unfused": unfused,
+                             "working_set_MiB": touched / (1 << 20), "regime": "HBM-resident: a batch is revisited after %.0f MiB went by (Infinity Cache: 256 MiB)" % (touched / (1 << 20)),
+                             # the same bytes over one whole pass of the pipeline (all kernels, the batches of the streams overlapped)
+                             "whole_pass_GBps": alg_bytes / (step_ms * 1e-3) / 1e9, "whole_pass_frac": alg_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                             "l3_resident": {"working_set_MiB": nin * per_batch_bytes / (1 << 20), "frames_per_s": world * FRAMES * passes_l3 / el_l3,
+                                             "ms_per_pass": l3_ms, "kernels_ms": {names[k]: km_l3[k] for k in live},
+                                             "frac": alg_bytes / (km_l3[dom] * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                                             "whole_pass_frac": alg_bytes / (l3_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
+                             "copy_ceiling_GBps": ceiling},
+                "pcm_digest_ok": digest_ok, "pcm_digests_checked": digest_n, "pcm_batches_timed": digest_total,
+                "c5": c5,
+            })
+            if world == 1 and not args.no_configs:
+                out["configs"] = config_lines(nv, torch, ctx, ROOT)
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    out["end_to_end"] = end_to_end(nv, ctx, headers, ll)
+                except Exception as e:  # reported beside the headline, never part of it
+                    out["end_to_end"] = {"error": repr(e)[:200]}
+                out["cpu_baseline"] = cpu_baseline(headers, ll)
         print(json.dumps(out), flush=True)
     for _, ctx_k, stream_k, batches_k in insts:
         for b, _ in batches_k:

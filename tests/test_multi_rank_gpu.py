@@ -23,8 +23,8 @@ def _last_json(text):
 def test_bench_two_ranks_share_one_gpu():
     env = dict(os.environ)
     env["NVH_BENCH_SHARE_GPU"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--min-timed-ms", "60",
-                        "--working-set-mib", "64", "--no-configs", "--no-cpu-baseline", "--no-unfused", "--c5-scale", "0.1"], cwd=ROOT, env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
+                        "--min-timed-ms", "60", "--working-set-mib", "64", "--no-configs", "--no-cpu-baseline", "--no-unfused", "--c5-scale", "0.1"], cwd=ROOT, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:]
     d = _last_json(r.stdout)
@@ -47,8 +47,8 @@ def test_bench_four_ranks_share_one_gpu():
     the gather into the root and its device-side word sums.  A dry run of the code path, not a rate."""
     env = dict(os.environ)
     env["NVH_BENCH_SHARE_GPU"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--min-timed-ms", "60",
-                        "--working-set-mib", "64", "--no-configs", "--no-cpu-baseline", "--no-unfused", "--c5-scale", "0.1", "--c5-workers", "4"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--full",
+                        "--min-timed-ms", "60", "--working-set-mib", "64", "--no-configs", "--no-cpu-baseline", "--no-unfused", "--c5-scale", "0.1", "--c5-workers", "4"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:]
     d = _last_json(r.stdout)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the interesting fields of bench.py's JSON line (stdin)."""
+"""Print the interesting fields of a bench.py --full JSON line (stdin)."""
 import json
 import sys
 for line in sys.stdin:

@@ -7,9 +7,9 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 NAME=${1:-r03}
 OUT=gpurun_out/prof_$NAME
 rm -rf $OUT; mkdir -p $OUT
-B="python bench.py --no-cpu-baseline --no-configs --no-unfused --c5-scale 0 --steps 20 --warmup 5 --min-timed-ms 300 --streams 1 $3"
+B="python bench.py --full --no-cpu-baseline --no-configs --no-unfused --c5-scale 0 --steps 20 --warmup 5 --min-timed-ms 300 --streams 1 $3"
 # (the counter passes serialise the launches: a shorter timed region there -- the counters are per launch, a few thousand launches are plenty)
-BP="python bench.py --no-cpu-baseline --no-configs --no-unfused --c5-scale 0 --steps 10 --warmup 2 --min-timed-ms 40 --streams 1 $3"
+BP="python bench.py --full --no-cpu-baseline --no-configs --no-unfused --c5-scale 0 --steps 10 --warmup 2 --min-timed-ms 40 --streams 1 $3"
 BUILD=$(python -c "from nvorbis_amd import native; print(native.build_id())" 2>/dev/null | tail -1)
 rocprofv3 --kernel-trace --stats -d $OUT/trace -- $B > $OUT/trace.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -- $BP > $OUT/fetch.log 2>&1

@@ -13,7 +13,7 @@ done
 python tools/pmc_dump.py $(find gpurun_out/ps* -name '*.db') > gpurun_out/r06e_stalls.txt 2>&1
 rm -rf gpurun_out/ps[0-9] gpurun_out/ps[0-9].log
 grep -A16 "^k_synth_group2" gpurun_out/r06e_stalls.txt | head -24
-BB="python bench.py --no-cpu-baseline --no-configs --no-unfused --c5-scale 0 --steps 100 --min-timed-ms 700"
+BB="python bench.py --full --no-cpu-baseline --no-configs --no-unfused --c5-scale 0 --steps 100 --min-timed-ms 700"
 for s in 1 3; do for f in 2 1; do
   echo -n "NVH_FPW=$f streams $s: "; NVH_FPW=$f timeout 120 $BB --streams $s 2>/dev/null | python tools/bench_brief.py
 done; done | tee gpurun_out/r06e_fpw.txt

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round6_gpu1.sh -- first GPU session of round 6: frame groups (NVH_FPW=2 / 4) against the one-frame form (NVH_FPW=1): the headline
 # loop with its digest check, one stream and three; then the file-level parity tests under each form.
-cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
+cd "$(dirname "$0")/.."; OUT=${OUT:-out}; mkdir -p "$OUT"
 brief='import json,sys
 t=sys.stdin.read().strip().splitlines()
 try:
@@ -12,7 +12,7 @@ for r in 1 2; do
   for f in 1 2 4; do
     for st in 3 1; do
       echo -n "FPW=$f streams=$st: "
-      NVH_FPW=$f timeout 300 python bench.py --no-configs --no-cpu-baseline --no-unfused --c5-scale 0 --steps 100 --min-timed-ms 1000 --streams $st 2>gpurun_out/r06a_err_$f.log | python -c "$brief"
+      NVH_FPW=$f timeout 300 python bench.py --full --no-configs --no-cpu-baseline --no-unfused --c5-scale 0 --steps 100 --min-timed-ms 1000 --streams $st 2>$OUT/r06a_err_$f.log | python -c "$brief"
     done
   done
 done

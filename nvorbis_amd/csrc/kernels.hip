@@ -585,13 +585,15 @@ k_couple_floor(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, int* __r
 
 // Parallel form: valid when no overlap region reaches into a tail (FrameBatch::sequential_ola == false),
 // i.e. every tail read here is an untouched windowed block.  One workgroup per frame.
-// (PCM: float, or int16_t for the _s16 twin -- kernels_common.h: pcm_s16_value -- here and in every emitting kernel below)
-// PLANAR: the channel-planar twins -- sample time t of channel c at pcm + c * plane_stride + t; the per-sample index runs plane-major
-// (o -> channel o / emit_count, time o % emit_count), so consecutive lanes write consecutive addresses of one plane.
-template <typename PCM, bool PLANAR = false>
-__device__ __forceinline__ void ola_emit_body(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work,
-                                              const float* __restrict__ carry, PCM* __restrict__ pcm, int clip,
-                                              int* __restrict__ clipped_flag, long long plane_stride = 0) {
+// The kernels that write PCM are templates, instantiated for every form of PCM at the end of their section (kernels_common.h:
+// NVH_FOR_PCM_TWINS).  PCM: float or int16_t samples (kernels_common.h: pcm_s16_value).  PLANAR: channel-planar output -- sample
+// time t of channel c at pcm + c * plane_stride + t (plane_stride: the last argument, empty in the interleaved forms:
+// pcm_stride_t); the per-sample index then runs plane-major (o -> channel o / emit_count, time o % emit_count), so consecutive
+// lanes write consecutive addresses of one plane.
+template <typename PCM, bool PLANAR>
+__global__ void __launch_bounds__(NVH_THREADS)
+k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry, PCM* __restrict__ pcm,
+           int clip, int* __restrict__ clipped_flag, pcm_stride_t<PLANAR> plane_stride) {
   const int f = blockIdx.x;
   const NvhFrame fr = Bt.frames[f];
   const int ch = S.channels;
@@ -620,34 +622,14 @@ __device__ __forceinline__ void ola_emit_body(NvhDevSetup S, NvhDevBatch Bt, con
   }
   report_clipped(clipped, clipped_flag);
 }
-extern "C" __global__ void __launch_bounds__(NVH_THREADS)
-k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
-           float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
-  ola_emit_body<float>(S, Bt, work, carry, pcm, clip, clipped_flag);
-}
-extern "C" __global__ void __launch_bounds__(NVH_THREADS)
-k_ola_emit_s16(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
-               int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
-  ola_emit_body<int16_t>(S, Bt, work, carry, pcm, clip, clipped_flag);
-}
-extern "C" __global__ void __launch_bounds__(NVH_THREADS)
-k_ola_emit_planar(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
-                  float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, long long plane_stride) {
-  ola_emit_body<float, true>(S, Bt, work, carry, pcm, clip, clipped_flag, plane_stride);
-}
-extern "C" __global__ void __launch_bounds__(NVH_THREADS)
-k_ola_emit_s16_planar(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
-                      int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, long long plane_stride) {
-  ola_emit_body<int16_t, true>(S, Bt, work, carry, pcm, clip, clipped_flag, plane_stride);
-}
 
 // Sequential form: one workgroup walks the frames in order and performs the adds in place, exactly
 // like the reference's ping-pong buffers (needed only for streams whose window flags disagree with
 // their neighbours so that an overlap reaches a block's own tail).
-template <typename PCM, bool PLANAR = false>  // (PLANAR: as ola_emit_body)
-__device__ __forceinline__ void ola_emit_seq_body(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work,
-                                                  const float* __restrict__ carry, PCM* __restrict__ pcm, int clip,
-                                                  int* __restrict__ clipped_flag, long long plane_stride = 0) {
+template <typename PCM, bool PLANAR>
+__global__ void __launch_bounds__(NVH_THREADS)
+k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry, PCM* __restrict__ pcm,
+               int clip, int* __restrict__ clipped_flag, pcm_stride_t<PLANAR> plane_stride) {
   const int ch = S.channels;
   int clipped = 0;
   for (int f = 0; f < Bt.nframes; ++f) {
@@ -677,27 +659,12 @@ __device__ __forceinline__ void ola_emit_seq_body(NvhDevSetup S, NvhDevBatch Bt,
   }
   report_clipped(clipped, clipped_flag);
 }
-extern "C" __global__ void __launch_bounds__(NVH_THREADS)
-k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry,
-               float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
-  ola_emit_seq_body<float>(S, Bt, work, carry, pcm, clip, clipped_flag);
-}
-extern "C" __global__ void __launch_bounds__(NVH_THREADS)
-k_ola_emit_seq_s16(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry,
-                   int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag) {
-  ola_emit_seq_body<int16_t>(S, Bt, work, carry, pcm, clip, clipped_flag);
-}
-extern "C" __global__ void __launch_bounds__(NVH_THREADS)
-k_ola_emit_seq_planar(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry,
-                      float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, long long plane_stride) {
-  ola_emit_seq_body<float, true>(S, Bt, work, carry, pcm, clip, clipped_flag, plane_stride);
-}
-extern "C" __global__ void __launch_bounds__(NVH_THREADS)
-k_ola_emit_seq_s16_planar(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry,
-                          int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, long long plane_stride) {
-  ola_emit_seq_body<int16_t, true>(S, Bt, work, carry, pcm, clip, clipped_flag, plane_stride);
-}
-
+#define NVH_OLA_EMIT_TWINS(PCM, PLANAR, SFX)                                                                                    \
+  template __global__ void k_ola_emit<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,   \
+                                                   pcm_stride_t<PLANAR>);                                                   \
+  template __global__ void k_ola_emit_seq<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, float*, const float*, PCM*, int, int*,     \
+                                                       pcm_stride_t<PLANAR>);
+NVH_FOR_PCM_TWINS(NVH_OLA_EMIT_TWINS)
 
 // ================================================================================================
 // Overlap-add + interleave + clip from the COMPACT block layout written by k_imdct_compact
@@ -744,10 +711,7 @@ __device__ __forceinline__ int ola_vec(const NvhDevSetup& S, const NvhFrame& fr,
                                     : compact_value4(pp, wp, fr.ov_n, (fr.ov_exec_mask >> c) & 1, fr.ov_src + j0);
         v.x = v.x + t4.x; v.y = v.y + t4.y; v.z = v.z + t4.z; v.w = v.w + t4.w;
       }
-      if (clip) {
-        v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
-        v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
-      }
+      if (clip) clip_value4(v, &clipped);
       flat[0 * CH + c] = v.x;
       flat[1 * CH + c] = v.y;
       flat[2 * CH + c] = v.z;
@@ -770,7 +734,10 @@ __device__ __forceinline__ int ola_vec(const NvhDevSetup& S, const NvhFrame& fr,
 // of the block are +-A[i], y[n/2+i] and y[n-1-i] of the predecessor are both B[i] (Mdct.cs:275-303), so the pair of
 // sample times (i, n/2-1-i) needs exactly A[i] and B[i].  A lane takes four consecutive i: two 16-byte loads per channel,
 // two groups of four sample times out (ola_vec reads every value twice: once for i, once, reversed, for n/2-1-i).
-// Same products, same additions, same order as ola_vec / the reference (Mode.cs:160-166, StreamDecoder.cs:532-541).
+// Same products, same additions, same order as ola_vec / the reference (Mode.cs:160-166, StreamDecoder.cs:532-541): the
+// arithmetic is kernels_common.h's ola_sym_mul_add, shared with the emitting synthesis kernels.  What is not shared is the
+// store: here a lane holds CH channels (CH a template argument, up to eight) and writes CH vectors per half, where the synthesis
+// kernels' pcm_emit_group holds at most two channels with the count in a register.
 template <int CH, typename PCM>
 __device__ __forceinline__ int ola_sym(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev,
                                        const float* __restrict__ w, const float* __restrict__ wp, PCM* out, int clip, int tid, int threads) {
@@ -788,19 +755,11 @@ __device__ __forceinline__ int ola_sym(const NvhDevSetup& S, const NvhFrame& fr,
     for (int c = 0; c < CH; ++c) {
       const float4 a = *reinterpret_cast<const float4*>(cur + (long long)c * S.block1 + i0);
       const float4 b = *reinterpret_cast<const float4*>(prev + (long long)c * S.block1 + n2 + i0);
-      // sample times i0 .. i0+3
-      float4 v = make_float4(a.x * wf.x, a.y * wf.y, a.z * wf.z, a.w * wf.w);
-      float4 t = make_float4(b.x * pf.x, b.y * pf.y, b.z * pf.z, b.w * pf.w);
-      v.x = v.x + t.x; v.y = v.y + t.y; v.z = v.z + t.z; v.w = v.w + t.w;
-      // sample times n/2-4-i0 .. n/2-1-i0: the block's values are -A reversed, the predecessor's B reversed
-      float4 u = make_float4(-a.w * wm.x, -a.z * wm.y, -a.y * wm.z, -a.x * wm.w);
-      float4 r = make_float4(b.w * pm.x, b.z * pm.y, b.y * pm.z, b.x * pm.w);
-      u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
+      float4 v, u;  // sample times i0 .. i0+3, and n/2-4-i0 .. n/2-1-i0 (the block's values are -A reversed, the predecessor's B reversed)
+      ola_sym_mul_add(a, b, wf, wm, pf, pm, v, u);
       if (clip) {
-        v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
-        v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
-        u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
-        u.z = clip_value(u.z, &clipped); u.w = clip_value(u.w, &clipped);
+        clip_value4(v, &clipped);
+        clip_value4(u, &clipped);
       }
       fwd[0 * CH + c] = v.x; fwd[1 * CH + c] = v.y; fwd[2 * CH + c] = v.z; fwd[3 * CH + c] = v.w;
       mir[0 * CH + c] = u.x; mir[1 * CH + c] = u.y; mir[2 * CH + c] = u.z; mir[3 * CH + c] = u.w;
@@ -847,12 +806,8 @@ __device__ __forceinline__ int ola_sym_lds(const NvhDevSetup& S, const NvhFrame&
     const float4 pm = *reinterpret_cast<const float4*>(wp + (n - 4 - i0));
     const float4 a = *reinterpret_cast<const float4*>(cur + (long long)c * S.block1 + i0);
     const float4 b = *reinterpret_cast<const float4*>(prev + (long long)c * S.block1 + n2 + i0);
-    float4 v = make_float4(a.x * wf.x, a.y * wf.y, a.z * wf.z, a.w * wf.w);
-    const float4 t = make_float4(b.x * pf.x, b.y * pf.y, b.z * pf.z, b.w * pf.w);
-    v.x = v.x + t.x; v.y = v.y + t.y; v.z = v.z + t.z; v.w = v.w + t.w;
-    float4 u = make_float4(-a.w * wm.x, -a.z * wm.y, -a.y * wm.z, -a.x * wm.w);
-    const float4 r = make_float4(b.w * pm.x, b.z * pm.y, b.y * pm.z, b.x * pm.w);
-    u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
+    float4 v, u;
+    ola_sym_mul_add(a, b, wf, wm, pf, pm, v, u);
     *reinterpret_cast<float4*>(sF + c * RUN + 4 * gl) = v;              // sample times 4 g0 + 4 gl ..
     *reinterpret_cast<float4*>(sM + c * RUN + 4 * (gw - 1 - gl)) = u;   // sample times n/2 - 4 (g0 + gw) + 4 (gw - 1 - gl) ..
   }
@@ -879,7 +834,7 @@ __device__ __forceinline__ int ola_sym_lds(const NvhDevSetup& S, const NvhFrame&
   return clipped;
 }
 
-// The channel-planar forms of ola_vec and ola_sym (k_ola_compact's _planar twins): the same arithmetic, one lane per (channel,
+// The channel-planar forms of ola_vec and ola_sym (k_ola_compact<PCM, true>): the same arithmetic, one lane per (channel,
 // group of four sample times), plane-major -- consecutive lanes take consecutive groups of one plane, and every vector leaves
 // as one store (16 bytes of float, 8 of int16_t) to its channel's plane: no interleave, no LDS.  `out` points at the frame's
 // first sample of plane 0, 16-byte aligned with the plane stride a multiple of four (nvh_launch.hip).
@@ -901,10 +856,7 @@ __device__ __forceinline__ int ola_vec_planar(const NvhDevSetup& S, const NvhFra
                                   : compact_value4(pp, wp, fr.ov_n, (fr.ov_exec_mask >> c) & 1, fr.ov_src + j0);
       v.x = v.x + t4.x; v.y = v.y + t4.y; v.z = v.z + t4.z; v.w = v.w + t4.w;
     }
-    if (clip) {
-      v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
-      v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
-    }
+    if (clip) clip_value4(v, &clipped);
     pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out + (long long)c * plane_stride) + g, v.x, v.y, v.z, v.w);
   }
   return clipped;
@@ -925,17 +877,11 @@ __device__ __forceinline__ int ola_sym_planar(const NvhDevSetup& S, const NvhFra
     const float4 pm = *reinterpret_cast<const float4*>(wp + (n - 4 - i0));
     const float4 a = *reinterpret_cast<const float4*>(cur + (long long)c * S.block1 + i0);
     const float4 b = *reinterpret_cast<const float4*>(prev + (long long)c * S.block1 + n2 + i0);
-    float4 v = make_float4(a.x * wf.x, a.y * wf.y, a.z * wf.z, a.w * wf.w);
-    const float4 t = make_float4(b.x * pf.x, b.y * pf.y, b.z * pf.z, b.w * pf.w);
-    v.x = v.x + t.x; v.y = v.y + t.y; v.z = v.z + t.z; v.w = v.w + t.w;
-    float4 u = make_float4(-a.w * wm.x, -a.z * wm.y, -a.y * wm.z, -a.x * wm.w);
-    const float4 r = make_float4(b.w * pm.x, b.z * pm.y, b.y * pm.z, b.x * pm.w);
-    u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
+    float4 v, u;
+    ola_sym_mul_add(a, b, wf, wm, pf, pm, v, u);
     if (clip) {
-      v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
-      v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
-      u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
-      u.z = clip_value(u.z, &clipped); u.w = clip_value(u.w, &clipped);
+      clip_value4(v, &clipped);
+      clip_value4(u, &clipped);
     }
     pcm4_t<PCM>* p = reinterpret_cast<pcm4_t<PCM>*>(out + (long long)c * plane_stride);
     pcm_store4(p + g, v.x, v.y, v.z, v.w);                   // sample times i0 .. i0 + 3
@@ -948,41 +894,139 @@ __device__ __forceinline__ int ola_sym_planar(const NvhDevSetup& S, const NvhFra
 // per frame leave the CUs with four wavefronts each): lane `OLA_TID` of `NVH_OLA_THREADS`.
 #define NVH_OLA_THREADS ((int)(blockDim.x * gridDim.y))
 #define NVH_OLA_TID ((int)(blockIdx.y * blockDim.x + threadIdx.x))
-extern "C" __global__ void __launch_bounds__(256)
+template <typename PCM, bool PLANAR>
+__global__ void __launch_bounds__(256)
 k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
-              float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out, int last_decoded,
-              int nosym, const int* __restrict__ list, int emitted) {
-  typedef float PCM;
-  constexpr bool PLANAR = false;
-  constexpr long long plane_stride = 0;
-#include "ola_compact_body.inc"
+              PCM* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out, int last_decoded,
+              int nosym, const int* __restrict__ list, int emitted, pcm_stride_t<PLANAR> plane_stride) {
+  // (The body is this kernel template's own and not an inlined function template's: as one, it compiles to a different register
+  // allocation.)
+  // list: the frames paired emission left to this kernel (nvh_launch.hip); emitted: k_synth wrote the PCM of every frame with
+  // NVH_EMIT_DONE (such a frame is on the list only as the block that becomes the carried tail)
+  const int f = list ? list[blockIdx.x] : (int)blockIdx.x;
+  const NvhFrame fr = Bt.frames[f];
+  const int ch = S.channels;
+  if (f == last_decoded && carry_out) {
+    // this block becomes the carried tail of the next batch (StreamDecoder's _prevPacketBuf), stored fully windowed
+    const float* __restrict__ wl = S.windows + fr.window_off;
+    for (int o = NVH_OLA_TID; o < (fr.n >> 2) * ch; o += NVH_OLA_THREADS) {
+      int c = o / (fr.n >> 2), g = o - c * (fr.n >> 2);
+      const float* plane = work + ((long long)f * ch + c) * S.block1;
+      *reinterpret_cast<float4*>(carry_out + (long long)c * S.block1 + 4 * g) =
+          compact_value4(plane, wl, fr.n, Bt.chans[fr.chan_off + c].exec, 4 * g);
+    }
+  }
+  const int total = fr.emit_count * ch;
+  if (total <= 0) return;
+  if (emitted && (fr.emit_flags & NVH_EMIT_DONE)) return;
+  const float* cur = work + (long long)f * ch * S.block1;
+  const float* prev = nullptr;
+  if (fr.ov_len > 0) prev = (fr.ov_frame == -2) ? carry : (fr.ov_frame >= 0 ? work + (long long)fr.ov_frame * ch * S.block1 : nullptr);
+  const float* __restrict__ w = S.windows + fr.window_off;
+  const float* __restrict__ wp = S.windows + fr.ov_window_off;
+  const NvhChan* chans = Bt.chans + fr.chan_off;
+  PCM* out = pcm + fr.out_pos * (PLANAR ? 1 : ch);
+  int clipped = 0;
+  // the carried block (ov_frame == -2) is always stored fully windowed (k_expand_carry); blocks of this batch are compact
+  const bool prev_full = fr.ov_frame == -2;
+
+  // fast path: everything in units of four samples (true for every frame of a well-formed stream except an
+  // EOS-trimmed last one), up to 8 channels
+  const bool vec = !PLANAR && fr.n != 0 && ch <= 8 && ((fr.emit_start | fr.emit_count | fr.start | fr.ov_src | fr.ov_len) & 3) == 0 &&
+                   ((fr.out_pos * ch) & 3) == 0;
+  // steady state: whole first half over the whole second half of an executing predecessor of the same size
+  const unsigned all_ch = ch >= 32 ? 0xFFFFFFFFu : ((1u << ch) - 1u);
+  if constexpr (PLANAR) {
+    // channel-planar: every plane's first sample of the frame on a 16-byte boundary (an aligned base, a plane stride and an
+    // output position in whole groups of four), up to 32 channels (the execute flags of the frame record's masks); else the
+    // per-sample form below
+    const bool pvec = fr.n != 0 && ch <= 32 && ((fr.emit_start | fr.emit_count | fr.start | fr.ov_src | fr.ov_len) & 3) == 0 &&
+                      ((fr.out_pos | plane_stride) & 3) == 0 && (reinterpret_cast<uintptr_t>(pcm) & 15u) == 0;
+    const unsigned pall = ch >= 32 ? 0xFFFFFFFFu : ((1u << ch) - 1u);
+    const bool psym = pvec && prev && !prev_full && fr.ov_n == fr.n && fr.start == 0 && fr.emit_start == 0 &&
+                      fr.emit_count == (fr.n >> 1) && fr.ov_src == (fr.n >> 1) && fr.ov_len == (fr.n >> 1) &&
+                      (fr.exec_mask & pall) == pall && (fr.ov_exec_mask & pall) == pall && !nosym;
+    if (psym || pvec) {
+      clipped = psym ? ola_sym_planar<PCM>(S, fr, cur, prev, w, wp, out, plane_stride, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS)
+                     : ola_vec_planar<PCM>(S, fr, cur, prev, prev_full, w, wp, out, plane_stride, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS);
+      report_clipped(clipped, clipped_flag);
+      return;
+    }
+  }
+  const bool sym = vec && prev && !prev_full && fr.ov_n == fr.n && fr.start == 0 && fr.emit_start == 0 && fr.emit_count == (fr.n >> 1) &&
+                   fr.ov_src == (fr.n >> 1) && fr.ov_len == (fr.n >> 1) && (fr.exec_mask & all_ch) == all_ch &&
+                   (fr.ov_exec_mask & all_ch) == all_ch && !nosym;
+  if (sym && ch > 2 && gridDim.y * NVH_OLA_GW >= (unsigned)(fr.n >> 4)) {
+    // more than two channels: per-(group, channel) lanes, interleave through LDS (the launch gives every frame gridDim.y
+    // workgroups of NVH_OLA_GW groups each: nvh_launch.hip)
+    __shared__ __attribute__((aligned(16))) float s_run[2 * 8 * 4 * NVH_OLA_GW];
+    switch (ch) {
+      case 3: clipped = ola_sym_lds<3, PCM>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
+      case 4: clipped = ola_sym_lds<4, PCM>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
+      case 5: clipped = ola_sym_lds<5, PCM>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
+      case 6: clipped = ola_sym_lds<6, PCM>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
+      case 7: clipped = ola_sym_lds<7, PCM>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
+      default: clipped = ola_sym_lds<8, PCM>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
+    }
+    report_clipped(clipped, clipped_flag);
+    return;
+  }
+  if (sym) {
+    switch (ch) {
+      case 1: clipped = ola_sym<1, PCM>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 2: clipped = ola_sym<2, PCM>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 3: clipped = ola_sym<3, PCM>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 4: clipped = ola_sym<4, PCM>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 5: clipped = ola_sym<5, PCM>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 6: clipped = ola_sym<6, PCM>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 7: clipped = ola_sym<7, PCM>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      default: clipped = ola_sym<8, PCM>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+    }
+    report_clipped(clipped, clipped_flag);
+    return;
+  }
+  if (vec) {
+    switch (ch) {
+      case 1: clipped = ola_vec<1, PCM>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 2: clipped = ola_vec<2, PCM>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 3: clipped = ola_vec<3, PCM>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 4: clipped = ola_vec<4, PCM>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 5: clipped = ola_vec<5, PCM>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 6: clipped = ola_vec<6, PCM>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      case 7: clipped = ola_vec<7, PCM>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+      default: clipped = ola_vec<8, PCM>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
+    }
+    report_clipped(clipped, clipped_flag);
+    return;
+  }
+
+  for (int o = NVH_OLA_TID; o < total; o += NVH_OLA_THREADS) {
+    int t = o / ch, c = o - t * ch;
+    if constexpr (PLANAR) c = o / fr.emit_count, t = o - c * fr.emit_count;  // plane-major: consecutive lanes, one plane
+    int idx = fr.emit_start + t;
+    const NvhChan cn = chans[c];
+    float v;
+    if (fr.n == 0) {
+      // drained carried tail (StreamDecoder.cs:352-356): the previous block's windowed samples as they are
+      v = prev[(long long)c * S.block1 + fr.ov_src + t];
+    } else {
+      v = compact_value(cur + (long long)c * S.block1, w, fr.n, cn.exec, idx);
+      int j = idx - fr.start;
+      if (prev && j >= 0 && j < fr.ov_len) {  // OverlapBuffers: next[start + j] += previous[prevStart + j]
+        const float* pp = prev + (long long)c * S.block1;
+        v = v + (prev_full ? pp[fr.ov_src + j] : compact_value(pp, wp, fr.ov_n, cn.ov_exec, fr.ov_src + j));
+      }
+    }
+    if (clip) v = clip_value(v, &clipped);
+    if constexpr (PLANAR) pcm_store1(out + c * plane_stride + t, v);
+    else pcm_store1(out + o, v);
+  }
+  report_clipped(clipped, clipped_flag);
 }
-extern "C" __global__ void __launch_bounds__(256)
-k_ola_compact_s16(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
-                  int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out, int last_decoded,
-                  int nosym, const int* __restrict__ list, int emitted) {
-  typedef int16_t PCM;
-  constexpr bool PLANAR = false;
-  constexpr long long plane_stride = 0;
-#include "ola_compact_body.inc"
-}
-// the channel-planar twins: plane_stride samples between the channels' planes
-extern "C" __global__ void __launch_bounds__(256)
-k_ola_compact_planar(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
-                     float* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out, int last_decoded,
-                     int nosym, const int* __restrict__ list, int emitted, long long plane_stride) {
-  typedef float PCM;
-  constexpr bool PLANAR = true;
-#include "ola_compact_body.inc"
-}
-extern "C" __global__ void __launch_bounds__(256)
-k_ola_compact_s16_planar(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
-                         int16_t* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out,
-                         int last_decoded, int nosym, const int* __restrict__ list, int emitted, long long plane_stride) {
-  typedef int16_t PCM;
-  constexpr bool PLANAR = true;
-#include "ola_compact_body.inc"
-}
+#define NVH_OLA_COMPACT_TWINS(PCM, PLANAR, SFX)                                                                                     \
+  template __global__ void k_ola_compact<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,    \
+                                                      float*, int, int, const int*, int, pcm_stride_t<PLANAR>);
+NVH_FOR_PCM_TWINS(NVH_OLA_COMPACT_TWINS)
 
 // Expands the compact planes of one frame into the fully windowed block (the carried tail format shared by all
 // overlap kernels).  One workgroup, launched once per batch for its last decoded frame.

@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#ifdef __HIPCC__
+#include <type_traits>
+#endif
 
 #include "nvh_format.h"
 
@@ -95,7 +98,18 @@ struct NvhSynthArgs {
   float* carry_out;         // receives the last decoded block, fully windowed (NVH_EMIT_CARRY_OUT); nullptr: k_ola_compact writes it
 };
 
+// The forms of PCM the emitting kernels write: M(sample type, channel-planar, suffix of the kernels' names).  Every such kernel
+// exists once per entry, written by its own file through this list and declared through it in nvh_internal.h; the host picks one
+// by the same pair (nvh_launch.hip: with_pcm_twins), so one more form is one more entry here.
+#define NVH_FOR_PCM_TWINS(M) M(float, false, ) M(int16_t, false, _s16) M(float, true, _planar) M(int16_t, true, _s16_planar)
+
 #ifdef __HIPCC__
+// The last argument of the k_ola_* kernels: the samples between the channels' planes, of the channel-planar forms only.  The
+// interleaved forms take an empty struct in its place, which leaves their kernel-argument layout what it was without the argument
+// (k_ola_compact reads the grid's shape from the implicit arguments behind it).
+struct NvhNoStride {};
+template <bool PLANAR> using pcm_stride_t = std::conditional_t<PLANAR, long long, NvhNoStride>;
+
 // PCM leaves the chip (a copy engine or the gather reads it next) and no kernel reads it again: streaming stores (`nt`), which do
 // not displace what the kernels do re-read -- the odd frames' planes, the slabs the odd launch touched for the even one -- from
 // the L2 / Infinity Cache.  Same box, three streams, working set past the Infinity Cache: 24.0 -> 22.2 us per 4096-frame pass.
@@ -189,6 +203,31 @@ __device__ __forceinline__ float clip_value(float v, int* clipped) {
   const bool hi = v > .99999994f, lo = v < -.99999994f;
   *clipped |= (int)(hi | lo);
   return hi ? 0.99999994f : (lo ? -0.99999994f : v);
+}
+
+__device__ __forceinline__ void clip_value4(float4& v, int* clipped) {
+  v.x = clip_value(v.x, clipped); v.y = clip_value(v.y, clipped);
+  v.z = clip_value(v.z, clipped); v.w = clip_value(v.w, clipped);
+}
+
+// ---- the symmetric overlap-add tail ------------------------------------------------------------------------------------------
+// The steady state of a stream: a block whose whole first half overlaps the whole second half of a predecessor of the same size.
+// Sample times i0 .. i0 + 3 (v) and n/2 - 4 - i0 .. n/2 - 1 - i0 (u, in time order) of the overlap need exactly a = the later
+// block's first quarter and b = the earlier block's third quarter at i0 .. i0 + 3 (Mdct.cs:275-303: y[n/2-1-x] = -y[x],
+// y[n-1-x] = y[n/2+x]), times the later block's window at i0 (wf) and n/2 - 4 - i0 (wm) and the earlier block's at n/2 + i0 (pf) and
+// n - 4 - i0 (pm): Mode.cs:160-166 windows, StreamDecoder.cs:532-541 adds, as separately rounded products and sums in this order
+// (the build has -ffp-contract=off; -a.w * wm.x is the product of the negated value, as the reference's mirrored read gives it).
+// k_ola_compact's read-once forms (kernels.hip: ola_sym, ola_sym_lds, ola_sym_planar) share it.  The emitting synthesis kernels
+// (kernels_synth.hip: synth_emit, synth_group_body, synth_emit8_direct) spell the same lines out in place: routed through a
+// shared helper, k_synth_emit and the frame-group kernels come out with another register allocation (profiles/pcm_twins_isa.txt).
+__device__ __forceinline__ void ola_sym_mul_add(const float4& a, const float4& b, const float4& wf, const float4& wm, const float4& pf,
+                                                const float4& pm, float4& v, float4& u) {
+  v = make_float4(a.x * wf.x, a.y * wf.y, a.z * wf.z, a.w * wf.w);
+  const float4 tt = make_float4(b.x * pf.x, b.y * pf.y, b.z * pf.z, b.w * pf.w);
+  v.x = v.x + tt.x; v.y = v.y + tt.y; v.z = v.z + tt.z; v.w = v.w + tt.w;
+  u = make_float4(-a.w * wm.x, -a.z * wm.y, -a.y * wm.z, -a.x * wm.w);
+  const float4 r = make_float4(b.w * pm.x, b.z * pm.y, b.y * pm.z, b.x * pm.w);
+  u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
 }
 
 // Four consecutive positions idx0 .. idx0+3 of a block (idx0 a multiple of 4: a group never straddles a quarter) from its compact

@@ -2106,33 +2106,19 @@ k_synth_tail(NvhSynthArgs A NVH_DBG_PARAMS) {
   synth_body<NVH_SYNTH_NT, 2, 1>(A, smem NVH_DBG_ARGS);
 }
 
-// up to eight channels, blocks up to 4096: 8 wavefronts per workgroup, the CU's LDS decides how many are resident
-extern "C" __global__ void __launch_bounds__(NVH_SYNTH_NT) __attribute__((amdgpu_waves_per_eu(NVH_SYNTH_WPE)))
-k_synth_emit(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_body<NVH_SYNTH_NT, 2, 2>(A, smem NVH_DBG_ARGS);
-}
-
-// The 16-bit twins of the kernels that write PCM (NVH_PCM_S16; A.pcm then points at int16_t samples: kernels_common.h,
-// pcm_s16_value).  k_synth, k_synth_tail and k_synth8 never store PCM (A.pcm is only tested in the emitting modes).
-extern "C" __global__ void __launch_bounds__(NVH_SYNTH_NT) __attribute__((amdgpu_waves_per_eu(NVH_SYNTH_WPE)))
-k_synth_emit_s16(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_body<NVH_SYNTH_NT, 2, 2, false, int16_t>(A, smem NVH_DBG_ARGS);
-}
-
-// The channel-planar twins (A.plane_stride: sample time t of channel c at pcm + c * plane_stride + t; kernels_common.h,
-// pcm_store_planes), float and 16-bit.
-extern "C" __global__ void __launch_bounds__(NVH_SYNTH_NT) __attribute__((amdgpu_waves_per_eu(NVH_SYNTH_WPE)))
-k_synth_emit_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_body<NVH_SYNTH_NT, 2, 2, false, float, true>(A, smem NVH_DBG_ARGS);
-}
-extern "C" __global__ void __launch_bounds__(NVH_SYNTH_NT) __attribute__((amdgpu_waves_per_eu(NVH_SYNTH_WPE)))
-k_synth_emit_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_body<NVH_SYNTH_NT, 2, 2, false, int16_t, true>(A, smem NVH_DBG_ARGS);
-}
+// The kernels that write PCM exist once per form of PCM (kernels_common.h: NVH_FOR_PCM_TWINS): PCM = float or int16_t samples
+// (A.pcm then points at int16_t: pcm_s16_value), PLANAR = channel-planar output (A.plane_stride: sample time t of channel c at
+// pcm + c * plane_stride + t), SFX = the suffix of the kernel's name.  One macro per family writes the four out where the float
+// interleaved kernel has always stood: the compiler's inlining follows the order of the functions in the file, and k_synth's own
+// code changes with it.  k_synth, k_synth_tail and k_synth8 never store PCM (A.pcm is only tested in the emitting modes).
+// paired emission, the even frames of a mono / stereo batch (synth_emit)
+#define NVH_SYNTH_EMIT(PCM, PLANAR, SFX)                                                                                   \
+  extern "C" __global__ void __launch_bounds__(NVH_SYNTH_NT) __attribute__((amdgpu_waves_per_eu(NVH_SYNTH_WPE)))           \
+  k_synth_emit##SFX(NvhSynthArgs A NVH_DBG_PARAMS) {                                                                       \
+    extern __shared__ __attribute__((aligned(16))) float smem[];                                                           \
+    synth_body<NVH_SYNTH_NT, 2, 2, false, PCM, PLANAR>(A, smem NVH_DBG_ARGS);                                              \
+  }
+NVH_FOR_PCM_TWINS(NVH_SYNTH_EMIT)
 
 // mono / stereo streams some of whose frames need the general bin walk (never with paired emission)
 extern "C" __global__ void __launch_bounds__(SP_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
@@ -2156,68 +2142,25 @@ k_synth8_g(NvhSynthArgs A NVH_DBG_PARAMS) {
 }
 
 // the even frames of a wide batch with paired emission: + the overlap-add of the steady-state overlaps (synth_emit8)
-extern "C" __global__ void __launch_bounds__(512)
-k_synth8_emit(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_body<512, NVH_SLAB_MAX_CH, 2>(A, smem NVH_DBG_ARGS);
-}
-extern "C" __global__ void __launch_bounds__(512)
-k_synth8_emit_s16(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_body<512, NVH_SLAB_MAX_CH, 2, false, int16_t>(A, smem NVH_DBG_ARGS);
-}
-extern "C" __global__ void __launch_bounds__(512)
-k_synth8_emit_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_body<512, NVH_SLAB_MAX_CH, 2, false, float, true>(A, smem NVH_DBG_ARGS);
-}
-extern "C" __global__ void __launch_bounds__(512)
-k_synth8_emit_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_body<512, NVH_SLAB_MAX_CH, 2, false, int16_t, true>(A, smem NVH_DBG_ARGS);
-}
+#define NVH_SYNTH8_EMIT(PCM, PLANAR, SFX)                                                  \
+  extern "C" __global__ void __launch_bounds__(512)                                        \
+  k_synth8_emit##SFX(NvhSynthArgs A NVH_DBG_PARAMS) {                                      \
+    extern __shared__ __attribute__((aligned(16))) float smem[];                           \
+    synth_body<512, NVH_SLAB_MAX_CH, 2, false, PCM, PLANAR>(A, smem NVH_DBG_ARGS);         \
+  }
+NVH_FOR_PCM_TWINS(NVH_SYNTH8_EMIT)
 
-// frame groups: two frames per workgroup (four wavefronts: one per (frame, channel)); LDS, not registers, decides the residency
-extern "C" __global__ void __launch_bounds__(256)
-k_synth_group2(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_group_body<256, 2>(A, smem NVH_DBG_ARGS);
-}
-
-// ... four frames per workgroup (eight wavefronts)
-extern "C" __global__ void __launch_bounds__(512)
-k_synth_group4(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_group_body<512, 4>(A, smem NVH_DBG_ARGS);
-}
-
-extern "C" __global__ void __launch_bounds__(256)
-k_synth_group2_s16(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_group_body<256, 2, int16_t>(A, smem NVH_DBG_ARGS);
-}
-extern "C" __global__ void __launch_bounds__(512)
-k_synth_group4_s16(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_group_body<512, 4, int16_t>(A, smem NVH_DBG_ARGS);
-}
-extern "C" __global__ void __launch_bounds__(256)
-k_synth_group2_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_group_body<256, 2, float, true>(A, smem NVH_DBG_ARGS);
-}
-extern "C" __global__ void __launch_bounds__(512)
-k_synth_group4_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_group_body<512, 4, float, true>(A, smem NVH_DBG_ARGS);
-}
-extern "C" __global__ void __launch_bounds__(256)
-k_synth_group2_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_group_body<256, 2, int16_t, true>(A, smem NVH_DBG_ARGS);
-}
-extern "C" __global__ void __launch_bounds__(512)
-k_synth_group4_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  synth_group_body<512, 4, int16_t, true>(A, smem NVH_DBG_ARGS);
-}
+// frame groups: two frames per workgroup (four wavefronts: one per (frame, channel)), and four frames per workgroup (eight
+// wavefronts); LDS, not registers, decides the residency
+#define NVH_SYNTH_GROUP(PCM, PLANAR, SFX)                                                  \
+  extern "C" __global__ void __launch_bounds__(256)                                        \
+  k_synth_group2##SFX(NvhSynthArgs A NVH_DBG_PARAMS) {                                     \
+    extern __shared__ __attribute__((aligned(16))) float smem[];                           \
+    synth_group_body<256, 2, PCM, PLANAR>(A, smem NVH_DBG_ARGS);                           \
+  }                                                                                        \
+  extern "C" __global__ void __launch_bounds__(512)                                        \
+  k_synth_group4##SFX(NvhSynthArgs A NVH_DBG_PARAMS) {                                     \
+    extern __shared__ __attribute__((aligned(16))) float smem[];                           \
+    synth_group_body<512, 4, PCM, PLANAR>(A, smem NVH_DBG_ARGS);                           \
+  }
+NVH_FOR_PCM_TWINS(NVH_SYNTH_GROUP)

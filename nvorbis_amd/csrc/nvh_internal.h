@@ -34,8 +34,6 @@ __global__ void k_imdct_window(NvhDevSetup S, NvhDevBatch Bt, float* work);
 __global__ void k_imdct_wave(NvhDevSetup S, NvhDevBatch Bt, float* work);
 __global__ void k_imdct_compact(NvhDevSetup S, NvhDevBatch Bt, float* work);
 __global__ void k_expand_carry(NvhDevSetup S, NvhDevBatch Bt, const float* work, float* carry_out, int f);
-__global__ void k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, float* pcm, int clip,
-                              int* clipped_flag, float* carry_out, int last_decoded, int nosym, const int* list, int emitted);
 __global__ void k_spectrum(NvhDevSetup S, NvhDevBatch Bt, float* work, int* err, int cap_pass, int cap_ops, int cap_ent NVH_DBG_PARAMS);
 __global__ void k_spectrum_f0(NvhDevSetup S, NvhDevBatch Bt, float* work, int* err, int cap_pass, int cap_ops, int cap_ent);
 __global__ void k_spectrum_imdct(NvhDevSetup S, NvhDevBatch Bt, float* work, int* err, int cap_pass, int cap_ops, int cap_ent NVH_DBG_PARAMS);
@@ -68,46 +66,16 @@ __global__ void k_copy_f4(const float4* src, float4* dst, long long n4);
 __global__ void k_synth(NvhSynthArgs A NVH_DBG_PARAMS);
 __global__ void k_synth_g(NvhSynthArgs A NVH_DBG_PARAMS);     // + the general bin walk (Residue0, odd dimensions, several passes)
 __global__ void k_synth_tail(NvhSynthArgs A NVH_DBG_PARAMS);  // + the carried tail written in place (kernels_synth.hip: MODE 1)
-__global__ void k_synth_emit(NvhSynthArgs A NVH_DBG_PARAMS);  // + paired emission (MODE 2)
-__global__ void k_synth_group2(NvhSynthArgs A NVH_DBG_PARAMS);  // frame groups: two / four frames per workgroup, the overlaps between them on chip
-__global__ void k_synth_group4(NvhSynthArgs A NVH_DBG_PARAMS);
 __global__ void k_synth8(NvhSynthArgs A NVH_DBG_PARAMS);
 __global__ void k_synth8_g(NvhSynthArgs A NVH_DBG_PARAMS);    // + the general bin walk
-__global__ void k_synth8_emit(NvhSynthArgs A NVH_DBG_PARAMS);  // wide frames + paired emission through LDS (synth_emit8)
-// the 16-bit twins of the kernels that write PCM (NVH_PCM_S16: A.pcm / pcm point at int16_t samples)
-__global__ void k_synth_emit_s16(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_synth8_emit_s16(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_synth_group2_s16(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_synth_group4_s16(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_ola_compact_s16(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, int16_t* pcm, int clip,
-                                  int* clipped_flag, float* carry_out, int last_decoded, int nosym, const int* list, int emitted);
-__global__ void k_ola_emit_s16(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, int16_t* pcm, int clip,
-                               int* clipped_flag);
-__global__ void k_ola_emit_seq_s16(NvhDevSetup S, NvhDevBatch Bt, float* work, const float* carry, int16_t* pcm, int clip,
-                                   int* clipped_flag);
-// the channel-planar twins (plane_stride: samples between the channels' planes; NvhSynthArgs::plane_stride for the slab kernels)
-__global__ void k_synth_emit_planar(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_synth_emit_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_synth8_emit_planar(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_synth8_emit_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_synth_group2_planar(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_synth_group2_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_synth_group4_planar(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_synth_group4_s16_planar(NvhSynthArgs A NVH_DBG_PARAMS);
-__global__ void k_ola_compact_planar(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, float* pcm, int clip,
-                                     int* clipped_flag, float* carry_out, int last_decoded, int nosym, const int* list, int emitted,
-                                     long long plane_stride);
-__global__ void k_ola_compact_s16_planar(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, int16_t* pcm, int clip,
-                                         int* clipped_flag, float* carry_out, int last_decoded, int nosym, const int* list, int emitted,
-                                         long long plane_stride);
-__global__ void k_ola_emit_planar(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, float* pcm, int clip,
-                                  int* clipped_flag, long long plane_stride);
-__global__ void k_ola_emit_s16_planar(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, int16_t* pcm, int clip,
-                                      int* clipped_flag, long long plane_stride);
-__global__ void k_ola_emit_seq_planar(NvhDevSetup S, NvhDevBatch Bt, float* work, const float* carry, float* pcm, int clip,
-                                      int* clipped_flag, long long plane_stride);
-__global__ void k_ola_emit_seq_s16_planar(NvhDevSetup S, NvhDevBatch Bt, float* work, const float* carry, int16_t* pcm, int clip,
-                                          int* clipped_flag, long long plane_stride);
+// The kernels that write PCM, once per form of PCM (kernels_common.h: NVH_FOR_PCM_TWINS).  The slab synthesis kernels carry the
+// form in their names (A.pcm points at PCM samples, A.plane_stride is the channel-planar forms' stride) ...
+#define NVH_SYNTH_DECL(PCM, PLANAR, SFX)                                                                                        \
+  __global__ void k_synth_emit##SFX(NvhSynthArgs A NVH_DBG_PARAMS);   /* + paired emission (MODE 2) */                           \
+  __global__ void k_synth8_emit##SFX(NvhSynthArgs A NVH_DBG_PARAMS);  /* wide frames + paired emission (synth_emit8) */           \
+  __global__ void k_synth_group2##SFX(NvhSynthArgs A NVH_DBG_PARAMS); /* frame groups: two / four frames per workgroup */         \
+  __global__ void k_synth_group4##SFX(NvhSynthArgs A NVH_DBG_PARAMS);
+NVH_FOR_PCM_TWINS(NVH_SYNTH_DECL)
 __global__ void k_window_apply(float* buf, const float* window, int n, long long stride, int batch);
 __global__ void k_overlap_buffers(const float* previous, float* next, int prev_start, int len, int next_start, int channels,
                                   long long plane_stride);
@@ -119,11 +87,28 @@ __global__ void k_floor1_apply(NvhDevSetup S, int floor_idx, const uint16_t* pos
                                long long stride, int* status);
 __global__ void k_residue(NvhDevSetup S, NvhDevBatch Bt, float* work, int clear);
 __global__ void k_couple_floor(NvhDevSetup S, NvhDevBatch Bt, float* work, int* err);
-__global__ void k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, float* pcm, int clip,
-                           int* clipped_flag);
-__global__ void k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* work, const float* carry, float* pcm, int clip,
-                               int* clipped_flag);
 }
+
+// ... and the overlap kernels are templates (kernels.hip), instantiated there for the same list; plane_stride: samples between the
+// channels' planes, an empty argument in the interleaved forms (kernels_common.h: pcm_stride_t)
+template <typename PCM, bool PLANAR>
+__global__ void k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, PCM* pcm, int clip,
+                              int* clipped_flag, float* carry_out, int last_decoded, int nosym, const int* list, int emitted,
+                              pcm_stride_t<PLANAR> plane_stride);
+template <typename PCM, bool PLANAR>
+__global__ void k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, PCM* pcm, int clip, int* clipped_flag,
+                           pcm_stride_t<PLANAR> plane_stride);
+template <typename PCM, bool PLANAR>
+__global__ void k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* work, const float* carry, PCM* pcm, int clip, int* clipped_flag,
+                               pcm_stride_t<PLANAR> plane_stride);
+#define NVH_OLA_DECL(PCM, PLANAR, SFX)                                                                                               \
+  extern template __global__ void k_ola_compact<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,  \
+                                                             float*, int, int, const int*, int, pcm_stride_t<PLANAR>);               \
+  extern template __global__ void k_ola_emit<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,     \
+                                                          pcm_stride_t<PLANAR>);                                                     \
+  extern template __global__ void k_ola_emit_seq<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, float*, const float*, PCM*, int, int*,       \
+                                                              pcm_stride_t<PLANAR>);
+NVH_FOR_PCM_TWINS(NVH_OLA_DECL)
 
 extern thread_local int g_last_hip_error;
 

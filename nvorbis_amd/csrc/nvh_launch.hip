@@ -728,58 +728,36 @@ static bool slab_size_ok(const nvh_batch* b) {
 
 static bool slab_path(const nvh_batch* b) { return slab_shape_ok(b) && slab_size_ok(b); }
 
-// ---- the kernels that write PCM, one set of twins per (sample type, layout) ----
-// The seven emitting kernels are template bodies instantiated per sample type (the _s16 twins: kernels_common.h pcm_s16_value)
-// and layout (the _planar twins, which take the planes' stride as one more argument); batch_launch picks a set here and nowhere
-// else.  `sfx` is the suffix of the set's kernel names.
+// ---- the kernels that write PCM, one set per form of PCM (kernels_common.h: NVH_FOR_PCM_TWINS) ----
+// batch_launch picks a set here and nowhere else: a tag with the sample type, the layout, the suffix of the set's slot names and
+// the set's slab synthesis kernels (the k_ola_* kernels are templates over the same pair).
 template <typename PCM, bool PLANAR>
-struct PcmTwins {
-  static constexpr bool planar = PLANAR;
-  static PCM* pcm(void* p) { return (PCM*)p; }
-};
-struct PcmF32 : PcmTwins<float, false> {
-  static constexpr const char* sfx = "";
-  static constexpr auto synth_emit = k_synth_emit, synth8_emit = k_synth8_emit, group2 = k_synth_group2, group4 = k_synth_group4;
-  static constexpr auto ola_compact = k_ola_compact;
-  static constexpr auto ola_emit = k_ola_emit;
-  static constexpr auto ola_emit_seq = k_ola_emit_seq;
-};
-struct PcmS16 : PcmTwins<int16_t, false> {
-  static constexpr const char* sfx = "_s16";
-  static constexpr auto synth_emit = k_synth_emit_s16, synth8_emit = k_synth8_emit_s16, group2 = k_synth_group2_s16,
-                        group4 = k_synth_group4_s16;
-  static constexpr auto ola_compact = k_ola_compact_s16;
-  static constexpr auto ola_emit = k_ola_emit_s16;
-  static constexpr auto ola_emit_seq = k_ola_emit_seq_s16;
-};
-struct PcmF32Planar : PcmTwins<float, true> {
-  static constexpr const char* sfx = "_planar";
-  static constexpr auto synth_emit = k_synth_emit_planar, synth8_emit = k_synth8_emit_planar, group2 = k_synth_group2_planar,
-                        group4 = k_synth_group4_planar;
-  static constexpr auto ola_compact = k_ola_compact_planar;
-  static constexpr auto ola_emit = k_ola_emit_planar;
-  static constexpr auto ola_emit_seq = k_ola_emit_seq_planar;
-};
-struct PcmS16Planar : PcmTwins<int16_t, true> {
-  static constexpr const char* sfx = "_s16_planar";
-  static constexpr auto synth_emit = k_synth_emit_s16_planar, synth8_emit = k_synth8_emit_s16_planar,
-                        group2 = k_synth_group2_s16_planar, group4 = k_synth_group4_s16_planar;
-  static constexpr auto ola_compact = k_ola_compact_s16_planar;
-  static constexpr auto ola_emit = k_ola_emit_s16_planar;
-  static constexpr auto ola_emit_seq = k_ola_emit_seq_s16_planar;
-};
+struct PcmTwins;
+#define NVH_PCM_TWINS(PCM, PLANAR, SFX)                                                                                \
+  template <>                                                                                                          \
+  struct PcmTwins<PCM, PLANAR> {                                                                                       \
+    typedef PCM pcm;                                                                                                   \
+    static constexpr bool planar = PLANAR;                                                                             \
+    static constexpr const char* sfx = #SFX;                                                                           \
+    static constexpr auto synth_emit = k_synth_emit##SFX, synth8_emit = k_synth8_emit##SFX, group2 = k_synth_group2##SFX, \
+                          group4 = k_synth_group4##SFX;                                                                \
+  };
+NVH_FOR_PCM_TWINS(NVH_PCM_TWINS)
 
-// f(twins) for the set that writes `out`
+// f(tag) for the set that writes `out`
 template <typename F>
 static auto with_pcm_twins(const PcmOut& out, F&& f) {
-  if (out.planar()) return out.s16() ? f(PcmS16Planar()) : f(PcmF32Planar());
-  return out.s16() ? f(PcmS16()) : f(PcmF32());
+#define NVH_PCM_PICK(PCM, PLANAR, SFX) \
+  if (out.planar() == PLANAR && out.s16() == std::is_same<PCM, int16_t>::value) return f(PcmTwins<PCM, PLANAR>());
+  NVH_FOR_PCM_TWINS(NVH_PCM_PICK)
+  __builtin_unreachable();
 }
 
-// pick(twins) of every set (the kernels that need a launch attribute)
+// f(tag) for every set (the kernels that need a launch attribute)
 template <typename F>
-static std::array<const void*, 4> pcm_twin_kernels(F pick) {
-  return {(const void*)pick(PcmF32()), (const void*)pick(PcmS16()), (const void*)pick(PcmF32Planar()), (const void*)pick(PcmS16Planar())};
+static void for_pcm_twins(F&& f) {
+#define NVH_PCM_EACH(PCM, PLANAR, SFX) f(PcmTwins<PCM, PLANAR>());
+  NVH_FOR_PCM_TWINS(NVH_PCM_EACH)
 }
 
 int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms, hipEvent_t* ext_ev,
@@ -791,7 +769,7 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
   // Channel-planar output: the _planar twins.  One channel is the same bytes either way: mono takes the interleaved kernels.
   // The twins' vector stores need every plane's first sample of a frame on a 16-byte boundary: an aligned base, a plane stride in
   // whole groups of four samples (below 2^31: NvhSynthArgs::plane_stride) and a frame position in whole groups of four
-  // (batch_upload: emit_planar_ok); otherwise the batch runs without paired emission and k_ola_compact_*planar takes each frame
+  // (batch_upload: emit_planar_ok); otherwise the batch runs without paired emission and k_ola_compact<PCM, true> takes each frame
   // by its vector form where that frame's own position allows it, else sample by sample.
   if (ch == 1) out.plane_stride = 0;
   const bool planar = out.planar();
@@ -799,10 +777,10 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
   const bool planar_emit = !planar || (((uintptr_t)d_pcm & 15u) == 0 && (plane_stride & 3) == 0 && plane_stride <= 0x7FFFFFFFll &&
                                        b->emit_planar_ok);
   const char* sfx = with_pcm_twins(out, [](auto t) { return t.sfx; });
-  // launches one of the set's k_ola_* kernels: the planar twins take the planes' stride as their last argument
-  auto launch_ola = [&](auto t, auto kern, dim3 grid, dim3 block, auto... args) {
-    if constexpr (decltype(t)::planar) hipLaunchKernelGGL(kern, grid, block, 0, st, args..., (long long)plane_stride);
-    else hipLaunchKernelGGL(kern, grid, block, 0, st, args...);
+  // the k_ola_* kernels' last argument: the planes' stride, nothing in the interleaved forms
+  auto ola_stride = [&](auto t) {
+    if constexpr (decltype(t)::planar) return (long long)plane_stride;
+    else return NvhNoStride();
   };
   float* work = (float*)b->work.p;
   int* flags = (int*)s->flags.p;
@@ -873,8 +851,11 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
     if (synth_lds > 64 * 1024 && !s->ctx->synth_lds_attr_set) {
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_g, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      for (const void* k : pcm_twin_kernels([](auto t) { return t.synth8_emit; }))
-        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      hipError_t attr_err = hipSuccess;
+      for_pcm_twins([&](auto t) {
+        if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void*)t.synth8_emit, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      });
+      HIP_TRY(attr_err);
       s->ctx->synth_lds_attr_set = true;
     }
     if (timing) HIP_TRY(hipEventRecord(ev[1], st));  // slot 0 stays empty: slot 1 = the synthesis kernel
@@ -900,10 +881,12 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       // between groups as well.
       const int gw = b->fpw, ngroups = (b->nframes + gw - 1) / gw;
       if (synth_lds > 64 * 1024 && !s->ctx->group_lds_attr_set) {
-        for (const void* k : pcm_twin_kernels([](auto t) { return t.group2; }))
-          HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        for (const void* k : pcm_twin_kernels([](auto t) { return t.group4; }))
-          HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipError_t attr_err = hipSuccess;
+        for_pcm_twins([&](auto t) {
+          for (const void* k : {(const void*)t.group2, (const void*)t.group4})
+            if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        });
+        HIP_TRY(attr_err);
         s->ctx->group_lds_attr_set = true;
       }
       auto kern = with_pcm_twins(out, [gw](auto t) { return gw == 2 ? t.group2 : t.group4; });
@@ -1080,8 +1063,10 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       if (ch > 2 && !T.no_ola_sym && T.ola_segs <= 0) segs = ((s->setup.block1 / 16) + NVH_OLA_GW - 1) / NVH_OLA_GW;
       auto ola_compact = [&](unsigned nwg, float* c_out, const int* list, int emitted_frames) {
         with_pcm_twins(out, [&](auto t) {
-          launch_ola(t, t.ola_compact, dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), s->dev, b->dev, (const float*)work, carry,
-                     t.pcm(d_pcm), s->clip, flags + 1, c_out, b->last_decoded, T.no_ola_sym ? 1 : 0, list, emitted_frames);
+          typedef decltype(t) TW;
+          hipLaunchKernelGGL((k_ola_compact<typename TW::pcm, TW::planar>), dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st,
+                             s->dev, b->dev, (const float*)work, carry, (typename TW::pcm*)d_pcm, s->clip, flags + 1, c_out,
+                             b->last_decoded, T.no_ola_sym ? 1 : 0, list, emitted_frames, ola_stride(t));
         });
       };
       if (!emitted)
@@ -1094,12 +1079,15 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
         ola_compact((unsigned)b->ola_count, (float*)nullptr /* k_synth wrote the carried tail */, b->d_ola_list, 1);
     } else if (!b->sequential_ola) {
       with_pcm_twins(out, [&](auto t) {
-        launch_ola(t, t.ola_emit, dim3((unsigned)b->nframes), dim3(256), s->dev, b->dev, (const float*)work, carry, t.pcm(d_pcm), s->clip,
-                   flags + 1);
+        typedef decltype(t) TW;
+        hipLaunchKernelGGL((k_ola_emit<typename TW::pcm, TW::planar>), dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev,
+                           (const float*)work, carry, (typename TW::pcm*)d_pcm, s->clip, flags + 1, ola_stride(t));
       });
     } else {
       with_pcm_twins(out, [&](auto t) {
-        launch_ola(t, t.ola_emit_seq, dim3(1), dim3(256), s->dev, b->dev, work, carry, t.pcm(d_pcm), s->clip, flags + 1);
+        typedef decltype(t) TW;
+        hipLaunchKernelGGL((k_ola_emit_seq<typename TW::pcm, TW::planar>), dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry,
+                           (typename TW::pcm*)d_pcm, s->clip, flags + 1, ola_stride(t));
       });
     }
     // the last decoded block becomes the carried tail (StreamDecoder's _prevPacketBuf), always fully windowed

@@ -395,7 +395,7 @@ _KERNEL_TOGGLES = ("NVH_EMIT_ALWAYS", "NVH_UNFUSED", "NVH_NO_FUSED_IMDCT", "NVH_
 @pytest.mark.parametrize("name", ["ch9_res2", "ch16_res1_4096", "ch40_res1"])
 def test_wide_configs_take_the_descriptor_kernels(oracle, gpu_ctx, name):
     """More than eight channels are outside the slab contract (NVH_SLAB_MAX_CH) and the GPU parser's: the descriptor kernels
-    and k_ola_compact's scalar loop (ola_compact_body.inc) decode them.  Sixteen channels at n = 4096 (128 KiB of spectra, a
+    and k_ola_compact's scalar loop (kernels.hip) decode them.  Sixteen channels at n = 4096 (128 KiB of spectra, a
     residue with vector overrun: no 152 KB LDS window) take the global-memory pair k_residue + k_couple_floor, nine and forty
     channels the LDS-resident k_spectrum_gen8.  Bit-exact against the oracle on the structured stream of tests/spec_pin.py,
     whose silent channels include channels beyond 31."""

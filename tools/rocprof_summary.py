@@ -10,7 +10,19 @@ FETCH_SIZE counts 128-byte requests of a wide coalesced stream as 64 bytes, so t
 """
 import argparse
 import json
+import re
 import sqlite3
+
+
+_TWIN_SUFFIX = {("float", "false"): "", ("short", "false"): "_s16", ("float", "true"): "_planar", ("short", "true"): "_s16_planar"}
+
+
+def slot_name(name):
+    """A trace's kernel name as the slot name profiles/traffic.json and the ABI's timing slots use: the k_ola_* kernels are templates
+    over (sample type, channel-planar), so a trace prints `void k_ola_compact<short, true>(NvhDevSetup, ...)` for the kernel whose
+    slot is `k_ola_compact_s16_planar` (family name + suffix); every other name stays as it is."""
+    m = re.match(r"(?:void )?(k_\w+)<(\w+), (true|false)>", name)
+    return m.group(1) + _TWIN_SUFFIX[m.group(2), m.group(3)] if m and (m.group(2), m.group(3)) in _TWIN_SUFFIX else name
 
 
 def kernels_from_trace(path):
@@ -22,7 +34,7 @@ def kernels_from_trace(path):
                        "group by name order by sum(duration) desc").fetchall()  # (a join, not a correlated subquery: minutes -> seconds)
     out = {}
     for r in rows:
-        out[r[0]] = dict(calls=r[1], avg_us=r[2] / 1e3, min_us=r[3] / 1e3, max_us=r[4] / 1e3, vgpr=r[5], agpr=r[6], sgpr=r[7],
+        out[slot_name(r[0])] = dict(calls=r[1], avg_us=r[2] / 1e3, min_us=r[3] / 1e3, max_us=r[4] / 1e3, vgpr=r[5], agpr=r[6], sgpr=r[7],
                          lds=r[8], scratch=r[9], grid=r[10], workgroup=r[11])
     return out
 
@@ -32,7 +44,7 @@ def counter_avg(path, counter):
     rows = cur.execute("select kernel_name, avg(value), count(*) from counters_collection c join "
                        "(select kernel_name n, max(grid_size_x) g from counters_collection group by kernel_name) m "
                        "on c.kernel_name = m.n and c.grid_size_x = m.g where counter_name=? group by kernel_name", (counter,)).fetchall()
-    return {r[0]: (r[1], r[2]) for r in rows}
+    return {slot_name(r[0]): (r[1], r[2]) for r in rows}
 
 
 def main():

@@ -28,6 +28,8 @@ namespace NVorbis.Hip
         float[] _ring = Array.Empty<float>();
         short[] _ring16 = Array.Empty<short>();   // pcm16: the ring holds 16-bit samples (nvh_stream_synth_pcm, NVH_PCM_S16)
         readonly bool _pcm16;
+        readonly bool _mono;   // the ring holds the channels' mean (nvh_stream_synth_mix, NVH_MIX_MONO): one sample per sample time
+        int _outChannels;      // samples of the ring per sample time: _channels, or 1 when mixing
         int _ringPos, _ringLen;
         bool _ended, _clip = true;
         long _skip;   // floats to drop in front of the next samples: SeekTo's roll-forward
@@ -44,10 +46,14 @@ namespace NVorbis.Hip
         /// lane walking its own, so that the parses of all workers fit the chip side by side (INTEGRATION.md).  The PCM does not depend on it.</param>
         /// <param name="pcm16">true: the decoder delivers 16-bit PCM through Read(Span&lt;short&gt;, ...) -- libvorbis ov_read's conversion,
         /// done in the kernels, half the bytes over PCIe -- and Read(Span&lt;float&gt;, ...) throws; false: float PCM, as the reference.</param>
+        /// <param name="monoMix">true: the decoder delivers the mean of the channels (summed in channel order, divided and clipped once,
+        /// inside the kernels): Read counts and returns those samples, one per sample time; Channels stays the stream's channel count,
+        /// OutputChannels is 1.  Positions and seeking are in samples per channel either way.</param>
         public GpuStreamDecoder(Contracts.IPacketProvider packetProvider, int device = 0, int batchPackets = 1024, int poolParseLanes = 0,
-                                bool pcm16 = false)
+                                bool pcm16 = false, bool monoMix = false)
         {
             _pcm16 = pcm16;
+            _mono = monoMix;
             _packetProvider = packetProvider ?? throw new ArgumentNullException(nameof(packetProvider));
             _batchPackets = batchPackets;
             NativeMethods.Check(NativeMethods.nvh_ctx_create(device, out _ctx));
@@ -59,6 +65,7 @@ namespace NVorbis.Hip
             fixed (byte* pi = id, pc = comment, ps = setup)
                 NativeMethods.Check(NativeMethods.nvh_stream_open(_ctx, pi, id.Length, pc, comment.Length, ps, setup.Length, out _stream));
             NativeMethods.Check(NativeMethods.nvh_stream_info(_stream, out _channels, out _sampleRate, out _block0, out _block1));
+            _outChannels = _mono ? 1 : _channels;
             NativeMethods.Check(NativeMethods.nvh_stream_bitrates(_stream, out _upperBitrate, out _nominalBitrate, out _lowerBitrate));
             ParseComments(comment, out _vendor, out _comments);                 // LoadComments (StreamDecoder.cs:206-224)
             _stats.SetSampleRate(_sampleRate);                                   // StreamDecoder.cs:200
@@ -105,6 +112,7 @@ namespace NVorbis.Hip
         }
 
         public int Channels => _channels;
+        public int OutputChannels => _outChannels;
         public int SampleRate => _sampleRate;
         public int UpperBitrate => _upperBitrate;
         public int NominalBitrate => _nominalBitrate;
@@ -123,7 +131,7 @@ namespace NVorbis.Hip
             {
                 NativeMethods.Check(NativeMethods.nvh_stream_position(_stream, out long pos, out _, out _));
                 NativeMethods.Check(NativeMethods.nvh_stream_pending(_stream, out _, out long pending));   // pushed, not yet synthesised (right after a seek)
-                return pos - pending - (_ringLen - _ringPos) / _channels + _skip / _channels;
+                return pos - pending - (_ringLen - _ringPos) / _outChannels + _skip / _outChannels;
             }
             set => SeekTo(value);
         }
@@ -166,19 +174,22 @@ namespace NVorbis.Hip
                 long written = 0;
                 if (frames != 0)
                 {
-                    long need = samples * _channels;
+                    long need = samples * _outChannels;
+                    int mix = _mono ? NativeMethods.NVH_MIX_MONO : NativeMethods.NVH_MIX_NONE;
                     int rc;
                     if (_pcm16)
                     {
                         if (_ring16.Length < need) _ring16 = new short[need];
                         fixed (short* dst = _ring16)
-                            rc = NativeMethods.nvh_stream_synth_pcm(_stream, NativeMethods.NVH_PCM_S16, dst, IntPtr.Zero, _ring16.Length, out written);
+                            rc = _mono ? NativeMethods.nvh_stream_synth_mix(_stream, NativeMethods.NVH_PCM_S16, mix, dst, IntPtr.Zero, _ring16.Length, out written)
+                                       : NativeMethods.nvh_stream_synth_pcm(_stream, NativeMethods.NVH_PCM_S16, dst, IntPtr.Zero, _ring16.Length, out written);
                     }
                     else
                     {
                         if (_ring.Length < need) _ring = new float[need];
                         fixed (float* dst = _ring)
-                            rc = NativeMethods.nvh_stream_synth(_stream, dst, IntPtr.Zero, _ring.Length, out written);
+                            rc = _mono ? NativeMethods.nvh_stream_synth_mix(_stream, NativeMethods.NVH_PCM_F32, mix, dst, IntPtr.Zero, _ring.Length, out written)
+                                       : NativeMethods.nvh_stream_synth(_stream, dst, IntPtr.Zero, _ring.Length, out written);
                     }
                     _ringPos = 0; _ringLen = (int)written;
                     if (rc != 0)
@@ -190,7 +201,7 @@ namespace NVorbis.Hip
                         fixed (int* pc = codes) fixed (long* pb = before)
                             NativeMethods.Check(NativeMethods.nvh_stream_parse_errors(_stream, pc, pb, n, out n));
                         for (int i = 0; i < n; i++)
-                            _pendingErrors.Enqueue(new KeyValuePair<Exception, int>(ToException(codes[i]), (int)Math.Min(before[i] * _channels, written)));
+                            _pendingErrors.Enqueue(new KeyValuePair<Exception, int>(ToException(codes[i]), (int)Math.Min(before[i] * _outChannels, written)));
                     }
                 }
                 if (pushError != null) _pendingErrors.Enqueue(new KeyValuePair<Exception, int>(pushError, (int)written));
@@ -223,7 +234,7 @@ namespace NVorbis.Hip
         int ReadRing<T>(Span<T> buffer, T[] ring, int offset, int count)
         {
             if (offset < 0 || offset + count > buffer.Length) throw new ArgumentOutOfRangeException(nameof(offset));
-            if (count % _channels != 0) throw new ArgumentOutOfRangeException(nameof(count), "Must be a multiple of Channels!");
+            if (count % _outChannels != 0) throw new ArgumentOutOfRangeException(nameof(count), _mono ? "Must be a multiple of OutputChannels!" : "Must be a multiple of Channels!");
             if (_stream == IntPtr.Zero) throw new ObjectDisposedException(nameof(GpuStreamDecoder));
             int idx = offset, tgt = offset + count;
             while (idx < tgt)
@@ -304,7 +315,7 @@ namespace NVorbis.Hip
             }
             // _prevPacketStart += rollForward; _currentPosition = samplePosition (:624-626): the pending frame's `count` samples are
             // ahead of the position, Read drops rollForward of them
-            _skip = (long)rollForward * _channels;
+            _skip = (long)rollForward * _outChannels;
             NativeMethods.Check(NativeMethods.nvh_stream_set_position_state(_stream, 1, samplePosition - rollForward + count));
         }
 

@@ -100,6 +100,12 @@ namespace NVorbis.Hip
         [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_pcm(IntPtr stream, int format, void* pcmHost, IntPtr dPcm, long capacity, out long written);
         [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_begin_pcm(IntPtr stream, int format, void* pcmHost, long capacity, out long expected);
         [DllImport(Lib)] public static extern int nvh_batch_synth_pcm(IntPtr batch, int format, IntPtr dPcm, long capacity);
+        /// <summary>Down-mixes of the *_mix synthesis calls: NVH_MIX_MONO is the mean of the channels, summed in channel order, divided and
+        /// clipped once inside the kernels; counts are output samples (one per sample time).</summary>
+        public const int NVH_MIX_NONE = 0, NVH_MIX_MONO = 1;
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_mix(IntPtr stream, int format, int mix, void* pcmHost, IntPtr dPcm, long capacity, out long written);
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_begin_mix(IntPtr stream, int format, int mix, void* pcmHost, long capacity, out long expected);
+        [DllImport(Lib)] public static extern int nvh_batch_synth_mix(IntPtr batch, int format, int mix, IntPtr dPcm, long capacity);
 
         /// <summary>The corpus gather (include/nvorbis_hip.h, "multi-GPU"): RCCL over xGMI through the library, one process per GPU (GpuCorpusGather.cs).</summary>
         public const int NVH_COMM_ID_BYTES = 128;

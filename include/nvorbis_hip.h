@@ -295,6 +295,26 @@ int nvh_stream_synth_begin_pcm(nvh_stream *s, int format, void *pcm_host, int64_
  * No counterpart in the reference (libvorbis' ov_read_float hands out planes). */
 int nvh_stream_synth_planar(nvh_stream *s, int format, void *pcm_host, void *d_pcm, int64_t plane_stride, int64_t *written);
 int nvh_stream_synth_begin_planar(nvh_stream *s, int format, void *pcm_host, int64_t plane_stride, int64_t *expected);
+/* Mixing forms of nvh_stream_synth_pcm / nvh_stream_synth_begin_pcm / nvh_batch_synth_pcm: the channels of a sample time are
+ * mixed into ONE output sample inside the emitting kernels (their _mono twins).  NVH_MIX_NONE is the *_pcm call.  NVH_MIX_MONO,
+ * for a stream of C channels, with x_c(t) the float sample the float path produces for channel c at time t BEFORE ClipSamples'
+ * clip (what it emits with clipping off; a channel that does not execute contributes the +0.0f it contributes today):
+ *     s = x_0;  s = s + x_1;  ...  s = s + x_{C-1}     (C - 1 fp32 additions, in channel order, each rounded once)
+ *     m = s / (float)C                                  (one correctly rounded fp32 division)
+ *     y = ClipSamples ? clip(m) : m                     (the clip every emitter applies, Utils.cs:30-43, applied ONCE, to the mix)
+ * NVH_PCM_S16 then converts y as it converts every float.  HasClipped becomes true when the MIX clips: a channel that alone
+ * leaves [-1, 1] does not set it in a mixed batch.  C = 1 is the identity (the existing kernels run).  Capacities, *written
+ * and *expected count output samples (NVH_MIX_MONO: samples per channel); nvh_stream_parse_errors' samples_before is per
+ * channel already, which for a mix is the output position.  A device base must be aligned to its sample size; the vector
+ * stores run where it is 16-byte aligned and every frame of the batch starts on a multiple of four samples, else the batch
+ * falls back to the per-frame overlap kernel (same bits).  nvh_stream_synth_end retires these flights too; mixed and unmixed
+ * batches, and formats, may alternate on one stream (the carried tail stays per-channel float planes).  NVH_ERR_ARGUMENT: an
+ * unknown mix or format, both destinations or neither (with PCM to write), a capacity below the pending samples, a misaligned
+ * device base, batches outstanding.  No counterpart in the reference (NVorbis emits channels as they are). */
+#define NVH_MIX_NONE 0
+#define NVH_MIX_MONO 1
+int nvh_stream_synth_mix(nvh_stream *s, int format, int mix, void *pcm_host, void *d_pcm, int64_t capacity, int64_t *written);
+int nvh_stream_synth_begin_mix(nvh_stream *s, int format, int mix, void *pcm_host, int64_t capacity, int64_t *expected);
 /* After nvh_stream_synth returned an error code together with *written > 0 (GPU-parse mode: packets of the batch made
  * the parser fail -- with the codes nvh_stream_push_packet returns for them in host-parse mode -- and the batch was
  * parsed again on the host without them): every such packet in stream order, codes[i] and samples_before[i] = the
@@ -330,6 +350,8 @@ int nvh_batch_synth(nvh_batch *b, float *d_pcm, int64_t capacity);
 int nvh_batch_synth_pcm(nvh_batch *b, int format, void *d_pcm, int64_t capacity);
 /* ... and channel-planar (see nvh_stream_synth_planar). */
 int nvh_batch_synth_planar(nvh_batch *b, int format, void *d_pcm, int64_t plane_stride);
+/* ... and mixed (see nvh_stream_synth_mix); capacity in output samples. */
+int nvh_batch_synth_mix(nvh_batch *b, int format, int mix, void *d_pcm, int64_t capacity);
 /* Time `iters` repetitions with hipEvents on the launch stream: total milliseconds for the whole
  * pipeline, and per timing slot (spectrum: residue | couple+floor, or fused in slot 1; imdct+window; overlap+emit;
  * see nvh_batch_kernels).  A slot brackets its launches with event records, which costs ~2 us per slot. */

@@ -17,6 +17,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp
          "-fno-slp-vectorize", "-Wall", "-Wno-unused-function"]
 
 
+# The mono down-mix divides by the channel count (kernels_common.h: mono_scale) and its parity rests on IEEE division: hipcc's
+# default, which these flags must not switch off.
+assert not any(f in FLAGS for f in ("-ffast-math", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-freciprocal-math")), FLAGS
+
+
 def hipcc():
     exe = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(exe):

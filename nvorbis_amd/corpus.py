@@ -175,7 +175,8 @@ def _flat_payload(parts, torch, dev):
     return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
-def transcode(files, decode_fn=None, rank=0, world=1, dist=None, device="cpu", gpu=0, workers=16, to_host=True, layout="interleaved"):
+def transcode(files, decode_fn=None, rank=0, world=1, dist=None, device="cpu", gpu=0, workers=16, to_host=True, layout="interleaved",
+              mix=None):
     """Decode `files` (list of bytes) file-parallel; rank 0 returns the list of PCM arrays in file order.
 
     decode_fn(bytes) -> float32 numpy PCM decodes one file; None = this package's GPU path with a pool of `workers`
@@ -184,6 +185,8 @@ def transcode(files, decode_fn=None, rank=0, world=1, dist=None, device="cpu", g
     layout="planar" raises ValueError."""
     if layout != "interleaved":
         raise ValueError("transcode gathers interleaved PCM only (layout %r)" % (layout,))
+    if mix is not None:  # (the gather's checks and digests are per file in interleaved units: a mix is refused like the planar layout)
+        raise ValueError("transcode gathers unmixed interleaved PCM only (mix %r)" % (mix,))
     shards = lpt_shards([len(f) for f in files], world)
     mine = shards[rank]
     if decode_fn is None:
@@ -538,7 +541,7 @@ def _index_pass(files, workers, full_index=False):
 
 
 def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_parse=False, keep_contexts=False, timings=None, tune_process=False,
-                           layout="interleaved"):
+                           layout="interleaved", mix=None):
     """Decode .ogg byte strings on ONE GPU into ONE device arena: returns (arena, views) with views[i] the interleaved
     float32 PCM of files[i] as a slice of `arena` (torch tensors on cuda:<device>), files back to back in list order.
 
@@ -546,14 +549,22 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
     file's slot holds its C_i planes with the plane stride padded to a multiple of 4 samples (so that the kernels' vector stores
     run): views[i] is then a STRIDED view of the arena (strides (S_i, 1), S_i >= T_i); .contiguous() makes a packed copy.
 
+    mix="mono": views[i] is the mean of the file's channels, shape (T_i,), summed, divided and clipped once inside the synthesis
+    kernels (their _mono twins; include/nvorbis_hip.h: nvh_stream_synth_mix); a one-channel file is what it is without.  Every
+    file's slot starts on a multiple of four samples of the arena (up to three unused samples behind a file), so that the
+    kernels' vector stores run -- a batch that starts elsewhere would take the per-frame fall-back.  Not together with
+    layout="planar".
+
     Two passes over the worker pool: a geometry-only index of every stream (nvh_stream_index_packets: packet type, mode
     number, window flags -- how many samples the serial decoder emits), which sizes the arena; then the decode, whose
     overlap-add kernels write each batch's PCM at its final address (nvh_stream_synth with a device destination).  No
     PCM crosses PCIe.  tune_process: see _tune_malloc (process-wide, opt-in)."""
     import torch
 
-    from .reader import Context, Stream, _layout, demux_ogg_array, index_ogg_array
+    from .reader import Context, Stream, _layout, _mix, demux_ogg_array, index_ogg_array
     planar = _layout(layout)
+    _mix(mix, planar)
+    mono = mix is not None
     n = len(files)
     full_index = bool(os.environ.get("NVH_CORPUS_FULL_INDEX"))  # A/B aid: the round-5 index (checksums + a copy of every packet)
 
@@ -595,9 +606,12 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
     t_index = time.perf_counter()
     # planar: per file C planes of S = T rounded up to whole groups of four samples
     per_ch = [int(totals[i]) // max(int(chans[i]), 1) for i in range(n)]
+    if mono:  # one sample per sample time
+        totals = np.asarray(per_ch, np.int64)
     strides = [(t + 3) & ~3 for t in per_ch]
     offs = np.zeros(n + 1, np.int64)
-    offs[1:] = np.cumsum([int(chans[i]) * strides[i] for i in range(n)] if planar else totals)
+    offs[1:] = np.cumsum([int(chans[i]) * strides[i] for i in range(n)] if planar else strides if mono else totals)
+    ends = [int(offs[i]) + int(totals[i]) for i in range(n)]  # (interleaved: offs[i + 1]; mono: in front of the slot's padding)
     total = int(offs[-1])
     if arena_box[0] is not None and total >= 1 and total <= int(arena_box[0].numel()) <= total + max(total // 50, 1 << 20):
         # allocated during the index pass from an upper bound (two maximal blocks per file beyond its last granule position): taken
@@ -644,11 +658,11 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
                     pos[0] += s.synth_device(base + 4 * (int(offs[i]) + pos[0]), 0, plane_stride=strides[i])
                     in_sink[0] += time.perf_counter() - ts
                     return
-                room = int(offs[i + 1]) - pos[0]
-                need = s.pending()[1] * s.channels
+                room = ends[i] - pos[0]
+                need = s.pending()[1] * (1 if mono else s.channels)
                 if need > room:
                     raise RuntimeError("file %d produces more than the %d floats its index says" % (i, totals[i]))
-                pos[0] += s.synth_device(base + 4 * pos[0], room)
+                pos[0] += s.synth_device(base + 4 * pos[0], room, mix=mix)
                 in_sink[0] += time.perf_counter() - ts
 
             if planar:
@@ -656,7 +670,7 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
             _decode_file_packets(st, pa, batch_frames, sink)
             if planar and pos[0] != per_ch[i]:
                 raise RuntimeError("file %d produced %d samples per channel, its index says %d" % (i, pos[0], per_ch[i]))
-            if not planar and pos[0] != int(offs[i + 1]):
+            if not planar and pos[0] != ends[i]:
                 raise RuntimeError("file %d produced %d floats, its index says %d" % (i, pos[0] - int(offs[i]), totals[i]))
         finally:
             t2 = time.perf_counter()
@@ -688,7 +702,7 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
     if planar:
         views = [arena[int(offs[i]):int(offs[i + 1])].view(int(chans[i]), strides[i])[:, :per_ch[i]] for i in range(n)]
     else:
-        views = [arena[int(offs[i]):int(offs[i + 1])] for i in range(n)]
+        views = [arena[int(offs[i]):ends[i]] for i in range(n)]
     if redo:
         # A page the index took at its word failed its checksum: the reference's reader drops it and resynchronises, the file's
         # packet list -- and with it its length -- is another.  Such a file gets a tensor of its own (views[i] is then not a slice
@@ -701,7 +715,7 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
                 try:
                     per = int(st.index_total(pa, 3))
                     nch = st.channels
-                    tot = per * nch
+                    tot = per * (1 if mono else nch)
                 finally:
                     st.close()
                 stride = (per + 3) & ~3
@@ -720,7 +734,7 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
                         if planar:
                             pos[0] += s_.synth_device(own.data_ptr() + 4 * pos[0], 0, plane_stride=stride)
                         else:
-                            pos[0] += s_.synth_device(own.data_ptr() + 4 * pos[0], tot - pos[0])
+                            pos[0] += s_.synth_device(own.data_ptr() + 4 * pos[0], tot - pos[0], mix=mix)
 
                     _decode_file_packets(st, pa, batch_frames, sink)
                     if pos[0] != (per if planar else tot):

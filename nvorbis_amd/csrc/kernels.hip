@@ -590,10 +590,11 @@ k_couple_floor(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, int* __r
 // time t of channel c at pcm + c * plane_stride + t (plane_stride: the last argument, empty in the interleaved forms:
 // pcm_stride_t); the per-sample index then runs plane-major (o -> channel o / emit_count, time o % emit_count), so consecutive
 // lanes write consecutive addresses of one plane.
-template <typename PCM, bool PLANAR>
+template <typename PCM, int LAYOUT>
 __global__ void __launch_bounds__(NVH_THREADS)
 k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry, PCM* __restrict__ pcm,
-           int clip, int* __restrict__ clipped_flag, pcm_stride_t<PLANAR> plane_stride) {
+           int clip, int* __restrict__ clipped_flag, pcm_stride_t<LAYOUT> plane_stride) {
+  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;
   const int f = blockIdx.x;
   const NvhFrame fr = Bt.frames[f];
   const int ch = S.channels;
@@ -602,8 +603,30 @@ k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const 
   const float* cur = work + (long long)f * ch * S.block1;
   const float* prev = nullptr;
   if (fr.ov_len > 0) prev = (fr.ov_frame == -2) ? carry : (fr.ov_frame >= 0 ? work + (long long)fr.ov_frame * ch * S.block1 : nullptr);
-  PCM* out = pcm + fr.out_pos * (PLANAR ? 1 : ch);
+  PCM* out = pcm + fr.out_pos * (PLANAR || MONO ? 1 : ch);
   int clipped = 0;
+  if constexpr (MONO) {
+    // the mono down-mix (kernels_common.h: mono_scale): one output sample per index, the channels' planes in channel order
+    for (int t = threadIdx.x; t < fr.emit_count; t += NVH_THREADS) {
+      const int idx = fr.emit_start + t, j = idx - fr.start;
+      float m = 0.0f;
+      for (int c = 0; c < ch; ++c) {
+        float v;
+        if (fr.n == 0) {
+          v = prev[(long long)c * S.block1 + fr.ov_src + t];
+        } else {
+          v = cur[(long long)c * S.block1 + idx];
+          if (prev && j >= 0 && j < fr.ov_len) v = v + prev[(long long)c * S.block1 + fr.ov_src + j];
+        }
+        m = c == 0 ? v : m + v;
+      }
+      m = mono_scale(m, ch);
+      if (clip) m = clip_value(m, &clipped);
+      pcm_store1(out + t, m);
+    }
+    report_clipped(clipped, clipped_flag);
+    return;
+  }
   for (int o = threadIdx.x; o < total; o += NVH_THREADS) {
     int t = o / ch, c = o - t * ch;
     if constexpr (PLANAR) c = o / fr.emit_count, t = o - c * fr.emit_count;
@@ -626,10 +649,11 @@ k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const 
 // Sequential form: one workgroup walks the frames in order and performs the adds in place, exactly
 // like the reference's ping-pong buffers (needed only for streams whose window flags disagree with
 // their neighbours so that an overlap reaches a block's own tail).
-template <typename PCM, bool PLANAR>
+template <typename PCM, int LAYOUT>
 __global__ void __launch_bounds__(NVH_THREADS)
 k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry, PCM* __restrict__ pcm,
-               int clip, int* __restrict__ clipped_flag, pcm_stride_t<PLANAR> plane_stride) {
+               int clip, int* __restrict__ clipped_flag, pcm_stride_t<LAYOUT> plane_stride) {
+  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;
   const int ch = S.channels;
   int clipped = 0;
   for (int f = 0; f < Bt.nframes; ++f) {
@@ -645,9 +669,20 @@ k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const fl
       }
     }
     __syncthreads();
-    PCM* out = pcm + fr.out_pos * (PLANAR ? 1 : ch);
-    const int total = fr.emit_count * ch;
+    PCM* out = pcm + fr.out_pos * (PLANAR || MONO ? 1 : ch);
+    const int total = fr.emit_count * (MONO ? 1 : ch);
     for (int o = threadIdx.x; o < total; o += NVH_THREADS) {
+      if constexpr (MONO) {  // the mono down-mix: one output sample per index, the channels' planes in channel order
+        float m = 0.0f;
+        for (int c = 0; c < ch; ++c) {
+          const float v = (fr.n == 0) ? prev[(long long)c * S.block1 + fr.ov_src + o] : cur[(long long)c * S.block1 + fr.emit_start + o];
+          m = c == 0 ? v : m + v;
+        }
+        m = mono_scale(m, ch);
+        if (clip) m = clip_value(m, &clipped);
+        pcm_store1(out + o, m);
+        continue;
+      }
       int t = o / ch, c = o - t * ch;
       if constexpr (PLANAR) c = o / fr.emit_count, t = o - c * fr.emit_count;
       float v = (fr.n == 0) ? prev[(long long)c * S.block1 + fr.ov_src + t] : cur[(long long)c * S.block1 + fr.emit_start + t];
@@ -659,11 +694,11 @@ k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const fl
   }
   report_clipped(clipped, clipped_flag);
 }
-#define NVH_OLA_EMIT_TWINS(PCM, PLANAR, SFX)                                                                                    \
-  template __global__ void k_ola_emit<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,   \
-                                                   pcm_stride_t<PLANAR>);                                                   \
-  template __global__ void k_ola_emit_seq<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, float*, const float*, PCM*, int, int*,     \
-                                                       pcm_stride_t<PLANAR>);
+#define NVH_OLA_EMIT_TWINS(PCM, LAYOUT, SFX)                                                                                    \
+  template __global__ void k_ola_emit<PCM, LAYOUT>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,   \
+                                                   pcm_stride_t<LAYOUT>);                                                   \
+  template __global__ void k_ola_emit_seq<PCM, LAYOUT>(NvhDevSetup, NvhDevBatch, float*, const float*, PCM*, int, int*,     \
+                                                       pcm_stride_t<LAYOUT>);
 NVH_FOR_PCM_TWINS(NVH_OLA_EMIT_TWINS)
 
 // ================================================================================================
@@ -890,17 +925,87 @@ __device__ __forceinline__ int ola_sym_planar(const NvhDevSetup& S, const NvhFra
   return clipped;
 }
 
+// The mono forms of ola_vec and ola_sym (k_ola_compact<PCM, NVH_LAYOUT_MONO>): one lane per group of four sample times reads
+// every channel (channel order), adds, divides and clips once (kernels_common.h: mono_scale) and stores one vector of the one
+// plane.  `out` points at the frame's first sample, 16-byte aligned (8 for 16-bit PCM): nvh_launch.hip.
+__device__ __forceinline__ float4 mono_finish(float4 m, int ch, int clip, int* clipped) {
+  m = make_float4(mono_scale(m.x, ch), mono_scale(m.y, ch), mono_scale(m.z, ch), mono_scale(m.w, ch));
+  if (clip) clip_value4(m, clipped);
+  return m;
+}
+template <typename PCM>
+__device__ __forceinline__ int ola_vec_mono(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev,
+                                            bool prev_full, const float* __restrict__ w, const float* __restrict__ wp, PCM* out,
+                                            int ch, int clip, int tid, int threads) {
+  int clipped = 0;
+  const int groups = fr.emit_count >> 2;
+  for (int g = tid; g < groups; g += threads) {
+    const int idx0 = fr.emit_start + 4 * g;
+    const int j0 = idx0 - fr.start;
+    const bool ov = prev && j0 >= 0 && j0 < fr.ov_len;
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int c = 0; c < ch; ++c) {
+      float4 v = compact_value4(cur + (long long)c * S.block1, w, fr.n, (fr.exec_mask >> c) & 1, idx0);
+      if (ov) {
+        const float* pp = prev + (long long)c * S.block1;
+        const float4 t4 = prev_full ? *reinterpret_cast<const float4*>(pp + fr.ov_src + j0)
+                                    : compact_value4(pp, wp, fr.ov_n, (fr.ov_exec_mask >> c) & 1, fr.ov_src + j0);
+        v.x = v.x + t4.x; v.y = v.y + t4.y; v.z = v.z + t4.z; v.w = v.w + t4.w;
+      }
+      if (c == 0) m = v;
+      else m.x = m.x + v.x, m.y = m.y + v.y, m.z = m.z + v.z, m.w = m.w + v.w;
+    }
+    m = mono_finish(m, ch, clip, &clipped);
+    pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + g, m.x, m.y, m.z, m.w);
+  }
+  return clipped;
+}
+template <typename PCM>
+__device__ __forceinline__ int ola_sym_mono(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev,
+                                            const float* __restrict__ w, const float* __restrict__ wp, PCM* out, int ch, int clip,
+                                            int tid, int threads) {
+  int clipped = 0;
+  const int n = fr.n, n2 = n >> 1;
+  const int groups = n >> 4;
+  for (int g = tid; g < groups; g += threads) {
+    const int i0 = 4 * g;
+    const float4 wf = *reinterpret_cast<const float4*>(w + i0);
+    const float4 wm = *reinterpret_cast<const float4*>(w + (n2 - 4 - i0));
+    const float4 pf = *reinterpret_cast<const float4*>(wp + (n2 + i0));
+    const float4 pm = *reinterpret_cast<const float4*>(wp + (n - 4 - i0));
+    float4 mv = make_float4(0.f, 0.f, 0.f, 0.f), mu = mv;
+    for (int c = 0; c < ch; ++c) {
+      const float4 a = *reinterpret_cast<const float4*>(cur + (long long)c * S.block1 + i0);
+      const float4 b = *reinterpret_cast<const float4*>(prev + (long long)c * S.block1 + n2 + i0);
+      float4 v, u;
+      ola_sym_mul_add(a, b, wf, wm, pf, pm, v, u);
+      if (c == 0) mv = v, mu = u;
+      else {
+        mv.x = mv.x + v.x; mv.y = mv.y + v.y; mv.z = mv.z + v.z; mv.w = mv.w + v.w;
+        mu.x = mu.x + u.x; mu.y = mu.y + u.y; mu.z = mu.z + u.z; mu.w = mu.w + u.w;
+      }
+    }
+    mv = mono_finish(mv, ch, clip, &clipped);
+    mu = mono_finish(mu, ch, clip, &clipped);
+    pcm4_t<PCM>* p = reinterpret_cast<pcm4_t<PCM>*>(out);
+    pcm_store4(p + g, mv.x, mv.y, mv.z, mv.w);                   // sample times i0 .. i0 + 3
+    pcm_store4(p + ((n >> 3) - 1 - g), mu.x, mu.y, mu.z, mu.w);  // sample times n/2 - 4 - i0 .. n/2 - 1 - i0
+  }
+  return clipped;
+}
+
 // A frame may be shared by gridDim.y workgroups (large frames: six channels at n = 4096 are 48 KB of PCM, and 128 lanes
 // per frame leave the CUs with four wavefronts each): lane `OLA_TID` of `NVH_OLA_THREADS`.
 #define NVH_OLA_THREADS ((int)(blockDim.x * gridDim.y))
 #define NVH_OLA_TID ((int)(blockIdx.y * blockDim.x + threadIdx.x))
-template <typename PCM, bool PLANAR>
+template <typename PCM, int LAYOUT>
 __global__ void __launch_bounds__(256)
 k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry,
               PCM* __restrict__ pcm, int clip, int* __restrict__ clipped_flag, float* __restrict__ carry_out, int last_decoded,
-              int nosym, const int* __restrict__ list, int emitted, pcm_stride_t<PLANAR> plane_stride) {
+              int nosym, const int* __restrict__ list, int emitted, pcm_stride_t<LAYOUT> plane_stride) {
   // (The body is this kernel template's own and not an inlined function template's: as one, it compiles to a different register
   // allocation.)
+  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;
   // list: the frames paired emission left to this kernel (nvh_launch.hip); emitted: k_synth wrote the PCM of every frame with
   // NVH_EMIT_DONE (such a frame is on the list only as the block that becomes the carried tail)
   const int f = list ? list[blockIdx.x] : (int)blockIdx.x;
@@ -925,7 +1030,7 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
   const float* __restrict__ w = S.windows + fr.window_off;
   const float* __restrict__ wp = S.windows + fr.ov_window_off;
   const NvhChan* chans = Bt.chans + fr.chan_off;
-  PCM* out = pcm + fr.out_pos * (PLANAR ? 1 : ch);
+  PCM* out = pcm + fr.out_pos * (PLANAR || MONO ? 1 : ch);
   int clipped = 0;
   // the carried block (ov_frame == -2) is always stored fully windowed (k_expand_carry); blocks of this batch are compact
   const bool prev_full = fr.ov_frame == -2;
@@ -952,6 +1057,45 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
       report_clipped(clipped, clipped_flag);
       return;
     }
+  }
+  if constexpr (MONO) {
+    // the mono down-mix: the frame's first sample on a 16-byte boundary (an aligned base and an output position in whole groups
+    // of four; 8 bytes of 16-bit PCM), up to 32 channels (the frame record's execute masks); else sample by sample, one lane
+    // per sample time, every channel read by that lane
+    const bool mvec = fr.n != 0 && ch <= 32 && ((fr.emit_start | fr.emit_count | fr.start | fr.ov_src | fr.ov_len) & 3) == 0 &&
+                      (fr.out_pos & 3) == 0 && (reinterpret_cast<uintptr_t>(pcm) & 15u) == 0;
+    const bool msym = mvec && prev && !prev_full && fr.ov_n == fr.n && fr.start == 0 && fr.emit_start == 0 &&
+                      fr.emit_count == (fr.n >> 1) && fr.ov_src == (fr.n >> 1) && fr.ov_len == (fr.n >> 1) &&
+                      (fr.exec_mask & all_ch) == all_ch && (fr.ov_exec_mask & all_ch) == all_ch && !nosym;
+    if (msym) {
+      clipped = ola_sym_mono<PCM>(S, fr, cur, prev, w, wp, out, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS);
+    } else if (mvec) {
+      clipped = ola_vec_mono<PCM>(S, fr, cur, prev, prev_full, w, wp, out, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS);
+    } else {
+      for (int t = NVH_OLA_TID; t < fr.emit_count; t += NVH_OLA_THREADS) {
+        const int idx = fr.emit_start + t, j = idx - fr.start;
+        float m = 0.0f;
+        for (int c = 0; c < ch; ++c) {
+          const NvhChan cn = chans[c];
+          float v;
+          if (fr.n == 0) {
+            v = prev[(long long)c * S.block1 + fr.ov_src + t];
+          } else {
+            v = compact_value(cur + (long long)c * S.block1, w, fr.n, cn.exec, idx);
+            if (prev && j >= 0 && j < fr.ov_len) {
+              const float* pp = prev + (long long)c * S.block1;
+              v = v + (prev_full ? pp[fr.ov_src + j] : compact_value(pp, wp, fr.ov_n, cn.ov_exec, fr.ov_src + j));
+            }
+          }
+          m = c == 0 ? v : m + v;
+        }
+        m = mono_scale(m, ch);
+        if (clip) m = clip_value(m, &clipped);
+        pcm_store1(out + t, m);
+      }
+    }
+    report_clipped(clipped, clipped_flag);
+    return;
   }
   const bool sym = vec && prev && !prev_full && fr.ov_n == fr.n && fr.start == 0 && fr.emit_start == 0 && fr.emit_count == (fr.n >> 1) &&
                    fr.ov_src == (fr.n >> 1) && fr.ov_len == (fr.n >> 1) && (fr.exec_mask & all_ch) == all_ch &&
@@ -1023,9 +1167,9 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
   }
   report_clipped(clipped, clipped_flag);
 }
-#define NVH_OLA_COMPACT_TWINS(PCM, PLANAR, SFX)                                                                                     \
-  template __global__ void k_ola_compact<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,    \
-                                                      float*, int, int, const int*, int, pcm_stride_t<PLANAR>);
+#define NVH_OLA_COMPACT_TWINS(PCM, LAYOUT, SFX)                                                                                     \
+  template __global__ void k_ola_compact<PCM, LAYOUT>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,    \
+                                                      float*, int, int, const int*, int, pcm_stride_t<LAYOUT>);
 NVH_FOR_PCM_TWINS(NVH_OLA_COMPACT_TWINS)
 
 // Expands the compact planes of one frame into the fully windowed block (the carried tail format shared by all

@@ -91,6 +91,7 @@ struct NvhSynthArgs {
   const float* windows;
   int clip;
   int plane_stride;         // the _planar twins: samples between the channels' planes (time t of channel c at pcm + c * plane_stride + t).
+                            // (The _mono twins write one plane and read no stride.)
                             // (In the padding in front of clipped_flag, not at the end: a larger struct moves the implicit kernel
                             // arguments behind it, which changes an s_load offset in every kernel that takes NvhSynthArgs.)
   int* clipped_flag;
@@ -98,17 +99,24 @@ struct NvhSynthArgs {
   float* carry_out;         // receives the last decoded block, fully windowed (NVH_EMIT_CARRY_OUT); nullptr: k_ola_compact writes it
 };
 
-// The forms of PCM the emitting kernels write: M(sample type, channel-planar, suffix of the kernels' names).  Every such kernel
+// The layouts of PCM: every channel's sample of one time side by side, one plane per channel, or ONE plane that holds the mean of
+// the channels (the mono down-mix: mono_mix below).
+// (plain ints, not an enum: the layout is part of the k_ola_* kernels' signatures, and an unnamed type in a mangled name is quoted)
+constexpr int NVH_LAYOUT_INTERLEAVED = 0, NVH_LAYOUT_PLANAR = 1, NVH_LAYOUT_MONO = 2;
+
+// The forms of PCM the emitting kernels write: M(sample type, layout, suffix of the kernels' names).  Every such kernel
 // exists once per entry, written by its own file through this list and declared through it in nvh_internal.h; the host picks one
 // by the same pair (nvh_launch.hip: with_pcm_twins), so one more form is one more entry here.
-#define NVH_FOR_PCM_TWINS(M) M(float, false, ) M(int16_t, false, _s16) M(float, true, _planar) M(int16_t, true, _s16_planar)
+#define NVH_FOR_PCM_TWINS(M)                                                                                             \
+  M(float, NVH_LAYOUT_INTERLEAVED, ) M(int16_t, NVH_LAYOUT_INTERLEAVED, _s16) M(float, NVH_LAYOUT_PLANAR, _planar)       \
+  M(int16_t, NVH_LAYOUT_PLANAR, _s16_planar) M(float, NVH_LAYOUT_MONO, _mono) M(int16_t, NVH_LAYOUT_MONO, _s16_mono)
 
 #ifdef __HIPCC__
 // The last argument of the k_ola_* kernels: the samples between the channels' planes, of the channel-planar forms only.  The
-// interleaved forms take an empty struct in its place, which leaves their kernel-argument layout what it was without the argument
+// interleaved and the mono forms take an empty struct in its place, which leaves their kernel-argument layout what it was without the argument
 // (k_ola_compact reads the grid's shape from the implicit arguments behind it).
 struct NvhNoStride {};
-template <bool PLANAR> using pcm_stride_t = std::conditional_t<PLANAR, long long, NvhNoStride>;
+template <int LAYOUT> using pcm_stride_t = std::conditional_t<LAYOUT == NVH_LAYOUT_PLANAR, long long, NvhNoStride>;
 
 // PCM leaves the chip (a copy engine or the gather reads it next) and no kernel reads it again: streaming stores (`nt`), which do
 // not displace what the kernels do re-read -- the odd frames' planes, the slabs the odd launch touched for the even one -- from
@@ -253,6 +261,36 @@ __device__ __forceinline__ float4 compact_value4(const float* __restrict__ plane
   }
   const float4 ww = *reinterpret_cast<const float4*>(w + idx0);
   return make_float4(y.x * ww.x, y.y * ww.y, y.z * ww.z, y.w * ww.w);
+}
+
+// ---- the mono down-mix (the _mono twins: one plane, sample time t at pcm + out_pos + t) --------------------------------------
+// m = (((x_0 + x_1) + x_2) + ... + x_{C-1}) / (float)C on the channels' samples BEFORE ClipSamples' clip: C - 1 additions in
+// channel order, each rounded once, then one correctly rounded division; the clip (and, for 16-bit PCM, pcm_s16_value) is applied
+// once, to the mix.  The division is IEEE's: the build has neither fast-math nor a reciprocal flag, so `s / 3.0f` is the v_div_scale /
+// v_div_fmas / v_div_fixup sequence, and for C a power of two the compiler's own x / C -> x * (1 / C) is exact.  The narrow
+// kernels (at most two channels, k_synth_emit at its 64-VGPR cap) spell the stereo case out as a multiply by 0.5f.
+__device__ __forceinline__ float mono_scale(float s, int nch) { return s / (float)nch; }
+// the narrow emission's eight values per half (sample time k of channel c at v[2 k + c], nch <= 2) -> the four mixed sample times
+__device__ __forceinline__ float4 mono_mix2(const float (&v)[8], int nch, int clip, int* clipped) {
+  float4 m = nch == 2 ? make_float4((v[0] + v[1]) * 0.5f, (v[2] + v[3]) * 0.5f, (v[4] + v[5]) * 0.5f, (v[6] + v[7]) * 0.5f)
+                      : make_float4(v[0], v[2], v[4], v[6]);
+  if (clip) clip_value4(m, clipped);
+  return m;
+}
+// CH channels per lane (sample time k of channel c at v[k * CH + c]) -> the four mixed sample times
+template <int CH>
+__device__ __forceinline__ float4 mono_mix(const float (&v)[4 * CH], int clip, int* clipped) {
+  float m[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float s = v[k * CH];
+#pragma unroll
+    for (int c = 1; c < CH; ++c) s = s + v[k * CH + c];
+    m[k] = s / (float)CH;
+  }
+  float4 r = make_float4(m[0], m[1], m[2], m[3]);
+  if (clip) clip_value4(r, clipped);
+  return r;
 }
 
 // HasClipped (StreamDecoder.cs:728) is sticky: one lane per wavefront that clipped looks at the flag and only sets it

@@ -691,13 +691,14 @@ __device__ __forceinline__ void synth_carry_out(const NvhSynthArgs& A, const flo
 // (k_ola_compact's prev_full case: no second window multiply, the tail in time order).  The frame's own first quarter A lies in
 // its channel's dead transform slice (synth_emit).  One workgroup per batch: out of line, so that the steady-state loop keeps
 // its registers.
-template <int NT, typename PCM = float, bool PLANAR = false>
+template <int NT, typename PCM = float, int LAYOUT = NVH_LAYOUT_INTERLEAVED>
 __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const float* spec, int n, int nch, unsigned window_off,
                                               unsigned out_pos, int tid, int cstride = 0) {
   const int half = n >> 1;
   if (cstride == 0) cstride = half;  // floats between the channels' first quarters
+  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;  // (MONO: kernels_common.h: mono_mix2)
   const float* __restrict__ w = A.windows + window_off;
-  PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)out_pos * (PLANAR ? 1 : nch);
+  PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)out_pos * (PLANAR || MONO ? 1 : nch);
   int clipped = 0;
   for (int g = tid; g < (n >> 4); g += NT) {
     const int i0 = 4 * g;
@@ -715,7 +716,7 @@ __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const fl
         v.x = v.x + tt.x; v.y = v.y + tt.y; v.z = v.z + tt.z; v.w = v.w + tt.w;
         float4 u = make_float4(-a.w * wm.x, -a.z * wm.y, -a.y * wm.z, -a.x * wm.w);
         u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
-        if (A.clip) {
+        if (!MONO && A.clip) {  // (the mono form clips the mix)
           v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
           v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
           u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
@@ -734,6 +735,8 @@ __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const fl
     // half-line streaming stores do)
     if constexpr (PLANAR) {
       // (stored per channel above)
+    } else if constexpr (MONO) {  // the mean of the channels, clipped once: one vector per half
+      pcm_store_plane(out, g, (n >> 3) - 1 - g, mono_mix2(fwd, nch, A.clip, &clipped), mono_mix2(mir, nch, A.clip, &clipped));
     } else if (nch == 2) {
       pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
       pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
@@ -766,13 +769,14 @@ __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const fl
 // registers into the channel's dead transform slice, and every lane of the workgroup then overlap-adds, clips and interleaves
 // one group of sample times of one overlap, straight into 16-byte vectors of PCM.
 // The frame's own plane is written only when k_ola_compact still needs it (not both overlaps emitted here).
-template <int NT, typename PCM = float, bool PLANAR = false>
+template <int NT, typename PCM = float, int LAYOUT = NVH_LAYOUT_INTERLEAVED>
 __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, float* spec, const uint32_t* s_chan, int n, int nch,
                                            unsigned frame, int sl, bool emit_self, bool emit_next, bool self_carry, bool carry_out,
                                            unsigned exec_mask, float* planes,
                                            const float* Aa, const float* Bb, const float* Cc, const float* TW, int tid,
                                            long long* stamps = nullptr) {
   const int wv = tid >> 6, lane = tid & 63, half = n >> 1;
+  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;  // (MONO: kernels_common.h: mono_mix2)
   // profiling builds: shader-clock stamps of thread 0 (15 staging issued, 16 transform done, 17 behind the barrier, 18 emitted;
   // 10..14: the transform's own, imdct_wave.h)
 #define EM_T(k) do { if (stamps && tid == 0) stamps[k] = clock64(); } while (0)
@@ -847,7 +851,7 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
   __syncthreads();  // drains the staging DMA (vmcnt(0) in front of the barrier): all four quarters of every channel are in LDS
   EM_T(17);
   if (carry_out) synth_carry_out<NT>(A, planes, n, nch, exec_mask, w_self, tid);  // (such a frame has no NEXT: its plane was written)
-  if (self_carry) synth_self_carry<NT, PCM, PLANAR>(A, spec, n, nch, w_self, out_self, tid);    // the batch's first frame
+  if (self_carry) synth_self_carry<NT, PCM, LAYOUT>(A, spec, n, nch, w_self, out_self, tid);    // the batch's first frame
   // ---- overlap-add + interleave + clip, every lane of the workgroup: lane task = (overlap, group of four compact indices i0);
   // it produces sample times i0 .. i0 + 3 and n/2 - 4 - i0 .. n/2 - 1 - i0 of every channel (kernels.hip: ola_sym) ----
   int clipped = 0;
@@ -887,7 +891,7 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
 #ifndef NVH_ABL_NO_CLIP
         // (a pre-test on the task's largest |x| in front of the compares and selects was tried twice: a wavefront's 1024 samples
         // of loud material nearly always hold one that clips, so the slow path runs anyway)
-        if (A.clip) {
+        if (!MONO && A.clip) {  // (the mono form clips the mix)
           v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
           v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
           u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
@@ -902,7 +906,7 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
         }
       }
     }
-    PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)(nx ? out_next : out_self) * (PLANAR ? 1 : nch);
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)(nx ? out_next : out_self) * (PLANAR || MONO ? 1 : nch);
 #ifdef NVH_ABL_PCM_SMALL
     out = reinterpret_cast<PCM*>(A.pcm) + (long long)((nx ? out_next : out_self) & 0x7FFF) * nch;  // (ablation build: every frame's PCM into the same 256 KB)
 #endif
@@ -911,6 +915,8 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
 #endif
     if constexpr (PLANAR) {
       // (stored per channel above)
+    } else if constexpr (MONO) {  // the mean of the channels, clipped once: one vector per half
+      pcm_store_plane(out, g, (n >> 3) - 1 - g, mono_mix2(fwd, nch, A.clip, &clipped), mono_mix2(mir, nch, A.clip, &clipped));
     } else if (nch == 2) {
       pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
       pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
@@ -958,13 +964,14 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
 // and puts its eight results into channel-planar LDS rows; behind a barrier the rows leave as 16-byte vectors of interleaved,
 // clipped PCM.  The overlap-add's memory phase then runs inside the synthesis kernel, next to other workgroups' arithmetic,
 // instead of as a launch of its own (k_ola_compact: 42 us per 2048 six-channel frames), and half the planes are read from L2.
-template <int NT, typename PCM = float, bool PLANAR = false>
+template <int NT, typename PCM = float, int LAYOUT = NVH_LAYOUT_INTERLEAVED>
 __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run, int n, int nch, unsigned frame, unsigned ef,
                                             unsigned exec_mask, int tid) {
   // One round per overlap: the rows of ALL groups fit the dead slices (2 x nch x n/4 floats: 48 KB for six channels at 4096),
   // so an overlap costs two barriers, and a lane's K tasks have their loads in flight together -- with one run of 64 groups
   // per round (k_ola_compact's shape) the eight rounds' round trips stood one behind the other: 87 -> 141 us for the pair of
   // launches on C4, more than the k_ola_compact launch they replace.
+  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;
   constexpr int K = 3;
   const int half = n >> 1, groups = n >> 4, gsh = 31 - __clz(groups), RUN = n >> 2;  // RUN = 4 * groups
   const unsigned ch_magic = (unsigned)((0x100000000ull + (unsigned)nch - 1) / (unsigned)nch);
@@ -978,7 +985,7 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
     const float* prev = from_carry ? A.carry : A.work + (long long)(frame + ov - 1) * nch * A.block1;  // the earlier block
     const float* __restrict__ w = A.windows + fr->window_off;
     const float* __restrict__ wp = A.windows + fr->ov_window_off;
-    PCM* out = reinterpret_cast<PCM*>(A.pcm) + fr->out_pos * (PLANAR ? 1 : nch);
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + fr->out_pos * (PLANAR || MONO ? 1 : nch);
     float* sF = s_run;
     float* sM = s_run + nch * RUN;
     for (int t0 = tid; t0 < total; t0 += K * NT) {
@@ -1034,6 +1041,27 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
     }
     if constexpr (PLANAR) continue;  // (no LDS rows, no barriers: every value has left already)
     __syncthreads();
+    if constexpr (MONO) {
+      // the mono down-mix: a lane takes four sample times of one half, adds the channels' rows in channel order, divides, clips
+      // and stores one vector of the one plane (consecutive lanes, consecutive vectors)
+      pcm4_t<PCM>* oF1 = reinterpret_cast<pcm4_t<PCM>*>(out);
+      pcm4_t<PCM>* oM1 = reinterpret_cast<pcm4_t<PCM>*>(out + (half >> 1));
+      for (int j = tid; j < 2 * groups; j += NT) {
+        const bool mir = j >= groups;
+        const int jj = mir ? j - groups : j;
+        const float* sr = (mir ? sM : sF) + 4 * jj;
+        float4 m = *reinterpret_cast<const float4*>(sr);
+        for (int c = 1; c < nch; ++c) {
+          const float4 x = *reinterpret_cast<const float4*>(sr + c * RUN);
+          m.x = m.x + x.x; m.y = m.y + x.y; m.z = m.z + x.z; m.w = m.w + x.w;
+        }
+        m = make_float4(mono_scale(m.x, nch), mono_scale(m.y, nch), mono_scale(m.z, nch), mono_scale(m.w, nch));
+        if (A.clip) clip_value4(m, &clipped);
+        pcm_store4((mir ? oM1 : oF1) + jj, m.x, m.y, m.z, m.w);
+      }
+      __syncthreads();
+      continue;
+    }
     // the forward rows hold sample times [0, n/4), the mirrored rows [n/4, n/2): together the frame's n/2 samples in time order
     const int nvec = total;  // 16-byte vectors per half: n/4 sample times x nch channels / 4
     pcm4_t<PCM>* oF = reinterpret_cast<pcm4_t<PCM>*>(out);
@@ -1110,8 +1138,9 @@ __device__ __forceinline__ void imdct_keep_quarters(const float* X, float* slice
   }
 }
 
-template <int NT, int CH, typename PCM = float, bool PLANAR = false>
+template <int NT, int CH, typename PCM = float, int LAYOUT = NVH_LAYOUT_INTERLEAVED>
 __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float* smem, int n, unsigned frame, int tid) {
+  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;
   const int half = n >> 1, groups = n >> 4, slice = half + (n >> 4);
   const NvhFrame* fs = A.frames + frame;
   const unsigned w_self = fs[0].window_off, wp_self = fs[0].ov_window_off, w_next = fs[1].window_off, wp_next = fs[1].ov_window_off;
@@ -1142,7 +1171,7 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
       float4 u = make_float4(-a.w * wm.x, -a.z * wm.y, -a.y * wm.z, -a.x * wm.w);
       const float4 r = make_float4(b.w * pm.x, b.z * pm.y, b.y * pm.z, b.x * pm.w);
       u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
-      if (A.clip) {
+      if (!MONO && A.clip) {  // (the mono form clips the mix)
         v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
         v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
         u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
@@ -1161,6 +1190,15 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
         pcm_store4(p + g, fwd[c], fwd[CH + c], fwd[2 * CH + c], fwd[3 * CH + c]);
         pcm_store4(p + ((n >> 3) - 1 - g), mir[c], mir[CH + c], mir[2 * CH + c], mir[3 * CH + c]);
       }
+      return;
+    }
+    if constexpr (MONO) {
+      // the mono down-mix: the lane holds every channel of its sample times -- one vector per half of the one plane; a store
+      // instruction's 64 lanes (consecutive groups) write whole lines, as in the planar form
+      pcm4_t<PCM>* p = reinterpret_cast<pcm4_t<PCM>*>(reinterpret_cast<PCM*>(A.pcm) + (nx ? o_next : o_self));
+      const float4 mf = mono_mix<CH>(fwd, A.clip, &clipped), mm = mono_mix<CH>(mir, A.clip, &clipped);
+      pcm_store4(p + g, mf.x, mf.y, mf.z, mf.w);
+      pcm_store4(p + ((n >> 3) - 1 - g), mm.x, mm.y, mm.z, mm.w);
       return;
     }
     pcm4_t<PCM>* out = reinterpret_cast<pcm4_t<PCM>*>(reinterpret_cast<PCM*>(A.pcm) + (nx ? o_next : o_self) * CH);
@@ -1387,7 +1425,7 @@ __device__ __forceinline__ void synth_frame_spectrum(const NvhSynthArgs& A, cons
 // MODE (k_synth only): 0 = synthesis alone, 1 = + the carried tail written by the last decoded block's workgroup, 2 = + paired
 // emission.  Three instantiations, so that the launches that never emit keep the registers of the kernel that cannot (62 instead
 // of 64 VGPRs at the 64-VGPR cap: 24.4 against 25.1 us for 4096 frames).
-template <int NT, int MAXCH, int MODE = 0, bool GENERAL = false, typename PCM = float, bool PLANAR = false>
+template <int NT, int MAXCH, int MODE = 0, bool GENERAL = false, typename PCM = float, int LAYOUT = NVH_LAYOUT_INTERLEAVED>
 __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NVH_DBG_PARAMS) {
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
 #ifdef NVH_ABL_EMPTY0
@@ -1505,10 +1543,10 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
   if (MAXCH <= 2 && MODE >= 2 && (emit_self || emit_next)) {
     if constexpr (MAXCH <= 2 && MODE >= 2)
 #ifdef NVH_DEBUG
-      synth_emit<NT, PCM, PLANAR>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
+      synth_emit<NT, PCM, LAYOUT>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
                      Aa, Bb, Cc, TW, tid, dbg ? dbg + (long long)f * 24 : nullptr);
 #else
-      synth_emit<NT, PCM, PLANAR>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
+      synth_emit<NT, PCM, LAYOUT>(A, smem, spec, s_chan, n, nch, frame, sl, emit_self, emit_next, self_carry, carry_out, exec_mask, planes,
                      Aa, Bb, Cc, TW, tid);
 #endif
   } else
@@ -1591,21 +1629,21 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
     if (direct8) {
       __syncthreads();  // every channel's own quarters are in its slice
       switch (nch) {
-        case 1: synth_emit8_direct<NT, 1, PCM, PLANAR>(A, smem, n, frame, tid); break;  // (mono / stereo land here with blocks beyond 2048)
-        case 2: synth_emit8_direct<NT, 2, PCM, PLANAR>(A, smem, n, frame, tid); break;
-        case 3: synth_emit8_direct<NT, 3, PCM, PLANAR>(A, smem, n, frame, tid); break;
-        case 4: synth_emit8_direct<NT, 4, PCM, PLANAR>(A, smem, n, frame, tid); break;
-        case 5: synth_emit8_direct<NT, 5, PCM, PLANAR>(A, smem, n, frame, tid); break;
-        case 6: synth_emit8_direct<NT, 6, PCM, PLANAR>(A, smem, n, frame, tid); break;
-        case 7: synth_emit8_direct<NT, 7, PCM, PLANAR>(A, smem, n, frame, tid); break;
-        case 8: synth_emit8_direct<NT, 8, PCM, PLANAR>(A, smem, n, frame, tid); break;
+        case 1: synth_emit8_direct<NT, 1, PCM, LAYOUT>(A, smem, n, frame, tid); break;  // (mono / stereo land here with blocks beyond 2048)
+        case 2: synth_emit8_direct<NT, 2, PCM, LAYOUT>(A, smem, n, frame, tid); break;
+        case 3: synth_emit8_direct<NT, 3, PCM, LAYOUT>(A, smem, n, frame, tid); break;
+        case 4: synth_emit8_direct<NT, 4, PCM, LAYOUT>(A, smem, n, frame, tid); break;
+        case 5: synth_emit8_direct<NT, 5, PCM, LAYOUT>(A, smem, n, frame, tid); break;
+        case 6: synth_emit8_direct<NT, 6, PCM, LAYOUT>(A, smem, n, frame, tid); break;
+        case 7: synth_emit8_direct<NT, 7, PCM, LAYOUT>(A, smem, n, frame, tid); break;
+        case 8: synth_emit8_direct<NT, 8, PCM, LAYOUT>(A, smem, n, frame, tid); break;
         default: __builtin_trap();
       }
     } else
     if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT | NVH_EMIT_CARRY_OUT)) {
       __syncthreads();
       if ((ef & NVH_EMIT_CARRY_OUT) && A.carry_out) synth_carry_out8<NT>(A, planes, n, nch, exec_mask, A.frames[frame].window_off, tid);
-      if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT)) synth_emit8<NT, PCM, PLANAR>(A, smem, n, nch, frame, ef, exec_mask, tid);
+      if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT)) synth_emit8<NT, PCM, LAYOUT>(A, smem, n, nch, frame, ef, exec_mask, tid);
     }
   }
   if constexpr (MAXCH > 2 && MODE < 2) {
@@ -1655,9 +1693,10 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
 // (Tried and removed, round 6: two frames per workgroup of EIGHT wavefronts, every 256 threads walking their own frame side by side --
 // k_synth's per-frame parallelism, 4 workgroups = 32 wavefronts per CU at 64 VGPRs: 171 M frames/s over three streams against 202 M for
 // this form, 124 M against 123 M on one.)
-template <int NT, int FPW, typename PCM = float, bool PLANAR = false>
+template <int NT, int FPW, typename PCM = float, int LAYOUT = NVH_LAYOUT_INTERLEAVED>
 __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* smem NVH_DBG_PARAMS) {
   static_assert(NT / 64 >= 2 * FPW, "one wavefront per (frame, channel) in the transform");
+  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;  // (MONO: kernels_common.h: mono_mix2)
   // (the wavefront's index through readfirstlane: what depends on it alone -- which frame and channel it transforms, where its
   // planes lie -- then lives in scalar registers)
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -1960,7 +1999,7 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
     if (cout_k[k])  // the block that becomes the next batch's carried tail (its whole plane was written above)
       synth_carry_out<NT>(A, A.work + (long long)(fa + k) * nch * A.block1, nn[k], nch, (w0[k] >> 16) & 0xFFu, cwin[k], tid);
   if (self_carry)  // the batch's first frame
-    synth_self_carry<NT, PCM, PLANAR>(A, slice0, nn[0], nch, __builtin_amdgcn_readfirstlane(otab[0]), __builtin_amdgcn_readfirstlane(otab[2]), tid, slice_words);
+    synth_self_carry<NT, PCM, LAYOUT>(A, slice0, nn[0], nch, __builtin_amdgcn_readfirstlane(otab[0]), __builtin_amdgcn_readfirstlane(otab[2]), tid, slice_words);
 
   // ---- overlap-add + interleave + clip: lane task = (overlap j, group of four compact indices i0); it produces sample times
   // i0 .. i0 + 3 and n/2 - 4 - i0 .. n/2 - 1 - i0 of every channel (kernels.hip: ola_sym) ----
@@ -1996,7 +2035,7 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
         float4 u = make_float4(-a.w * wm.x, -a.z * wm.y, -a.y * wm.z, -a.x * wm.w);
         const float4 r = make_float4(b.w * pm.x, b.z * pm.y, b.y * pm.z, b.x * pm.w);
         u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
-        if (A.clip) {
+        if (!MONO && A.clip) {  // (the mono form clips the mix)
           v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
           v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
           u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
@@ -2010,9 +2049,11 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
         }
       }
     }
-    PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)r0.z * (PLANAR ? 1 : nch);
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)r0.z * (PLANAR || MONO ? 1 : nch);
     if constexpr (PLANAR) {
       // (stored per channel above)
+    } else if constexpr (MONO) {  // the mean of the channels, clipped once: one vector per half
+      pcm_store_plane(out, g, (n >> 3) - 1 - g, mono_mix2(fwd, nch, A.clip, &clipped), mono_mix2(mir, nch, A.clip, &clipped));
     } else if (nch == 2) {
       pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
       pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
@@ -2057,7 +2098,7 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
         const float4 x = *reinterpret_cast<const float4*>(smem + r0.w + c * slice_words + src);
         float4 v = second ? make_float4(x.x * wv4.x, x.y * wv4.y, x.z * wv4.z, x.w * wv4.w)
                           : make_float4(-x.w * wv4.x, -x.z * wv4.y, -x.y * wv4.z, -x.x * wv4.w);
-        if (A.clip) {
+        if (!MONO && A.clip) {
           v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
           v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
         }
@@ -2069,9 +2110,12 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
         }
       }
     }
-    PCM* out = reinterpret_cast<PCM*>(A.pcm) + ((long long)r0.y + (idx0 - (int)r1.w)) * (PLANAR ? 1 : nch);
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + ((long long)r0.y + (idx0 - (int)r1.w)) * (PLANAR || MONO ? 1 : nch);
     if constexpr (PLANAR) {
       // (stored per channel above)
+    } else if constexpr (MONO) {
+      const float4 m = mono_mix2(o, nch, A.clip, &clipped);
+      pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out), m.x, m.y, m.z, m.w);
     } else if (nch == 2) {
       if constexpr (std::is_same<PCM, int16_t>::value) {
         pcm_store4x2(reinterpret_cast<pcm4_t<PCM>*>(out), o);
@@ -2112,11 +2156,11 @@ k_synth_tail(NvhSynthArgs A NVH_DBG_PARAMS) {
 // interleaved kernel has always stood: the compiler's inlining follows the order of the functions in the file, and k_synth's own
 // code changes with it.  k_synth, k_synth_tail and k_synth8 never store PCM (A.pcm is only tested in the emitting modes).
 // paired emission, the even frames of a mono / stereo batch (synth_emit)
-#define NVH_SYNTH_EMIT(PCM, PLANAR, SFX)                                                                                   \
+#define NVH_SYNTH_EMIT(PCM, LAYOUT, SFX)                                                                                   \
   extern "C" __global__ void __launch_bounds__(NVH_SYNTH_NT) __attribute__((amdgpu_waves_per_eu(NVH_SYNTH_WPE)))           \
   k_synth_emit##SFX(NvhSynthArgs A NVH_DBG_PARAMS) {                                                                       \
     extern __shared__ __attribute__((aligned(16))) float smem[];                                                           \
-    synth_body<NVH_SYNTH_NT, 2, 2, false, PCM, PLANAR>(A, smem NVH_DBG_ARGS);                                              \
+    synth_body<NVH_SYNTH_NT, 2, 2, false, PCM, LAYOUT>(A, smem NVH_DBG_ARGS);                                              \
   }
 NVH_FOR_PCM_TWINS(NVH_SYNTH_EMIT)
 
@@ -2142,25 +2186,25 @@ k_synth8_g(NvhSynthArgs A NVH_DBG_PARAMS) {
 }
 
 // the even frames of a wide batch with paired emission: + the overlap-add of the steady-state overlaps (synth_emit8)
-#define NVH_SYNTH8_EMIT(PCM, PLANAR, SFX)                                                  \
+#define NVH_SYNTH8_EMIT(PCM, LAYOUT, SFX)                                                  \
   extern "C" __global__ void __launch_bounds__(512)                                        \
   k_synth8_emit##SFX(NvhSynthArgs A NVH_DBG_PARAMS) {                                      \
     extern __shared__ __attribute__((aligned(16))) float smem[];                           \
-    synth_body<512, NVH_SLAB_MAX_CH, 2, false, PCM, PLANAR>(A, smem NVH_DBG_ARGS);         \
+    synth_body<512, NVH_SLAB_MAX_CH, 2, false, PCM, LAYOUT>(A, smem NVH_DBG_ARGS);         \
   }
 NVH_FOR_PCM_TWINS(NVH_SYNTH8_EMIT)
 
 // frame groups: two frames per workgroup (four wavefronts: one per (frame, channel)), and four frames per workgroup (eight
 // wavefronts); LDS, not registers, decides the residency
-#define NVH_SYNTH_GROUP(PCM, PLANAR, SFX)                                                  \
+#define NVH_SYNTH_GROUP(PCM, LAYOUT, SFX)                                                  \
   extern "C" __global__ void __launch_bounds__(256)                                        \
   k_synth_group2##SFX(NvhSynthArgs A NVH_DBG_PARAMS) {                                     \
     extern __shared__ __attribute__((aligned(16))) float smem[];                           \
-    synth_group_body<256, 2, PCM, PLANAR>(A, smem NVH_DBG_ARGS);                           \
+    synth_group_body<256, 2, PCM, LAYOUT>(A, smem NVH_DBG_ARGS);                           \
   }                                                                                        \
   extern "C" __global__ void __launch_bounds__(512)                                        \
   k_synth_group4##SFX(NvhSynthArgs A NVH_DBG_PARAMS) {                                     \
     extern __shared__ __attribute__((aligned(16))) float smem[];                           \
-    synth_group_body<512, 4, PCM, PLANAR>(A, smem NVH_DBG_ARGS);                           \
+    synth_group_body<512, 4, PCM, LAYOUT>(A, smem NVH_DBG_ARGS);                           \
   }
 NVH_FOR_PCM_TWINS(NVH_SYNTH_GROUP)

@@ -578,7 +578,8 @@ extern "C" int nvh_stream_pending(const nvh_stream* s, int* frames, int64_t* pcm
 // A host destination is staged on the device and read back in one copy.  Interleaved PCM is one plane of n * channels samples.
 // Channel-planar PCM (the _planar calls: channel c's samples at base + c * plane_stride, counts per channel) is staged as
 // [C, n4] planes (n4: the batch's samples per channel rounded up to whole groups of four, so that the emission's vector stores
-// run) and read back as one 2-D copy; one plain copy when the planes are contiguous.
+// run) and read back as one 2-D copy; one plain copy when the planes are contiguous.  The mono mix (the _mix calls) is the
+// one-plane case: n samples, staged and read back like interleaved PCM of one channel.
 static int64_t planar_stage_stride(int64_t n) { return (n + 3) & ~(int64_t)3; }
 static int64_t planar_launch_stride(int64_t plane_stride) { return plane_stride > 0 ? plane_stride : 4; }  // (0 only with no samples)
 
@@ -588,10 +589,10 @@ struct PcmShape {
   int64_t len, stage, stride;
   int planes;
   PcmShape(const PcmOut& out, int64_t n, int ch)
-      : len(out.planar() ? n : n * ch), stage(out.planar() ? planar_stage_stride(n) : len),
+      : len(out.planar() || out.mono() ? n : n * ch), stage(out.planar() ? planar_stage_stride(n) : len),
         stride(out.planar() ? out.plane_stride : len), planes(out.planar() ? ch : 1) {}
   size_t stage_bytes(size_t sb) const { return (size_t)(stage > 0 ? stage : 1) * (size_t)planes * sb; }
-  PcmOut staged(const PcmOut& out) const { return {out.format, out.planar() ? planar_launch_stride(stage) : 0}; }
+  PcmOut staged(const PcmOut& out) const { return {out.format, out.planar() ? planar_launch_stride(stage) : 0, out.mix}; }
 };
 
 // `n` samples of each of `planes` planes from device planes at stride `src_stride` to host planes at stride `dst_stride`
@@ -769,6 +770,31 @@ extern "C" int nvh_stream_synth_begin_planar(nvh_stream* s, int format, void* pc
   });
 }
 
+// The *_mix forms: the *_pcm calls with a down-mix of the channels (NVH_MIX_MONO: one plane, counts per channel).  The mix of
+// one channel is that channel: such a stream takes the *_pcm call, its alignment rule included.
+static PcmOut mix_out(const nvh_stream* s, int format, int mix) {
+  return PcmOut{format, 0, s && s->setup.channels == 1 ? NVH_MIX_NONE : mix};
+}
+extern "C" int nvh_stream_synth_mix(nvh_stream* s, int format, int mix, void* pcm_host, void* d_pcm, int64_t capacity, int64_t* written) {
+  return nvh_guard([&]() -> int {
+    const PcmOut out = mix_out(s, format, mix);
+    if (!s || (pcm_host && d_pcm) || !PcmOut::format_ok(format) || !PcmOut::mix_ok(mix) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
+    if (written) *written = 0;
+    if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
+    if (capacity < PcmShape(out, s->pending.pcm_samples, s->setup.channels).len) return NVH_ERR_ARGUMENT;
+    return stream_synth(s, out, pcm_host, d_pcm, capacity, written);
+  });
+}
+
+extern "C" int nvh_stream_synth_begin_mix(nvh_stream* s, int format, int mix, void* pcm_host, int64_t capacity, int64_t* expected) {
+  return nvh_guard([&]() -> int {
+    if (!s || !pcm_host || !PcmOut::format_ok(format) || !PcmOut::mix_ok(mix)) return NVH_ERR_ARGUMENT;
+    if (expected) *expected = 0;
+    if (capacity < PcmShape(mix_out(s, format, mix), s->pending.pcm_samples, s->setup.channels).len) return NVH_ERR_ARGUMENT;
+    return stream_synth_begin(s, mix_out(s, format, mix), pcm_host, capacity, expected);
+  });
+}
+
 extern "C" int nvh_stream_synth_end(nvh_stream* s, int64_t* written) {
   return nvh_guard([&]() -> int {
     if (!s) return NVH_ERR_ARGUMENT;
@@ -880,7 +906,7 @@ extern "C" int nvh_batch_synth(nvh_batch* b, float* d_pcm, int64_t capacity) {
 // nvh_batch_synth_pcm / _planar: `capacity` in the unit of the batch's PCM in `out` (samples per channel for planar PCM)
 static int batch_synth(nvh_batch* b, const PcmOut& out, void* d_pcm, int64_t capacity) {
   return nvh_guard([&]() -> int {
-    if (!b || !b->s || !PcmOut::format_ok(out.format) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
+    if (!b || !b->s || !PcmOut::format_ok(out.format) || !PcmOut::mix_ok(out.mix) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
     nvh_stream* s = b->s;
     if (capacity < PcmShape(out, b->pcm_samples, s->setup.channels).len) return NVH_ERR_ARGUMENT;
     if (b->pcm_samples > 0 && !d_pcm) return NVH_ERR_ARGUMENT;
@@ -892,6 +918,11 @@ static int batch_synth(nvh_batch* b, const PcmOut& out, void* d_pcm, int64_t cap
 
 extern "C" int nvh_batch_synth_pcm(nvh_batch* b, int format, void* d_pcm, int64_t capacity) {
   return batch_synth(b, PcmOut{format, 0}, d_pcm, capacity);
+}
+
+extern "C" int nvh_batch_synth_mix(nvh_batch* b, int format, int mix, void* d_pcm, int64_t capacity) {
+  if (!PcmOut::mix_ok(mix)) return NVH_ERR_ARGUMENT;
+  return batch_synth(b, mix_out(b ? b->s : nullptr, format, mix), d_pcm, capacity);
 }
 
 extern "C" int nvh_batch_synth_planar(nvh_batch* b, int format, void* d_pcm, int64_t plane_stride) {

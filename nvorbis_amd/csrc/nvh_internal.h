@@ -70,7 +70,7 @@ __global__ void k_synth8(NvhSynthArgs A NVH_DBG_PARAMS);
 __global__ void k_synth8_g(NvhSynthArgs A NVH_DBG_PARAMS);    // + the general bin walk
 // The kernels that write PCM, once per form of PCM (kernels_common.h: NVH_FOR_PCM_TWINS).  The slab synthesis kernels carry the
 // form in their names (A.pcm points at PCM samples, A.plane_stride is the channel-planar forms' stride) ...
-#define NVH_SYNTH_DECL(PCM, PLANAR, SFX)                                                                                        \
+#define NVH_SYNTH_DECL(PCM, LAYOUT, SFX)                                                                                        \
   __global__ void k_synth_emit##SFX(NvhSynthArgs A NVH_DBG_PARAMS);   /* + paired emission (MODE 2) */                           \
   __global__ void k_synth8_emit##SFX(NvhSynthArgs A NVH_DBG_PARAMS);  /* wide frames + paired emission (synth_emit8) */           \
   __global__ void k_synth_group2##SFX(NvhSynthArgs A NVH_DBG_PARAMS); /* frame groups: two / four frames per workgroup */         \
@@ -90,24 +90,24 @@ __global__ void k_couple_floor(NvhDevSetup S, NvhDevBatch Bt, float* work, int* 
 }
 
 // ... and the overlap kernels are templates (kernels.hip), instantiated there for the same list; plane_stride: samples between the
-// channels' planes, an empty argument in the interleaved forms (kernels_common.h: pcm_stride_t)
-template <typename PCM, bool PLANAR>
+// channels' planes, an empty argument in the interleaved and mono forms (kernels_common.h: pcm_stride_t)
+template <typename PCM, int LAYOUT>
 __global__ void k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, PCM* pcm, int clip,
                               int* clipped_flag, float* carry_out, int last_decoded, int nosym, const int* list, int emitted,
-                              pcm_stride_t<PLANAR> plane_stride);
-template <typename PCM, bool PLANAR>
+                              pcm_stride_t<LAYOUT> plane_stride);
+template <typename PCM, int LAYOUT>
 __global__ void k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* work, const float* carry, PCM* pcm, int clip, int* clipped_flag,
-                           pcm_stride_t<PLANAR> plane_stride);
-template <typename PCM, bool PLANAR>
+                           pcm_stride_t<LAYOUT> plane_stride);
+template <typename PCM, int LAYOUT>
 __global__ void k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* work, const float* carry, PCM* pcm, int clip, int* clipped_flag,
-                               pcm_stride_t<PLANAR> plane_stride);
-#define NVH_OLA_DECL(PCM, PLANAR, SFX)                                                                                               \
-  extern template __global__ void k_ola_compact<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,  \
-                                                             float*, int, int, const int*, int, pcm_stride_t<PLANAR>);               \
-  extern template __global__ void k_ola_emit<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,     \
-                                                          pcm_stride_t<PLANAR>);                                                     \
-  extern template __global__ void k_ola_emit_seq<PCM, PLANAR>(NvhDevSetup, NvhDevBatch, float*, const float*, PCM*, int, int*,       \
-                                                              pcm_stride_t<PLANAR>);
+                               pcm_stride_t<LAYOUT> plane_stride);
+#define NVH_OLA_DECL(PCM, LAYOUT, SFX)                                                                                               \
+  extern template __global__ void k_ola_compact<PCM, LAYOUT>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,  \
+                                                             float*, int, int, const int*, int, pcm_stride_t<LAYOUT>);               \
+  extern template __global__ void k_ola_emit<PCM, LAYOUT>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,     \
+                                                          pcm_stride_t<LAYOUT>);                                                     \
+  extern template __global__ void k_ola_emit_seq<PCM, LAYOUT>(NvhDevSetup, NvhDevBatch, float*, const float*, PCM*, int, int*,       \
+                                                              pcm_stride_t<LAYOUT>);
 NVH_FOR_PCM_TWINS(NVH_OLA_DECL)
 
 extern thread_local int g_last_hip_error;
@@ -321,7 +321,7 @@ struct nvh_batch {
   bool sequential_ola = false;
   int last_decoded = -1;  // last frame with n != 0 (its block becomes the next carried tail)
   const char* slot_name[4] = {"-", "-", "-", "-"};  // kernels behind the four timing slots of the last launch
-  std::string slot_name_buf[4];  // storage of the names built with a twin's suffix (_s16, _planar, _s16_planar)
+  std::string slot_name_buf[4];  // storage of the names built with a twin's suffix (_s16, _planar, _s16_planar, _mono, _s16_mono)
   bool links_ok = false;  // op_link chains usable (every frame has < 32767 ops): k_spectrum's chain walk
   int max_ops = 0, max_ent = 0, max_pass = 0;  // largest per-frame op / entry / pass slice (LDS staging capacity of k_spectrum)
   int max_vecs = 0;     // GPU-parsed batch in slab mode: its largest slab, as k_parse reported it
@@ -457,18 +457,23 @@ int upload_setup(nvh_stream* s);                                 // nvh_setup.hi
 int upload_parse_tables(nvh_stream* s);                          // nvh_setup.hip
 int batch_upload(nvh_stream* s, nvh_batch* b);                   // nvh_launch.hip
 // A PCM destination: the sample format (NVH_PCM_*: float, or int16_t for the kernels' _s16 twins) and the layout -- interleaved
-// (plane_stride == 0), or channel-planar with channel c's samples at base + c * plane_stride (the _planar twins)
+// (plane_stride == 0), or channel-planar with channel c's samples at base + c * plane_stride (the _planar twins) -- and the mix
+// (NVH_MIX_*): NVH_MIX_MONO is ONE plane holding the mean of the channels (the _mono twins; never together with a plane stride)
 struct PcmOut {
   int format = NVH_PCM_F32;
   int64_t plane_stride = 0;
+  int mix = NVH_MIX_NONE;
+  static bool mix_ok(int mix) { return mix == NVH_MIX_NONE || mix == NVH_MIX_MONO; }
+  bool mono() const { return mix == NVH_MIX_MONO; }
+  int layout() const { return mono() ? NVH_LAYOUT_MONO : planar() ? NVH_LAYOUT_PLANAR : NVH_LAYOUT_INTERLEAVED; }
   static bool format_ok(int format) { return format == NVH_PCM_F32 || format == NVH_PCM_S16; }
   bool s16() const { return format == NVH_PCM_S16; }
   bool planar() const { return plane_stride > 0; }
   size_t sample_bytes() const { return s16() ? sizeof(int16_t) : sizeof(float); }
   // a device destination: interleaved 16-bit PCM 16-byte aligned (the stereo twins store eight samples at a time), planar PCM
-  // aligned to its samples
+  // and the mono mix aligned to their samples (their vector stores run where the base is 16-byte aligned, else the fall-back)
   bool dest_ok(const void* d_pcm) const {
-    return planar() ? ((uintptr_t)d_pcm % sample_bytes()) == 0 : (!s16() || ((uintptr_t)d_pcm & 15u) == 0);
+    return planar() || mono() ? ((uintptr_t)d_pcm % sample_bytes()) == 0 : (!s16() || ((uintptr_t)d_pcm & 15u) == 0);
   }
 };
 int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms,

@@ -730,14 +730,15 @@ static bool slab_path(const nvh_batch* b) { return slab_shape_ok(b) && slab_size
 
 // ---- the kernels that write PCM, one set per form of PCM (kernels_common.h: NVH_FOR_PCM_TWINS) ----
 // batch_launch picks a set here and nowhere else: a tag with the sample type, the layout, the suffix of the set's slot names and
-// the set's slab synthesis kernels (the k_ola_* kernels are templates over the same pair).
-template <typename PCM, bool PLANAR>
+// the set's slab synthesis kernels (the k_ola_* kernels are templates over the same pair).  (format, layout, mix) of a PcmOut map
+// to a set in with_pcm_twins alone.
+template <typename PCM, int LAYOUT>
 struct PcmTwins;
-#define NVH_PCM_TWINS(PCM, PLANAR, SFX)                                                                                \
+#define NVH_PCM_TWINS(PCM, LAYOUT, SFX)                                                                                \
   template <>                                                                                                          \
-  struct PcmTwins<PCM, PLANAR> {                                                                                       \
+  struct PcmTwins<PCM, LAYOUT> {                                                                                       \
     typedef PCM pcm;                                                                                                   \
-    static constexpr bool planar = PLANAR;                                                                             \
+    static constexpr int layout = LAYOUT;                                                                              \
     static constexpr const char* sfx = #SFX;                                                                           \
     static constexpr auto synth_emit = k_synth_emit##SFX, synth8_emit = k_synth8_emit##SFX, group2 = k_synth_group2##SFX, \
                           group4 = k_synth_group4##SFX;                                                                \
@@ -747,8 +748,8 @@ NVH_FOR_PCM_TWINS(NVH_PCM_TWINS)
 // f(tag) for the set that writes `out`
 template <typename F>
 static auto with_pcm_twins(const PcmOut& out, F&& f) {
-#define NVH_PCM_PICK(PCM, PLANAR, SFX) \
-  if (out.planar() == PLANAR && out.s16() == std::is_same<PCM, int16_t>::value) return f(PcmTwins<PCM, PLANAR>());
+#define NVH_PCM_PICK(PCM, LAYOUT, SFX) \
+  if (out.layout() == LAYOUT && out.s16() == std::is_same<PCM, int16_t>::value) return f(PcmTwins<PCM, LAYOUT>());
   NVH_FOR_PCM_TWINS(NVH_PCM_PICK)
   __builtin_unreachable();
 }
@@ -756,7 +757,7 @@ static auto with_pcm_twins(const PcmOut& out, F&& f) {
 // f(tag) for every set (the kernels that need a launch attribute)
 template <typename F>
 static void for_pcm_twins(F&& f) {
-#define NVH_PCM_EACH(PCM, PLANAR, SFX) f(PcmTwins<PCM, PLANAR>());
+#define NVH_PCM_EACH(PCM, LAYOUT, SFX) f(PcmTwins<PCM, LAYOUT>());
   NVH_FOR_PCM_TWINS(NVH_PCM_EACH)
 }
 
@@ -771,15 +772,18 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
   // whole groups of four samples (below 2^31: NvhSynthArgs::plane_stride) and a frame position in whole groups of four
   // (batch_upload: emit_planar_ok); otherwise the batch runs without paired emission and k_ola_compact<PCM, true> takes each frame
   // by its vector form where that frame's own position allows it, else sample by sample.
-  if (ch == 1) out.plane_stride = 0;
+  // The mono mix (the _mono twins): one plane, so the same condition without the stride, and the same fall-back; the mix of one
+  // channel is that channel.
+  if (ch == 1) out.plane_stride = 0, out.mix = NVH_MIX_NONE;
   const bool planar = out.planar();
   const int64_t plane_stride = out.plane_stride;
-  const bool planar_emit = !planar || (((uintptr_t)d_pcm & 15u) == 0 && (plane_stride & 3) == 0 && plane_stride <= 0x7FFFFFFFll &&
-                                       b->emit_planar_ok);
+  const bool planar_emit = out.mono() ? (((uintptr_t)d_pcm & 15u) == 0 && b->emit_planar_ok)
+                                      : !planar || (((uintptr_t)d_pcm & 15u) == 0 && (plane_stride & 3) == 0 &&
+                                                    plane_stride <= 0x7FFFFFFFll && b->emit_planar_ok);
   const char* sfx = with_pcm_twins(out, [](auto t) { return t.sfx; });
   // the k_ola_* kernels' last argument: the planes' stride, nothing in the interleaved forms
   auto ola_stride = [&](auto t) {
-    if constexpr (decltype(t)::planar) return (long long)plane_stride;
+    if constexpr (decltype(t)::layout == NVH_LAYOUT_PLANAR) return (long long)plane_stride;
     else return NvhNoStride();
   };
   float* work = (float*)b->work.p;
@@ -1064,7 +1068,7 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       auto ola_compact = [&](unsigned nwg, float* c_out, const int* list, int emitted_frames) {
         with_pcm_twins(out, [&](auto t) {
           typedef decltype(t) TW;
-          hipLaunchKernelGGL((k_ola_compact<typename TW::pcm, TW::planar>), dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st,
+          hipLaunchKernelGGL((k_ola_compact<typename TW::pcm, TW::layout>), dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st,
                              s->dev, b->dev, (const float*)work, carry, (typename TW::pcm*)d_pcm, s->clip, flags + 1, c_out,
                              b->last_decoded, T.no_ola_sym ? 1 : 0, list, emitted_frames, ola_stride(t));
         });
@@ -1080,13 +1084,13 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
     } else if (!b->sequential_ola) {
       with_pcm_twins(out, [&](auto t) {
         typedef decltype(t) TW;
-        hipLaunchKernelGGL((k_ola_emit<typename TW::pcm, TW::planar>), dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev,
+        hipLaunchKernelGGL((k_ola_emit<typename TW::pcm, TW::layout>), dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev,
                            (const float*)work, carry, (typename TW::pcm*)d_pcm, s->clip, flags + 1, ola_stride(t));
       });
     } else {
       with_pcm_twins(out, [&](auto t) {
         typedef decltype(t) TW;
-        hipLaunchKernelGGL((k_ola_emit_seq<typename TW::pcm, TW::planar>), dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry,
+        hipLaunchKernelGGL((k_ola_emit_seq<typename TW::pcm, TW::layout>), dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry,
                            (typename TW::pcm*)d_pcm, s->clip, flags + 1, ola_stride(t));
       });
     }

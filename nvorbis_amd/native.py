@@ -14,6 +14,7 @@ ERR_INVALID_DATA, ERR_ARGUMENT, ERR_RUNTIME, ERR_NOMEM = -1, -2, -3, -4
 ERR_NOT_VORBIS, ERR_DEVICE, ERR_UNSUPPORTED, ERR_NO_GPU = -5, -6, -7, -8
 PKT_EOS, PKT_RESYNC = 1, 2
 PCM_F32, PCM_S16 = 0, 1  # output formats of the *_pcm synthesis calls (NVH_PCM_*)
+MIX_NONE, MIX_MONO = 0, 1  # down-mixes of the *_mix synthesis calls (NVH_MIX_*)
 
 _ERRNAMES = {
     ERR_INVALID_DATA: "InvalidDataException", ERR_ARGUMENT: "ArgumentOutOfRangeException",
@@ -96,6 +97,8 @@ SIGNATURES = {
     "nvh_stream_synth_begin_pcm": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _i64p]),
     "nvh_stream_synth_planar": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, _i64p]),
     "nvh_stream_synth_begin_planar": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _i64p]),
+    "nvh_stream_synth_mix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int64, _i64p]),
+    "nvh_stream_synth_begin_mix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int64, _i64p]),
     "nvh_stream_parse_errors": (C.c_int, [_vp, _i32p, _i64p, C.c_int, _ip]),
     "nvh_batch_upload": (C.c_int, [_vp, _vpp]),
     "nvh_batch_info": (C.c_int, [_vp, _ip, _ip, _i64p, _i64p]),
@@ -105,6 +108,7 @@ SIGNATURES = {
     "nvh_batch_synth": (C.c_int, [_vp, _vp, C.c_int64]),
     "nvh_batch_synth_pcm": (C.c_int, [_vp, C.c_int, _vp, C.c_int64]),
     "nvh_batch_synth_planar": (C.c_int, [_vp, C.c_int, _vp, C.c_int64]),
+    "nvh_batch_synth_mix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int64]),
     "nvh_batch_time": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _f32p, _f32p]),
     "nvh_batch_free": (None, [_vp]),
     "nvh_ogg_demux": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int64, _vp, _vp, _vp, C.c_int, _ip, _i64p]),

@@ -39,6 +39,19 @@ def _layout(name):
     return name == "planar"
 
 
+_MIXES = (None, "mono")
+
+
+def _mix(name, planar=False):
+    """native.MIX_MONO for "mono" (the channels' mean, one sample per sample time: the kernels' _mono twins), native.MIX_NONE for
+    None; ValueError for anything else, and for a mix together with the planar layout (one plane is both layouts)."""
+    if name not in _MIXES:
+        raise ValueError("mix must be None or 'mono', not %r" % (name,))
+    if name is not None and planar:
+        raise ValueError("mix=%r together with layout='planar': a mix is one plane, ask for it without a layout" % (name,))
+    return native.MIX_MONO if name == "mono" else native.MIX_NONE
+
+
 def _host_shape(samples, channels, planar):
     """A host array for `samples` per channel, never empty: (channels, m) planes, or (m,) interleaved."""
     return (channels, max(samples, 1)) if planar else (max(samples * channels, 1),)
@@ -298,11 +311,15 @@ class Batch:
         check(lib().nvh_batch_kernels(self._h, buf, 256), "nvh_batch_kernels")
         return buf.value.decode().split(",")
 
-    def synth(self, d_pcm_ptr, capacity, dtype=np.float32, plane_stride=None):
+    def synth(self, d_pcm_ptr, capacity, dtype=np.float32, plane_stride=None, mix=None):
         """Launch the synthesis into d_pcm_ptr (capacity in samples) as float32 or int16 PCM (a 16-byte aligned int16 destination).
         plane_stride (samples, >= self.samples): channel-planar PCM instead, channel c at d_pcm_ptr + c * plane_stride samples
-        (capacity is then not used)."""
+        (capacity is then not used).  mix="mono": the channels' mean, self.samples samples (capacity counts those)."""
         fmt, _ = _pcm_format(dtype)
+        mx = _mix(mix, plane_stride is not None)
+        if mx != native.MIX_NONE:
+            check(lib().nvh_batch_synth_mix(self._h, fmt, mx, C.c_void_p(d_pcm_ptr), int(capacity)), "nvh_batch_synth_mix")
+            return
         if plane_stride is not None:
             check(lib().nvh_batch_synth_planar(self._h, fmt, C.c_void_p(d_pcm_ptr), int(plane_stride)), "nvh_batch_synth_planar")
             return
@@ -361,6 +378,7 @@ class Stream:
         # pipelined read-back (synth_begin / synth_end): one buffer per native flight slot, the array each flight fills
         self._flight_bufs = (_PinnedBuffer(), _PinnedBuffer())
         self._flight_out = [None, None]
+        self._flight_per_channel = [False, False]  # the flight's counts are samples per channel (planar, mixed)
         self._pipe_next = self._pipe_first = self._pipe_out = 0
         self._h = C.c_void_p()
         check(lib().nvh_stream_open(ctx._h if ctx is not None else None, id_pkt, len(id_pkt), comment_pkt,
@@ -572,7 +590,7 @@ class Stream:
         check(lib().nvh_stream_has_clipped(self._h, C.byref(v)), "nvh_stream_has_clipped")
         return bool(v.value)
 
-    def synth_host(self, pinned=False, out=None, dtype=np.float32, planar=False):
+    def synth_host(self, pinned=False, out=None, dtype=np.float32, planar=False, mix=None):
         """Synthesise the pending batch; returns interleaved PCM (numpy) of `dtype`: float32, or int16 (ov_read's conversion,
         done in the kernels: half the bytes over PCIe).
 
@@ -582,10 +600,14 @@ class Stream:
         directly, no extra copy) and stays valid until the next call.
 
         planar=True: channel-planar PCM, a (channels, n) array (n samples per channel); `out` is then a C-contiguous
-        (channels, m) array of the dtype with m >= the pending samples per channel, and the result is out[:, :n]."""
+        (channels, m) array of the dtype with m >= the pending samples per channel, and the result is out[:, :n].
+
+        mix="mono": the mean of the channels (summed in channel order, divided, clipped once: include/nvorbis_hip.h), a
+        (n,) array of n samples; not together with planar."""
         fmt, dt = _pcm_format(dtype)
+        mx = _mix(mix, planar)
         _, smp = self.pending()
-        ch = self.channels
+        ch = self.channels if mx == native.MIX_NONE else 1  # (samples of the output per sample time)
         if out is None:
             shape = _host_shape(smp, ch, planar)
             n = int(np.prod(shape))
@@ -603,22 +625,27 @@ class Stream:
         if planar:
             where = "nvh_stream_synth_planar"
             rc = lib().nvh_stream_synth_planar(self._h, fmt, out.ctypes.data, None, out.shape[1], C.byref(wr))
+        elif mx != native.MIX_NONE:
+            where = "nvh_stream_synth_mix"
+            rc = lib().nvh_stream_synth_mix(self._h, fmt, mx, out.ctypes.data, None, out.size, C.byref(wr))
         else:
             where = "nvh_stream_synth_pcm"
             rc = lib().nvh_stream_synth_pcm(self._h, fmt, out.ctypes.data, None, out.size, C.byref(wr))
-        self._note_parse_error(rc, wr.value, where, planar=planar)
+        self._note_parse_error(rc, wr.value, where, planar=planar or mx != native.MIX_NONE)
         return out[:, :wr.value] if planar else out[:wr.value]
 
     # ---- pipelined read-back (nvh_stream_synth_begin / _end) ----
-    def synth_begin(self, dtype=np.float32, planar=False):
+    def synth_begin(self, dtype=np.float32, planar=False, mix=None):
         """Queue the pending batch (upload, GPU parse, synthesis, transfer of the PCM on a copy stream) and return at once.
         Two batches may be outstanding; synth_end() hands them back in order, each in the dtype of its begin (float32 / int16),
-        and -- planar=True -- as a (channels, n) view of channel-planar PCM (the return value is then per channel too)."""
+        and -- planar=True -- as a (channels, n) view of channel-planar PCM (the return value is then per channel too);
+        mix="mono": the channels' mean, n samples."""
         fmt, dt = _pcm_format(dtype)
+        mx = _mix(mix, planar)
         if self._pipe_out >= 2:
             # refuse before touching a buffer: slot k is still the DMA destination of the oldest outstanding batch
             raise native.NvhError(native.ERR_ARGUMENT, "nvh_stream_synth_begin (two batches are outstanding: call synth_end first)")
-        shape = _host_shape(self.pending()[1], self.channels, planar)
+        shape = _host_shape(self.pending()[1], self.channels if mx == native.MIX_NONE else 1, planar)
         n = int(np.prod(shape))
         k = self._pipe_next
         out = self._flight_bufs[k].get(n, dt)
@@ -626,10 +653,13 @@ class Stream:
         if planar:
             check(lib().nvh_stream_synth_begin_planar(self._h, fmt, out.ctypes.data, shape[1], C.byref(exp)), "nvh_stream_synth_begin_planar")
             out = out[:n].reshape(shape)
+        elif mx != native.MIX_NONE:
+            check(lib().nvh_stream_synth_begin_mix(self._h, fmt, mx, out.ctypes.data, out.size, C.byref(exp)), "nvh_stream_synth_begin_mix")
         else:
             check(lib().nvh_stream_synth_begin_pcm(self._h, fmt, out.ctypes.data, out.size, C.byref(exp)), "nvh_stream_synth_begin_pcm")
         # only a begin that succeeded occupies a slot
         self._flight_out[k] = out
+        self._flight_per_channel[k] = planar or mx != native.MIX_NONE  # (what the flight's counts mean)
         self._pipe_next = k ^ 1
         self._pipe_out += 1
         return exp.value
@@ -650,15 +680,21 @@ class Stream:
         self._pipe_out -= 1
         out = self._flight_out[k]
         planar = out.ndim == 2
-        self._note_parse_error(rc, wr.value, "nvh_stream_synth_end", planar=planar)
+        self._note_parse_error(rc, wr.value, "nvh_stream_synth_end", planar=self._flight_per_channel[k])
         return out[:, :wr.value] if planar else out[:wr.value]
 
-    def synth_device(self, d_ptr, capacity, dtype=np.float32, plane_stride=None):
+    def synth_device(self, d_ptr, capacity, dtype=np.float32, plane_stride=None, mix=None):
         """Synthesise the pending batch into device memory (capacity in samples; int16: 16-byte aligned); returns the samples written.
         plane_stride (samples): channel-planar PCM instead, channel c at d_ptr + c * plane_stride samples; returns the samples
-        written per channel (capacity is then not used)."""
+        written per channel (capacity is then not used).  mix="mono": the channels' mean (capacity and the return value count
+        its samples, one per sample time)."""
         fmt, _ = _pcm_format(dtype)
+        mx = _mix(mix, plane_stride is not None)
         wr = C.c_int64(0)
+        if mx != native.MIX_NONE:
+            rc = lib().nvh_stream_synth_mix(self._h, fmt, mx, None, C.c_void_p(d_ptr), int(capacity), C.byref(wr))
+            self._note_parse_error(rc, wr.value, "nvh_stream_synth_mix", planar=True)
+            return wr.value
         if plane_stride is not None:
             rc = lib().nvh_stream_synth_planar(self._h, fmt, None, C.c_void_p(d_ptr), int(plane_stride), C.byref(wr))
             self._note_parse_error(rc, wr.value, "nvh_stream_synth_planar", planar=True)
@@ -671,7 +707,7 @@ class Stream:
         """A synthesis call that returns an error code together with PCM (GPU-parse mode: a packet of the batch made the
         parser fail and the batch was parsed again without them): the PCM is complete; the errors are kept in
         `parse_errors` = [(NvhError, floats of this batch's PCM that precede the failing packet), ...] in stream order for
-        the caller to raise where the reference would have thrown (planar calls: samples per channel that precede it).  Any
+        the caller to raise where the reference would have thrown (planar and mixing calls: samples per channel that precede it).  Any
         other failure raises here."""
         self.parse_errors = []
         if rc == native.OK:
@@ -696,6 +732,7 @@ class Stream:
             lib().nvh_stream_close(self._h)
             self._h = C.c_void_p()
         self._flight_out = [None, None]
+        self._flight_per_channel = [False, False]
         for b in (self._pinned,) + self._flight_bufs:
             b.free()
 
@@ -710,13 +747,18 @@ class StreamDecoder:
     """IStreamDecoder-shaped object (Contracts/IStreamDecoder.cs:9-105) over a packet list."""
 
     def __init__(self, ctx, packets, granules=None, flags=None, batch_frames=1024, gpu_parse=False, sample_format="f32",
-                 layout="interleaved"):
+                 layout="interleaved", mix=None):
         # sample_format "s16": the ring is decoded as int16 (ov_read's conversion, in the kernels); Read then takes int16 buffers
         self._dtype = _sample_format(sample_format)
         # layout "planar": the ring is channel-planar PCM (the kernels' _planar twins); Read then takes (Channels, m) buffers and
         # counts samples per channel.  The bookkeeping below (ring position, roll-forward, error positions) stays in interleaved
         # units -- whole multiples of Channels -- either way.
         self._planar = _layout(layout)
+        # mix "mono": the ring is the channels' mean (the kernels' _mono twins), one sample per sample time; Read then counts and
+        # returns those.  Channels stays the stream's channel count, OutputChannels is what Read delivers per sample time (1).
+        # Positions, seeking and the roll-forward are in samples per channel either way.
+        self._mix_name = mix
+        self._mix = _mix(mix, self._planar)
         if len(packets) < 3:
             raise native.NvhError(native.ERR_NOT_VORBIS, "StreamDecoder")
         self._stream = Stream(ctx, packets[0], packets[1], packets[2])
@@ -751,6 +793,7 @@ class StreamDecoder:
     NominalBitrate = property(lambda self: self._stream.bitrates()[1])
     LowerBitrate = property(lambda self: self._stream.bitrates()[2])
     Channels = property(lambda self: self._stream.channels)
+    OutputChannels = property(lambda self: self._stream.channels if self._mix == native.MIX_NONE else 1)
     SampleRate = property(lambda self: self._stream.sample_rate)
     HasClipped = property(lambda self: self._stream.has_clipped())
 
@@ -771,7 +814,7 @@ class StreamDecoder:
     def SamplePosition(self):
         pos, _, _ = self._stream.position()
         pending = self._stream.pending()[1]  # pushed, not yet synthesised (only right after a seek)
-        return pos - pending - (self._ring.size - self._ring_pos) // self.Channels + self._skip // self.Channels
+        return pos - pending - (self._ring.size - self._ring_pos) // self.OutputChannels + self._skip // self.OutputChannels
 
     def _refill(self):
         """Parse up to batch_frames packets ahead and synthesise them."""
@@ -818,7 +861,7 @@ class StreamDecoder:
             pcm = None
             if frames:
                 # the ring is only replaced once it has been read out, so the stream's pinned buffer can be it
-                pcm = self._stream.synth_host(pinned=True, dtype=self._dtype, planar=self._planar)
+                pcm = self._stream.synth_host(pinned=True, dtype=self._dtype, planar=self._planar, mix=self._mix_name)
             got = pcm is not None and pcm.size > 0
             if got:
                 self._ring = pcm
@@ -838,8 +881,8 @@ class StreamDecoder:
 
     def Read(self, buffer, offset, count):
         """StreamDecoder.Read (StreamDecoder.cs:320-389).  Planar layout: buffer is a (Channels, m) array, offset and count are
-        samples per channel, and so is the return value."""
-        ch = self.Channels
+        samples per channel, and so is the return value.  A mixing decoder counts and returns output samples."""
+        ch = self.Channels if self._planar else self.OutputChannels
         if self._planar:
             if getattr(buffer, "dtype", None) != self._dtype:
                 raise TypeError("this decoder delivers %s samples: the buffer must be a numpy %s array" % (self._dtype, self._dtype))
@@ -1021,7 +1064,7 @@ class StreamDecoder:
             self._ended = True
             raise native.NvhError(native.ERR_RUNTIME, "SeekTo: roll-forward of %d samples into a packet that emits %d: the "
                                   "reference's Read does not return from here" % (roll, count))
-        self._skip = roll * self.Channels
+        self._skip = roll * self.OutputChannels
         # _currentPosition = samplePosition (:626): the pending frame's `count` samples are ahead of it
         self._stream.set_position_state(True, s - roll + count)
 
@@ -1036,13 +1079,17 @@ class VorbisReader:
     """VorbisReader-shaped facade (VorbisReader.cs): first logical stream of an .ogg file or byte string."""
 
     def __init__(self, source, ctx=None, device=0, batch_frames=8192, gpu_parse=True, forward_only=False, sample_format="f32",
-                 layout="interleaved"):
+                 layout="interleaved", mix=None):
         # sample_format: "f32" (float32 PCM, the reference's) or "s16" (int16, libvorbis ov_read's conversion in the kernels)
         self._dtype = _sample_format(sample_format)
         self._sample_format = sample_format
         # layout: "interleaved" (the reference's) or "planar" (ReadSamples takes (Channels, m) arrays, counts per channel)
         self._planar = _layout(layout)
         self._layout = layout
+        # mix: None, or "mono" (the channels' mean: ReadSamples / read_all count and return (samples,) arrays; Channels stays the
+        # stream's channel count, OutputChannels is 1)
+        _mix(mix, self._planar)
+        self._mix = mix
         # gpu_parse: parse the packets on the GPU too when the stream shape allows it (StreamDecoder falls back silently)
         # forward_only: read the container the way the reference reads a source that cannot seek (ContainerReader picks
         # ForwardOnlyPageReader for !stream.CanSeek, Ogg/ContainerReader.cs); SeekTo then raises as IPacketProvider.CanSeek is false
@@ -1067,7 +1114,7 @@ class VorbisReader:
             raise native.NvhError(native.ERR_NOT_VORBIS, "VorbisReader")  # ArgumentException: could not load the container
         self._stream_index = 0
         self._dec = StreamDecoder(self._ctx, demux_ogg_array(data, self._stream_ids[0], self._forward_only), None, None, batch_frames, gpu_parse,
-                                  sample_format, layout)
+                                  sample_format, layout, mix)
         if self._forward_only:
             self._dec.can_seek = False
         else:
@@ -1098,7 +1145,7 @@ class VorbisReader:
         clip = self.ClipSamples
         if index not in self._decs:
             self._decs[index] = StreamDecoder(self._ctx, demux_ogg_array(self._data, self._stream_ids[index], self._forward_only), None,
-                                              None, self._batch_frames, self._gpu_parse, self._sample_format, self._layout)
+                                              None, self._batch_frames, self._gpu_parse, self._sample_format, self._layout, self._mix)
             if self._forward_only:
                 self._decs[index].can_seek = False
             else:
@@ -1109,6 +1156,7 @@ class VorbisReader:
         return (self.Channels, self.SampleRate) != old
 
     Channels = property(lambda self: self._dec.Channels)
+    OutputChannels = property(lambda self: self._dec.OutputChannels)
     SampleRate = property(lambda self: self._dec.SampleRate)
     IsEndOfStream = property(lambda self: self._dec.IsEndOfStream)
     HasClipped = property(lambda self: self._dec.HasClipped)
@@ -1155,15 +1203,15 @@ class VorbisReader:
             return self._dec.Read(buffer, offset, count) if count > 0 else 0
         if count is None:
             count = len(buffer) - offset
-        count -= count % self.Channels
+        count -= count % self.OutputChannels
         if count > 0:
             return self._dec.Read(buffer, offset, count)
         return 0
 
     def read_all(self):
-        """Everything from the current position: interleaved, or (Channels, T) in the planar layout."""
+        """Everything from the current position: interleaved, (Channels, T) in the planar layout, or (T,) mixed samples."""
         chunks = []
-        buf = np.empty((self.Channels, 65536) if self._planar else (65536 * self.Channels,), dtype=self._dtype)
+        buf = np.empty((self.Channels, 65536) if self._planar else (65536 * self.OutputChannels,), dtype=self._dtype)
         while True:
             n = self.ReadSamples(buf, 0, buf.shape[-1])
             if n <= 0:

@@ -104,11 +104,15 @@ def main():
             if hard:
                 bad = 1
             print("%-28s %-34s %5s %5s %6s %8s %6s %8s  %s / %s" % (
-                oname, re.sub(r"^void ", "", nname.split("(")[0]), nf.get(".vgpr_count"), nf.get(".sgpr_count"), nf.get(".vgpr_spill_count"),
+                re.sub(r"^void ", "", oname.split("(")[0]), re.sub(r"^void ", "", nname.split("(")[0]), nf.get(".vgpr_count"), nf.get(".sgpr_count"), nf.get(".vgpr_spill_count"),
                 nf.get(".private_segment_fixed_size"), nf.get(".group_segment_fixed_size"), nf.get(".kernarg_segment_size"), rtxt, verdict))
         for k in new:
-            if k not in old:
-                print("%-28s NEW in %s" % (k, new_path))
+            if k not in old:  # a kernel the old listing does not have: its own figures
+                nname, nf, nb = new[k]
+                print("%-28s %-34s %5s %5s %6s %8s %6s %8s  NEW in %s (%d)" % (
+                    "-", k, nf.get(".vgpr_count"), nf.get(".sgpr_count"), nf.get(".vgpr_spill_count"),
+                    nf.get(".private_segment_fixed_size"), nf.get(".group_segment_fixed_size"), nf.get(".kernarg_segment_size"),
+                    os.path.basename(new_path), len(nb)))
     return bad
 
 

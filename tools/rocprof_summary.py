@@ -14,14 +14,17 @@ import re
 import sqlite3
 
 
-_TWIN_SUFFIX = {("float", "false"): "", ("short", "false"): "_s16", ("float", "true"): "_planar", ("short", "true"): "_s16_planar"}
+# (sample type, layout: NVH_LAYOUT_* of kernels_common.h; `true` / `false`: listings from when the layout was a bool, planar or not)
+_TWIN_SUFFIX = {("float", "0"): "", ("short", "0"): "_s16", ("float", "1"): "_planar", ("short", "1"): "_s16_planar",
+                ("float", "2"): "_mono", ("short", "2"): "_s16_mono",
+                ("float", "false"): "", ("short", "false"): "_s16", ("float", "true"): "_planar", ("short", "true"): "_s16_planar"}
 
 
 def slot_name(name):
     """A trace's kernel name as the slot name profiles/traffic.json and the ABI's timing slots use: the k_ola_* kernels are templates
-    over (sample type, channel-planar), so a trace prints `void k_ola_compact<short, true>(NvhDevSetup, ...)` for the kernel whose
+    over (sample type, layout), so a trace prints `void k_ola_compact<short, 1>(NvhDevSetup, ...)` for the kernel whose
     slot is `k_ola_compact_s16_planar` (family name + suffix); every other name stays as it is."""
-    m = re.match(r"(?:void )?(k_\w+)<(\w+), (true|false)>", name)
+    m = re.match(r"(?:void )?(k_\w+)<(\w+), (true|false|\d)>", name)
     return m.group(1) + _TWIN_SUFFIX[m.group(2), m.group(3)] if m and (m.group(2), m.group(3)) in _TWIN_SUFFIX else name
 
 

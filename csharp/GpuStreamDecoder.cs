@@ -29,7 +29,8 @@ namespace NVorbis.Hip
         short[] _ring16 = Array.Empty<short>();   // pcm16: the ring holds 16-bit samples (nvh_stream_synth_pcm, NVH_PCM_S16)
         readonly bool _pcm16;
         readonly bool _mono;   // the ring holds the channels' mean (nvh_stream_synth_mix, NVH_MIX_MONO): one sample per sample time
-        int _outChannels;      // samples of the ring per sample time: _channels, or 1 when mixing
+        readonly int[] _map;   // the ring holds _map.Length output channels, slot j = source channel _map[j] (nvh_stream_synth_map); null: none
+        int _outChannels;      // samples of the ring per sample time: _channels, 1 when mixing, or _map.Length
         int _ringPos, _ringLen;
         bool _ended, _clip = true;
         long _skip;   // floats to drop in front of the next samples: SeekTo's roll-forward
@@ -49,11 +50,17 @@ namespace NVorbis.Hip
         /// <param name="monoMix">true: the decoder delivers the mean of the channels (summed in channel order, divided and clipped once,
         /// inside the kernels): Read counts and returns those samples, one per sample time; Channels stays the stream's channel count,
         /// OutputChannels is 1.  Positions and seeking are in samples per channel either way.</param>
+        /// <param name="channelMap">null, or the decoder delivers channelMap.Length channels per sample time, output slot j holding source
+        /// channel channelMap[j] exactly as the un-mapped decoder delivers it (picked inside the kernels); WaveChannelMap(channels) is the
+        /// Vorbis-to-WAVE order.  Entries distinct and in [0, Channels); not together with monoMix.  OutputChannels is its length.</param>
         public GpuStreamDecoder(Contracts.IPacketProvider packetProvider, int device = 0, int batchPackets = 1024, int poolParseLanes = 0,
-                                bool pcm16 = false, bool monoMix = false)
+                                bool pcm16 = false, bool monoMix = false, int[] channelMap = null)
         {
+            if (channelMap != null && monoMix) throw new ArgumentException("A channel map cannot be combined with a mix!", nameof(channelMap));
+            if (channelMap != null && channelMap.Length == 0) throw new ArgumentException("A channel map names at least one channel!", nameof(channelMap));
             _pcm16 = pcm16;
             _mono = monoMix;
+            _map = channelMap == null ? null : (int[])channelMap.Clone();
             _packetProvider = packetProvider ?? throw new ArgumentNullException(nameof(packetProvider));
             _batchPackets = batchPackets;
             NativeMethods.Check(NativeMethods.nvh_ctx_create(device, out _ctx));
@@ -65,7 +72,17 @@ namespace NVorbis.Hip
             fixed (byte* pi = id, pc = comment, ps = setup)
                 NativeMethods.Check(NativeMethods.nvh_stream_open(_ctx, pi, id.Length, pc, comment.Length, ps, setup.Length, out _stream));
             NativeMethods.Check(NativeMethods.nvh_stream_info(_stream, out _channels, out _sampleRate, out _block0, out _block1));
-            _outChannels = _mono ? 1 : _channels;
+            _outChannels = _mono ? 1 : _map != null ? _map.Length : _channels;
+            if (_map != null)
+            {
+                var seen = new bool[_channels];
+                if (_map.Length > _channels) throw new ArgumentException("A channel map names at most Channels channels!", nameof(channelMap));
+                foreach (int c in _map)
+                {
+                    if (c < 0 || c >= _channels || seen[c]) throw new ArgumentException("Channel map entries must be distinct and in [0, Channels)!", nameof(channelMap));
+                    seen[c] = true;
+                }
+            }
             NativeMethods.Check(NativeMethods.nvh_stream_bitrates(_stream, out _upperBitrate, out _nominalBitrate, out _lowerBitrate));
             ParseComments(comment, out _vendor, out _comments);                 // LoadComments (StreamDecoder.cs:206-224)
             _stats.SetSampleRate(_sampleRate);                                   // StreamDecoder.cs:200
@@ -109,6 +126,15 @@ namespace NVorbis.Hip
             if (n < 0 || (long)n * 4 > p.Length - pos) throw new System.IO.InvalidDataException("Could not read full string!");
             comments = new string[n];
             for (int i = 0; i < n; i++) comments[i] = ReadString();
+        }
+
+        /// <summary>The Vorbis-to-WAVE channel permutation for 1 to 8 channels (nvh_channel_map_wave).</summary>
+        public static int[] WaveChannelMap(int channels)
+        {
+            if (channels < 1 || channels > 8) throw new ArgumentOutOfRangeException(nameof(channels));
+            var map = new int[channels];
+            fixed (int* p = map) NativeMethods.Check(NativeMethods.nvh_channel_map_wave(channels, p));
+            return map;
         }
 
         public int Channels => _channels;
@@ -181,14 +207,18 @@ namespace NVorbis.Hip
                     {
                         if (_ring16.Length < need) _ring16 = new short[need];
                         fixed (short* dst = _ring16)
-                            rc = _mono ? NativeMethods.nvh_stream_synth_mix(_stream, NativeMethods.NVH_PCM_S16, mix, dst, IntPtr.Zero, _ring16.Length, out written)
+                        fixed (int* map = _map)
+                            rc = _map != null ? NativeMethods.nvh_stream_synth_map(_stream, NativeMethods.NVH_PCM_S16, map, _map.Length, dst, IntPtr.Zero, _ring16.Length, out written) :
+                                 _mono ? NativeMethods.nvh_stream_synth_mix(_stream, NativeMethods.NVH_PCM_S16, mix, dst, IntPtr.Zero, _ring16.Length, out written)
                                        : NativeMethods.nvh_stream_synth_pcm(_stream, NativeMethods.NVH_PCM_S16, dst, IntPtr.Zero, _ring16.Length, out written);
                     }
                     else
                     {
                         if (_ring.Length < need) _ring = new float[need];
                         fixed (float* dst = _ring)
-                            rc = _mono ? NativeMethods.nvh_stream_synth_mix(_stream, NativeMethods.NVH_PCM_F32, mix, dst, IntPtr.Zero, _ring.Length, out written)
+                        fixed (int* map = _map)
+                            rc = _map != null ? NativeMethods.nvh_stream_synth_map(_stream, NativeMethods.NVH_PCM_F32, map, _map.Length, dst, IntPtr.Zero, _ring.Length, out written) :
+                                 _mono ? NativeMethods.nvh_stream_synth_mix(_stream, NativeMethods.NVH_PCM_F32, mix, dst, IntPtr.Zero, _ring.Length, out written)
                                        : NativeMethods.nvh_stream_synth(_stream, dst, IntPtr.Zero, _ring.Length, out written);
                     }
                     _ringPos = 0; _ringLen = (int)written;
@@ -234,7 +264,7 @@ namespace NVorbis.Hip
         int ReadRing<T>(Span<T> buffer, T[] ring, int offset, int count)
         {
             if (offset < 0 || offset + count > buffer.Length) throw new ArgumentOutOfRangeException(nameof(offset));
-            if (count % _outChannels != 0) throw new ArgumentOutOfRangeException(nameof(count), _mono ? "Must be a multiple of OutputChannels!" : "Must be a multiple of Channels!");
+            if (count % _outChannels != 0) throw new ArgumentOutOfRangeException(nameof(count), _mono || _map != null ? "Must be a multiple of OutputChannels!" : "Must be a multiple of Channels!");
             if (_stream == IntPtr.Zero) throw new ObjectDisposedException(nameof(GpuStreamDecoder));
             int idx = offset, tgt = offset + count;
             while (idx < tgt)

@@ -106,6 +106,16 @@ namespace NVorbis.Hip
         [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_mix(IntPtr stream, int format, int mix, void* pcmHost, IntPtr dPcm, long capacity, out long written);
         [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_begin_mix(IntPtr stream, int format, int mix, void* pcmHost, long capacity, out long expected);
         [DllImport(Lib)] public static extern int nvh_batch_synth_mix(IntPtr batch, int format, int mix, IntPtr dPcm, long capacity);
+        /// <summary>Channel-map forms (include/nvorbis_hip.h): outChannels output slots per sample time, slot j holding source channel map[j]
+        /// exactly as the un-mapped call emits it; interleaved (*_map: counts in output samples) or one plane per slot (*_planar_map:
+        /// counts per channel).  nvh_channel_map_wave fills the Vorbis-to-WAVE permutation for 1 to 8 channels.</summary>
+        [DllImport(Lib)] public static extern unsafe int nvh_channel_map_wave(int channels, int* map);
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_map(IntPtr stream, int format, int* map, int outChannels, void* pcmHost, IntPtr dPcm, long capacity, out long written);
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_begin_map(IntPtr stream, int format, int* map, int outChannels, void* pcmHost, long capacity, out long expected);
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_planar_map(IntPtr stream, int format, int* map, int outChannels, void* pcmHost, IntPtr dPcm, long planeStride, out long written);
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_begin_planar_map(IntPtr stream, int format, int* map, int outChannels, void* pcmHost, long planeStride, out long expected);
+        [DllImport(Lib)] public static extern unsafe int nvh_batch_synth_map(IntPtr batch, int format, int* map, int outChannels, IntPtr dPcm, long capacity);
+        [DllImport(Lib)] public static extern unsafe int nvh_batch_synth_planar_map(IntPtr batch, int format, int* map, int outChannels, IntPtr dPcm, long planeStride);
 
         /// <summary>The corpus gather (include/nvorbis_hip.h, "multi-GPU"): RCCL over xGMI through the library, one process per GPU (GpuCorpusGather.cs).</summary>
         public const int NVH_COMM_ID_BYTES = 128;

@@ -315,6 +315,41 @@ int nvh_stream_synth_begin_planar(nvh_stream *s, int format, void *pcm_host, int
 #define NVH_MIX_MONO 1
 int nvh_stream_synth_mix(nvh_stream *s, int format, int mix, void *pcm_host, void *d_pcm, int64_t capacity, int64_t *written);
 int nvh_stream_synth_begin_mix(nvh_stream *s, int format, int mix, void *pcm_host, int64_t capacity, int64_t *expected);
+/* Channel-map forms of the *_pcm and *_planar calls: the emitting kernels (their _map twins) write `out_channels` output slots
+ * per sample time, and output slot j holds source channel map[j] -- a permutation (WAVE order), a selection ("front pair only",
+ * "drop the LFE", "channel 3 as a mono plane"), or both.  THE RULE: output slot j at time t is exactly the sample the un-mapped call
+ * of the same format emits for channel map[j] at time t, ClipSamples' clip and the 16-bit conversion included; a map has no
+ * arithmetic of its own.  1 <= out_channels <= channels; the entries are distinct and in [0, channels).  The map belongs to the
+ * call, like format and layout: mapped and un-mapped batches (and formats, layouts, mixes) of one stream may alternate, because
+ * the carried tail stays per-channel float planes.  HasClipped follows the EMITTED samples: a channel the map drops does not set
+ * it in that batch.  The identity map (out_channels == channels, map[j] == j) IS the un-mapped call: the existing kernels run
+ * (nvh_stream_kernels shows their names) under that call's own rules.  Interleaved (*_map): out_channels samples per sample
+ * time; capacities, *written and *expected count output samples.  Planar (*_planar_map): output slot j at
+ * base + j * plane_stride; counts per channel, as in the planar calls.  A device base must be aligned to its sample size; the
+ * vector stores run where it is 16-byte aligned and every frame of the batch starts on a multiple of four samples per channel
+ * (planar: and the stride is a multiple of four), else the batch falls back to the per-frame overlap kernel (same bits).
+ * Streams of three to eight channels keep paired emission under a map (k_synth8_emit*_map).  The mono / stereo emitting kernels
+ * have no mapped forms: there a map that is not the identity is a swap or a single channel, and its batch runs without paired
+ * emission (k_synth + the mapped k_ola_compact) -- the route of a planar call with a misaligned destination; blocks beyond
+ * 2048 take the wide kernel and keep it.
+ * Errors, in this order: NVH_ERR_ARGUMENT for no stream, a null map, out_channels outside [1, channels], an entry out of range
+ * or named twice; NVH_ERR_UNSUPPORTED for a map other than the identity on a stream of more than 8 channels (the map travels
+ * as eight nibbles); then the un-mapped twin's own argument errors in its own order.  A map cannot be combined with a mix.
+ * No counterpart in the reference (NVorbis emits channels in Vorbis order).
+ *
+ * nvh_channel_map_wave fills map[0 .. channels) with the Vorbis-to-WAVE permutation for 1 to 8 channels (other counts:
+ * NVH_ERR_ARGUMENT).  Derivation: Vorbis I 4.3.9 fixes the order of a stream's channels --
+ *   1: M | 2: L R | 3: L C R | 4: FL FR RL RR | 5: FL C FR RL RR | 6: FL C FR RL RR LFE | 7: FL C FR SL SR RC LFE |
+ *   8: FL C FR SL SR RL RR LFE
+ * -- and WAVE_FORMAT_EXTENSIBLE orders the channels present by the bit order of dwChannelMask: FL FR FC LFE BL BR (FLC FRC) BC
+ * SL SR.  Sorting each Vorbis layout by those bits (rear = back) gives, by output slot with the source channel as value,
+ *   1: {0}  2: {0,1}  3: {0,2,1}  4: {0,1,2,3}  5: {0,2,1,3,4}  6: {0,2,1,5,3,4}  7: {0,2,1,6,5,3,4}  8: {0,2,1,7,5,6,3,4}
+ * (7: FL FR FC LFE BC SL SR; 8: FL FR FC LFE BL BR SL SR). */
+int nvh_channel_map_wave(int channels, int32_t *map);
+int nvh_stream_synth_map(nvh_stream *s, int format, const int32_t *map, int out_channels, void *pcm_host, void *d_pcm, int64_t capacity, int64_t *written);
+int nvh_stream_synth_begin_map(nvh_stream *s, int format, const int32_t *map, int out_channels, void *pcm_host, int64_t capacity, int64_t *expected);
+int nvh_stream_synth_planar_map(nvh_stream *s, int format, const int32_t *map, int out_channels, void *pcm_host, void *d_pcm, int64_t plane_stride, int64_t *written);
+int nvh_stream_synth_begin_planar_map(nvh_stream *s, int format, const int32_t *map, int out_channels, void *pcm_host, int64_t plane_stride, int64_t *expected);
 /* After nvh_stream_synth returned an error code together with *written > 0 (GPU-parse mode: packets of the batch made
  * the parser fail -- with the codes nvh_stream_push_packet returns for them in host-parse mode -- and the batch was
  * parsed again on the host without them): every such packet in stream order, codes[i] and samples_before[i] = the
@@ -352,6 +387,9 @@ int nvh_batch_synth_pcm(nvh_batch *b, int format, void *d_pcm, int64_t capacity)
 int nvh_batch_synth_planar(nvh_batch *b, int format, void *d_pcm, int64_t plane_stride);
 /* ... and mixed (see nvh_stream_synth_mix); capacity in output samples. */
 int nvh_batch_synth_mix(nvh_batch *b, int format, int mix, void *d_pcm, int64_t capacity);
+/* ... and with a channel map (see nvh_stream_synth_map); capacity in output samples, plane_stride per channel. */
+int nvh_batch_synth_map(nvh_batch *b, int format, const int32_t *map, int out_channels, void *d_pcm, int64_t capacity);
+int nvh_batch_synth_planar_map(nvh_batch *b, int format, const int32_t *map, int out_channels, void *d_pcm, int64_t plane_stride);
 /* Time `iters` repetitions with hipEvents on the launch stream: total milliseconds for the whole
  * pipeline, and per timing slot (spectrum: residue | couple+floor, or fused in slot 1; imdct+window; overlap+emit;
  * see nvh_batch_kernels).  A slot brackets its launches with event records, which costs ~2 us per slot. */

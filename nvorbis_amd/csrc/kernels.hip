@@ -594,16 +594,20 @@ template <typename PCM, int LAYOUT>
 __global__ void __launch_bounds__(NVH_THREADS)
 k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const float* __restrict__ carry, PCM* __restrict__ pcm,
            int clip, int* __restrict__ clipped_flag, pcm_stride_t<LAYOUT> plane_stride) {
-  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;
+  constexpr bool PLANAR = nvh_layout_planes(LAYOUT), MONO = LAYOUT == NVH_LAYOUT_MONO, MAP = nvh_layout_mapped(LAYOUT);
   const int f = blockIdx.x;
   const NvhFrame fr = Bt.frames[f];
   const int ch = S.channels;
-  const int total = fr.emit_count * ch;
+  // the mapped forms: oc output slots, slot j from source channel map_src(fwd, j) -- below `c` is the slot, `sc` its source
+  const NvhChanMap cm = pcm_map_of(plane_stride);
+  const long long pstride = pcm_stride_of(plane_stride);
+  const int oc = MAP ? cm.oc : ch;
+  const int total = fr.emit_count * oc;
   if (total <= 0) return;
   const float* cur = work + (long long)f * ch * S.block1;
   const float* prev = nullptr;
   if (fr.ov_len > 0) prev = (fr.ov_frame == -2) ? carry : (fr.ov_frame >= 0 ? work + (long long)fr.ov_frame * ch * S.block1 : nullptr);
-  PCM* out = pcm + fr.out_pos * (PLANAR || MONO ? 1 : ch);
+  PCM* out = pcm + fr.out_pos * (PLANAR || MONO ? 1 : oc);
   int clipped = 0;
   if constexpr (MONO) {
     // the mono down-mix (kernels_common.h: mono_scale): one output sample per index, the channels' planes in channel order
@@ -628,19 +632,20 @@ k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const 
     return;
   }
   for (int o = threadIdx.x; o < total; o += NVH_THREADS) {
-    int t = o / ch, c = o - t * ch;
+    int t = o / oc, c = o - t * oc;
     if constexpr (PLANAR) c = o / fr.emit_count, t = o - c * fr.emit_count;
+    const int sc = MAP ? map_src(cm.fwd, c) : c;
     int idx = fr.emit_start + t;
     float v;
     if (fr.n == 0) {
-      v = prev[(long long)c * S.block1 + fr.ov_src + t];  // drained carried tail, emitted as it is
+      v = prev[(long long)sc * S.block1 + fr.ov_src + t];  // drained carried tail, emitted as it is
     } else {
-      v = cur[(long long)c * S.block1 + idx];
+      v = cur[(long long)sc * S.block1 + idx];
       int j = idx - fr.start;
-      if (prev && j >= 0 && j < fr.ov_len) v = v + prev[(long long)c * S.block1 + fr.ov_src + j];  // OverlapBuffers
+      if (prev && j >= 0 && j < fr.ov_len) v = v + prev[(long long)sc * S.block1 + fr.ov_src + j];  // OverlapBuffers
     }
     if (clip) v = clip_value(v, &clipped);
-    if constexpr (PLANAR) pcm_store1(out + c * plane_stride + t, v);
+    if constexpr (PLANAR) pcm_store1(out + c * pstride + t, v);
     else pcm_store1(out + o, v);
   }
   report_clipped(clipped, clipped_flag);
@@ -653,8 +658,11 @@ template <typename PCM, int LAYOUT>
 __global__ void __launch_bounds__(NVH_THREADS)
 k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const float* __restrict__ carry, PCM* __restrict__ pcm,
                int clip, int* __restrict__ clipped_flag, pcm_stride_t<LAYOUT> plane_stride) {
-  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;
+  constexpr bool PLANAR = nvh_layout_planes(LAYOUT), MONO = LAYOUT == NVH_LAYOUT_MONO, MAP = nvh_layout_mapped(LAYOUT);
   const int ch = S.channels;
+  const NvhChanMap cm = pcm_map_of(plane_stride);  // (k_ola_emit: slot c, source sc; the adds in place cover every channel)
+  const long long pstride = pcm_stride_of(plane_stride);
+  const int oc = MAP ? cm.oc : ch;
   int clipped = 0;
   for (int f = 0; f < Bt.nframes; ++f) {
     const NvhFrame fr = Bt.frames[f];
@@ -669,8 +677,8 @@ k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const fl
       }
     }
     __syncthreads();
-    PCM* out = pcm + fr.out_pos * (PLANAR || MONO ? 1 : ch);
-    const int total = fr.emit_count * (MONO ? 1 : ch);
+    PCM* out = pcm + fr.out_pos * (PLANAR || MONO ? 1 : oc);
+    const int total = fr.emit_count * (MONO ? 1 : oc);
     for (int o = threadIdx.x; o < total; o += NVH_THREADS) {
       if constexpr (MONO) {  // the mono down-mix: one output sample per index, the channels' planes in channel order
         float m = 0.0f;
@@ -683,11 +691,12 @@ k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const fl
         pcm_store1(out + o, m);
         continue;
       }
-      int t = o / ch, c = o - t * ch;
+      int t = o / oc, c = o - t * oc;
       if constexpr (PLANAR) c = o / fr.emit_count, t = o - c * fr.emit_count;
-      float v = (fr.n == 0) ? prev[(long long)c * S.block1 + fr.ov_src + t] : cur[(long long)c * S.block1 + fr.emit_start + t];
+      const int sc = MAP ? map_src(cm.fwd, c) : c;
+      float v = (fr.n == 0) ? prev[(long long)sc * S.block1 + fr.ov_src + t] : cur[(long long)sc * S.block1 + fr.emit_start + t];
       if (clip) v = clip_value(v, &clipped);
-      if constexpr (PLANAR) pcm_store1(out + c * plane_stride + t, v);
+      if constexpr (PLANAR) pcm_store1(out + c * pstride + t, v);
       else pcm_store1(out + o, v);
     }
     __syncthreads();
@@ -700,6 +709,7 @@ k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const fl
   template __global__ void k_ola_emit_seq<PCM, LAYOUT>(NvhDevSetup, NvhDevBatch, float*, const float*, PCM*, int, int*,     \
                                                        pcm_stride_t<LAYOUT>);
 NVH_FOR_PCM_TWINS(NVH_OLA_EMIT_TWINS)
+NVH_FOR_PCM_MAP_TWINS(NVH_OLA_EMIT_TWINS)
 
 // ================================================================================================
 // Overlap-add + interleave + clip from the COMPACT block layout written by k_imdct_compact
@@ -726,9 +736,12 @@ __device__ __forceinline__ float compact_value(const float* __restrict__ plane, 
 
 // Overlap-add of one frame, CH channels, everything in units of four samples: a lane produces four consecutive
 // sample times of every channel and writes them as CH 16-byte stores (its 4*CH interleaved floats are contiguous).
-template <int CH, typename PCM>
+// (MAP, the mapped forms: CH is the number of output slots and slot c comes from source channel sc = map_src(fmap, c) -- a
+// run-time ADDRESS under a compile-time register index, so nothing is indexed by a run-time channel.)
+template <int CH, typename PCM, bool MAP = false>
 __device__ __forceinline__ int ola_vec(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev, bool prev_full,
-                                       const float* __restrict__ w, const float* __restrict__ wp, PCM* out, int clip, int tid, int threads) {
+                                       const float* __restrict__ w, const float* __restrict__ wp, PCM* out, int clip, int tid, int threads,
+                                       uint32_t fmap = 0u) {
   int clipped = 0;
   const int groups = fr.emit_count >> 2;
   for (int g = tid; g < groups; g += threads) {
@@ -739,11 +752,12 @@ __device__ __forceinline__ int ola_vec(const NvhDevSetup& S, const NvhFrame& fr,
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       // exec_mask / ov_exec_mask mirror NvhChan::exec / ov_exec: no dependent load
-      float4 v = compact_value4(cur + (long long)c * S.block1, w, fr.n, (fr.exec_mask >> c) & 1, idx0);
+      const int sc = MAP ? map_src(fmap, c) : c;
+      float4 v = compact_value4(cur + (long long)sc * S.block1, w, fr.n, (fr.exec_mask >> sc) & 1, idx0);
       if (ov) {
-        const float* pp = prev + (long long)c * S.block1;
+        const float* pp = prev + (long long)sc * S.block1;
         const float4 t4 = prev_full ? *reinterpret_cast<const float4*>(pp + fr.ov_src + j0)
-                                    : compact_value4(pp, wp, fr.ov_n, (fr.ov_exec_mask >> c) & 1, fr.ov_src + j0);
+                                    : compact_value4(pp, wp, fr.ov_n, (fr.ov_exec_mask >> sc) & 1, fr.ov_src + j0);
         v.x = v.x + t4.x; v.y = v.y + t4.y; v.z = v.z + t4.z; v.w = v.w + t4.w;
       }
       if (clip) clip_value4(v, &clipped);
@@ -773,9 +787,10 @@ __device__ __forceinline__ int ola_vec(const NvhDevSetup& S, const NvhFrame& fr,
 // arithmetic is kernels_common.h's ola_sym_mul_add, shared with the emitting synthesis kernels.  What is not shared is the
 // store: here a lane holds CH channels (CH a template argument, up to eight) and writes CH vectors per half, where the synthesis
 // kernels' pcm_emit_group holds at most two channels with the count in a register.
-template <int CH, typename PCM>
+template <int CH, typename PCM, bool MAP = false>
 __device__ __forceinline__ int ola_sym(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev,
-                                       const float* __restrict__ w, const float* __restrict__ wp, PCM* out, int clip, int tid, int threads) {
+                                       const float* __restrict__ w, const float* __restrict__ wp, PCM* out, int clip, int tid, int threads,
+                                       uint32_t fmap = 0u) {
   int clipped = 0;
   const int n = fr.n, n2 = n >> 1;
   const int groups = n >> 4;  // n/4 compact values per quarter, four per lane
@@ -788,8 +803,9 @@ __device__ __forceinline__ int ola_sym(const NvhDevSetup& S, const NvhFrame& fr,
     float fwd[4 * CH], mir[4 * CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
-      const float4 a = *reinterpret_cast<const float4*>(cur + (long long)c * S.block1 + i0);
-      const float4 b = *reinterpret_cast<const float4*>(prev + (long long)c * S.block1 + n2 + i0);
+      const int sc = MAP ? map_src(fmap, c) : c;
+      const float4 a = *reinterpret_cast<const float4*>(cur + (long long)sc * S.block1 + i0);
+      const float4 b = *reinterpret_cast<const float4*>(prev + (long long)sc * S.block1 + n2 + i0);
       float4 v, u;  // sample times i0 .. i0+3, and n/2-4-i0 .. n/2-1-i0 (the block's values are -A reversed, the predecessor's B reversed)
       ola_sym_mul_add(a, b, wf, wm, pf, pm, v, u);
       if (clip) {
@@ -820,10 +836,10 @@ __device__ __forceinline__ int ola_sym(const NvhDevSetup& S, const NvhFrame& fr,
 // through LDS: a lane's eight results go to channel-planar rows of the workgroup's two runs of sample times (the forward run
 // [4 g0, 4 g0 + 4 GW) and the mirrored run [n/2 - 4 (g0 + GW), n/2 - 4 g0)), and after one barrier the runs leave as whole
 // 16-byte vectors of interleaved, clipped PCM.  Workgroup blockIdx.y owns groups [GW y, GW y + GW).
-template <int CH, typename PCM>
+template <int CH, typename PCM, bool MAP = false>
 __device__ __forceinline__ int ola_sym_lds(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev,
                                            const float* __restrict__ w, const float* __restrict__ wp, PCM* out, int clip,
-                                           float* s_run /* [2][CH][4 * NVH_OLA_GW] */) {
+                                           float* s_run /* [2][CH][4 * NVH_OLA_GW] */, uint32_t fmap = 0u) {
   constexpr int GW = NVH_OLA_GW, RUN = 4 * GW;
   const int n = fr.n, n2 = n >> 1;
   const int groups = n >> 4;
@@ -839,8 +855,9 @@ __device__ __forceinline__ int ola_sym_lds(const NvhDevSetup& S, const NvhFrame&
     const float4 wm = *reinterpret_cast<const float4*>(w + (n2 - 4 - i0));
     const float4 pf = *reinterpret_cast<const float4*>(wp + (n2 + i0));
     const float4 pm = *reinterpret_cast<const float4*>(wp + (n - 4 - i0));
-    const float4 a = *reinterpret_cast<const float4*>(cur + (long long)c * S.block1 + i0);
-    const float4 b = *reinterpret_cast<const float4*>(prev + (long long)c * S.block1 + n2 + i0);
+    const int sc = MAP ? map_src(fmap, c) : c;
+    const float4 a = *reinterpret_cast<const float4*>(cur + (long long)sc * S.block1 + i0);
+    const float4 b = *reinterpret_cast<const float4*>(prev + (long long)sc * S.block1 + n2 + i0);
     float4 v, u;
     ola_sym_mul_add(a, b, wf, wm, pf, pm, v, u);
     *reinterpret_cast<float4*>(sF + c * RUN + 4 * gl) = v;              // sample times 4 g0 + 4 gl ..
@@ -873,10 +890,11 @@ __device__ __forceinline__ int ola_sym_lds(const NvhDevSetup& S, const NvhFrame&
 // group of four sample times), plane-major -- consecutive lanes take consecutive groups of one plane, and every vector leaves
 // as one store (16 bytes of float, 8 of int16_t) to its channel's plane: no interleave, no LDS.  `out` points at the frame's
 // first sample of plane 0, 16-byte aligned with the plane stride a multiple of four (nvh_launch.hip).
-template <typename PCM>
+// (MAP: `ch` counts the output slots, plane c holds source channel sc = map_src(fmap, c).)
+template <typename PCM, bool MAP = false>
 __device__ __forceinline__ int ola_vec_planar(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev,
                                               bool prev_full, const float* __restrict__ w, const float* __restrict__ wp, PCM* out,
-                                              long long plane_stride, int ch, int clip, int tid, int threads) {
+                                              long long plane_stride, int ch, int clip, int tid, int threads, uint32_t fmap = 0u) {
   int clipped = 0;
   const int groups = fr.emit_count >> 2;
   for (int task = tid; task < groups * ch; task += threads) {
@@ -884,11 +902,12 @@ __device__ __forceinline__ int ola_vec_planar(const NvhDevSetup& S, const NvhFra
     const int idx0 = fr.emit_start + 4 * g;
     const int j0 = idx0 - fr.start;
     const bool ov = prev && j0 >= 0 && j0 < fr.ov_len;
-    float4 v = compact_value4(cur + (long long)c * S.block1, w, fr.n, (fr.exec_mask >> c) & 1, idx0);
+    const int sc = MAP ? map_src(fmap, c) : c;
+    float4 v = compact_value4(cur + (long long)sc * S.block1, w, fr.n, (fr.exec_mask >> sc) & 1, idx0);
     if (ov) {
-      const float* pp = prev + (long long)c * S.block1;
+      const float* pp = prev + (long long)sc * S.block1;
       const float4 t4 = prev_full ? *reinterpret_cast<const float4*>(pp + fr.ov_src + j0)
-                                  : compact_value4(pp, wp, fr.ov_n, (fr.ov_exec_mask >> c) & 1, fr.ov_src + j0);
+                                  : compact_value4(pp, wp, fr.ov_n, (fr.ov_exec_mask >> sc) & 1, fr.ov_src + j0);
       v.x = v.x + t4.x; v.y = v.y + t4.y; v.z = v.z + t4.z; v.w = v.w + t4.w;
     }
     if (clip) clip_value4(v, &clipped);
@@ -896,10 +915,10 @@ __device__ __forceinline__ int ola_vec_planar(const NvhDevSetup& S, const NvhFra
   }
   return clipped;
 }
-template <typename PCM>
+template <typename PCM, bool MAP = false>
 __device__ __forceinline__ int ola_sym_planar(const NvhDevSetup& S, const NvhFrame& fr, const float* cur, const float* prev,
                                               const float* __restrict__ w, const float* __restrict__ wp, PCM* out,
-                                              long long plane_stride, int ch, int clip, int tid, int threads) {
+                                              long long plane_stride, int ch, int clip, int tid, int threads, uint32_t fmap = 0u) {
   int clipped = 0;
   const int n = fr.n, n2 = n >> 1;
   const int groups = n >> 4;
@@ -910,8 +929,9 @@ __device__ __forceinline__ int ola_sym_planar(const NvhDevSetup& S, const NvhFra
     const float4 wm = *reinterpret_cast<const float4*>(w + (n2 - 4 - i0));
     const float4 pf = *reinterpret_cast<const float4*>(wp + (n2 + i0));
     const float4 pm = *reinterpret_cast<const float4*>(wp + (n - 4 - i0));
-    const float4 a = *reinterpret_cast<const float4*>(cur + (long long)c * S.block1 + i0);
-    const float4 b = *reinterpret_cast<const float4*>(prev + (long long)c * S.block1 + n2 + i0);
+    const int sc = MAP ? map_src(fmap, c) : c;
+    const float4 a = *reinterpret_cast<const float4*>(cur + (long long)sc * S.block1 + i0);
+    const float4 b = *reinterpret_cast<const float4*>(prev + (long long)sc * S.block1 + n2 + i0);
     float4 v, u;
     ola_sym_mul_add(a, b, wf, wm, pf, pm, v, u);
     if (clip) {
@@ -1005,7 +1025,10 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
               int nosym, const int* __restrict__ list, int emitted, pcm_stride_t<LAYOUT> plane_stride) {
   // (The body is this kernel template's own and not an inlined function template's: as one, it compiles to a different register
   // allocation.)
-  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;
+  constexpr bool PLANAR = nvh_layout_planes(LAYOUT), MONO = LAYOUT == NVH_LAYOUT_MONO, MAP = nvh_layout_mapped(LAYOUT);
+  // the mapped forms: oc output slots, slot j from source channel map_src(fwd, j); the carried tail below is every channel's
+  const NvhChanMap cm = pcm_map_of(plane_stride);
+  const long long pstride = pcm_stride_of(plane_stride);
   // list: the frames paired emission left to this kernel (nvh_launch.hip); emitted: k_synth wrote the PCM of every frame with
   // NVH_EMIT_DONE (such a frame is on the list only as the block that becomes the carried tail)
   const int f = list ? list[blockIdx.x] : (int)blockIdx.x;
@@ -1021,7 +1044,8 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
           compact_value4(plane, wl, fr.n, Bt.chans[fr.chan_off + c].exec, 4 * g);
     }
   }
-  const int total = fr.emit_count * ch;
+  const int oc = MAP ? cm.oc : ch;
+  const int total = fr.emit_count * oc;
   if (total <= 0) return;
   if (emitted && (fr.emit_flags & NVH_EMIT_DONE)) return;
   const float* cur = work + (long long)f * ch * S.block1;
@@ -1030,7 +1054,7 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
   const float* __restrict__ w = S.windows + fr.window_off;
   const float* __restrict__ wp = S.windows + fr.ov_window_off;
   const NvhChan* chans = Bt.chans + fr.chan_off;
-  PCM* out = pcm + fr.out_pos * (PLANAR || MONO ? 1 : ch);
+  PCM* out = pcm + fr.out_pos * (PLANAR || MONO ? 1 : oc);
   int clipped = 0;
   // the carried block (ov_frame == -2) is always stored fully windowed (k_expand_carry); blocks of this batch are compact
   const bool prev_full = fr.ov_frame == -2;
@@ -1038,7 +1062,8 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
   // fast path: everything in units of four samples (true for every frame of a well-formed stream except an
   // EOS-trimmed last one), up to 8 channels
   const bool vec = !PLANAR && fr.n != 0 && ch <= 8 && ((fr.emit_start | fr.emit_count | fr.start | fr.ov_src | fr.ov_len) & 3) == 0 &&
-                   ((fr.out_pos * ch) & 3) == 0;
+                   ((fr.out_pos * oc) & 3) == 0 && (!MAP || (reinterpret_cast<uintptr_t>(pcm) & 15u) == 0);  // (the mapped forms ask
+                                                                                                               // for the aligned base here)
   // steady state: whole first half over the whole second half of an executing predecessor of the same size
   const unsigned all_ch = ch >= 32 ? 0xFFFFFFFFu : ((1u << ch) - 1u);
   if constexpr (PLANAR) {
@@ -1046,14 +1071,18 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
     // output position in whole groups of four), up to 32 channels (the execute flags of the frame record's masks); else the
     // per-sample form below
     const bool pvec = fr.n != 0 && ch <= 32 && ((fr.emit_start | fr.emit_count | fr.start | fr.ov_src | fr.ov_len) & 3) == 0 &&
-                      ((fr.out_pos | plane_stride) & 3) == 0 && (reinterpret_cast<uintptr_t>(pcm) & 15u) == 0;
+                      ((fr.out_pos | pstride) & 3) == 0 && (reinterpret_cast<uintptr_t>(pcm) & 15u) == 0;
     const unsigned pall = ch >= 32 ? 0xFFFFFFFFu : ((1u << ch) - 1u);
     const bool psym = pvec && prev && !prev_full && fr.ov_n == fr.n && fr.start == 0 && fr.emit_start == 0 &&
                       fr.emit_count == (fr.n >> 1) && fr.ov_src == (fr.n >> 1) && fr.ov_len == (fr.n >> 1) &&
                       (fr.exec_mask & pall) == pall && (fr.ov_exec_mask & pall) == pall && !nosym;
     if (psym || pvec) {
-      clipped = psym ? ola_sym_planar<PCM>(S, fr, cur, prev, w, wp, out, plane_stride, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS)
-                     : ola_vec_planar<PCM>(S, fr, cur, prev, prev_full, w, wp, out, plane_stride, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS);
+      if constexpr (MAP)
+        clipped = psym ? ola_sym_planar<PCM, true>(S, fr, cur, prev, w, wp, out, pstride, oc, clip, NVH_OLA_TID, NVH_OLA_THREADS, cm.fwd)
+                       : ola_vec_planar<PCM, true>(S, fr, cur, prev, prev_full, w, wp, out, pstride, oc, clip, NVH_OLA_TID, NVH_OLA_THREADS, cm.fwd);
+      else
+      clipped = psym ? ola_sym_planar<PCM>(S, fr, cur, prev, w, wp, out, pstride, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS)
+                     : ola_vec_planar<PCM>(S, fr, cur, prev, prev_full, w, wp, out, pstride, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS);
       report_clipped(clipped, clipped_flag);
       return;
     }
@@ -1100,6 +1129,28 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
   const bool sym = vec && prev && !prev_full && fr.ov_n == fr.n && fr.start == 0 && fr.emit_start == 0 && fr.emit_count == (fr.n >> 1) &&
                    fr.ov_src == (fr.n >> 1) && fr.ov_len == (fr.n >> 1) && (fr.exec_mask & all_ch) == all_ch &&
                    (fr.ov_exec_mask & all_ch) == all_ch && !nosym;
+  if constexpr (MAP) {
+    // the mapped interleaved forms: the same three vector forms over the oc output slots (a stream of one or two channels, or a
+    // map that keeps one or two, takes ola_sym's lanes; the launch's rows of workgroups serve either)
+    if (sym || vec) {
+      __shared__ __attribute__((aligned(16))) float s_run[2 * 8 * 4 * NVH_OLA_GW];
+      const bool lds = sym && oc > 2 && gridDim.y * NVH_OLA_GW >= (unsigned)(fr.n >> 4);
+#define NVH_OLA_MAP_CASE(N)                                                                                                          \
+  case N:                                                                                                                            \
+    clipped = (N > 2 && lds) ? ola_sym_lds<(N < 3 ? 3 : N), PCM, true>(S, fr, cur, prev, w, wp, out, clip, s_run, cm.fwd)                      \
+              : sym ? ola_sym<N, PCM, true>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS, cm.fwd)                \
+                    : ola_vec<N, PCM, true>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS, cm.fwd);    \
+    break;
+      switch (oc) {
+        NVH_OLA_MAP_CASE(1) NVH_OLA_MAP_CASE(2) NVH_OLA_MAP_CASE(3) NVH_OLA_MAP_CASE(4)
+        NVH_OLA_MAP_CASE(5) NVH_OLA_MAP_CASE(6) NVH_OLA_MAP_CASE(7)
+        default: NVH_OLA_MAP_CASE(8)
+      }
+#undef NVH_OLA_MAP_CASE
+      report_clipped(clipped, clipped_flag);
+      return;
+    }
+  } else {
   if (sym && ch > 2 && gridDim.y * NVH_OLA_GW >= (unsigned)(fr.n >> 4)) {
     // more than two channels: per-(group, channel) lanes, interleave through LDS (the launch gives every frame gridDim.y
     // workgroups of NVH_OLA_GW groups each: nvh_launch.hip)
@@ -1143,26 +1194,28 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
     report_clipped(clipped, clipped_flag);
     return;
   }
+  }
 
   for (int o = NVH_OLA_TID; o < total; o += NVH_OLA_THREADS) {
-    int t = o / ch, c = o - t * ch;
+    int t = o / oc, c = o - t * oc;
     if constexpr (PLANAR) c = o / fr.emit_count, t = o - c * fr.emit_count;  // plane-major: consecutive lanes, one plane
+    const int sc = MAP ? map_src(cm.fwd, c) : c;
     int idx = fr.emit_start + t;
-    const NvhChan cn = chans[c];
+    const NvhChan cn = chans[sc];
     float v;
     if (fr.n == 0) {
       // drained carried tail (StreamDecoder.cs:352-356): the previous block's windowed samples as they are
-      v = prev[(long long)c * S.block1 + fr.ov_src + t];
+      v = prev[(long long)sc * S.block1 + fr.ov_src + t];
     } else {
-      v = compact_value(cur + (long long)c * S.block1, w, fr.n, cn.exec, idx);
+      v = compact_value(cur + (long long)sc * S.block1, w, fr.n, cn.exec, idx);
       int j = idx - fr.start;
       if (prev && j >= 0 && j < fr.ov_len) {  // OverlapBuffers: next[start + j] += previous[prevStart + j]
-        const float* pp = prev + (long long)c * S.block1;
+        const float* pp = prev + (long long)sc * S.block1;
         v = v + (prev_full ? pp[fr.ov_src + j] : compact_value(pp, wp, fr.ov_n, cn.ov_exec, fr.ov_src + j));
       }
     }
     if (clip) v = clip_value(v, &clipped);
-    if constexpr (PLANAR) pcm_store1(out + c * plane_stride + t, v);
+    if constexpr (PLANAR) pcm_store1(out + c * pstride + t, v);
     else pcm_store1(out + o, v);
   }
   report_clipped(clipped, clipped_flag);
@@ -1171,6 +1224,7 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
   template __global__ void k_ola_compact<PCM, LAYOUT>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,    \
                                                       float*, int, int, const int*, int, pcm_stride_t<LAYOUT>);
 NVH_FOR_PCM_TWINS(NVH_OLA_COMPACT_TWINS)
+NVH_FOR_PCM_MAP_TWINS(NVH_OLA_COMPACT_TWINS)
 
 // Expands the compact planes of one frame into the fully windowed block (the carried tail format shared by all
 // overlap kernels).  One workgroup, launched once per batch for its last decoded frame.

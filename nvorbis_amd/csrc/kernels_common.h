@@ -103,6 +103,25 @@ struct NvhSynthArgs {
 // the channels (the mono down-mix: mono_mix below).
 // (plain ints, not an enum: the layout is part of the k_ola_* kernels' signatures, and an unnamed type in a mangled name is quoted)
 constexpr int NVH_LAYOUT_INTERLEAVED = 0, NVH_LAYOUT_PLANAR = 1, NVH_LAYOUT_MONO = 2;
+// ... and the two layouts of a channel map (NvhChanMap below): OC output slots per sample time, slot j holding source channel
+// map[j] -- interleaved (time t of slot j at pcm + t * OC + j) or one plane per slot (pcm + j * plane_stride + t).
+constexpr int NVH_LAYOUT_INTERLEAVED_MAP = 3, NVH_LAYOUT_PLANAR_MAP = 4;
+constexpr bool nvh_layout_mapped(int layout) { return layout == NVH_LAYOUT_INTERLEAVED_MAP || layout == NVH_LAYOUT_PLANAR_MAP; }
+constexpr bool nvh_layout_planes(int layout) { return layout == NVH_LAYOUT_PLANAR || layout == NVH_LAYOUT_PLANAR_MAP; }
+
+// A channel map as the mapped kernels take it: eight nibbles each way (a map is refused on streams of more than eight channels).
+// fwd: nibble j = the source channel of output slot j (j < oc); inv: nibble c = the output slot of source channel c, 0xF = the map
+// drops it.  It is an argument of the mapped forms alone (k_synth8_emit*_map: behind NvhSynthArgs; k_ola_*: the last one) and NOT
+// a member of NvhSynthArgs: a larger struct moves the implicit kernel arguments of every kernel that takes it (see plane_stride).
+struct NvhChanMap {
+  uint32_t fwd, inv;
+  int32_t oc;
+};
+// the k_ola_* planar mapped forms' last argument: the planes' stride and the map
+struct NvhStrideMap {
+  long long plane_stride;
+  NvhChanMap map;
+};
 
 // The forms of PCM the emitting kernels write: M(sample type, layout, suffix of the kernels' names).  Every such kernel
 // exists once per entry, written by its own file through this list and declared through it in nvh_internal.h; the host picks one
@@ -110,13 +129,35 @@ constexpr int NVH_LAYOUT_INTERLEAVED = 0, NVH_LAYOUT_PLANAR = 1, NVH_LAYOUT_MONO
 #define NVH_FOR_PCM_TWINS(M)                                                                                             \
   M(float, NVH_LAYOUT_INTERLEAVED, ) M(int16_t, NVH_LAYOUT_INTERLEAVED, _s16) M(float, NVH_LAYOUT_PLANAR, _planar)       \
   M(int16_t, NVH_LAYOUT_PLANAR, _s16_planar) M(float, NVH_LAYOUT_MONO, _mono) M(int16_t, NVH_LAYOUT_MONO, _s16_mono)
+// The mapped forms, of the families that have them: k_synth8_emit (the steady path of three to eight channels) and the three
+// k_ola_* templates.  The narrow families (k_synth_emit, k_synth_group2 / 4) have none: a mono or stereo stream with a map that is
+// not the identity runs without paired emission (nvh_launch.hip).
+#define NVH_FOR_PCM_MAP_TWINS(M)                                                                          \
+  M(float, NVH_LAYOUT_INTERLEAVED_MAP, _map) M(int16_t, NVH_LAYOUT_INTERLEAVED_MAP, _s16_map)             \
+  M(float, NVH_LAYOUT_PLANAR_MAP, _planar_map) M(int16_t, NVH_LAYOUT_PLANAR_MAP, _s16_planar_map)
 
 #ifdef __HIPCC__
 // The last argument of the k_ola_* kernels: the samples between the channels' planes, of the channel-planar forms only.  The
 // interleaved and the mono forms take an empty struct in its place, which leaves their kernel-argument layout what it was without the argument
 // (k_ola_compact reads the grid's shape from the implicit arguments behind it).
 struct NvhNoStride {};
-template <int LAYOUT> using pcm_stride_t = std::conditional_t<LAYOUT == NVH_LAYOUT_PLANAR, long long, NvhNoStride>;
+// The mapped forms take the map there (NvhChanMap), the planar mapped forms the stride and the map (NvhStrideMap).
+template <int LAYOUT> using pcm_stride_t =
+    std::conditional_t<LAYOUT == NVH_LAYOUT_PLANAR, long long,
+    std::conditional_t<LAYOUT == NVH_LAYOUT_INTERLEAVED_MAP, NvhChanMap,
+    std::conditional_t<LAYOUT == NVH_LAYOUT_PLANAR_MAP, NvhStrideMap, NvhNoStride>>>;
+// the stride and the map out of that argument (0 / the empty map where the form has none)
+__device__ __forceinline__ long long pcm_stride_of(long long s) { return s; }
+__device__ __forceinline__ long long pcm_stride_of(const NvhStrideMap& s) { return s.plane_stride; }
+__device__ __forceinline__ long long pcm_stride_of(const NvhChanMap&) { return 0; }
+__device__ __forceinline__ long long pcm_stride_of(const NvhNoStride&) { return 0; }
+__device__ __forceinline__ NvhChanMap pcm_map_of(const NvhChanMap& m) { return m; }
+__device__ __forceinline__ NvhChanMap pcm_map_of(const NvhStrideMap& s) { return s.map; }
+__device__ __forceinline__ NvhChanMap pcm_map_of(long long) { return NvhChanMap{0u, 0u, 0}; }
+__device__ __forceinline__ NvhChanMap pcm_map_of(const NvhNoStride&) { return NvhChanMap{0u, 0u, 0}; }
+// source channel of output slot j / output slot of source channel c (15: dropped)
+__device__ __forceinline__ int map_src(uint32_t fwd, int j) { return (int)((fwd >> (4 * j)) & 15u); }
+__device__ __forceinline__ int map_slot(uint32_t inv, int c) { return (int)((inv >> (4 * c)) & 15u); }
 
 // PCM leaves the chip (a copy engine or the gather reads it next) and no kernel reads it again: streaming stores (`nt`), which do
 // not displace what the kernels do re-read -- the odd frames' planes, the slabs the odd launch touched for the even one -- from

@@ -966,16 +966,20 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
 // instead of as a launch of its own (k_ola_compact: 42 us per 2048 six-channel frames), and half the planes are read from L2.
 template <int NT, typename PCM = float, int LAYOUT = NVH_LAYOUT_INTERLEAVED>
 __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run, int n, int nch, unsigned frame, unsigned ef,
-                                            unsigned exec_mask, int tid) {
+                                            unsigned exec_mask, int tid, const NvhChanMap cm = NvhChanMap{0u, 0u, 0}) {
   // One round per overlap: the rows of ALL groups fit the dead slices (2 x nch x n/4 floats: 48 KB for six channels at 4096),
   // so an overlap costs two barriers, and a lane's K tasks have their loads in flight together -- with one run of 64 groups
   // per round (k_ola_compact's shape) the eight rounds' round trips stood one behind the other: 87 -> 141 us for the pair of
   // launches on C4, more than the k_ola_compact launch they replace.
-  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;
+  constexpr bool PLANAR = nvh_layout_planes(LAYOUT), MONO = LAYOUT == NVH_LAYOUT_MONO, MAP = nvh_layout_mapped(LAYOUT);
   constexpr int K = 3;
   const int half = n >> 1, groups = n >> 4, gsh = 31 - __clz(groups), RUN = n >> 2;  // RUN = 4 * groups
-  const unsigned ch_magic = (unsigned)((0x100000000ull + (unsigned)nch - 1) / (unsigned)nch);
-  const int total = groups * nch;
+  // The mapped forms (kernels_common.h: NvhChanMap): the tasks run over the oc OUTPUT slots -- a task's row, plane and position
+  // in the interleaved sample are its slot's, its loads come from the slot's source channel, and a channel the map drops is
+  // neither read nor clipped.  Elsewhere oc is the channel count and slot and source are one.
+  const int oc = MAP ? cm.oc : nch;
+  const unsigned ch_magic = (unsigned)((0x100000000ull + (unsigned)oc - 1) / (unsigned)oc);
+  const int total = groups * oc;
   int clipped = 0;
   for (int ov = 0; ov < 2; ++ov) {
     if (ov == 0 ? !(ef & NVH_EMIT_SELF) : !(ef & NVH_EMIT_NEXT)) continue;  // uniform
@@ -985,9 +989,9 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
     const float* prev = from_carry ? A.carry : A.work + (long long)(frame + ov - 1) * nch * A.block1;  // the earlier block
     const float* __restrict__ w = A.windows + fr->window_off;
     const float* __restrict__ wp = A.windows + fr->ov_window_off;
-    PCM* out = reinterpret_cast<PCM*>(A.pcm) + fr->out_pos * (PLANAR || MONO ? 1 : nch);
+    PCM* out = reinterpret_cast<PCM*>(A.pcm) + fr->out_pos * (PLANAR || MONO ? 1 : oc);
     float* sF = s_run;
-    float* sM = s_run + nch * RUN;
+    float* sM = s_run + oc * RUN;
     for (int t0 = tid; t0 < total; t0 += K * NT) {
       float4 wf[K], wm[K], pf[K], pm[K], a[K], b[K], bm[K];
       int cc[K], gl[K];
@@ -997,16 +1001,17 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
         cc[k] = t >> gsh;
         gl[k] = t - (cc[k] << gsh);
         const int i0 = 4 * gl[k];
+        const int sc = MAP ? map_src(cm.fwd, cc[k]) : cc[k];
         wf[k] = *reinterpret_cast<const float4*>(w + i0);
         wm[k] = *reinterpret_cast<const float4*>(w + (half - 4 - i0));
-        a[k] = *reinterpret_cast<const float4*>(cur + (long long)cc[k] * A.block1 + i0);
+        a[k] = *reinterpret_cast<const float4*>(cur + (long long)sc * A.block1 + i0);
         if (from_carry) {  // time order, already windowed: samples half + i0 .. and n - 4 - i0 ..
-          b[k] = *reinterpret_cast<const float4*>(prev + (long long)cc[k] * A.block1 + half + i0);
-          bm[k] = *reinterpret_cast<const float4*>(prev + (long long)cc[k] * A.block1 + (n - 4 - i0));
+          b[k] = *reinterpret_cast<const float4*>(prev + (long long)sc * A.block1 + half + i0);
+          bm[k] = *reinterpret_cast<const float4*>(prev + (long long)sc * A.block1 + (n - 4 - i0));
         } else {
           pf[k] = *reinterpret_cast<const float4*>(wp + (half + i0));
           pm[k] = *reinterpret_cast<const float4*>(wp + (n - 4 - i0));
-          b[k] = *reinterpret_cast<const float4*>(prev + (long long)cc[k] * A.block1 + half + i0);
+          b[k] = *reinterpret_cast<const float4*>(prev + (long long)sc * A.block1 + half + i0);
         }
       }
 #pragma unroll
@@ -1065,7 +1070,7 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
     // the forward rows hold sample times [0, n/4), the mirrored rows [n/4, n/2): together the frame's n/2 samples in time order
     const int nvec = total;  // 16-byte vectors per half: n/4 sample times x nch channels / 4
     pcm4_t<PCM>* oF = reinterpret_cast<pcm4_t<PCM>*>(out);
-    pcm4_t<PCM>* oM = reinterpret_cast<pcm4_t<PCM>*>(out + (long long)(half >> 1) * nch);
+    pcm4_t<PCM>* oM = reinterpret_cast<pcm4_t<PCM>*>(out + (long long)(half >> 1) * oc);
     for (int j = tid; j < 2 * nvec; j += NT) {
       const bool mir = j >= nvec;
       const int jj = mir ? j - nvec : j;
@@ -1074,7 +1079,8 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const unsigned idx = 4u * (unsigned)jj + (unsigned)k;  // position in the half's interleaved floats
-        const unsigned tt = __umulhi(idx, ch_magic), c = idx - tt * (unsigned)nch;  // idx < 2^16, nch <= 8: exact
+        // (idx < 2^16, oc <= 8: exact -- but for a divisor of 1 the magic number is 2^32, which does not fit: a map may keep ONE channel)
+        const unsigned tt = MAP && oc == 1 ? idx : __umulhi(idx, ch_magic), c = idx - tt * (unsigned)oc;
         float x = sr[c * (unsigned)RUN + tt];
         if (A.clip) x = clip_value(x, &clipped);
         e[k] = x;
@@ -1139,8 +1145,13 @@ __device__ __forceinline__ void imdct_keep_quarters(const float* X, float* slice
 }
 
 template <int NT, int CH, typename PCM = float, int LAYOUT = NVH_LAYOUT_INTERLEAVED>
-__device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float* smem, int n, unsigned frame, int tid) {
-  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;
+__device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float* smem, int n, unsigned frame, int tid,
+                                                   const NvhChanMap cm = NvhChanMap{0u, 0u, 0}) {
+  constexpr bool PLANAR = nvh_layout_planes(LAYOUT), MONO = LAYOUT == NVH_LAYOUT_MONO, MAP = nvh_layout_mapped(LAYOUT);
+  // The mapped forms work from the INVERSE map (kernels_common.h: NvhChanMap): the loops below stay over the CH source channels
+  // at compile time -- the lane's registers are never indexed by a run-time channel -- and channel c asks for its output slot
+  // (uniform, a scalar register); a channel without one is neither read nor clipped nor stored.
+  auto slot_of = [&](int c) { return MAP ? map_slot(cm.inv, c) : c; };
   const int half = n >> 1, groups = n >> 4, slice = half + (n >> 4);
   const NvhFrame* fs = A.frames + frame;
   const unsigned w_self = fs[0].window_off, wp_self = fs[0].ov_window_off, w_next = fs[1].window_off, wp_next = fs[1].ov_window_off;
@@ -1158,10 +1169,18 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
     const float* nb = nx ? A.work + (long long)(frame + 1) * CH * A.block1 + i0 : A.work + (long long)(frame - 1) * CH * A.block1 + half + i0;
     float4 q[CH];
 #pragma unroll
-    for (int c = 0; c < CH; ++c) q[c] = stream_load4(nb + (long long)c * A.block1);  // read once, by this lane
+    for (int c = 0; c < CH; ++c) {
+      if (MAP && slot_of(c) == 15) q[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+      else q[c] = stream_load4(nb + (long long)c * A.block1);  // read once, by this lane
+    }
     float fwd[4 * CH], mir[4 * CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
+      if (MAP && slot_of(c) == 15) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) fwd[k * CH + c] = mir[k * CH + c] = 0.f;
+        continue;
+      }
       const float* own = smem + c * slice;
       const float4 o = *reinterpret_cast<const float4*>(own + (nx ? (half >> 1) : 0) + i0);  // NEXT: B(this), SELF: A(this)
       const float4 a = nx ? q[c] : o, b = nx ? o : q[c];
@@ -1186,7 +1205,8 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
       PCM* base = reinterpret_cast<PCM*>(A.pcm) + (nx ? o_next : o_self);
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
-        pcm4_t<PCM>* p = reinterpret_cast<pcm4_t<PCM>*>(base + (long long)c * A.plane_stride);
+        if (MAP && slot_of(c) == 15) continue;
+        pcm4_t<PCM>* p = reinterpret_cast<pcm4_t<PCM>*>(base + (long long)slot_of(c) * A.plane_stride);
         pcm_store4(p + g, fwd[c], fwd[CH + c], fwd[2 * CH + c], fwd[3 * CH + c]);
         pcm_store4(p + ((n >> 3) - 1 - g), mir[c], mir[CH + c], mir[2 * CH + c], mir[3 * CH + c]);
       }
@@ -1199,6 +1219,49 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
       const float4 mf = mono_mix<CH>(fwd, A.clip, &clipped), mm = mono_mix<CH>(mir, A.clip, &clipped);
       pcm_store4(p + g, mf.x, mf.y, mf.z, mf.w);
       pcm_store4(p + ((n >> 3) - 1 - g), mm.x, mm.y, mm.z, mm.w);
+      return;
+    }
+    if constexpr (MAP) {
+      // interleaved, mapped: the wavefront's 64 tasks cover ONE contiguous run of 256 sample times x oc slots per half, so the
+      // 64 x CH transposition below becomes 64 x oc with a channel's row chosen by its slot -- channel c's four sample times go
+      // as one vector to row slot_of(c) (the own-quarter piece of slice slot_of(c): 256 floats, these 64 tasks' own; oc <= CH),
+      // and the run leaves as oc fully coalesced streaming stores per half, each lane gathering its four samples (float e of the
+      // run: time e / oc, slot e % oc).  A run-time oc: the loops over it are not unrolled, which keeps the registers of the
+      // un-mapped form.  (Whole wavefronts only: synth_body keeps blocks below 1024 on synth_emit8.)
+      const int OC = cm.oc;
+      const unsigned oc_magic = (unsigned)((0x100000000ull + (unsigned)OC - 1) / (unsigned)OC);
+      pcm4_t<PCM>* out = reinterpret_cast<pcm4_t<PCM>*>(reinterpret_cast<PCM*>(A.pcm) + (nx ? o_next : o_self) * OC);
+      const int l = tid & 63, g0 = g - l;
+      float* piece0 = smem + (nx ? (half >> 1) : 0) + 4 * g0;
+      pcm4_t<PCM>* rf = out + (long long)g0 * OC;                         // the forward half: groups g0 .. g0 + 63 ascending
+      pcm4_t<PCM>* rm = out + (long long)((n >> 3) - 1 - (g0 + 63)) * OC;  // the mirrored half: the same groups, descending
+      auto leave = [&](pcm4_t<PCM>* r) {
+        for (int k = 0; k < OC; ++k) {
+          float e[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const unsigned idx = 4u * (unsigned)(k * 64 + l) + (unsigned)i;  // position in the run's interleaved floats
+            // (idx < 2^11, OC <= 8: exact; OC == 1: the magic number 2^32 does not fit, and the quotient is idx)
+            const unsigned tt = OC == 1 ? idx : __umulhi(idx, oc_magic), sl = idx - tt * (unsigned)OC;
+            e[i] = piece0[sl * (unsigned)slice + tt];
+          }
+          pcm_store4(r + k * 64 + l, e[0], e[1], e[2], e[3]);
+        }
+      };
+      wave_sync();  // every lane's own-quarter reads are through
+#pragma unroll
+      for (int c = 0; c < CH; ++c)
+        if (slot_of(c) != 15)
+          *reinterpret_cast<float4*>(piece0 + slot_of(c) * slice + 4 * l) = make_float4(fwd[c], fwd[CH + c], fwd[2 * CH + c], fwd[3 * CH + c]);
+      wave_sync();
+      leave(rf);
+      wave_sync();
+#pragma unroll
+      for (int c = 0; c < CH; ++c)
+        if (slot_of(c) != 15)
+          *reinterpret_cast<float4*>(piece0 + slot_of(c) * slice + 4 * (63 - l)) = make_float4(mir[c], mir[CH + c], mir[2 * CH + c], mir[3 * CH + c]);
+      wave_sync();
+      leave(rm);
       return;
     }
     pcm4_t<PCM>* out = reinterpret_cast<pcm4_t<PCM>*>(reinterpret_cast<PCM*>(A.pcm) + (nx ? o_next : o_self) * CH);
@@ -1426,7 +1489,8 @@ __device__ __forceinline__ void synth_frame_spectrum(const NvhSynthArgs& A, cons
 // emission.  Three instantiations, so that the launches that never emit keep the registers of the kernel that cannot (62 instead
 // of 64 VGPRs at the 64-VGPR cap: 24.4 against 25.1 us for 4096 frames).
 template <int NT, int MAXCH, int MODE = 0, bool GENERAL = false, typename PCM = float, int LAYOUT = NVH_LAYOUT_INTERLEAVED>
-__device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NVH_DBG_PARAMS) {
+__device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NVH_DBG_PARAMS,
+                                           const NvhChanMap cm = NvhChanMap{0u, 0u, 0}) {  // cm: the mapped forms' channel map
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
 #ifdef NVH_ABL_EMPTY0
   if (A.f0 >= 0) return;  // (ablation build: the launch alone)
@@ -1538,7 +1602,8 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
   // words are all taken); the direct form (synth_emit8_direct) takes the frames in the middle of the steady state
   unsigned ef8 = 0u;
   if constexpr (MAXCH > 2 && MODE >= 2) ef8 = A.pcm != nullptr ? A.frames[frame].emit_flags : 0u;  // uniform
-  const bool direct8 = MAXCH > 2 && MODE >= 2 && n <= 4096 &&
+  // (the interleaved mapped form's direct emission transposes per whole wavefront: blocks from 1024)
+  const bool direct8 = MAXCH > 2 && MODE >= 2 && n <= 4096 && (LAYOUT != NVH_LAYOUT_INTERLEAVED_MAP || n >= 1024) &&
                        (ef8 & (NVH_EMIT_SELF | NVH_EMIT_NEXT | NVH_EMIT_SELF_CARRY | NVH_EMIT_CARRY_OUT)) == (NVH_EMIT_SELF | NVH_EMIT_NEXT);
   if (MAXCH <= 2 && MODE >= 2 && (emit_self || emit_next)) {
     if constexpr (MAXCH <= 2 && MODE >= 2)
@@ -1629,21 +1694,21 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
     if (direct8) {
       __syncthreads();  // every channel's own quarters are in its slice
       switch (nch) {
-        case 1: synth_emit8_direct<NT, 1, PCM, LAYOUT>(A, smem, n, frame, tid); break;  // (mono / stereo land here with blocks beyond 2048)
-        case 2: synth_emit8_direct<NT, 2, PCM, LAYOUT>(A, smem, n, frame, tid); break;
-        case 3: synth_emit8_direct<NT, 3, PCM, LAYOUT>(A, smem, n, frame, tid); break;
-        case 4: synth_emit8_direct<NT, 4, PCM, LAYOUT>(A, smem, n, frame, tid); break;
-        case 5: synth_emit8_direct<NT, 5, PCM, LAYOUT>(A, smem, n, frame, tid); break;
-        case 6: synth_emit8_direct<NT, 6, PCM, LAYOUT>(A, smem, n, frame, tid); break;
-        case 7: synth_emit8_direct<NT, 7, PCM, LAYOUT>(A, smem, n, frame, tid); break;
-        case 8: synth_emit8_direct<NT, 8, PCM, LAYOUT>(A, smem, n, frame, tid); break;
+        case 1: synth_emit8_direct<NT, 1, PCM, LAYOUT>(A, smem, n, frame, tid, cm); break;  // (mono / stereo land here with blocks beyond 2048)
+        case 2: synth_emit8_direct<NT, 2, PCM, LAYOUT>(A, smem, n, frame, tid, cm); break;
+        case 3: synth_emit8_direct<NT, 3, PCM, LAYOUT>(A, smem, n, frame, tid, cm); break;
+        case 4: synth_emit8_direct<NT, 4, PCM, LAYOUT>(A, smem, n, frame, tid, cm); break;
+        case 5: synth_emit8_direct<NT, 5, PCM, LAYOUT>(A, smem, n, frame, tid, cm); break;
+        case 6: synth_emit8_direct<NT, 6, PCM, LAYOUT>(A, smem, n, frame, tid, cm); break;
+        case 7: synth_emit8_direct<NT, 7, PCM, LAYOUT>(A, smem, n, frame, tid, cm); break;
+        case 8: synth_emit8_direct<NT, 8, PCM, LAYOUT>(A, smem, n, frame, tid, cm); break;
         default: __builtin_trap();
       }
     } else
     if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT | NVH_EMIT_CARRY_OUT)) {
       __syncthreads();
       if ((ef & NVH_EMIT_CARRY_OUT) && A.carry_out) synth_carry_out8<NT>(A, planes, n, nch, exec_mask, A.frames[frame].window_off, tid);
-      if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT)) synth_emit8<NT, PCM, LAYOUT>(A, smem, n, nch, frame, ef, exec_mask, tid);
+      if (ef & (NVH_EMIT_SELF | NVH_EMIT_NEXT)) synth_emit8<NT, PCM, LAYOUT>(A, smem, n, nch, frame, ef, exec_mask, tid, cm);
     }
   }
   if constexpr (MAXCH > 2 && MODE < 2) {
@@ -2193,6 +2258,14 @@ k_synth8_g(NvhSynthArgs A NVH_DBG_PARAMS) {
     synth_body<512, NVH_SLAB_MAX_CH, 2, false, PCM, LAYOUT>(A, smem NVH_DBG_ARGS);         \
   }
 NVH_FOR_PCM_TWINS(NVH_SYNTH8_EMIT)
+// ... and its mapped forms (kernels_common.h: NVH_FOR_PCM_MAP_TWINS): the channel map is an argument of their own
+#define NVH_SYNTH8_EMIT_MAP(PCM, LAYOUT, SFX)                                              \
+  extern "C" __global__ void __launch_bounds__(512)                                        \
+  k_synth8_emit##SFX(NvhSynthArgs A, NvhChanMap M NVH_DBG_PARAMS) {                        \
+    extern __shared__ __attribute__((aligned(16))) float smem[];                           \
+    synth_body<512, NVH_SLAB_MAX_CH, 2, false, PCM, LAYOUT>(A, smem NVH_DBG_ARGS, M);      \
+  }
+NVH_FOR_PCM_MAP_TWINS(NVH_SYNTH8_EMIT_MAP)
 
 // frame groups: two frames per workgroup (four wavefronts: one per (frame, channel)), and four frames per workgroup (eight
 // wavefronts); LDS, not registers, decides the residency

@@ -3,6 +3,8 @@
 // entry point fails with NVH_ERR_NO_GPU / NVH_ERR_DEVICE.
 #include "nvh_internal.h"
 
+#include <bitset>
+
 thread_local int g_last_hip_error = 0;
 
 const NvhToggles& nvh_toggles() {
@@ -579,7 +581,8 @@ extern "C" int nvh_stream_pending(const nvh_stream* s, int* frames, int64_t* pcm
 // Channel-planar PCM (the _planar calls: channel c's samples at base + c * plane_stride, counts per channel) is staged as
 // [C, n4] planes (n4: the batch's samples per channel rounded up to whole groups of four, so that the emission's vector stores
 // run) and read back as one 2-D copy; one plain copy when the planes are contiguous.  The mono mix (the _mix calls) is the
-// one-plane case: n samples, staged and read back like interleaved PCM of one channel.
+// one-plane case: n samples, staged and read back like interleaved PCM of one channel.  A channel map (the _map calls) is the
+// out_channels case of either layout: n * out_channels interleaved samples, or out_channels planes.
 static int64_t planar_stage_stride(int64_t n) { return (n + 3) & ~(int64_t)3; }
 static int64_t planar_launch_stride(int64_t plane_stride) { return plane_stride > 0 ? plane_stride : 4; }  // (0 only with no samples)
 
@@ -589,10 +592,10 @@ struct PcmShape {
   int64_t len, stage, stride;
   int planes;
   PcmShape(const PcmOut& out, int64_t n, int ch)
-      : len(out.planar() || out.mono() ? n : n * ch), stage(out.planar() ? planar_stage_stride(n) : len),
-        stride(out.planar() ? out.plane_stride : len), planes(out.planar() ? ch : 1) {}
+      : len(out.planar() || out.mono() ? n : n * out.out_channels(ch)), stage(out.planar() ? planar_stage_stride(n) : len),
+        stride(out.planar() ? out.plane_stride : len), planes(out.planar() ? out.out_channels(ch) : 1) {}
   size_t stage_bytes(size_t sb) const { return (size_t)(stage > 0 ? stage : 1) * (size_t)planes * sb; }
-  PcmOut staged(const PcmOut& out) const { return {out.format, out.planar() ? planar_launch_stride(stage) : 0, out.mix}; }
+  PcmOut staged(const PcmOut& out) const { return {out.format, out.planar() ? planar_launch_stride(stage) : 0, out.mix, out.map}; }
 };
 
 // `n` samples of each of `planes` planes from device planes at stride `src_stride` to host planes at stride `dst_stride`
@@ -795,6 +798,99 @@ extern "C" int nvh_stream_synth_begin_mix(nvh_stream* s, int format, int mix, vo
   });
 }
 
+// The *_map forms: the *_pcm / *_planar calls with a channel map (include/nvorbis_hip.h: output slot j = source channel map[j]).
+// The Vorbis-to-WAVE permutations (Vorbis I 4.3.9 against the dwChannelMask bit order; the derivation is in the public header).
+extern "C" int nvh_channel_map_wave(int channels, int32_t* map) {
+  static const int8_t kWave[8][8] = {{0}, {0, 1}, {0, 2, 1}, {0, 1, 2, 3}, {0, 2, 1, 3, 4}, {0, 2, 1, 5, 3, 4},
+                                     {0, 2, 1, 6, 5, 3, 4}, {0, 2, 1, 7, 5, 6, 3, 4}};
+  if (channels < 1 || channels > 8 || !map) return NVH_ERR_ARGUMENT;
+  for (int j = 0; j < channels; j++) map[j] = kWave[channels - 1][j];
+  return NVH_OK;
+}
+
+// Checks a map against the stream and packs it into `out` (kernels_common.h: NvhChanMap).  The identity map leaves `out`
+// un-mapped: the call is then its un-mapped twin.  NVH_ERR_ARGUMENT: no stream, no map, a count outside [1, channels], an entry
+// outside [0, channels) or named twice; NVH_ERR_UNSUPPORTED: any other map on a stream of more than eight channels (eight nibbles).
+static int map_out(const nvh_stream* s, const int32_t* map, int out_channels, PcmOut* out) {
+  if (!s || !map) return NVH_ERR_ARGUMENT;
+  const int ch = s->setup.channels;
+  if (out_channels < 1 || out_channels > ch) return NVH_ERR_ARGUMENT;
+  std::bitset<256> seen;  // (a Vorbis stream has at most 255 channels)
+  bool identity = out_channels == ch;
+  for (int j = 0; j < out_channels; j++) {
+    if (map[j] < 0 || map[j] >= ch || seen[(size_t)map[j]]) return NVH_ERR_ARGUMENT;
+    seen[(size_t)map[j]] = true;
+    identity = identity && map[j] == j;
+  }
+  if (identity) return NVH_OK;
+  if (ch > 8) return NVH_ERR_UNSUPPORTED;
+  NvhChanMap cm{0u, 0xFFFFFFFFu, out_channels};
+  for (int j = 0; j < out_channels; j++) {
+    cm.fwd |= (uint32_t)map[j] << (4 * j);
+    cm.inv = (cm.inv & ~(0xFu << (4 * map[j]))) | ((uint32_t)j << (4 * map[j]));
+  }
+  out->map = cm;
+  return NVH_OK;
+}
+
+extern "C" int nvh_stream_synth_map(nvh_stream* s, int format, const int32_t* map, int out_channels, void* pcm_host, void* d_pcm,
+                                    int64_t capacity, int64_t* written) {
+  return nvh_guard([&]() -> int {
+    PcmOut out{format, 0};
+    const int rc = map_out(s, map, out_channels, &out);
+    if (rc != NVH_OK) return rc;
+    if (!out.mapped()) return nvh_stream_synth_pcm(s, format, pcm_host, d_pcm, capacity, written);
+    if ((pcm_host && d_pcm) || !PcmOut::format_ok(format) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
+    if (written) *written = 0;
+    if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
+    if (capacity < PcmShape(out, s->pending.pcm_samples, s->setup.channels).len) return NVH_ERR_ARGUMENT;
+    return stream_synth(s, out, pcm_host, d_pcm, capacity, written);
+  });
+}
+
+extern "C" int nvh_stream_synth_begin_map(nvh_stream* s, int format, const int32_t* map, int out_channels, void* pcm_host,
+                                          int64_t capacity, int64_t* expected) {
+  return nvh_guard([&]() -> int {
+    PcmOut out{format, 0};
+    const int rc = map_out(s, map, out_channels, &out);
+    if (rc != NVH_OK) return rc;
+    if (!out.mapped()) return nvh_stream_synth_begin_pcm(s, format, pcm_host, capacity, expected);
+    if (!pcm_host || !PcmOut::format_ok(format)) return NVH_ERR_ARGUMENT;
+    if (expected) *expected = 0;
+    if (capacity < PcmShape(out, s->pending.pcm_samples, s->setup.channels).len) return NVH_ERR_ARGUMENT;
+    return stream_synth_begin(s, out, pcm_host, capacity, expected);
+  });
+}
+
+extern "C" int nvh_stream_synth_planar_map(nvh_stream* s, int format, const int32_t* map, int out_channels, void* pcm_host,
+                                           void* d_pcm, int64_t plane_stride, int64_t* written) {
+  return nvh_guard([&]() -> int {
+    PcmOut out{format, planar_launch_stride(plane_stride)};
+    const int rc = map_out(s, map, out_channels, &out);
+    if (rc != NVH_OK) return rc;
+    if (!out.mapped()) return nvh_stream_synth_planar(s, format, pcm_host, d_pcm, plane_stride, written);
+    if ((pcm_host && d_pcm) || !PcmOut::format_ok(format) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
+    if (written) *written = 0;
+    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
+    if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
+    return stream_synth(s, out, pcm_host, d_pcm, plane_stride, written);
+  });
+}
+
+extern "C" int nvh_stream_synth_begin_planar_map(nvh_stream* s, int format, const int32_t* map, int out_channels, void* pcm_host,
+                                                 int64_t plane_stride, int64_t* expected) {
+  return nvh_guard([&]() -> int {
+    PcmOut out{format, planar_launch_stride(plane_stride)};
+    const int rc = map_out(s, map, out_channels, &out);
+    if (rc != NVH_OK) return rc;
+    if (!out.mapped()) return nvh_stream_synth_begin_planar(s, format, pcm_host, plane_stride, expected);
+    if (!pcm_host || !PcmOut::format_ok(format)) return NVH_ERR_ARGUMENT;
+    if (expected) *expected = 0;
+    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
+    return stream_synth_begin(s, out, pcm_host, plane_stride, expected);
+  });
+}
+
 extern "C" int nvh_stream_synth_end(nvh_stream* s, int64_t* written) {
   return nvh_guard([&]() -> int {
     if (!s) return NVH_ERR_ARGUMENT;
@@ -927,6 +1023,20 @@ extern "C" int nvh_batch_synth_mix(nvh_batch* b, int format, int mix, void* d_pc
 
 extern "C" int nvh_batch_synth_planar(nvh_batch* b, int format, void* d_pcm, int64_t plane_stride) {
   return batch_synth(b, PcmOut{format, planar_launch_stride(plane_stride)}, d_pcm, plane_stride);
+}
+
+// ... and with a channel map (the identity map leaves `out` un-mapped: the calls above)
+extern "C" int nvh_batch_synth_map(nvh_batch* b, int format, const int32_t* map, int out_channels, void* d_pcm, int64_t capacity) {
+  PcmOut out{format, 0};
+  const int rc = map_out(b ? b->s : nullptr, map, out_channels, &out);
+  return rc != NVH_OK ? rc : batch_synth(b, out, d_pcm, capacity);
+}
+
+extern "C" int nvh_batch_synth_planar_map(nvh_batch* b, int format, const int32_t* map, int out_channels, void* d_pcm,
+                                          int64_t plane_stride) {
+  PcmOut out{format, planar_launch_stride(plane_stride)};
+  const int rc = map_out(b ? b->s : nullptr, map, out_channels, &out);
+  return rc != NVH_OK ? rc : batch_synth(b, out, d_pcm, plane_stride);
 }
 
 extern "C" int nvh_batch_time(nvh_batch* b, float* d_pcm, int64_t capacity, int iters, float* total_ms,

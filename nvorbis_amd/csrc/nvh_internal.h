@@ -76,6 +76,9 @@ __global__ void k_synth8_g(NvhSynthArgs A NVH_DBG_PARAMS);    // + the general b
   __global__ void k_synth_group2##SFX(NvhSynthArgs A NVH_DBG_PARAMS); /* frame groups: two / four frames per workgroup */         \
   __global__ void k_synth_group4##SFX(NvhSynthArgs A NVH_DBG_PARAMS);
 NVH_FOR_PCM_TWINS(NVH_SYNTH_DECL)
+// ... the mapped forms (kernels_common.h: NVH_FOR_PCM_MAP_TWINS) of the wide emitting kernel alone, the map an argument of theirs
+#define NVH_SYNTH_MAP_DECL(PCM, LAYOUT, SFX) __global__ void k_synth8_emit##SFX(NvhSynthArgs A, NvhChanMap M NVH_DBG_PARAMS);
+NVH_FOR_PCM_MAP_TWINS(NVH_SYNTH_MAP_DECL)
 __global__ void k_window_apply(float* buf, const float* window, int n, long long stride, int batch);
 __global__ void k_overlap_buffers(const float* previous, float* next, int prev_start, int len, int next_start, int channels,
                                   long long plane_stride);
@@ -109,6 +112,7 @@ __global__ void k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* work, const
   extern template __global__ void k_ola_emit_seq<PCM, LAYOUT>(NvhDevSetup, NvhDevBatch, float*, const float*, PCM*, int, int*,       \
                                                               pcm_stride_t<LAYOUT>);
 NVH_FOR_PCM_TWINS(NVH_OLA_DECL)
+NVH_FOR_PCM_MAP_TWINS(NVH_OLA_DECL)
 
 extern thread_local int g_last_hip_error;
 
@@ -321,7 +325,7 @@ struct nvh_batch {
   bool sequential_ola = false;
   int last_decoded = -1;  // last frame with n != 0 (its block becomes the next carried tail)
   const char* slot_name[4] = {"-", "-", "-", "-"};  // kernels behind the four timing slots of the last launch
-  std::string slot_name_buf[4];  // storage of the names built with a twin's suffix (_s16, _planar, _s16_planar, _mono, _s16_mono)
+  std::string slot_name_buf[4];  // storage of the names built with a twin's suffix (_s16, _planar, _s16_planar, _mono, _s16_mono, *_map)
   bool links_ok = false;  // op_link chains usable (every frame has < 32767 ops): k_spectrum's chain walk
   int max_ops = 0, max_ent = 0, max_pass = 0;  // largest per-frame op / entry / pass slice (LDS staging capacity of k_spectrum)
   int max_vecs = 0;     // GPU-parsed batch in slab mode: its largest slab, as k_parse reported it
@@ -459,21 +463,30 @@ int batch_upload(nvh_stream* s, nvh_batch* b);                   // nvh_launch.h
 // A PCM destination: the sample format (NVH_PCM_*: float, or int16_t for the kernels' _s16 twins) and the layout -- interleaved
 // (plane_stride == 0), or channel-planar with channel c's samples at base + c * plane_stride (the _planar twins) -- and the mix
 // (NVH_MIX_*): NVH_MIX_MONO is ONE plane holding the mean of the channels (the _mono twins; never together with a plane stride)
+// -- and the channel map (the *_map calls; never together with a mix): map.oc output slots, interleaved or one plane each (the
+// _map twins).  map.oc == 0: no map.  The identity map is no map (pcm_map below), so the un-mapped kernels run.
 struct PcmOut {
   int format = NVH_PCM_F32;
   int64_t plane_stride = 0;
   int mix = NVH_MIX_NONE;
+  NvhChanMap map = NvhChanMap{0u, 0u, 0};
+  bool mapped() const { return map.oc > 0; }
+  int out_channels(int ch) const { return mapped() ? map.oc : ch; }  // samples per sample time of an interleaved destination / planes
   static bool mix_ok(int mix) { return mix == NVH_MIX_NONE || mix == NVH_MIX_MONO; }
   bool mono() const { return mix == NVH_MIX_MONO; }
-  int layout() const { return mono() ? NVH_LAYOUT_MONO : planar() ? NVH_LAYOUT_PLANAR : NVH_LAYOUT_INTERLEAVED; }
+  int layout() const {
+    if (mapped()) return planar() ? NVH_LAYOUT_PLANAR_MAP : NVH_LAYOUT_INTERLEAVED_MAP;
+    return mono() ? NVH_LAYOUT_MONO : planar() ? NVH_LAYOUT_PLANAR : NVH_LAYOUT_INTERLEAVED;
+  }
   static bool format_ok(int format) { return format == NVH_PCM_F32 || format == NVH_PCM_S16; }
   bool s16() const { return format == NVH_PCM_S16; }
   bool planar() const { return plane_stride > 0; }
   size_t sample_bytes() const { return s16() ? sizeof(int16_t) : sizeof(float); }
   // a device destination: interleaved 16-bit PCM 16-byte aligned (the stereo twins store eight samples at a time), planar PCM
-  // and the mono mix aligned to their samples (their vector stores run where the base is 16-byte aligned, else the fall-back)
+  // the mono mix and mapped PCM aligned to their samples (their vector stores run where the base is 16-byte aligned, else the
+  // fall-back)
   bool dest_ok(const void* d_pcm) const {
-    return planar() || mono() ? ((uintptr_t)d_pcm % sample_bytes()) == 0 : (!s16() || ((uintptr_t)d_pcm & 15u) == 0);
+    return planar() || mono() || mapped() ? ((uintptr_t)d_pcm % sample_bytes()) == 0 : (!s16() || ((uintptr_t)d_pcm & 15u) == 0);
   }
 };
 int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms,

@@ -744,6 +744,16 @@ struct PcmTwins;
                           group4 = k_synth_group4##SFX;                                                                \
   };
 NVH_FOR_PCM_TWINS(NVH_PCM_TWINS)
+// the mapped sets (kernels_common.h: NVH_FOR_PCM_MAP_TWINS) have the wide emitting kernel alone, which takes the map
+#define NVH_PCM_MAP_TWINS(PCM, LAYOUT, SFX)                  \
+  template <>                                                \
+  struct PcmTwins<PCM, LAYOUT> {                             \
+    typedef PCM pcm;                                         \
+    static constexpr int layout = LAYOUT;                    \
+    static constexpr const char* sfx = #SFX;                 \
+    static constexpr auto synth8_emit = k_synth8_emit##SFX;  \
+  };
+NVH_FOR_PCM_MAP_TWINS(NVH_PCM_MAP_TWINS)
 
 // f(tag) for the set that writes `out`
 template <typename F>
@@ -751,14 +761,28 @@ static auto with_pcm_twins(const PcmOut& out, F&& f) {
 #define NVH_PCM_PICK(PCM, LAYOUT, SFX) \
   if (out.layout() == LAYOUT && out.s16() == std::is_same<PCM, int16_t>::value) return f(PcmTwins<PCM, LAYOUT>());
   NVH_FOR_PCM_TWINS(NVH_PCM_PICK)
+  NVH_FOR_PCM_MAP_TWINS(NVH_PCM_PICK)
   __builtin_unreachable();
 }
 
-// f(tag) for every set (the kernels that need a launch attribute)
+// f(tag) for every set (the kernels that need a launch attribute); the mapped sets apart: they lack the narrow families
 template <typename F>
 static void for_pcm_twins(F&& f) {
 #define NVH_PCM_EACH(PCM, LAYOUT, SFX) f(PcmTwins<PCM, LAYOUT>());
   NVH_FOR_PCM_TWINS(NVH_PCM_EACH)
+}
+template <typename F>
+static void for_pcm_map_twins(F&& f) {
+  NVH_FOR_PCM_MAP_TWINS(NVH_PCM_EACH)
+}
+// f(tag) for the un-mapped set that writes `out` (the narrow families' kernels: never launched for a mapped call)
+template <typename F>
+static auto with_unmapped_twins(PcmOut out, F&& f) {
+  out.map.oc = 0;
+#define NVH_PCM_PICK_U(PCM, LAYOUT, SFX) \
+  if (out.layout() == LAYOUT && out.s16() == std::is_same<PCM, int16_t>::value) return f(PcmTwins<PCM, LAYOUT>());
+  NVH_FOR_PCM_TWINS(NVH_PCM_PICK_U)
+  __builtin_unreachable();
 }
 
 int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms, hipEvent_t* ext_ev,
@@ -774,16 +798,23 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
   // by its vector form where that frame's own position allows it, else sample by sample.
   // The mono mix (the _mono twins): one plane, so the same condition without the stride, and the same fall-back; the mix of one
   // channel is that channel.
-  if (ch == 1) out.plane_stride = 0, out.mix = NVH_MIX_NONE;
+  // A channel map (the _map twins): interleaved, the vector stores need the aligned base and every emitted frame at
+  // out_pos * out_channels in whole groups of four -- asked of out_pos itself, the planar condition; planar, the planar condition
+  // as it is.  Only the wide emitting kernel has mapped forms: a mono / stereo stream's mapped batch (blocks up to 2048) runs
+  // without paired emission, k_synth + the mapped k_ola_compact, the route of a misaligned planar destination.
+  if (ch == 1 && !out.mapped()) out.plane_stride = 0, out.mix = NVH_MIX_NONE;
   const bool planar = out.planar();
   const int64_t plane_stride = out.plane_stride;
-  const bool planar_emit = out.mono() ? (((uintptr_t)d_pcm & 15u) == 0 && b->emit_planar_ok)
-                                      : !planar || (((uintptr_t)d_pcm & 15u) == 0 && (plane_stride & 3) == 0 &&
-                                                    plane_stride <= 0x7FFFFFFFll && b->emit_planar_ok);
+  const bool planar_emit = out.mono() || (out.mapped() && !planar)
+                               ? (((uintptr_t)d_pcm & 15u) == 0 && b->emit_planar_ok)
+                               : !planar || (((uintptr_t)d_pcm & 15u) == 0 && (plane_stride & 3) == 0 &&
+                                             plane_stride <= 0x7FFFFFFFll && b->emit_planar_ok);
   const char* sfx = with_pcm_twins(out, [](auto t) { return t.sfx; });
   // the k_ola_* kernels' last argument: the planes' stride, nothing in the interleaved forms
   auto ola_stride = [&](auto t) {
     if constexpr (decltype(t)::layout == NVH_LAYOUT_PLANAR) return (long long)plane_stride;
+    else if constexpr (decltype(t)::layout == NVH_LAYOUT_INTERLEAVED_MAP) return out.map;
+    else if constexpr (decltype(t)::layout == NVH_LAYOUT_PLANAR_MAP) return NvhStrideMap{(long long)plane_stride, out.map};
     else return NvhNoStride();
   };
   float* work = (float*)b->work.p;
@@ -842,7 +873,8 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
     const bool wide = slab_wide(s);
     // paired emission (nvh_format.h: NVH_EMIT_*): the host marked the frames at upload; it needs the PCM buffer and the slabs
     // in frame order
-    emitted = b->emit_frames > 0 && d_pcm != nullptr && !b->block_only && !T.no_emit && !s->shared->slab_general && planar_emit;
+    emitted = b->emit_frames > 0 && d_pcm != nullptr && !b->block_only && !T.no_emit && !s->shared->slab_general && planar_emit &&
+              (wide || !out.mapped());
     A.pcm = emitted ? (float*)d_pcm : nullptr;  // (int16_t samples for the _s16 twins)
     A.windows = s->dev.windows;
     A.clip = s->clip;
@@ -856,9 +888,11 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_g, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       hipError_t attr_err = hipSuccess;
-      for_pcm_twins([&](auto t) {
+      auto big_lds = [&](auto t) {
         if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void*)t.synth8_emit, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      });
+      };
+      for_pcm_twins(big_lds);
+      for_pcm_map_twins(big_lds);
       HIP_TRY(attr_err);
       s->ctx->synth_lds_attr_set = true;
     }
@@ -873,8 +907,11 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       A.f0 = 1;
       if (b->nframes > 1) hipLaunchKernelGGL(k_synth8, dim3((unsigned)(b->nframes / 2)), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
       A.f0 = 0;
-      auto kern8 = with_pcm_twins(out, [](auto t) { return t.synth8_emit; });
-      hipLaunchKernelGGL(kern8, dim3((unsigned)((b->nframes + 1) / 2)), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
+      with_pcm_twins(out, [&](auto t) {
+        const dim3 grid((unsigned)((b->nframes + 1) / 2));
+        if constexpr (nvh_layout_mapped(decltype(t)::layout)) hipLaunchKernelGGL(t.synth8_emit, grid, dim3(512), synth_lds, st, A, out.map NVH_DBG_LAUNCH);
+        else hipLaunchKernelGGL(t.synth8_emit, grid, dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
+      });
     } else if (wide_general) hipLaunchKernelGGL(k_synth8_g, dim3((unsigned)b->nframes), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
     else if (wide) hipLaunchKernelGGL(k_synth8, dim3((unsigned)b->nframes), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
     else if (narrow_general) hipLaunchKernelGGL(k_synth_g, dim3((unsigned)b->nframes), dim3(256), synth_lds, st, A NVH_DBG_LAUNCH);
@@ -893,7 +930,7 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
         HIP_TRY(attr_err);
         s->ctx->group_lds_attr_set = true;
       }
-      auto kern = with_pcm_twins(out, [gw](auto t) { return gw == 2 ? t.group2 : t.group4; });
+      auto kern = with_unmapped_twins(out, [gw](auto t) { return gw == 2 ? t.group2 : t.group4; });
       const unsigned nt = gw == 2 ? 256u : 512u;
       if (T.debug_occ) {
         int nb = -1;
@@ -926,7 +963,7 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       }
       A.f0 = 0;
       A.prefetch_prev = 0;
-      auto kern = with_pcm_twins(out, [](auto t) { return t.synth_emit; });
+      auto kern = with_unmapped_twins(out, [](auto t) { return t.synth_emit; });
       hipLaunchKernelGGL(kern, dim3((unsigned)((b->nframes + 1) / 2)), dim3(NVH_SYNTH_NT), synth_lds, st, A NVH_DBG_LAUNCH);
     }
     if (emitted) {  // odd frames, then the emitting even frames; the twins' names carry the format's / layout's suffix

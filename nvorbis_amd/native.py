@@ -99,6 +99,11 @@ SIGNATURES = {
     "nvh_stream_synth_begin_planar": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _i64p]),
     "nvh_stream_synth_mix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int64, _i64p]),
     "nvh_stream_synth_begin_mix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int64, _i64p]),
+    "nvh_channel_map_wave": (C.c_int, [C.c_int, _i32p]),
+    "nvh_stream_synth_map": (C.c_int, [_vp, C.c_int, _i32p, C.c_int, _vp, _vp, C.c_int64, _i64p]),
+    "nvh_stream_synth_begin_map": (C.c_int, [_vp, C.c_int, _i32p, C.c_int, _vp, C.c_int64, _i64p]),
+    "nvh_stream_synth_planar_map": (C.c_int, [_vp, C.c_int, _i32p, C.c_int, _vp, _vp, C.c_int64, _i64p]),
+    "nvh_stream_synth_begin_planar_map": (C.c_int, [_vp, C.c_int, _i32p, C.c_int, _vp, C.c_int64, _i64p]),
     "nvh_stream_parse_errors": (C.c_int, [_vp, _i32p, _i64p, C.c_int, _ip]),
     "nvh_batch_upload": (C.c_int, [_vp, _vpp]),
     "nvh_batch_info": (C.c_int, [_vp, _ip, _ip, _i64p, _i64p]),
@@ -109,6 +114,8 @@ SIGNATURES = {
     "nvh_batch_synth_pcm": (C.c_int, [_vp, C.c_int, _vp, C.c_int64]),
     "nvh_batch_synth_planar": (C.c_int, [_vp, C.c_int, _vp, C.c_int64]),
     "nvh_batch_synth_mix": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int64]),
+    "nvh_batch_synth_map": (C.c_int, [_vp, C.c_int, _i32p, C.c_int, _vp, C.c_int64]),
+    "nvh_batch_synth_planar_map": (C.c_int, [_vp, C.c_int, _i32p, C.c_int, _vp, C.c_int64]),
     "nvh_batch_time": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _f32p, _f32p]),
     "nvh_batch_free": (None, [_vp]),
     "nvh_ogg_demux": (C.c_int, [_vp, C.c_size_t, _vp, C.c_int64, _vp, _vp, _vp, C.c_int, _ip, _i64p]),

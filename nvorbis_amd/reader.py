@@ -52,6 +52,54 @@ def _mix(name, planar=False):
     return native.MIX_MONO if name == "mono" else native.MIX_NONE
 
 
+def wave_channel_map(channels):
+    """The Vorbis-to-WAVE channel permutation for 1 to 8 channels (nvh_channel_map_wave: Vorbis I 4.3.9 against the dwChannelMask
+    bit order), by output slot with the source channel as value: 6 -> (0, 2, 1, 5, 3, 4).  ValueError for other counts."""
+    if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or not 1 <= channels <= 8:
+        raise ValueError("the WAVE order is defined for 1 to 8 channels, not %r" % (channels,))
+    m = (C.c_int32 * 8)()
+    check(lib().nvh_channel_map_wave(int(channels), m), "nvh_channel_map_wave")
+    return tuple(int(m[j]) for j in range(int(channels)))
+
+
+def _channel_map(channel_map, channels, mix=None):
+    """None, or the map as a tuple of ints checked against a stream of `channels` channels: output slot j holds source channel
+    map[j] (include/nvorbis_hip.h: nvh_stream_synth_map).  "wave": wave_channel_map(channels).  ValueError for anything that is
+    not a map of that stream -- an unknown string, no entries or more than channels, an entry that is not an int, out of range
+    or named twice -- and for a map together with a mix.  channels=None (the stream is not open yet): what can be said without
+    it, and "wave" stays "wave"."""
+    if channel_map is None:
+        return None
+    if mix is not None:
+        raise ValueError("channel_map together with mix=%r: a map cannot be combined with a mix" % (mix,))
+    if isinstance(channel_map, str):
+        if channel_map != "wave":
+            raise ValueError("channel_map must be a sequence of ints or 'wave', not %r" % (channel_map,))
+        return wave_channel_map(channels) if channels is not None else channel_map
+    try:
+        m = tuple(channel_map)
+    except TypeError:
+        raise ValueError("channel_map must be a sequence of ints or 'wave', not %r" % (channel_map,))
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in m):
+        raise ValueError("channel_map entries must be ints: %r" % (channel_map,))
+    m = tuple(int(v) for v in m)
+    if not 1 <= len(m) <= (255 if channels is None else channels):
+        raise ValueError("channel_map must name 1 to %s channels, not %d" % ("the stream's" if channels is None else channels, len(m)))
+    if any(v < 0 or (channels is not None and v >= channels) for v in m) or len(set(m)) != len(m):
+        raise ValueError("channel_map entries must be distinct and in [0, channels): %r" % (m,))
+    return m
+
+
+def _map_array(m):
+    return (C.c_int32 * len(m))(*m)
+
+
+def _ident_channels(packet):
+    """audio_channels of a Vorbis identification header packet (Vorbis I 4.2.2), or None if it is not one."""
+    b = bytes(packet[:12])
+    return b[11] if len(b) >= 12 and b[:7] == b"\x01vorbis" else None
+
+
 def _host_shape(samples, channels, planar):
     """A host array for `samples` per channel, never empty: (channels, m) planes, or (m,) interleaved."""
     return (channels, max(samples, 1)) if planar else (max(samples * channels, 1),)
@@ -311,12 +359,23 @@ class Batch:
         check(lib().nvh_batch_kernels(self._h, buf, 256), "nvh_batch_kernels")
         return buf.value.decode().split(",")
 
-    def synth(self, d_pcm_ptr, capacity, dtype=np.float32, plane_stride=None, mix=None):
+    def synth(self, d_pcm_ptr, capacity, dtype=np.float32, plane_stride=None, mix=None, channel_map=None):
         """Launch the synthesis into d_pcm_ptr (capacity in samples) as float32 or int16 PCM (a 16-byte aligned int16 destination).
         plane_stride (samples, >= self.samples): channel-planar PCM instead, channel c at d_pcm_ptr + c * plane_stride samples
-        (capacity is then not used).  mix="mono": the channels' mean, self.samples samples (capacity counts those)."""
+        (capacity is then not used).  mix="mono": the channels' mean, self.samples samples (capacity counts those).
+        channel_map (a sequence of ints, or "wave"): len(map) output channels, output slot j = source channel map[j], in either
+        layout (capacity counts output samples); not together with mix."""
         fmt, _ = _pcm_format(dtype)
         mx = _mix(mix, plane_stride is not None)
+        cmap = _channel_map(channel_map, self._stream.channels, mix)
+        if cmap is not None:
+            if plane_stride is not None:
+                check(lib().nvh_batch_synth_planar_map(self._h, fmt, _map_array(cmap), len(cmap), C.c_void_p(d_pcm_ptr), int(plane_stride)),
+                      "nvh_batch_synth_planar_map")
+            else:
+                check(lib().nvh_batch_synth_map(self._h, fmt, _map_array(cmap), len(cmap), C.c_void_p(d_pcm_ptr), int(capacity)),
+                      "nvh_batch_synth_map")
+            return
         if mx != native.MIX_NONE:
             check(lib().nvh_batch_synth_mix(self._h, fmt, mx, C.c_void_p(d_pcm_ptr), int(capacity)), "nvh_batch_synth_mix")
             return
@@ -379,6 +438,7 @@ class Stream:
         self._flight_bufs = (_PinnedBuffer(), _PinnedBuffer())
         self._flight_out = [None, None]
         self._flight_per_channel = [False, False]  # the flight's counts are samples per channel (planar, mixed)
+        self._flight_channels = [0, 0]  # ... and its samples per sample time (the channels, 1 for a mix, len(channel_map))
         self._pipe_next = self._pipe_first = self._pipe_out = 0
         self._h = C.c_void_p()
         check(lib().nvh_stream_open(ctx._h if ctx is not None else None, id_pkt, len(id_pkt), comment_pkt,
@@ -590,7 +650,7 @@ class Stream:
         check(lib().nvh_stream_has_clipped(self._h, C.byref(v)), "nvh_stream_has_clipped")
         return bool(v.value)
 
-    def synth_host(self, pinned=False, out=None, dtype=np.float32, planar=False, mix=None):
+    def synth_host(self, pinned=False, out=None, dtype=np.float32, planar=False, mix=None, channel_map=None):
         """Synthesise the pending batch; returns interleaved PCM (numpy) of `dtype`: float32, or int16 (ov_read's conversion,
         done in the kernels: half the bytes over PCIe).
 
@@ -603,11 +663,18 @@ class Stream:
         (channels, m) array of the dtype with m >= the pending samples per channel, and the result is out[:, :n].
 
         mix="mono": the mean of the channels (summed in channel order, divided, clipped once: include/nvorbis_hip.h), a
-        (n,) array of n samples; not together with planar."""
+        (n,) array of n samples; not together with planar.
+
+        channel_map (a sequence of ints, or "wave" for the Vorbis-to-WAVE order): len(map) output channels, output slot j holding
+        source channel map[j] -- exactly the samples the un-mapped call emits for that channel -- in either layout; not together
+        with mix."""
         fmt, dt = _pcm_format(dtype)
         mx = _mix(mix, planar)
+        cmap = _channel_map(channel_map, self.channels, mix)
         _, smp = self.pending()
         ch = self.channels if mx == native.MIX_NONE else 1  # (samples of the output per sample time)
+        if cmap is not None:
+            ch = len(cmap)
         if out is None:
             shape = _host_shape(smp, ch, planar)
             n = int(np.prod(shape))
@@ -622,7 +689,13 @@ class Stream:
             if out.size == 0:
                 out = np.empty(1, dtype=dt)
         wr = C.c_int64(0)
-        if planar:
+        if cmap is not None and planar:
+            where = "nvh_stream_synth_planar_map"
+            rc = lib().nvh_stream_synth_planar_map(self._h, fmt, _map_array(cmap), ch, out.ctypes.data, None, out.shape[1], C.byref(wr))
+        elif cmap is not None:
+            where = "nvh_stream_synth_map"
+            rc = lib().nvh_stream_synth_map(self._h, fmt, _map_array(cmap), ch, out.ctypes.data, None, out.size, C.byref(wr))
+        elif planar:
             where = "nvh_stream_synth_planar"
             rc = lib().nvh_stream_synth_planar(self._h, fmt, out.ctypes.data, None, out.shape[1], C.byref(wr))
         elif mx != native.MIX_NONE:
@@ -631,26 +704,35 @@ class Stream:
         else:
             where = "nvh_stream_synth_pcm"
             rc = lib().nvh_stream_synth_pcm(self._h, fmt, out.ctypes.data, None, out.size, C.byref(wr))
-        self._note_parse_error(rc, wr.value, where, planar=planar or mx != native.MIX_NONE)
+        self._note_parse_error(rc, wr.value, where, planar=planar or mx != native.MIX_NONE, channels=ch)
         return out[:, :wr.value] if planar else out[:wr.value]
 
     # ---- pipelined read-back (nvh_stream_synth_begin / _end) ----
-    def synth_begin(self, dtype=np.float32, planar=False, mix=None):
+    def synth_begin(self, dtype=np.float32, planar=False, mix=None, channel_map=None):
         """Queue the pending batch (upload, GPU parse, synthesis, transfer of the PCM on a copy stream) and return at once.
         Two batches may be outstanding; synth_end() hands them back in order, each in the dtype of its begin (float32 / int16),
         and -- planar=True -- as a (channels, n) view of channel-planar PCM (the return value is then per channel too);
-        mix="mono": the channels' mean, n samples."""
+        mix="mono": the channels' mean, n samples.  channel_map: as in synth_host."""
         fmt, dt = _pcm_format(dtype)
         mx = _mix(mix, planar)
+        cmap = _channel_map(channel_map, self.channels, mix)
         if self._pipe_out >= 2:
             # refuse before touching a buffer: slot k is still the DMA destination of the oldest outstanding batch
             raise native.NvhError(native.ERR_ARGUMENT, "nvh_stream_synth_begin (two batches are outstanding: call synth_end first)")
-        shape = _host_shape(self.pending()[1], self.channels if mx == native.MIX_NONE else 1, planar)
+        och = len(cmap) if cmap is not None else self.channels if mx == native.MIX_NONE else 1
+        shape = _host_shape(self.pending()[1], och, planar)
         n = int(np.prod(shape))
         k = self._pipe_next
         out = self._flight_bufs[k].get(n, dt)
         exp = C.c_int64(0)
-        if planar:
+        if cmap is not None and planar:
+            check(lib().nvh_stream_synth_begin_planar_map(self._h, fmt, _map_array(cmap), och, out.ctypes.data, shape[1], C.byref(exp)),
+                  "nvh_stream_synth_begin_planar_map")
+            out = out[:n].reshape(shape)
+        elif cmap is not None:
+            check(lib().nvh_stream_synth_begin_map(self._h, fmt, _map_array(cmap), och, out.ctypes.data, out.size, C.byref(exp)),
+                  "nvh_stream_synth_begin_map")
+        elif planar:
             check(lib().nvh_stream_synth_begin_planar(self._h, fmt, out.ctypes.data, shape[1], C.byref(exp)), "nvh_stream_synth_begin_planar")
             out = out[:n].reshape(shape)
         elif mx != native.MIX_NONE:
@@ -660,6 +742,7 @@ class Stream:
         # only a begin that succeeded occupies a slot
         self._flight_out[k] = out
         self._flight_per_channel[k] = planar or mx != native.MIX_NONE  # (what the flight's counts mean)
+        self._flight_channels[k] = och
         self._pipe_next = k ^ 1
         self._pipe_out += 1
         return exp.value
@@ -680,17 +763,27 @@ class Stream:
         self._pipe_out -= 1
         out = self._flight_out[k]
         planar = out.ndim == 2
-        self._note_parse_error(rc, wr.value, "nvh_stream_synth_end", planar=self._flight_per_channel[k])
+        self._note_parse_error(rc, wr.value, "nvh_stream_synth_end", planar=self._flight_per_channel[k], channels=self._flight_channels[k])
         return out[:, :wr.value] if planar else out[:wr.value]
 
-    def synth_device(self, d_ptr, capacity, dtype=np.float32, plane_stride=None, mix=None):
+    def synth_device(self, d_ptr, capacity, dtype=np.float32, plane_stride=None, mix=None, channel_map=None):
         """Synthesise the pending batch into device memory (capacity in samples; int16: 16-byte aligned); returns the samples written.
         plane_stride (samples): channel-planar PCM instead, channel c at d_ptr + c * plane_stride samples; returns the samples
         written per channel (capacity is then not used).  mix="mono": the channels' mean (capacity and the return value count
-        its samples, one per sample time)."""
+        its samples, one per sample time).  channel_map: as in synth_host (capacity and the return value count output samples;
+        a mapped destination need only be aligned to its samples)."""
         fmt, _ = _pcm_format(dtype)
         mx = _mix(mix, plane_stride is not None)
+        cmap = _channel_map(channel_map, self.channels, mix)
         wr = C.c_int64(0)
+        if cmap is not None and plane_stride is not None:
+            rc = lib().nvh_stream_synth_planar_map(self._h, fmt, _map_array(cmap), len(cmap), None, C.c_void_p(d_ptr), int(plane_stride), C.byref(wr))
+            self._note_parse_error(rc, wr.value, "nvh_stream_synth_planar_map", planar=True)
+            return wr.value
+        if cmap is not None:
+            rc = lib().nvh_stream_synth_map(self._h, fmt, _map_array(cmap), len(cmap), None, C.c_void_p(d_ptr), int(capacity), C.byref(wr))
+            self._note_parse_error(rc, wr.value, "nvh_stream_synth_map", channels=len(cmap))
+            return wr.value
         if mx != native.MIX_NONE:
             rc = lib().nvh_stream_synth_mix(self._h, fmt, mx, None, C.c_void_p(d_ptr), int(capacity), C.byref(wr))
             self._note_parse_error(rc, wr.value, "nvh_stream_synth_mix", planar=True)
@@ -703,7 +796,7 @@ class Stream:
         self._note_parse_error(rc, wr.value, "nvh_stream_synth_pcm")
         return wr.value
 
-    def _note_parse_error(self, rc, written, where, planar=False):
+    def _note_parse_error(self, rc, written, where, planar=False, channels=None):
         """A synthesis call that returns an error code together with PCM (GPU-parse mode: a packet of the batch made the
         parser fail and the batch was parsed again without them): the PCM is complete; the errors are kept in
         `parse_errors` = [(NvhError, floats of this batch's PCM that precede the failing packet), ...] in stream order for
@@ -719,7 +812,7 @@ class Stream:
         codes, before = np.zeros(n.value, np.int32), np.zeros(n.value, np.int64)
         check(lib().nvh_stream_parse_errors(self._h, codes.ctypes.data_as(C.POINTER(C.c_int32)), before.ctypes.data_as(C.POINTER(C.c_int64)),
                                             n.value, C.byref(n)), "nvh_stream_parse_errors")
-        per = 1 if planar else self.channels
+        per = 1 if planar else (channels or self.channels)  # (channels: the call's samples per sample time, where not the stream's)
         self.parse_errors = [(native.NvhError(int(c), where), int(b) * per) for c, b in zip(codes, before)]
 
     def upload_batch(self):
@@ -747,7 +840,7 @@ class StreamDecoder:
     """IStreamDecoder-shaped object (Contracts/IStreamDecoder.cs:9-105) over a packet list."""
 
     def __init__(self, ctx, packets, granules=None, flags=None, batch_frames=1024, gpu_parse=False, sample_format="f32",
-                 layout="interleaved", mix=None):
+                 layout="interleaved", mix=None, channel_map=None):
         # sample_format "s16": the ring is decoded as int16 (ov_read's conversion, in the kernels); Read then takes int16 buffers
         self._dtype = _sample_format(sample_format)
         # layout "planar": the ring is channel-planar PCM (the kernels' _planar twins); Read then takes (Channels, m) buffers and
@@ -759,8 +852,19 @@ class StreamDecoder:
         # Positions, seeking and the roll-forward are in samples per channel either way.
         self._mix_name = mix
         self._mix = _mix(mix, self._planar)
+        # channel_map (a sequence of ints, or "wave"): the ring holds len(map) output channels, slot j = source channel map[j] (the
+        # kernels' _map twins), in either layout; Read counts and returns those, OutputChannels says how many.  Checked against the
+        # identification header's channel count before anything touches the device.
+        if mix is not None and channel_map is not None:
+            _channel_map(channel_map, None, mix)  # (raises)
         if len(packets) < 3:
             raise native.NvhError(native.ERR_NOT_VORBIS, "StreamDecoder")
+        self._channel_map = None
+        if channel_map is not None:
+            ident = _ident_channels(packets[0])
+            if ident is None:
+                raise native.NvhError(native.ERR_NOT_VORBIS, "StreamDecoder")
+            self._channel_map = _channel_map(channel_map, ident)
         self._stream = Stream(ctx, packets[0], packets[1], packets[2])
         if gpu_parse:  # packets parsed by k_parse; stream shapes outside its limits silently keep the host parser
             try:
@@ -793,7 +897,8 @@ class StreamDecoder:
     NominalBitrate = property(lambda self: self._stream.bitrates()[1])
     LowerBitrate = property(lambda self: self._stream.bitrates()[2])
     Channels = property(lambda self: self._stream.channels)
-    OutputChannels = property(lambda self: self._stream.channels if self._mix == native.MIX_NONE else 1)
+    OutputChannels = property(lambda self: len(self._channel_map) if self._channel_map is not None
+                              else self._stream.channels if self._mix == native.MIX_NONE else 1)
     SampleRate = property(lambda self: self._stream.sample_rate)
     HasClipped = property(lambda self: self._stream.has_clipped())
 
@@ -861,14 +966,15 @@ class StreamDecoder:
             pcm = None
             if frames:
                 # the ring is only replaced once it has been read out, so the stream's pinned buffer can be it
-                pcm = self._stream.synth_host(pinned=True, dtype=self._dtype, planar=self._planar, mix=self._mix_name)
+                pcm = self._stream.synth_host(pinned=True, dtype=self._dtype, planar=self._planar, mix=self._mix_name,
+                                              channel_map=self._channel_map)
             got = pcm is not None and pcm.size > 0
             if got:
                 self._ring = pcm
                 self._ring_pos = 0
             size = pcm.size if got else 0
             if self._stream.parse_errors:  # GPU-parse mode: packets inside the batch failed
-                per = self.Channels if self._planar else 1  # (planar calls report samples per channel)
+                per = self.OutputChannels if self._planar else 1  # (planar calls report samples per channel)
                 self._pending_errors = [(e, min(at * per, size)) for e, at in self._stream.parse_errors]
                 self._stream.parse_errors = []
             if push_error is not None:  # host-parse mode: everything parsed before the packet comes first
@@ -882,7 +988,7 @@ class StreamDecoder:
     def Read(self, buffer, offset, count):
         """StreamDecoder.Read (StreamDecoder.cs:320-389).  Planar layout: buffer is a (Channels, m) array, offset and count are
         samples per channel, and so is the return value.  A mixing decoder counts and returns output samples."""
-        ch = self.Channels if self._planar else self.OutputChannels
+        ch = self.OutputChannels  # (a planar decoder has no mix: the stream's channels, or the map's)
         if self._planar:
             if getattr(buffer, "dtype", None) != self._dtype:
                 raise TypeError("this decoder delivers %s samples: the buffer must be a numpy %s array" % (self._dtype, self._dtype))
@@ -1079,7 +1185,7 @@ class VorbisReader:
     """VorbisReader-shaped facade (VorbisReader.cs): first logical stream of an .ogg file or byte string."""
 
     def __init__(self, source, ctx=None, device=0, batch_frames=8192, gpu_parse=True, forward_only=False, sample_format="f32",
-                 layout="interleaved", mix=None):
+                 layout="interleaved", mix=None, channel_map=None):
         # sample_format: "f32" (float32 PCM, the reference's) or "s16" (int16, libvorbis ov_read's conversion in the kernels)
         self._dtype = _sample_format(sample_format)
         self._sample_format = sample_format
@@ -1090,6 +1196,11 @@ class VorbisReader:
         # stream's channel count, OutputChannels is 1)
         _mix(mix, self._planar)
         self._mix = mix
+        # channel_map: None, a sequence of ints, or "wave" (the Vorbis-to-WAVE order of each logical stream's channel count):
+        # ReadSamples / read_all deliver OutputChannels = len(map) channels, output slot j = source channel map[j]
+        if channel_map is not None:
+            _channel_map(channel_map, None, mix)  # (the shape of the argument, before anything is opened; each stream checks its own)
+        self._channel_map = channel_map
         # gpu_parse: parse the packets on the GPU too when the stream shape allows it (StreamDecoder falls back silently)
         # forward_only: read the container the way the reference reads a source that cannot seek (ContainerReader picks
         # ForwardOnlyPageReader for !stream.CanSeek, Ogg/ContainerReader.cs); SeekTo then raises as IPacketProvider.CanSeek is false
@@ -1114,7 +1225,7 @@ class VorbisReader:
             raise native.NvhError(native.ERR_NOT_VORBIS, "VorbisReader")  # ArgumentException: could not load the container
         self._stream_index = 0
         self._dec = StreamDecoder(self._ctx, demux_ogg_array(data, self._stream_ids[0], self._forward_only), None, None, batch_frames, gpu_parse,
-                                  sample_format, layout, mix)
+                                  sample_format, layout, mix, channel_map)
         if self._forward_only:
             self._dec.can_seek = False
         else:
@@ -1145,7 +1256,8 @@ class VorbisReader:
         clip = self.ClipSamples
         if index not in self._decs:
             self._decs[index] = StreamDecoder(self._ctx, demux_ogg_array(self._data, self._stream_ids[index], self._forward_only), None,
-                                              None, self._batch_frames, self._gpu_parse, self._sample_format, self._layout, self._mix)
+                                              None, self._batch_frames, self._gpu_parse, self._sample_format, self._layout, self._mix,
+                                              self._channel_map)
             if self._forward_only:
                 self._decs[index].can_seek = False
             else:
@@ -1196,8 +1308,8 @@ class VorbisReader:
         if getattr(buffer, "dtype", None) != self._dtype:
             raise TypeError("this reader delivers %s samples: the buffer must be a numpy %s array" % (self._dtype, self._dtype))
         if self._planar:
-            if buffer.ndim != 2 or buffer.shape[0] != self.Channels:
-                raise ValueError("planar layout: the buffer must have shape (%d, m), not %s" % (self.Channels, buffer.shape))
+            if buffer.ndim != 2 or buffer.shape[0] != self.OutputChannels:
+                raise ValueError("planar layout: the buffer must have shape (%d, m), not %s" % (self.OutputChannels, buffer.shape))
             if count is None:
                 count = buffer.shape[1] - offset
             return self._dec.Read(buffer, offset, count) if count > 0 else 0
@@ -1211,7 +1323,7 @@ class VorbisReader:
     def read_all(self):
         """Everything from the current position: interleaved, (Channels, T) in the planar layout, or (T,) mixed samples."""
         chunks = []
-        buf = np.empty((self.Channels, 65536) if self._planar else (65536 * self.OutputChannels,), dtype=self._dtype)
+        buf = np.empty((self.OutputChannels, 65536) if self._planar else (65536 * self.OutputChannels,), dtype=self._dtype)
         while True:
             n = self.ReadSamples(buf, 0, buf.shape[-1])
             if n <= 0:

@@ -17,6 +17,7 @@ import sqlite3
 # (sample type, layout: NVH_LAYOUT_* of kernels_common.h; `true` / `false`: listings from when the layout was a bool, planar or not)
 _TWIN_SUFFIX = {("float", "0"): "", ("short", "0"): "_s16", ("float", "1"): "_planar", ("short", "1"): "_s16_planar",
                 ("float", "2"): "_mono", ("short", "2"): "_s16_mono",
+                ("float", "3"): "_map", ("short", "3"): "_s16_map", ("float", "4"): "_planar_map", ("short", "4"): "_s16_planar_map",
                 ("float", "false"): "", ("short", "false"): "_s16", ("float", "true"): "_planar", ("short", "true"): "_s16_planar"}
 
 

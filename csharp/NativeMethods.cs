@@ -69,6 +69,8 @@ namespace NVorbis.Hip
         [DllImport(Lib)] public static extern int nvh_stream_reset(IntPtr stream);
         /// <summary>Geometry-only index of a run of audio packets (positions, emitted samples, decodable / lead-in flags).</summary>
         [DllImport(Lib)] public static extern unsafe int nvh_stream_index_packets(IntPtr stream, byte* bytes, long* offsets, long* granules, byte* flags, int n, long* positionAfter, long* emittedAfter, byte* stateAfter, out long totalEmitted);
+        /// <summary>Per codebook: the route its symbols take through the GPU packet parser (tables in LDS, second-level tables, whole-list scans) and the host parser.</summary>
+        [DllImport(Lib)] public static extern int nvh_stream_parse_book_info(IntPtr stream, int bookIndex, out int gpuParseOk, out int prefixInLds, out int overflowInLds, out int secondLevel, out int scanAllSlots, out int hostScanSlots);
         [DllImport(Lib)] public static extern int nvh_stream_mode_info(IntPtr stream, int modeIndex, out int blockFlag, out int blockSize, out int mapping);
         [DllImport(Lib)] public static extern int nvh_stream_floor_info(IntPtr stream, int floorIndex, out int type, out int postCount, out int range);
         [DllImport(Lib)] public static extern int nvh_stream_pending(IntPtr stream, out int frames, out long samplesPerChannel);

@@ -116,6 +116,16 @@ int nvh_stream_codebook_info(const nvh_stream *s, int book_index, int *dimension
  * as (present, value, length, bits, mask) (Huffman.cs:15-76).  Any pointer may be NULL. */
 int nvh_stream_codebook_tables(const nvh_stream *s, int book_index, int32_t *lengths, float *lookup, int32_t *prefix,
                                int32_t *overflow);
+/* Read-only: the route a symbol of codebook `book_index` takes through the two packet parsers, as decided per book at stream
+ * open.  GPU parser (nvh_stream_set_gpu_parse): gpu_parse_ok = the stream shape is inside its limits (the other four are 0
+ * when it is not); prefix_in_lds / overflow_in_lds = the book's prefix table / its overflow nodes, grouped by prefix slot, are
+ * held in LDS (else read from global memory); second_level = its long codes are looked up in second-level tables (else their
+ * slot's group is scanned); scan_all_slots = prefix slots whose long codes are found by scanning the book's whole overflow
+ * list.  Host parser: host_scan_slots = prefix slots for which it scans the whole list.  A slot counts only if no short code
+ * fills it.  A stream with a context reports what it uploaded, a host-only stream the same decisions made without a device.
+ * Any pointer may be NULL. */
+int nvh_stream_parse_book_info(const nvh_stream *s, int book_index, int *gpu_parse_ok, int *prefix_in_lds, int *overflow_in_lds,
+                               int *second_level, int *scan_all_slots, int *host_scan_slots);
 
 /* IResidue.Decode(IPacket, bool[] doNotDecodeChannel, int blockSize, float[][] buffer) (Contracts/IResidue.cs:6;
  * Residue0.cs:119-201, Residue1.cs:8-26, Residue2.cs:10-47) for residue `residue_index` of stream `s`: reads the

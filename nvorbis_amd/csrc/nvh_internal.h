@@ -280,6 +280,7 @@ struct SharedSetup {
   DevBuf parse_arena;
   NvhDevParse parse{};
   bool gpu_parse_ok = false;
+  std::vector<int> parse_routes;  // per book the four numbers of nvh_stream_parse_book_info (nvh_setup.hip: book_routes)
 };
 
 struct nvh_ctx {
@@ -459,6 +460,7 @@ static inline size_t wave_lds_bytes(int n) { return (size_t)2 * ((size_t)(n / 4)
 int get_mdct(nvh_ctx* c, int n, MdctDev** out);                 // nvh_ops.hip
 int upload_setup(nvh_stream* s);                                 // nvh_setup.hip
 int upload_parse_tables(nvh_stream* s);                          // nvh_setup.hip
+int parse_book_routes(const nvh_stream* s, int book, int* gpu_parse_ok, int out[4]);  // nvh_setup.hip
 int batch_upload(nvh_stream* s, nvh_batch* b);                   // nvh_launch.hip
 // A PCM destination: the sample format (NVH_PCM_*: float, or int16_t for the kernels' _s16 twins) and the layout -- interleaved
 // (plane_stride == 0), or channel-planar with channel c's samples at base + c * plane_stride (the _planar twins) -- and the mix

@@ -296,6 +296,30 @@ extern "C" int nvh_stream_codebook_info(const nvh_stream* s, int book_index, int
   });
 }
 
+extern "C" int nvh_stream_parse_book_info(const nvh_stream* s, int book_index, int* gpu_parse_ok, int* prefix_in_lds, int* overflow_in_lds,
+                                          int* second_level, int* scan_all_slots, int* host_scan_slots) {
+  return nvh_guard([&]() -> int {
+    if (!s || book_index < 0 || book_index >= (int)s->setup.books.size()) return NVH_ERR_ARGUMENT;
+    int ok = 0, r[4] = {0, 0, 0, 0};
+    const int rc = parse_book_routes(s, book_index, &ok, r);
+    if (rc != NVH_OK) return rc;
+    if (gpu_parse_ok) *gpu_parse_ok = ok;
+    if (prefix_in_lds) *prefix_in_lds = r[0];
+    if (overflow_in_lds) *overflow_in_lds = r[1];
+    if (second_level) *second_level = r[2];
+    if (scan_all_slots) *scan_all_slots = r[3];
+    if (host_scan_slots) {  // slots only longer codes start with, whose group the host parser does not scan (host_setup.cpp: generate_table)
+      const nvh::Codebook& b = s->setup.books[(size_t)book_index];
+      int n = 0;
+      if (b.has_overflow)
+        for (size_t k = 0; k < b.prefix.size() && k < b.slot_group.size(); k++)
+          if (!b.prefix[k].present && (b.slot_group[k] & 0xFFu) == 0xFFu) n++;
+      *host_scan_slots = n;
+    }
+    return NVH_OK;
+  });
+}
+
 extern "C" int nvh_stream_codebook_tables(const nvh_stream* s, int book_index, int32_t* lengths, float* lookup, int32_t* prefix,
                                           int32_t* overflow) {
   return nvh_guard([&]() -> int {

@@ -273,26 +273,35 @@ int upload_setup(nvh_stream* s) {
 // ------------------------------------------------------------------------------------------------
 
 // Moves s->pending into `b` (device resident) and advances the stream's batch boundary.
-// Device tables of the GPU packet parser (kernels_parse.hip) and the worst-case slab capacities of this setup.
-// Streams outside its limits (Floor0, > 8 channels, ...) simply keep the host parser.
-int upload_parse_tables(nvh_stream* s) {
-  const nvh::Setup& S = s->setup;
-  SharedSetup& sh = *s->shared;
-  sh.gpu_parse_ok = false;
-  if (S.channels > NVH_PARSE_MAX_CH || S.books.size() > 256) return NVH_OK;
-  for (const nvh::Floor& f : S.floors)
-    if (f.type != 1) return NVH_OK;
-  for (const nvh::Mapping& m : S.mappings)
-    if (m.submap_floor.size() > NVH_PARSE_MAX_SUBMAPS || m.coupling_angle.size() > NVH_PARSE_MAX_COUPLING) return NVH_OK;
+namespace {
 
-  std::vector<NvhPBook> books(S.books.size());
-  std::vector<uint32_t> prefix;
+// The host half of upload_parse_tables: every decision (which book's tables go where, whether the stream shape is inside the GPU
+// parser's limits) and the arena image, without a device.  nvh_stream_parse_book_info reads the decisions back.
+struct ParsePlan {
+  std::vector<NvhPBook> books;
+  std::vector<uint32_t> prefix, lds_image, dm_lds, vis_lds, sub_image;
+  int cap_ops = 1, cap_ent = 8, cap_pass = 1, cap_parts = 1;
+  ArenaBuilder ab;
+  size_t o_bk = 0, o_fl = 0, o_rs = 0, o_mp = 0, o_px = 0, o_ov = 0, o_ip = 0, o_li = 0, o_si = 0, meta_end = 0;
+};
+
+// false: the stream keeps the host parser
+bool plan_parse_tables(const nvh::Setup& S, const SharedSetup& sh, ParsePlan& plan) {
+  if (S.channels > NVH_PARSE_MAX_CH || S.books.size() > 256) return false;
+  for (const nvh::Floor& f : S.floors)
+    if (f.type != 1) return false;
+  for (const nvh::Mapping& m : S.mappings)
+    if (m.submap_floor.size() > NVH_PARSE_MAX_SUBMAPS || m.coupling_angle.size() > NVH_PARSE_MAX_COUPLING) return false;
+
+  std::vector<NvhPBook>& books = plan.books;
+  books.resize(S.books.size());
+  std::vector<uint32_t>& prefix = plan.prefix;
   std::vector<NvhPOverflow> overflow;
   for (size_t i = 0; i < S.books.size(); i++) {
     const nvh::Codebook& b = S.books[i];
     NvhPBook& d = books[i];
     std::memset(&d, 0, sizeof d);
-    if (b.entries > 0xFFFFFF || b.prefix_bits > 16 || b.max_bits > 32 || b.dimensions > 0xFFFF) return NVH_OK;
+    if (b.entries > 0xFFFFFF || b.prefix_bits > 16 || b.max_bits > 32 || b.dimensions > 0xFFFF) return false;
     d.prefix_off = (uint32_t)prefix.size();
     d.ovf_off = (uint32_t)overflow.size();
     d.entries = (uint32_t)b.entries;
@@ -312,7 +321,7 @@ int upload_parse_tables(nvh_stream* s) {
     for (size_t k = 0; k < b.prefix.size(); k++) {
       const nvh::HuffNode& n = b.prefix[k];
       if (n.present) {
-        if (n.length < 0 || n.length > 0x7F || n.value < 0 || n.value > 0xFFFFFF) return NVH_OK;
+        if (n.length < 0 || n.length > 0x7F || n.value < 0 || n.value > 0xFFFFFF) return false;
         prefix.push_back(((uint32_t)n.value << 8) | 0x80u | (uint32_t)n.length);
       } else {
         uint32_t g = b.has_overflow && k < b.slot_group.size() ? b.slot_group[k] : 0u;
@@ -339,7 +348,7 @@ int upload_parse_tables(nvh_stream* s) {
     d.ovf_count = (uint32_t)b.overflow.size();
   }
   // LDS image: the decode maps and visit descriptors, the residue VQ books, then the class and floor books, while they fit
-  std::vector<uint32_t> lds_image, dm_lds, vis_lds, sub_image;
+  std::vector<uint32_t>&lds_image = plan.lds_image, &dm_lds = plan.dm_lds, &vis_lds = plan.vis_lds, &sub_image = plan.sub_image;
   {
     const size_t budget = 16 * 1024;  // words (64 KB; + <= 8 KB of book / floor / residue / mapping records).  The residue books first:
                                       // they fill 13 k words for a libvorbis setup, and one of them out of LDS costs more than
@@ -510,7 +519,7 @@ int upload_parse_tables(nvh_stream* s) {
   std::vector<int32_t> ipool;
   std::vector<NvhPResidue> residues(S.residues.size());
   std::vector<int> r_parts(S.residues.size()), r_ops(S.residues.size()), r_ent(S.residues.size());
-  int cap_parts = 1;
+  int& cap_parts = plan.cap_parts;
   for (size_t i = 0; i < S.residues.size(); i++) {
     const nvh::Residue& r = S.residues[i];
     NvhPResidue& d = residues[i];
@@ -523,7 +532,7 @@ int upload_parse_tables(nvh_stream* s) {
     d.general = (i < sh.slab.residue_general.size() && sh.slab.residue_general[i] && !d.alias_b1 &&
                  !(i < sh.slab.residue_pair.size() && sh.slab.residue_pair[i])) ? 1u : 0u;
     d.rch_magic = r.real_channels > 1 ? (uint32_t)((0x100000000ull + (uint64_t)r.real_channels - 1) / (uint64_t)r.real_channels) : 0u;
-    if ((uint64_t)S.block1 * (uint64_t)std::max(S.channels, 1) * (uint64_t)std::max(r.real_channels, 1) >= 0x100000000ull) return NVH_OK;
+    if ((uint64_t)S.block1 * (uint64_t)std::max(S.channels, 1) * (uint64_t)std::max(r.real_channels, 1) >= 0x100000000ull) return false;
     d.decode_map_off = (uint32_t)ipool.size();
     d.decode_map_lds = dm_lds[i];
     d.vis_lds = vis_lds[i];
@@ -538,7 +547,7 @@ int upload_parse_tables(nvh_stream* s) {
         if (c < r.classifications && r.books[c][k] >= 0) {
           const int dm = S.books[(size_t)r.books[c][k]].dimensions;
           // k_parse divides (partition_size + dims - 1) by dims with the book's 32-bit reciprocal: exact below 2^32 / dims
-          if (dm > 1 && ((uint64_t)r.partition_size + (uint64_t)dm) * (uint64_t)dm >= 0x100000000ull) return NVH_OK;
+          if (dm > 1 && ((uint64_t)r.partition_size + (uint64_t)dm) * (uint64_t)dm >= 0x100000000ull) return false;
           if (dm > 0 && dm < min_dims) min_dims = dm;
         }
       }
@@ -559,7 +568,7 @@ int upload_parse_tables(nvh_stream* s) {
   }
   if (ipool.empty()) ipool.push_back(0);
   std::vector<NvhPMapping> mappings(S.mappings.size());
-  int cap_ops = 1, cap_ent = 8, cap_pass = 1;
+  int &cap_ops = plan.cap_ops, &cap_ent = plan.cap_ent, &cap_pass = plan.cap_pass;
   for (size_t i = 0; i < S.mappings.size(); i++) {
     const nvh::Mapping& m = S.mappings[i];
     NvhPMapping& d = mappings[i];
@@ -588,9 +597,9 @@ int upload_parse_tables(nvh_stream* s) {
   cap_ops = (cap_ops + 7) & ~7;
   cap_ent = (cap_ent + 15) & ~7;
   // keep a frame's slabs within reason (and op indices within the 15-bit links where possible)
-  if ((size_t)cap_ops * 10 + (size_t)cap_ent * 2 + (size_t)cap_parts * 8 > ((size_t)1 << 20)) return NVH_OK;
+  if ((size_t)cap_ops * 10 + (size_t)cap_ent * 2 + (size_t)cap_parts * 8 > ((size_t)1 << 20)) return false;
 
-  ArenaBuilder ab;
+  ArenaBuilder& ab = plan.ab;
   // books | floors | residues | mappings back to back: k_parse copies this block into LDS
   size_t o_bk = ab.add(books.data(), books.size() * sizeof(NvhPBook));
   size_t o_fl = ab.add(floors.data(), floors.size() * sizeof(NvhPFloor1));
@@ -603,7 +612,57 @@ int upload_parse_tables(nvh_stream* s) {
   size_t o_ip = ab.add(ipool.data(), ipool.size() * sizeof(int32_t));
   size_t o_li = ab.add(lds_image.data(), lds_image.size() * sizeof(uint32_t));
   size_t o_si = ab.add(sub_image.data(), sub_image.size() * sizeof(uint32_t));
-  if (meta_end - o_bk > 8 * 1024) return NVH_OK;  // unusually large setup: keep the host parser
+  if (meta_end - o_bk > 8 * 1024) return false;  // unusually large setup: keep the host parser
+  plan.o_bk = o_bk; plan.o_fl = o_fl; plan.o_rs = o_rs; plan.o_mp = o_mp; plan.o_px = o_px;
+  plan.o_ov = o_ov; plan.o_ip = o_ip; plan.o_li = o_li; plan.o_si = o_si; plan.meta_end = meta_end;
+  return true;
+}
+
+// nvh_stream_parse_book_info's four numbers of one book
+void book_routes(const ParsePlan& plan, const nvh::Codebook& cb, size_t b, int out[4]) {
+  const NvhPBook& d = plan.books[b];
+  out[0] = d.lds_off != 0xFFFFFFFFu;
+  out[1] = d.ovf_lds != 0xFFFFFFFFu;
+  out[2] = d.sub_dir != 0xFFFFFFFFu;
+  out[3] = 0;
+  for (size_t k = 0; k < cb.prefix.size(); k++) {
+    const uint32_t w = plan.prefix[d.prefix_off + k];
+    if (!(w & 0x80u) && (w & 0x7Fu) == 0x7Fu) out[3]++;
+  }
+}
+
+}  // namespace
+
+// Which route the GPU parser's symbol decode takes for book `book` (include/nvorbis_hip.h: nvh_stream_parse_book_info): what
+// upload_parse_tables uploaded for a stream with a context, the same plan computed on the spot for a host-only stream.
+int parse_book_routes(const nvh_stream* s, int book, int* gpu_parse_ok, int out[4]) {
+  const SharedSetup& sh = *s->shared;
+  if (s->ctx) {
+    *gpu_parse_ok = sh.gpu_parse_ok ? 1 : 0;
+    for (int k = 0; k < 4; k++) out[k] = sh.gpu_parse_ok ? sh.parse_routes[(size_t)book * 4 + (size_t)k] : 0;
+    return NVH_OK;
+  }
+  ParsePlan plan;
+  const bool ok = plan_parse_tables(s->setup, sh, plan);
+  *gpu_parse_ok = ok ? 1 : 0;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (ok) book_routes(plan, s->setup.books[(size_t)book], (size_t)book, out);
+  return NVH_OK;
+}
+
+// Device tables of the GPU packet parser (kernels_parse.hip) and the worst-case slab capacities of this setup.
+// Streams outside its limits (Floor0, > 8 channels, ...) simply keep the host parser.
+int upload_parse_tables(nvh_stream* s) {
+  const nvh::Setup& S = s->setup;
+  SharedSetup& sh = *s->shared;
+  sh.gpu_parse_ok = false;
+  ParsePlan plan;
+  if (!plan_parse_tables(S, sh, plan)) return NVH_OK;
+  const std::vector<uint32_t>&lds_image = plan.lds_image, &dm_lds = plan.dm_lds, &vis_lds = plan.vis_lds, &sub_image = plan.sub_image;
+  const int cap_ops = plan.cap_ops, cap_ent = plan.cap_ent, cap_pass = plan.cap_pass, cap_parts = plan.cap_parts;
+  const ArenaBuilder& ab = plan.ab;
+  const size_t o_bk = plan.o_bk, o_fl = plan.o_fl, o_rs = plan.o_rs, o_mp = plan.o_mp, o_px = plan.o_px, o_ov = plan.o_ov, o_ip = plan.o_ip,
+               o_li = plan.o_li, o_si = plan.o_si, meta_end = plan.meta_end;
   sh.parse_arena.pool = &s->ctx->pool;
   int rc = sh.parse_arena.reserve(ab.bytes.size());
   if (rc != NVH_OK) return rc;
@@ -660,6 +719,8 @@ int upload_parse_tables(nvh_stream* s) {
     v = (v + 3) & ~(size_t)3;
     if (ok && v <= 0xFFFFu && cap_ops <= 0xFFFF && cap_ent <= 0xFFFF) P.slab_stride_vecs = (int32_t)v;
   }
+  sh.parse_routes.assign(S.books.size() * 4, 0);
+  for (size_t b = 0; b < S.books.size(); b++) book_routes(plan, S.books[b], b, &sh.parse_routes[b * 4]);
   sh.gpu_parse_ok = true;
   return NVH_OK;
 }

@@ -638,6 +638,14 @@ class Stream:
                                      C.c_void_p(d_residue), int(stride), status.ctypes.data), "nvh_floor1_apply")
         return status
 
+    def parse_book_info(self, book_index):
+        """Which route codebook `book_index` takes through the packet parsers (nvh_stream_parse_book_info): a dict of gpu_parse_ok,
+        prefix_in_lds, overflow_in_lds, second_level, scan_all_slots, host_scan_slots.  Works on a host-only stream too."""
+        v = [C.c_int(0) for _ in range(6)]
+        check(lib().nvh_stream_parse_book_info(self._h, int(book_index), *[C.byref(x) for x in v]), "nvh_stream_parse_book_info")
+        names = ("gpu_parse_ok", "prefix_in_lds", "overflow_in_lds", "second_level", "scan_all_slots", "host_scan_slots")
+        return {k: x.value for k, x in zip(names, v)}
+
     def set_gpu_parse(self, on):
         """Parse packets on the GPU (kernels_parse.hip); raises NvhError(UNSUPPORTED) for ineligible stream shapes."""
         check(lib().nvh_stream_set_gpu_parse(self._h, 1 if on else 0), "nvh_stream_set_gpu_parse")

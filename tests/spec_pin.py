@@ -41,6 +41,9 @@ QUIRKS = {
     "ch9_res2": ("B4",),                        # 1.5e-7
     "ch16_res1_4096": ("B2", "B4"),             # 1.1e-7
     "ch40_res1": ("B2", "B4"),                  # 1.5e-7
+    "longcode_res1": (),                        # 1.6e-7
+    "longcode_res2": (),                        # 2.0e-7
+    "longcode_many_books": (),                  # 1.7e-7
 }
 
 FLOOR1_BOUND = 1e-6  # x peak
@@ -83,3 +86,31 @@ def spec_pcm(name, quirks):
         outs = [dec.packet(p) for p in pk[3:]]
     outs.append(dec.prev_tail)
     return np.concatenate(outs, axis=1).T.reshape(-1).copy()
+
+
+# the long-code configurations (tests/synth_stream.py: LONGCODE_NAMES) also get a longer stream, 24 frames, so that every code
+# length of every book is written and the slab test's frame / vector minimum is met: long x 4, short x 3, long x 5, short x 4, long x 8
+KINDS24 = np.array([1] * 4 + [0] * 3 + [1] * 5 + [0] * 4 + [1] * 8, dtype=bool)
+
+
+@functools.lru_cache(maxsize=None)
+def stream24(name, seed=24):
+    """(packets, granules, stats) of a configuration's 24-frame structured stream; stats["symbols"][(book, code length)] counts
+    the symbols the encoder wrote (tests/vorbis_encode.py: BookEnc.put)."""
+    hdr = list(headers(name))
+    stats = {}
+    pk, gr = ve.encode_stream(ve.setup_of(hdr), hdr, KINDS24, seed, p_silent=P_SILENT, stats=stats)
+    return tuple(pk), tuple(gr), stats
+
+
+@functools.lru_cache(maxsize=None)
+def stream24_cut(name, seed=24):
+    """stream24 with every second audio packet cut at a seeded random byte count somewhere in its second half: packets that end
+    inside a long code (the reference then matches against the zero-padded word, Codebook.cs:299-318)."""
+    pk, gr, _ = stream24(name, seed)
+    rng = np.random.default_rng(seed + 1)
+    out = list(pk)
+    for i in range(3, len(out), 2):
+        n = len(out[i])
+        out[i] = out[i][:int(rng.integers(n // 2, n))]
+    return tuple(out), gr

@@ -5,7 +5,9 @@ writes *setup headers* for arbitrary configurations (Floor0, Residue0, >2 channe
 several submaps, block sizes 64..8192, codebooks whose dimension does not divide the partition size, ...)
 and fills the audio packets with random bits.  Every codebook is a complete fixed-length prefix code (entries
 a power of two), so any bit string decodes to *some* side information: no Huffman encoder is needed, and the
-oracle and the product are compared on whatever the bits mean.  Header layouts follow what the reference
+oracle and the product are compared on whatever the bits mean.  (The longcode_* configurations are the exception: their
+books are VarBooks with long, sparse, ordered and under-subscribed code lists, and their streams are written by the structured
+encoder of tests/vorbis_encode.py, which chooses entries and so writes the long codes.)  Header layouts follow what the reference
 parses (StreamDecoder.cs:179-289, Codebook.cs:59-283, Floor0.cs:28-65, Floor1.cs:30-133, Residue0.cs:35-117,
 Mapping.cs:16-93, Mode.cs:24-67).
 """
@@ -82,6 +84,9 @@ class Book:
         w.write(0, 1)  # not sparse
         for _ in range(self.entries):
             w.write(self.bits - 1, 5)
+        self._write_lookup(w, rng)
+
+    def _write_lookup(self, w, rng):
         w.write(self.lookup, 4)
         if self.lookup == 0:
             return
@@ -94,6 +99,51 @@ class Book:
         assert len(mults) == count, (len(mults), count)
         for m in mults:
             w.write(int(m), self.value_bits)
+
+
+class VarBook(Book):
+    """Codebook with an arbitrary list of codeword lengths (0: the entry is unused), written in one of the three forms a setup
+    header can carry (Codebook.cs:76-104): "dense" (five bits per entry, no entry unused), "sparse" (a used flag per entry) or
+    "ordered" (runs of equal lengths, rising by one: the list must not fall and has no unused entry).  The lookup part is
+    Book's.  Codewords follow from the lengths (spec 3.2.1), so a list may leave the tree under-subscribed."""
+
+    def __init__(self, lengths, encoding="dense", dims=1, lookup=0, min_me=(0, 0), delta_me=(1, 0), value_bits=4, sequence_p=0, mults=None):
+        self.lengths = [int(x) for x in lengths]
+        assert encoding in ("dense", "sparse", "ordered") and all(0 <= x <= 32 for x in self.lengths) and max(self.lengths) > 0
+        if encoding != "sparse":
+            assert min(self.lengths) > 0
+        if encoding == "ordered":
+            assert all(a <= b for a, b in zip(self.lengths, self.lengths[1:]))
+        self.encoding = encoding
+        self.bits, self.dims, self.lookup = max(self.lengths), dims, lookup
+        self.entries = len(self.lengths)
+        self.min_me, self.delta_me, self.value_bits, self.sequence_p, self.mults = min_me, delta_me, value_bits, sequence_p, mults
+
+    def write(self, w, rng):
+        w.write(0x564342, 24)
+        w.write(self.dims, 16)
+        w.write(self.entries, 24)
+        if self.encoding == "ordered":
+            w.write(1, 1)
+            cur, i = self.lengths[0], 0
+            w.write(cur - 1, 5)
+            while i < self.entries:
+                cnt = 0
+                while i + cnt < self.entries and self.lengths[i + cnt] == cur:
+                    cnt += 1
+                w.write(cnt, ilog(self.entries - i))
+                i += cnt
+                cur += 1
+        else:
+            w.write(0, 1)
+            sparse = self.encoding == "sparse"
+            w.write(1 if sparse else 0, 1)
+            for n in self.lengths:
+                if sparse:
+                    w.write(1 if n else 0, 1)
+                if n:
+                    w.write(n - 1, 5)
+        self._write_lookup(w, rng)
 
 
 class IncompleteBook(Book):
@@ -303,6 +353,68 @@ def _floor1_long(class_book, sub_book, rangebits, n_parts=5):
     return lambda w: write_floor1(w, [0] * n_parts, {0: 2}, {0: 1}, {0: class_book}, {0: [sub_book, -1]}, 2, rangebits, xs)
 
 
+def _ladder(a, b):
+    return list(range(a, b + 1))
+
+
+LONGCODE_NAMES = ("longcode_res1", "longcode_res2", "longcode_many_books")
+
+
+def _longcode_config(name, books):
+    """Setups whose codebooks libvorbis never writes (long, sparse, ordered, under-subscribed), one shape per route of the two
+    parsers' symbol decode (host_setup.cpp: generate_table / Codebook::decode_scalar; nvh_setup.hip: upload_parse_tables).
+    Stereo, blocks 256 / 2048.  DESIGN.md section 3 lists which book exists for which route; tests/test_long_codes.py asserts,
+    through nvh_stream_parse_book_info, that each book takes it."""
+    T2 = dict(lookup=2, min_me=(-9, -5), delta_me=(1, -4), value_bits=5)
+    LAT = dict(lookup=1, min_me=(-4, -3), delta_me=(1, -2), value_bits=3)
+    cls = VarBook([1, 3, 3, 4, 4, 5, 5, 6, 6, 11, 11, 12, 12, 12, 13, 13], dims=2)  # classbook: 16 words, 7 of them past the prefix
+    fm = VarBook([1, 11, 12, 12])               # floor1 masterbook (under-subscribed)
+    fs = VarBook([1, 11, 12, 12], "ordered")    # floor1 subclass book, written ordered (the reference's max_bits: 13)
+    sparse_few = [0] * 64
+    for k, n in enumerate(_ladder(1, 10) + [14, 14]):
+        sparse_few[5 * k + 1] = n               # 12 of 64 used: stays sparse, entries reached through values[]
+    sparse_many = [0] * 64
+    for pos, n in zip([i for i in range(64) if i % 8 < 5], [2, 11, 3, 12, 13, 3, 4, 11, 4, 12] + [4, 5, 5, 5, 5, 13] + [11, 12, 13] * 8):
+        sparse_many[pos] = n                    # 40 of 64 used: converted to dense, 24 entries stay unused
+    if name == "longcode_res1":
+        new = [cls, fm, fs,
+               VarBook(_ladder(1, 30) + [31, 31], dims=2, **T2),                      # 14: the ladder, dense: max_bits 31
+               VarBook([1] + [12] * 2048, dims=2, **T2),                              # 15: 512 groups of four codes
+               VarBook(_ladder(1, 10) + [17] * 71, dims=2, **LAT),                    # 16: lattice 9 x 9, one group of 71
+               VarBook(_ladder(1, 10) + [18] * 200, dims=2, **T2),                    # 17: one group of 200
+               VarBook(_ladder(1, 10) + [18] * 256, dims=4, **T2),                    # 18: one group of 256
+               VarBook(sparse_few, "sparse", dims=2, **LAT),                          # 19: lattice 8 x 8, sparse
+               VarBook(sparse_many, "sparse", dims=2, **LAT),                         # 20: lattice 8 x 8, sparse -> dense
+               VarBook(_ladder(1, 31) + [31], "ordered", dims=4, **T2)]               # 21: the ladder, ordered: max_bits 32
+        floors = [_floor1_small(0, 1), _floor1_long(12, 13, 10)]
+        residues = [lambda w: write_residue(w, 1, 0, 128, 16, 11, [1, 2, 7, 0], [14, 16, 17, 20, 19]),
+                    lambda w: write_residue(w, 1, 8, 1000, 32, 11, [3, 5, 6, 7], [15, 21, 18, 17, 14, 16, 20, 19, 16])]
+    elif name == "longcode_res2":
+        sparse_t2 = [0] * 64
+        for k, n in enumerate(_ladder(1, 9) + [12]):
+            sparse_t2[6 * k + 2] = n
+        new = [cls, fm, fs,
+               VarBook([5] * 16 + [13] * 4096, dims=2, **T2),                         # 14: 4096 overflow nodes
+               VarBook(_ladder(1, 12) + [24] * 16, dims=2, **T2),                     # 15: a group 14 bits deep
+               VarBook(_ladder(1, 9) + (_ladder(11, 22) + [22]) * 2, dims=4, **T2),   # 16: two groups 12 bits deep
+               VarBook(_ladder(1, 10) + [17] * 71, dims=4, **LAT),                    # 17: lattice 3^4
+               VarBook(_ladder(1, 10) + [15] * 20, dims=3, **T2),                     # 18: dimension 3, explicit table
+               VarBook(_ladder(1, 10) + [16] * 17, dims=3, **LAT),                    # 19: lattice 3^3
+               VarBook(sparse_t2, "sparse", dims=2, **T2)]                            # 20: explicit table, sparse
+        floors = [_floor1_small(12, 13), _floor1_long(0, 1, 10)]
+        residues = [lambda w: write_residue(w, 2, 0, 200, 16, 11, [1, 2, 7, 0], [15, 17, 14, 16, 20]),
+                    lambda w: write_residue(w, 2, 6, 1986, 36, 11, [3, 5, 6, 7], [18, 15, 19, 14, 16, 17, 18, 20, 19])]
+    else:  # eighteen residue books with a 1024-slot prefix table each: 18 K words, the LDS image takes 16 K
+        new = [VarBook(_ladder(1, 10) + [11, 11], dims=2, **T2) for _ in range(18)]  # 11 .. 28
+        floors = [_floor1_small(0, 1), _floor1_long(0, 1, 10)]
+        residues = [lambda w: write_residue(w, 1, 0, 128, 16, 2, [0x3F, 0x1F, 0x3F, 1], list(range(11, 29))),
+                    lambda w: write_residue(w, 1, 8, 1000, 32, 2, [0xAA, 0x55, 3, 0], [28, 27, 26, 25, 24, 23, 22, 21, 12, 11])]
+    return dict(books=books + new, channels=2, block0=256, block1=2048, floors=floors, residues=residues,
+                mappings=[lambda w: write_mapping(w, 2, 1, [(0, 1)], None, [(0, 0)]),
+                          lambda w: write_mapping(w, 2, 1, [(1, 0)], None, [(1, 1)])],
+                modes=[(0, 0), (1, 1)])
+
+
 def config(name):
     # common books: 0 = 1-bit scalar (masterbook / class word helper), 1 = 2-bit scalar (floor posts 0..3),
     # 2 = 4-bit classbook (dim 2, 4 classes), 3 = VQ dim2 16 entries lattice, 4 = VQ dim4 256 entries lattice,
@@ -506,6 +618,8 @@ def config(name):
                  mappings=[lambda w: write_mapping(w, 40, 1, cpl, None, [(0, 0)]),
                            lambda w: write_mapping(w, 40, 1, cpl[::-1], None, [(1, 1)])],
                  modes=[(0, 0), (1, 1)])
+    elif name in LONGCODE_NAMES:
+        c.update(_longcode_config(name, books))
     else:
         raise KeyError(name)
     return c
@@ -514,7 +628,7 @@ def config(name):
 CONFIG_NAMES = ["mono_res0_small_blocks", "stereo_res1_coupled", "three_ch_res2_misaligned", "six_ch_res2_4096",
                 "floor0_stereo", "floor0_slab", "two_submaps", "equal_blocks_overrun", "mono_8192", "stereo_8192", "ch4_res1", "ch5_res2", "ch7_res1", "ch8_res2", "mono_res1_2048",
                 "res0_slab", "odd_dims_slab", "res2_alias_stereo", "two_pass_slab", "res0_3ch",
-                "table_books_pair", "table_books_general", "table_books_b1", "ch9_res2", "ch16_res1_4096", "ch40_res1"]
+                "table_books_pair", "table_books_general", "table_books_b1", "ch9_res2", "ch16_res1_4096", "ch40_res1"] + list(LONGCODE_NAMES)
 
 
 def filtered_stream(oracle, name, npackets, seed, consistent_windows=True):

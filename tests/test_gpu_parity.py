@@ -1085,7 +1085,7 @@ def test_stream_chunks_on_gpu_equal_serial(oracle, gpu_ctx, ogg_bytes, name, gpu
         assert clipped == info["has_clipped"]
 
 
-@pytest.mark.parametrize("name", ["stereo_res1_coupled", "three_ch_res2_misaligned", "equal_blocks_overrun"])
+@pytest.mark.parametrize("name", ["stereo_res1_coupled", "three_ch_res2_misaligned", "equal_blocks_overrun", "longcode_res2"])
 @pytest.mark.parametrize("consistent", [True, False])
 def test_stream_chunks_synthetic(oracle, gpu_ctx, name, consistent):
     """The same on random-bit streams, including inconsistent window flags: cuts are only placed where the lead-in

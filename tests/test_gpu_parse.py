@@ -219,6 +219,76 @@ def test_parse_lanes_of_a_context_do_not_change_the_pcm(oracle, ogg_bytes, lanes
         ctx.close()
 
 
+def _long_code_stream(name, cut):
+    from tests import spec_pin
+    pk, gr = spec_pin.stream24_cut(name) if cut else spec_pin.stream24(name)[:2]
+    return list(pk), list(gr), [0] * len(pk)
+
+
+@pytest.mark.parametrize("name", ["longcode_res1", "longcode_res2", "longcode_many_books"])
+@pytest.mark.parametrize("cut", [False, True])
+def test_long_code_books_equal_oracle(oracle, gpu_ctx, name, cut):
+    """Codebooks libvorbis never writes -- 31-bit ladders (dense and ordered), hundreds of small groups, groups of 200 and 256
+    codes, groups 14 and 21 bits deep, 4096 overflow nodes, sparse books, books left out of LDS, a classbook and floor books with
+    long codes (tests/synth_stream.py: _longcode_config; tests/test_long_codes.py asserts the route each book takes) -- on
+    structured streams that write every code, whole and with every second packet cut inside its second half: the PCM of the host
+    parser and of the GPU parser equals the oracle's bit for bit.  (The replays of test_multi_packet_parser_forms_bit_exact take
+    this through every kernel form.)"""
+    import nvorbis_amd as nv
+    pk, gr, fl = _long_code_stream(name, cut)
+    ref, _ = oracle.decode_packets(pk, gr, fl, clip=True)
+    assert ref.size > 20 * 512 * 2
+    st = nv.Stream(gpu_ctx, pk[0], pk[1], pk[2])
+    try:
+        st.set_gpu_parse(True)  # raises if the shape were outside the GPU parser's limits
+        host = nv.Stream(None, pk[0], pk[1], pk[2])
+        try:  # what the context uploaded is what the host-only plan (the CPU suite's reach assertions) says
+            for b in range(11, 21):
+                assert st.parse_book_info(b) == host.parse_book_info(b), (name, b)
+        finally:
+            host.close()
+    finally:
+        st.close()
+    for gpu_parse in (False, True):
+        for bf in (3, 64):
+            got = _decode(nv, gpu_ctx, pk, gr, fl, gpu_parse, bf)
+            assert got.size == ref.size and np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (name, cut, gpu_parse, bf)
+        # A packet k_parse reports as throwing sends its whole batch through the host parser again (nvh_launch.hip: replay_on_host),
+        # and the PCM above would be right all the same.  No packet here throws: the GPU-parsed batch must go up as k_parse left
+        # it, without residue descriptors from the host (a host-parsed batch, and a replayed one, carries them).
+        st = nv.Stream(gpu_ctx, pk[0], pk[1], pk[2])
+        try:
+            st.set_gpu_parse(gpu_parse)
+            for i in range(3, len(pk)):
+                st.push_packet(pk[i], gr[i], fl[i])
+            b = st.upload_batch()
+            ops = b.stats()["ops"]
+            b.free()
+            assert st.parse_errors == []
+            assert (ops == 0) == gpu_parse, (name, cut, gpu_parse, ops)
+        finally:
+            st.close()
+
+
+@pytest.mark.parametrize("lanes", [1, 8, 32])
+def test_long_code_books_under_parse_lanes(oracle, lanes):
+    """The same streams with the parser's launch shape set on the context: the wave-uniform kernel (1) and several packets per
+    wavefront (8, 32)."""
+    import nvorbis_amd as nv
+    ctx = nv.Context(0)
+    try:
+        ctx.set_parse_lanes(lanes)
+        for name in ("longcode_res1", "longcode_res2", "longcode_many_books"):
+            for cut in (False, True):
+                pk, gr, fl = _long_code_stream(name, cut)
+                ref, _ = oracle.decode_packets(pk, gr, fl, clip=True)
+                got = _decode(nv, ctx, pk, gr, fl, True, 64)
+                assert got.size == ref.size and np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (name, cut, lanes)
+        ctx.set_parse_lanes(0)
+    finally:
+        ctx.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("form", ["NVH_PARSE_LANES=8", "NVH_PARSE_LANES=32", "NVH_PARSE_LANES=16+NVH_NO_PARSE_SUB=1",
                                   "NVH_PARSE_LANES=8+NVH_PARSE_CUR=1", "NVH_PARSE_LANES=8+NVH_PARSE_CUR=0"])

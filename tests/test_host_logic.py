@@ -374,11 +374,12 @@ def _tables(info_fn, tables_fn, handle, b, ok):
                 prefix=prefix[:max(n_prefix, 0) * 5].reshape(-1, 5), overflow=overflow[:max(n_overflow, 0) * 5].reshape(-1, 5))
 
 
-@pytest.mark.parametrize("source", ["1test", "2test", "3test", "issue6test", "synthetic", "synthetic_floor0"])
+@pytest.mark.parametrize("source", ["1test", "2test", "3test", "issue6test", "synthetic", "synthetic_floor0",
+                                    "synthetic_longcode_res1", "synthetic_longcode_res2", "synthetic_longcode_many_books"])
 def test_codebook_tables_product_vs_oracle_vs_spec(oracle, ogg_bytes, source):
     """Codebook.Init / InitLookupTable / Huffman.GenerateTable (Codebook.cs:59-283, Huffman.cs:15-76) compared DIRECTLY, not
     through decoded PCM: for every codebook of the four shipped files and of the synthetic setups (lookup type 2 and
-    sequence_p books included) the product's lengths, VQ lookup table (bit patterns), prefix table and overflow list
+    sequence_p books included; the long-code setups' ordered, sparse, under-subscribed and 31-bit books) the product's lengths, VQ lookup table (bit patterns), prefix table and overflow list
     (nvh_stream_codebook_tables) equal the oracle's, node for node in list order (first-match semantics); and both agree with
     the spec-derived decoder, which shares no code or reading with either: codeword assignment by spec 3.2.1 ("lowest valued
     available codeword", bit-reversed because the stream is LSb-first) and the VQ unpack of spec 3.2.1 / 3.3 in double."""
@@ -386,6 +387,8 @@ def test_codebook_tables_product_vs_oracle_vs_spec(oracle, ogg_bytes, source):
     from tests import synth_stream as ss, vorbis_spec as vs
     if source.startswith("synthetic"):
         name = "floor0_stereo" if source.endswith("floor0") else "three_ch_res2_misaligned"
+        if source[len("synthetic_"):] in ss.LONGCODE_NAMES:
+            name = source[len("synthetic_"):]
         try:
             cfg = ss.config(name)
         except Exception:
@@ -436,6 +439,8 @@ def test_codebook_tables_product_vs_oracle_vs_spec(oracle, ogg_bytes, source):
                 assert np.abs(tab - ref).max() <= 1e-6 * max(1.0, np.abs(ref).max()), b
         if source == "synthetic":
             assert {(1, 0), (1, 1), (2, 0)} <= kinds, kinds
+        if source in ("synthetic_longcode_res1", "synthetic_longcode_res2"):
+            assert {(1, 0), (2, 0)} <= kinds, kinds
     finally:
         O.orc_close(d)
         st.close()

@@ -360,18 +360,26 @@ def _slab_residue_sums(words, h, lat, nch, half, vq=None):
 
 @pytest.mark.parametrize("name", ["3test", "2test", "stereo_res1_coupled", "six_ch_res2_4096", "three_ch_res2_misaligned", "res0_slab",
                                   "odd_dims_slab", "res2_alias_stereo", "two_pass_slab", "res0_3ch", "floor0_slab",
-                                  "table_books_pair", "table_books_general", "table_books_b1", "equal_blocks_overrun"])
+                                  "table_books_pair", "table_books_general", "table_books_b1", "equal_blocks_overrun",
+                                  "longcode_res1", "longcode_res1+cut", "longcode_res2", "longcode_res2+cut",
+                                  "longcode_many_books", "longcode_many_books+cut"])
 def test_slab_residue_sums_match_oracle(oracle, ogg_bytes, name):
     """The residue half of the host-written slabs against the oracle's IResidue.Decode (oracle/orc_residue.c), without a GPU: the
     chains, records and entries of a frame, walked here in the reference's order of additions, must give the oracle's residue
     vectors bit for bit -- for the pair walk (shipped files, coupled stereo, six channels), the quirk-B-1 bin walk and the general
-    walk (Residue0, odd dimensions, aliasing stereo Residue2, two passes, three channels)."""
+    walk (Residue0, odd dimensions, aliasing stereo Residue2, two passes, three channels).  The long-code setups run on their
+    structured 24-frame streams (tests/spec_pin.py: stream24), whole and with every second packet cut short (+cut): every route of
+    the host's symbol decode (prefix table, the slot's group, the plain scan), packets that end inside a long code."""
     import nvorbis_amd as nv
     from tests import synth_stream as ss
     from tests.test_gpu_parity import _open_headers
     if name in ogg_bytes:
         pk, _, _ = nv.demux_ogg(ogg_bytes[name])
         ids = list(range(3, 40)) + list(range(40, len(pk), max(1, (len(pk) - 40) // 12)))
+    elif name.split("+")[0] in ss.LONGCODE_NAMES:
+        from tests import spec_pin
+        pk = list((spec_pin.stream24_cut if name.endswith("+cut") else spec_pin.stream24)(name.split("+")[0])[0])
+        ids = range(3, len(pk))
     else:
         pk, _, _ = ss.filtered_stream(oracle, name, 40, 9)
         ids = range(3, len(pk))

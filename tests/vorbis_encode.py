@@ -34,9 +34,12 @@ class BookEnc:
                 self.code[e] = (_bitrev(w[0], w[1]), w[1])
         self.used = np.asarray(sorted(self.code), dtype=np.int64)
 
-    def put(self, w, e):
+    def put(self, w, e, stats=None, number=None):
         c, n = self.code[int(e)]
         w.write(c, n)
+        if stats is not None:  # written symbols per (book number, code length)
+            sym = stats.setdefault("symbols", {})
+            sym[(number, n)] = sym.get((number, n), 0) + 1
 
 
 class PacketEncoder:
@@ -85,7 +88,7 @@ class PacketEncoder:
             subs.append(cval)
         return ys, subs
 
-    def put_floor(self, w, fl, ys, subs):
+    def put_floor(self, w, fl, ys, subs, stats=None):
         if ys is None:
             w.write(0, 1)
             return
@@ -96,13 +99,13 @@ class PacketEncoder:
         for c, cval in zip(fl.partition_class, subs):
             cdim, cbits = fl.class_dims[c], fl.class_subs[c]
             if cbits:
-                self.enc[fl.class_master[c]].put(w, cval)
+                self.enc[fl.class_master[c]].put(w, cval, stats, fl.class_master[c])
             csub = (1 << cbits) - 1
             for _ in range(cdim):
                 bk = fl.sub_books[c][cval & csub]
                 cval >>= cbits
                 if bk >= 0:
-                    self.enc[bk].put(w, ys[k])
+                    self.enc[bk].put(w, ys[k], stats, bk)
                 else:
                     assert ys[k] == 0
                 k += 1
@@ -182,7 +185,7 @@ class PacketEncoder:
             while part < nparts:
                 if stage == 0:
                     for c in range(ch):
-                        cb.put(w, cw[c, k])
+                        cb.put(w, cw[c, k], stats, res.classbook)
                 for _d in range(cdim):
                     if part >= nparts:
                         break
@@ -197,8 +200,7 @@ class PacketEncoder:
                                 cnt = res.psize // dims if res.type == 0 else (res.psize + dims - 1) // dims
                                 es = be.used[rng.integers(0, be.used.size, cnt)]
                                 for e in es:
-                                    c_, n_ = be.code[int(e)]
-                                    w.write(c_, n_)
+                                    be.put(w, e, stats, bk)
                                 if stats is not None:
                                     stats["vectors"] = stats.get("vectors", 0) + cnt
                                     stats.setdefault("stages", set()).add(stage)
@@ -226,7 +228,7 @@ class PacketEncoder:
                 self.put_floor(w, fl, None, None)
             else:
                 ys, subs = self.random_floor(rng, fl, **(floor_kw or {}))
-                self.put_floor(w, fl, ys, subs)
+                self.put_floor(w, fl, ys, subs, stats)
         if len(silent) < S.channels:  # Residue0.cs:125: nothing is read when every channel is silent
             for sm in range(m.submaps):
                 self.put_residue(w, rng, S.residues[m.submap_residue[sm]], n, class_weights, stats)

@@ -31,6 +31,7 @@ namespace NVorbis.Hip
         readonly bool _mono;   // the ring holds the channels' mean (nvh_stream_synth_mix, NVH_MIX_MONO): one sample per sample time
         readonly int[] _map;   // the ring holds _map.Length output channels, slot j = source channel _map[j] (nvh_stream_synth_map); null: none
         int _outChannels;      // samples of the ring per sample time: _channels, 1 when mixing, or _map.Length
+        NativeMethods.NvhPcmOut _out;   // the above as the descriptor of nvh_stream_synth_out (map and extent are set per call)
         int _ringPos, _ringLen;
         bool _ended, _clip = true;
         long _skip;   // floats to drop in front of the next samples: SeekTo's roll-forward
@@ -61,6 +62,12 @@ namespace NVorbis.Hip
             _pcm16 = pcm16;
             _mono = monoMix;
             _map = channelMap == null ? null : (int[])channelMap.Clone();
+            _out = new NativeMethods.NvhPcmOut
+            {
+                format = pcm16 ? NativeMethods.NVH_PCM_S16 : NativeMethods.NVH_PCM_F32,
+                mix = monoMix ? NativeMethods.NVH_MIX_MONO : NativeMethods.NVH_MIX_NONE,
+                outChannels = _map != null ? _map.Length : 0,
+            };
             _packetProvider = packetProvider ?? throw new ArgumentNullException(nameof(packetProvider));
             _batchPackets = batchPackets;
             NativeMethods.Check(NativeMethods.nvh_ctx_create(device, out _ctx));
@@ -201,26 +208,30 @@ namespace NVorbis.Hip
                 if (frames != 0)
                 {
                     long need = samples * _outChannels;
-                    int mix = _mono ? NativeMethods.NVH_MIX_MONO : NativeMethods.NVH_MIX_NONE;
                     int rc;
                     if (_pcm16)
                     {
                         if (_ring16.Length < need) _ring16 = new short[need];
+                        _out.extent = _ring16.Length;
                         fixed (short* dst = _ring16)
                         fixed (int* map = _map)
-                            rc = _map != null ? NativeMethods.nvh_stream_synth_map(_stream, NativeMethods.NVH_PCM_S16, map, _map.Length, dst, IntPtr.Zero, _ring16.Length, out written) :
-                                 _mono ? NativeMethods.nvh_stream_synth_mix(_stream, NativeMethods.NVH_PCM_S16, mix, dst, IntPtr.Zero, _ring16.Length, out written)
-                                       : NativeMethods.nvh_stream_synth_pcm(_stream, NativeMethods.NVH_PCM_S16, dst, IntPtr.Zero, _ring16.Length, out written);
+                        {
+                            _out.map = map;
+                            rc = NativeMethods.nvh_stream_synth_out(_stream, ref _out, dst, IntPtr.Zero, out written);
+                        }
                     }
                     else
                     {
                         if (_ring.Length < need) _ring = new float[need];
+                        _out.extent = _ring.Length;
                         fixed (float* dst = _ring)
                         fixed (int* map = _map)
-                            rc = _map != null ? NativeMethods.nvh_stream_synth_map(_stream, NativeMethods.NVH_PCM_F32, map, _map.Length, dst, IntPtr.Zero, _ring.Length, out written) :
-                                 _mono ? NativeMethods.nvh_stream_synth_mix(_stream, NativeMethods.NVH_PCM_F32, mix, dst, IntPtr.Zero, _ring.Length, out written)
-                                       : NativeMethods.nvh_stream_synth(_stream, dst, IntPtr.Zero, _ring.Length, out written);
+                        {
+                            _out.map = map;
+                            rc = NativeMethods.nvh_stream_synth_out(_stream, ref _out, dst, IntPtr.Zero, out written);
+                        }
                     }
+                    _out.map = null;
                     _ringPos = 0; _ringLen = (int)written;
                     if (rc != 0)
                     {

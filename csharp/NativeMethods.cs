@@ -93,6 +93,19 @@ namespace NVorbis.Hip
         [DllImport(Lib)] public static extern unsafe int nvh_dev_upload(IntPtr ctx, IntPtr dDst, void* hSrc, UIntPtr bytes);
         [DllImport(Lib)] public static extern unsafe int nvh_dev_download(IntPtr ctx, void* hDst, IntPtr dSrc, UIntPtr bytes);
         [DllImport(Lib)] public static extern int nvh_measure_copy(IntPtr ctx, IntPtr dSrc, IntPtr dDst, UIntPtr bytes, int iters, out float ms);
+        /// <summary>nvh_pcm_out (include/nvorbis_hip.h): what a synthesis call writes.  format NVH_PCM_*, mix NVH_MIX_*, planar 0 / 1,
+        /// outChannels 0 = no channel map (else the entries of map, pinned for the call), extent = capacity in output samples or, planar,
+        /// the plane stride in samples per channel.  The three *_out calls take it; every named synthesis call below is shorthand for one.</summary>
+        [StructLayout(LayoutKind.Sequential)]
+        public unsafe struct NvhPcmOut
+        {
+            public int format, mix, planar, outChannels;
+            public int* map;
+            public long extent;
+        }
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_out(IntPtr stream, ref NvhPcmOut o, void* pcmHost, IntPtr dPcm, out long written);
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_begin_out(IntPtr stream, ref NvhPcmOut o, void* pcmHost, out long expected);
+        [DllImport(Lib)] public static extern unsafe int nvh_batch_synth_out(IntPtr batch, ref NvhPcmOut o, IntPtr dPcm);
         [DllImport(Lib)] public static extern unsafe int nvh_stream_synth(IntPtr stream, float* pcmHost, IntPtr dPcm, long capacity, out long written);
         /// <summary>Pipelined form (pinned destination): the transfer of one batch overlaps the pushes, parse and kernels of the next.</summary>
         [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_begin(IntPtr stream, float* pcmHost, long capacity, out long expected);

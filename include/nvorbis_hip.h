@@ -270,9 +270,43 @@ int nvh_stream_lattice_pool(const nvh_stream *s, uint32_t *out, int64_t cap_word
  * Host only, for tests and tools.  *floats is set even when cap_floats is too small (NVH_ERR_ARGUMENT then). */
 int nvh_stream_vq_pool(const nvh_stream *s, float *out, int64_t cap_floats, int64_t *floats);
 
+/* ---- synthesis: one PCM output descriptor, three calls that take it ----
+ * What a synthesis call writes is said by ONE descriptor: the sample format, the down-mix, the layout, the channel map and
+ * the room the destination has.  nvh_stream_synth_out synthesises the pending batch (H2D descriptors -> kernels -> PCM) into
+ * exactly one of pcm_host / d_pcm and advances the overlap state; nvh_stream_synth_begin_out is its pipelined form for a
+ * page-locked pcm_host (nvh_stream_synth_end retires it); nvh_batch_synth_out launches a device-resident batch.  Every
+ * named synthesis call below (nvh_stream_synth*, nvh_stream_synth_begin*, nvh_batch_synth*) is shorthand for one of the three
+ * with a descriptor filled from its arguments, and keeps the comment that explains its form; a further output form is a
+ * further field here, not a further set of calls.
+ *   format        NVH_PCM_F32 / NVH_PCM_S16 (see nvh_stream_synth_pcm)
+ *   mix           NVH_MIX_NONE / NVH_MIX_MONO (see nvh_stream_synth_mix); not together with planar or a map
+ *   planar        0: interleaved; 1: channel-planar (see nvh_stream_synth_planar).  A field of its own: a planar call with a
+ *                 stride of 0 and nothing to write is legal, so a positive stride cannot be what marks the layout
+ *   out_channels  0: no channel map; else the number of entries of map (see nvh_stream_synth_map)
+ *   map           out_channels entries, read during the call only; ignored when out_channels == 0
+ *   extent        interleaved / mixed: the destination's capacity in output samples; planar: the plane stride in samples per
+ *                 channel.  *written and *expected count in the same unit.
+ * Errors, in this order: NVH_ERR_ARGUMENT for no stream or no descriptor, a planar flag other than 0 / 1, a mix together with
+ * planar or a map; the map's errors (NVH_ERR_ARGUMENT / NVH_ERR_UNSUPPORTED, see nvh_stream_synth_map); NVH_ERR_ARGUMENT for an
+ * unknown format or mix, both destinations (begin: no pcm_host), a misaligned device base; from here on *written / *expected
+ * is 0; NVH_ERR_ARGUMENT for an extent below the pending samples or no destination with PCM to write; NVH_ERR_NO_GPU for a
+ * host-only stream.  (Interleaved unmixed un-mapped PCM -- the descriptor of nvh_stream_synth_pcm -- compares its capacity only
+ * after the device was found and an empty batch returned NVH_OK.) */
+typedef struct nvh_pcm_out {
+  int32_t format;       /* NVH_PCM_* */
+  int32_t mix;          /* NVH_MIX_* */
+  int32_t planar;       /* 0: interleaved; 1: channel-planar (extent is then the plane stride) */
+  int32_t out_channels; /* 0: no channel map; else the number of entries of map */
+  const int32_t *map;   /* out_channels entries, or NULL */
+  int64_t extent;       /* capacity in output samples, or plane stride in samples per channel */
+} nvh_pcm_out;
+int nvh_stream_synth_out(nvh_stream *s, const nvh_pcm_out *out, void *pcm_host, void *d_pcm, int64_t *written);
+int nvh_stream_synth_begin_out(nvh_stream *s, const nvh_pcm_out *out, void *pcm_host, int64_t *expected);
+
 /* Synthesise the pending batch: H2D descriptors -> kernels -> interleaved PCM.  Exactly one of
  * pcm_host / d_pcm is non-NULL; capacity is in floats and must hold pending samples * channels.
- * Advances the overlap state (the last block's tail is carried to the next batch). */
+ * Advances the overlap state (the last block's tail is carried to the next batch).
+ * Shorthand for nvh_stream_synth_out with {NVH_PCM_F32, extent = capacity}. */
 int nvh_stream_synth(nvh_stream *s, float *pcm_host, float *d_pcm, int64_t capacity, int64_t *written);
 /* Pipelined form for a destination in page-locked host memory (nvh_pinned_alloc): nvh_stream_synth_begin queues the upload, the
  * synthesis and -- on a copy stream of its own -- the transfer of the PCM and returns (*expected = floats the batch will
@@ -281,7 +315,8 @@ int nvh_stream_synth(nvh_stream *s, float *pcm_host, float *d_pcm, int64_t capac
  * upload, the parse and the kernels of batch i+1 (begin itself first waits for the kernels of the batch before it -- both flights
  * share one scratch batch -- so what overlaps batch i's kernels is the pushing of batch i+1, which happens before its begin);
  * each needs its own destination buffer until its end call returns.  No counterpart in the
- * reference (its Read is synchronous); nvh_stream_synth must not be mixed in while batches are outstanding (NVH_ERR_ARGUMENT). */
+ * reference (its Read is synchronous); nvh_stream_synth must not be mixed in while batches are outstanding (NVH_ERR_ARGUMENT).
+ * nvh_stream_synth_begin is shorthand for nvh_stream_synth_begin_out with {NVH_PCM_F32, extent = capacity}. */
 int nvh_stream_synth_begin(nvh_stream *s, float *pcm_host, int64_t capacity, int64_t *expected);
 int nvh_stream_synth_end(nvh_stream *s, int64_t *written);
 /* Output formats of the *_pcm forms of the synthesis calls.  NVH_PCM_S16 is libvorbis ov_read's conversion, done inside the
@@ -289,7 +324,7 @@ int nvh_stream_synth_end(nvh_stream *s, int64_t *written);
  * NaN -> 0; out-of-range values saturate without touching HasClipped.  No counterpart in the reference.  The format belongs to
  * the call, not the stream (batches of one stream may alternate).  Capacities, *written and *expected count samples; a 16-bit
  * d_pcm must be 16-byte aligned.  An unknown format, or a misaligned 16-bit d_pcm: NVH_ERR_ARGUMENT.  The float forms above are
- * these with NVH_PCM_F32; nvh_stream_synth_end serves both. */
+ * these with NVH_PCM_F32; nvh_stream_synth_end serves both.  Shorthand for the descriptor calls with {format, extent = capacity}. */
 #define NVH_PCM_F32 0
 #define NVH_PCM_S16 1
 int nvh_stream_synth_pcm(nvh_stream *s, int format, void *pcm_host, void *d_pcm, int64_t capacity, int64_t *written);
@@ -302,7 +337,8 @@ int nvh_stream_synth_begin_pcm(nvh_stream *s, int format, void *pcm_host, int64_
  * when plane_stride equals the batch's length); pinned memory takes it without a bounce.  nvh_stream_synth_end retires planar
  * flights too; planar and interleaved batches of one stream may alternate.  NVH_ERR_ARGUMENT: an unknown format, both
  * destinations or neither (with PCM to write), plane_stride too small, a misaligned device base, batches outstanding.
- * No counterpart in the reference (libvorbis' ov_read_float hands out planes). */
+ * No counterpart in the reference (libvorbis' ov_read_float hands out planes).  Shorthand for the descriptor calls with
+ * {format, planar = 1, extent = plane_stride}. */
 int nvh_stream_synth_planar(nvh_stream *s, int format, void *pcm_host, void *d_pcm, int64_t plane_stride, int64_t *written);
 int nvh_stream_synth_begin_planar(nvh_stream *s, int format, void *pcm_host, int64_t plane_stride, int64_t *expected);
 /* Mixing forms of nvh_stream_synth_pcm / nvh_stream_synth_begin_pcm / nvh_batch_synth_pcm: the channels of a sample time are
@@ -320,7 +356,9 @@ int nvh_stream_synth_begin_planar(nvh_stream *s, int format, void *pcm_host, int
  * falls back to the per-frame overlap kernel (same bits).  nvh_stream_synth_end retires these flights too; mixed and unmixed
  * batches, and formats, may alternate on one stream (the carried tail stays per-channel float planes).  NVH_ERR_ARGUMENT: an
  * unknown mix or format, both destinations or neither (with PCM to write), a capacity below the pending samples, a misaligned
- * device base, batches outstanding.  No counterpart in the reference (NVorbis emits channels as they are). */
+ * device base, batches outstanding.  No counterpart in the reference (NVorbis emits channels as they are).  Shorthand for the
+ * descriptor calls with {format, mix, extent = capacity}; with NVH_MIX_NONE these calls still compare the capacity before
+ * they look for the device, as they do for every mix, where the *_pcm calls compare it after. */
 #define NVH_MIX_NONE 0
 #define NVH_MIX_MONO 1
 int nvh_stream_synth_mix(nvh_stream *s, int format, int mix, void *pcm_host, void *d_pcm, int64_t capacity, int64_t *written);
@@ -345,7 +383,9 @@ int nvh_stream_synth_begin_mix(nvh_stream *s, int format, int mix, void *pcm_hos
  * Errors, in this order: NVH_ERR_ARGUMENT for no stream, a null map, out_channels outside [1, channels], an entry out of range
  * or named twice; NVH_ERR_UNSUPPORTED for a map other than the identity on a stream of more than 8 channels (the map travels
  * as eight nibbles); then the un-mapped twin's own argument errors in its own order.  A map cannot be combined with a mix.
- * No counterpart in the reference (NVorbis emits channels in Vorbis order).
+ * No counterpart in the reference (NVorbis emits channels in Vorbis order).  Shorthand for the descriptor calls with
+ * {format, planar, out_channels, map, extent = capacity or plane_stride}; these calls always ask for a map (a count of 0 is
+ * refused here, where a descriptor with out_channels == 0 has none).
  *
  * nvh_channel_map_wave fills map[0 .. channels) with the Vorbis-to-WAVE permutation for 1 to 8 channels (other counts:
  * NVH_ERR_ARGUMENT).  Derivation: Vorbis I 4.3.9 fixes the order of a stream's channels --
@@ -388,10 +428,13 @@ int nvh_batch_stats(const nvh_batch *b, int64_t *out8);
 int nvh_batch_kernels(const nvh_batch *b, char *buf, int cap);
 /* The same for the batch nvh_stream_synth / nvh_stream_synth_begin launched last (the stream's own look-ahead batch). */
 int nvh_stream_kernels(const nvh_stream *s, char *buf, int cap);
-/* Launch the synthesis kernels for a resident batch (asynchronous on the context's stream);
- * may be repeated, results are identical each time.  d_pcm holds samples*channels floats. */
+/* Launch the synthesis kernels for a resident batch (asynchronous on the context's stream) into the destination `out`
+ * describes (nvh_pcm_out, above); may be repeated, results are identical each time. */
+int nvh_batch_synth_out(nvh_batch *b, const nvh_pcm_out *out, void *d_pcm);
+/* Shorthands for nvh_batch_synth_out, as the stream's named calls are for theirs: interleaved float PCM, d_pcm holds
+ * samples*channels floats ... */
 int nvh_batch_synth(nvh_batch *b, float *d_pcm, int64_t capacity);
-/* The same in an output format (NVH_PCM_*; see nvh_stream_synth_pcm). */
+/* ... the same in an output format (NVH_PCM_*; see nvh_stream_synth_pcm) ... */
 int nvh_batch_synth_pcm(nvh_batch *b, int format, void *d_pcm, int64_t capacity);
 /* ... and channel-planar (see nvh_stream_synth_planar). */
 int nvh_batch_synth_planar(nvh_batch *b, int format, void *d_pcm, int64_t plane_stride);

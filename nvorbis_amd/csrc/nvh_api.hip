@@ -615,8 +615,33 @@ static bool host_pinned(const void* p) {
   return false;
 }
 
-// nvh_stream_synth_pcm / _planar past their own argument checks; `capacity` in the unit of *written (samples, or samples per
-// channel for planar PCM)
+// The head the synchronous and the pipelined path share: upload the pending batch, size its PCM in the layout of `out`, launch the
+// kernels -- into d_pcm where the caller has a device destination, else into `staging` -- and flip the carried tail.  *P: the
+// batch's shape; *dst: where its PCM lies on the device.  `capacity` in the unit of *written.
+static int synth_stage(nvh_stream* s, const PcmOut& out, int64_t capacity, DevBuf& staging, void* d_pcm, PcmShape* P, void** dst) {
+  nvh_batch* b = &s->scratch;
+  s->replay_error = NVH_OK;
+  s->replay_errors.clear();
+  int rc = batch_upload(s, b);
+  if (rc != NVH_OK) return rc;
+  // GPU-parse mode: a batch with a throwing packet was parsed again on the host (nvh_launch.hip: replay_on_host); the
+  // throwing packet contributes nothing, so the batch may emit less than the look-ahead said
+  *P = PcmShape(out, b->pcm_samples, s->setup.channels);
+  if (capacity < P->len) return NVH_ERR_ARGUMENT;
+  *dst = d_pcm;
+  if (!d_pcm) {
+    if ((rc = staging.reserve(P->stage_bytes(out.sample_bytes()))) != NVH_OK) return rc;
+    *dst = staging.p;
+  }
+  rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, *dst, false, nullptr, nullptr,
+                    d_pcm ? out : P->staged(out));
+  if (rc != NVH_OK) return rc;
+  if (b->last_decoded >= 0) s->carry_cur ^= 1;  // the batch wrote its last block's tail into the other buffer
+  return NVH_OK;
+}
+
+// nvh_stream_synth_out past the resolver's argument checks (resolve_out); `capacity` in the unit of *written (samples, or samples
+// per channel for planar PCM)
 static int stream_synth(nvh_stream* s, const PcmOut& out, void* pcm_host, void* d_pcm, int64_t capacity, int64_t* written) {
   if (!s->ctx) return NVH_ERR_NO_GPU;
   if (s->flight[0].on || s->flight[1].on) return NVH_ERR_ARGUMENT;  // pipelined batches outstanding: end them first
@@ -625,26 +650,12 @@ static int stream_synth(nvh_stream* s, const PcmOut& out, void* pcm_host, void* 
   if (s->pending.frames.empty()) return NVH_OK;
   if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
   if (capacity < PcmShape(out, s->pending.pcm_samples, ch).len) return NVH_ERR_ARGUMENT;
-  nvh_batch* b = &s->scratch;
-  s->replay_error = NVH_OK;
-  s->replay_errors.clear();
-  int rc = batch_upload(s, b);
+  PcmShape P(out, 0, ch);
+  void* dst = nullptr;
+  int rc = synth_stage(s, out, capacity, s->pcm, d_pcm, &P, &dst);
   if (rc != NVH_OK) return rc;
-  // GPU-parse mode: a batch with a throwing packet was parsed again on the host (nvh_launch.hip: replay_on_host); the
-  // throwing packet contributes nothing, so the batch may emit less than the look-ahead said
-  const PcmShape P(out, b->pcm_samples, ch);
-  if (capacity < P.len) return NVH_ERR_ARGUMENT;
   const size_t sb = out.sample_bytes();
-  void* dst = d_pcm;
-  if (!dst) {
-    if ((rc = s->pcm.reserve(P.stage_bytes(sb))) != NVH_OK) return rc;
-    dst = s->pcm.p;
-  }
-  rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
-                    d_pcm ? out : P.staged(out));
-  if (rc != NVH_OK) return rc;
   hipStream_t st = s->ctx->stream;
-  if (b->last_decoded >= 0) s->carry_cur ^= 1;  // the batch wrote its last block's tail into the other buffer
   // one read-back, one synchronisation: PCM and the two flag words land in a pinned bounce buffer.  A destination in pinned
   // host memory is written by the copy engine directly; anything else goes through the bounce buffer and one memcpy per plane
   // on this thread.
@@ -697,27 +708,17 @@ static int stream_synth_begin(nvh_stream* s, const PcmOut& out, void* pcm_host, 
     return NVH_OK;
   }
   if (capacity < PcmShape(out, s->pending.pcm_samples, ch).len) return NVH_ERR_ARGUMENT;
-  nvh_batch* b = &s->scratch;
-  s->replay_error = NVH_OK;
-  s->replay_errors.clear();
-  int rc = batch_upload(s, b);
+  int rc = s->h_flags2.reserve(4 * sizeof(int));
   if (rc != NVH_OK) return rc;
-  const PcmShape P(out, b->pcm_samples, ch);
-  if (capacity < P.len) return NVH_ERR_ARGUMENT;
-  const size_t sb = out.sample_bytes();
-  if ((rc = s->pcm2[slot].reserve(P.stage_bytes(sb))) != NVH_OK) return rc;
-  if ((rc = s->h_flags2.reserve(4 * sizeof(int))) != NVH_OK) return rc;
-  void* dst = s->pcm2[slot].p;
-  rc = batch_launch(b, (const float*)s->carry[s->carry_cur].p, (float*)s->carry[s->carry_cur ^ 1].p, dst, false, nullptr, nullptr,
-                    P.staged(out));
-  if (rc != NVH_OK) return rc;
-  if (b->last_decoded >= 0) s->carry_cur ^= 1;
+  PcmShape P(out, 0, ch);
+  void* dst = nullptr;
+  if ((rc = synth_stage(s, out, capacity, s->pcm2[slot], nullptr, &P, &dst)) != NVH_OK) return rc;
   // this batch's flag words, then a clean pair for the next one (all on the launch stream, in order)
   HIP_TRY(hipMemcpyAsync((int*)s->h_flags2.p + 2 * slot, s->flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), st));
   HIP_TRY(hipEventRecord(F.kernels, st));
   HIP_TRY(hipStreamWaitEvent(s->copy_stream, F.kernels, 0));
-  HIP_TRY(planar_readback(pcm_host, P.stride, dst, P.stage, P.len, P.planes, sb, s->copy_stream));
+  HIP_TRY(planar_readback(pcm_host, P.stride, dst, P.stage, P.len, P.planes, out.sample_bytes(), s->copy_stream));
   HIP_TRY(hipEventRecord(F.done, s->copy_stream));
   F.need = P.len;  // (nvh_stream_synth_end reports it: samples per channel for a planar flight)
   F.replay_error = s->replay_error;
@@ -728,77 +729,6 @@ static int stream_synth_begin(nvh_stream* s, const PcmOut& out, void* pcm_host, 
   return NVH_OK;
 }
 
-extern "C" int nvh_stream_synth(nvh_stream* s, float* pcm_host, float* d_pcm, int64_t capacity, int64_t* written) {
-  return nvh_stream_synth_pcm(s, NVH_PCM_F32, pcm_host, d_pcm, capacity, written);
-}
-
-extern "C" int nvh_stream_synth_pcm(nvh_stream* s, int format, void* pcm_host, void* d_pcm, int64_t capacity, int64_t* written) {
-  return nvh_guard([&]() -> int {
-    const PcmOut out{format, 0};
-    if (!s || (pcm_host && d_pcm) || !PcmOut::format_ok(format) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
-    if (written) *written = 0;
-    return stream_synth(s, out, pcm_host, d_pcm, capacity, written);
-  });
-}
-
-extern "C" int nvh_stream_synth_planar(nvh_stream* s, int format, void* pcm_host, void* d_pcm, int64_t plane_stride, int64_t* written) {
-  return nvh_guard([&]() -> int {
-    const PcmOut out{format, planar_launch_stride(plane_stride)};
-    if (!s || (pcm_host && d_pcm) || !PcmOut::format_ok(format) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
-    if (written) *written = 0;
-    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
-    if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
-    return stream_synth(s, out, pcm_host, d_pcm, plane_stride, written);
-  });
-}
-
-extern "C" int nvh_stream_synth_begin(nvh_stream* s, float* pcm_host, int64_t capacity, int64_t* expected) {
-  return nvh_stream_synth_begin_pcm(s, NVH_PCM_F32, pcm_host, capacity, expected);
-}
-
-extern "C" int nvh_stream_synth_begin_pcm(nvh_stream* s, int format, void* pcm_host, int64_t capacity, int64_t* expected) {
-  return nvh_guard([&]() -> int {
-    if (!s || !pcm_host || !PcmOut::format_ok(format)) return NVH_ERR_ARGUMENT;
-    if (expected) *expected = 0;
-    return stream_synth_begin(s, PcmOut{format, 0}, pcm_host, capacity, expected);
-  });
-}
-
-extern "C" int nvh_stream_synth_begin_planar(nvh_stream* s, int format, void* pcm_host, int64_t plane_stride, int64_t* expected) {
-  return nvh_guard([&]() -> int {
-    if (!s || !pcm_host || !PcmOut::format_ok(format)) return NVH_ERR_ARGUMENT;
-    if (expected) *expected = 0;
-    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
-    return stream_synth_begin(s, PcmOut{format, planar_launch_stride(plane_stride)}, pcm_host, plane_stride, expected);
-  });
-}
-
-// The *_mix forms: the *_pcm calls with a down-mix of the channels (NVH_MIX_MONO: one plane, counts per channel).  The mix of
-// one channel is that channel: such a stream takes the *_pcm call, its alignment rule included.
-static PcmOut mix_out(const nvh_stream* s, int format, int mix) {
-  return PcmOut{format, 0, s && s->setup.channels == 1 ? NVH_MIX_NONE : mix};
-}
-extern "C" int nvh_stream_synth_mix(nvh_stream* s, int format, int mix, void* pcm_host, void* d_pcm, int64_t capacity, int64_t* written) {
-  return nvh_guard([&]() -> int {
-    const PcmOut out = mix_out(s, format, mix);
-    if (!s || (pcm_host && d_pcm) || !PcmOut::format_ok(format) || !PcmOut::mix_ok(mix) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
-    if (written) *written = 0;
-    if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
-    if (capacity < PcmShape(out, s->pending.pcm_samples, s->setup.channels).len) return NVH_ERR_ARGUMENT;
-    return stream_synth(s, out, pcm_host, d_pcm, capacity, written);
-  });
-}
-
-extern "C" int nvh_stream_synth_begin_mix(nvh_stream* s, int format, int mix, void* pcm_host, int64_t capacity, int64_t* expected) {
-  return nvh_guard([&]() -> int {
-    if (!s || !pcm_host || !PcmOut::format_ok(format) || !PcmOut::mix_ok(mix)) return NVH_ERR_ARGUMENT;
-    if (expected) *expected = 0;
-    if (capacity < PcmShape(mix_out(s, format, mix), s->pending.pcm_samples, s->setup.channels).len) return NVH_ERR_ARGUMENT;
-    return stream_synth_begin(s, mix_out(s, format, mix), pcm_host, capacity, expected);
-  });
-}
-
-// The *_map forms: the *_pcm / *_planar calls with a channel map (include/nvorbis_hip.h: output slot j = source channel map[j]).
 // The Vorbis-to-WAVE permutations (Vorbis I 4.3.9 against the dwChannelMask bit order; the derivation is in the public header).
 extern "C" int nvh_channel_map_wave(int channels, int32_t* map) {
   static const int8_t kWave[8][8] = {{0}, {0, 1}, {0, 2, 1}, {0, 1, 2, 3}, {0, 2, 1, 3, 4}, {0, 2, 1, 5, 3, 4},
@@ -833,62 +763,131 @@ static int map_out(const nvh_stream* s, const int32_t* map, int out_channels, Pc
   return NVH_OK;
 }
 
-extern "C" int nvh_stream_synth_map(nvh_stream* s, int format, const int32_t* map, int out_channels, void* pcm_host, void* d_pcm,
-                                    int64_t capacity, int64_t* written) {
-  return nvh_guard([&]() -> int {
-    PcmOut out{format, 0};
-    const int rc = map_out(s, map, out_channels, &out);
+// ---- the PCM output descriptor (include/nvorbis_hip.h: nvh_pcm_out) ----
+// Where a named call asks for more than its descriptor says (the behaviour these calls had before the descriptor, kept):
+enum NamedForm {
+  kDescriptor,  // an *_out call, or a named call that is exactly its descriptor
+  kNamedMix,    // nvh_stream_synth_mix / _begin_mix: the early checks below run for NVH_MIX_NONE too
+  kNamedMap,    // the *_map calls: a map is asked for whatever the count, so a count of 0 is the map's error, not "no map"
+};
+
+// The one place that turns (stream, descriptor, destinations) into a checked PcmOut: the argument checks in the order the header
+// states, map_out, the identity map and the mix of one channel falling through to the un-mapped / un-mixed kernels (with those
+// calls' own alignment rule), and *wr = 0.  `b`: the resident batch of nvh_batch_synth_out, else the stream's look-ahead batch
+// is meant; `begin`: the pipelined call, which needs pcm_host and has no device destination.  d->extent is the capacity.
+static int resolve_out(const nvh_stream* s, const nvh_batch* b, const nvh_pcm_out* d, NamedForm form, bool begin, const void* pcm_host,
+                       const void* d_pcm, int64_t* wr, PcmOut* out) {
+  // what no named call can say
+  if (!d || (d->planar & ~1) || (d->mix != NVH_MIX_NONE && (d->planar || d->out_channels != 0))) return NVH_ERR_ARGUMENT;
+  *out = PcmOut{d->format, d->planar ? planar_launch_stride(d->extent) : 0};
+  if (d->out_channels != 0 || form == kNamedMap) {
+    const int rc = map_out(s, d->map, d->out_channels, out);
     if (rc != NVH_OK) return rc;
-    if (!out.mapped()) return nvh_stream_synth_pcm(s, format, pcm_host, d_pcm, capacity, written);
-    if ((pcm_host && d_pcm) || !PcmOut::format_ok(format) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
-    if (written) *written = 0;
-    if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
-    if (capacity < PcmShape(out, s->pending.pcm_samples, s->setup.channels).len) return NVH_ERR_ARGUMENT;
-    return stream_synth(s, out, pcm_host, d_pcm, capacity, written);
+  }
+  if (!s) return NVH_ERR_ARGUMENT;
+  const int ch = s->setup.channels;
+  out->mix = ch == 1 ? NVH_MIX_NONE : d->mix;  // the mix of one channel is that channel
+  if ((begin ? !pcm_host : pcm_host && d_pcm) || !PcmOut::format_ok(d->format) || !PcmOut::mix_ok(d->mix) || !out->dest_ok(d_pcm))
+    return NVH_ERR_ARGUMENT;
+  if (wr) *wr = 0;
+  // The extent against the samples the batch is known to hold, and a destination where there is PCM to write.  NOT for a
+  // stream's interleaved, unmixed, un-mapped PCM (the *_pcm calls, and the identity map that falls through to them):
+  // stream_synth / stream_synth_begin compare that capacity themselves, after the device check, the outstanding-flight check
+  // and the empty batch's NVH_OK.  The forms differed in this before there was a descriptor; the difference is kept as it was.
+  if (b || d->planar || d->mix != NVH_MIX_NONE || out->mapped() || form == kNamedMix) {
+    const int64_t pending = b ? b->pcm_samples : s->pending.pcm_samples;
+    if (d->extent < PcmShape(*out, pending, ch).len || (pending > 0 && !pcm_host && !d_pcm)) return NVH_ERR_ARGUMENT;
+  }
+  return NVH_OK;
+}
+
+static int synth_out(nvh_stream* s, const nvh_pcm_out* d, void* pcm_host, void* d_pcm, int64_t* written, NamedForm form = kDescriptor) {
+  return nvh_guard([&]() -> int {
+    PcmOut out;
+    const int rc = resolve_out(s, nullptr, d, form, false, pcm_host, d_pcm, written, &out);
+    return rc != NVH_OK ? rc : stream_synth(s, out, pcm_host, d_pcm, d->extent, written);
   });
 }
 
-extern "C" int nvh_stream_synth_begin_map(nvh_stream* s, int format, const int32_t* map, int out_channels, void* pcm_host,
-                                          int64_t capacity, int64_t* expected) {
+static int synth_begin_out(nvh_stream* s, const nvh_pcm_out* d, void* pcm_host, int64_t* expected, NamedForm form = kDescriptor) {
   return nvh_guard([&]() -> int {
-    PcmOut out{format, 0};
-    const int rc = map_out(s, map, out_channels, &out);
-    if (rc != NVH_OK) return rc;
-    if (!out.mapped()) return nvh_stream_synth_begin_pcm(s, format, pcm_host, capacity, expected);
-    if (!pcm_host || !PcmOut::format_ok(format)) return NVH_ERR_ARGUMENT;
-    if (expected) *expected = 0;
-    if (capacity < PcmShape(out, s->pending.pcm_samples, s->setup.channels).len) return NVH_ERR_ARGUMENT;
-    return stream_synth_begin(s, out, pcm_host, capacity, expected);
+    PcmOut out;
+    const int rc = resolve_out(s, nullptr, d, form, true, pcm_host, nullptr, expected, &out);
+    return rc != NVH_OK ? rc : stream_synth_begin(s, out, pcm_host, d->extent, expected);
   });
+}
+
+extern "C" int nvh_stream_synth_out(nvh_stream* s, const nvh_pcm_out* out, void* pcm_host, void* d_pcm, int64_t* written) {
+  return synth_out(s, out, pcm_host, d_pcm, written);
+}
+
+extern "C" int nvh_stream_synth_begin_out(nvh_stream* s, const nvh_pcm_out* out, void* pcm_host, int64_t* expected) {
+  return synth_begin_out(s, out, pcm_host, expected);
+}
+
+// The named calls: each fills a descriptor {format, mix, planar, out_channels, map, extent}
+extern "C" int nvh_stream_synth(nvh_stream* s, float* pcm_host, float* d_pcm, int64_t capacity, int64_t* written) {
+  const nvh_pcm_out d{NVH_PCM_F32, NVH_MIX_NONE, 0, 0, nullptr, capacity};
+  return nvh_stream_synth_out(s, &d, pcm_host, d_pcm, written);
+}
+
+extern "C" int nvh_stream_synth_pcm(nvh_stream* s, int format, void* pcm_host, void* d_pcm, int64_t capacity, int64_t* written) {
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 0, 0, nullptr, capacity};
+  return nvh_stream_synth_out(s, &d, pcm_host, d_pcm, written);
+}
+
+extern "C" int nvh_stream_synth_planar(nvh_stream* s, int format, void* pcm_host, void* d_pcm, int64_t plane_stride, int64_t* written) {
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 1, 0, nullptr, plane_stride};
+  return nvh_stream_synth_out(s, &d, pcm_host, d_pcm, written);
+}
+
+extern "C" int nvh_stream_synth_mix(nvh_stream* s, int format, int mix, void* pcm_host, void* d_pcm, int64_t capacity, int64_t* written) {
+  const nvh_pcm_out d{format, mix, 0, 0, nullptr, capacity};
+  return synth_out(s, &d, pcm_host, d_pcm, written, kNamedMix);
+}
+
+extern "C" int nvh_stream_synth_map(nvh_stream* s, int format, const int32_t* map, int out_channels, void* pcm_host, void* d_pcm,
+                                    int64_t capacity, int64_t* written) {
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 0, out_channels, map, capacity};
+  return synth_out(s, &d, pcm_host, d_pcm, written, kNamedMap);
 }
 
 extern "C" int nvh_stream_synth_planar_map(nvh_stream* s, int format, const int32_t* map, int out_channels, void* pcm_host,
                                            void* d_pcm, int64_t plane_stride, int64_t* written) {
-  return nvh_guard([&]() -> int {
-    PcmOut out{format, planar_launch_stride(plane_stride)};
-    const int rc = map_out(s, map, out_channels, &out);
-    if (rc != NVH_OK) return rc;
-    if (!out.mapped()) return nvh_stream_synth_planar(s, format, pcm_host, d_pcm, plane_stride, written);
-    if ((pcm_host && d_pcm) || !PcmOut::format_ok(format) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
-    if (written) *written = 0;
-    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
-    if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
-    return stream_synth(s, out, pcm_host, d_pcm, plane_stride, written);
-  });
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 1, out_channels, map, plane_stride};
+  return synth_out(s, &d, pcm_host, d_pcm, written, kNamedMap);
+}
+
+extern "C" int nvh_stream_synth_begin(nvh_stream* s, float* pcm_host, int64_t capacity, int64_t* expected) {
+  const nvh_pcm_out d{NVH_PCM_F32, NVH_MIX_NONE, 0, 0, nullptr, capacity};
+  return nvh_stream_synth_begin_out(s, &d, pcm_host, expected);
+}
+
+extern "C" int nvh_stream_synth_begin_pcm(nvh_stream* s, int format, void* pcm_host, int64_t capacity, int64_t* expected) {
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 0, 0, nullptr, capacity};
+  return nvh_stream_synth_begin_out(s, &d, pcm_host, expected);
+}
+
+extern "C" int nvh_stream_synth_begin_planar(nvh_stream* s, int format, void* pcm_host, int64_t plane_stride, int64_t* expected) {
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 1, 0, nullptr, plane_stride};
+  return nvh_stream_synth_begin_out(s, &d, pcm_host, expected);
+}
+
+extern "C" int nvh_stream_synth_begin_mix(nvh_stream* s, int format, int mix, void* pcm_host, int64_t capacity, int64_t* expected) {
+  const nvh_pcm_out d{format, mix, 0, 0, nullptr, capacity};
+  return synth_begin_out(s, &d, pcm_host, expected, kNamedMix);
+}
+
+extern "C" int nvh_stream_synth_begin_map(nvh_stream* s, int format, const int32_t* map, int out_channels, void* pcm_host,
+                                          int64_t capacity, int64_t* expected) {
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 0, out_channels, map, capacity};
+  return synth_begin_out(s, &d, pcm_host, expected, kNamedMap);
 }
 
 extern "C" int nvh_stream_synth_begin_planar_map(nvh_stream* s, int format, const int32_t* map, int out_channels, void* pcm_host,
                                                  int64_t plane_stride, int64_t* expected) {
-  return nvh_guard([&]() -> int {
-    PcmOut out{format, planar_launch_stride(plane_stride)};
-    const int rc = map_out(s, map, out_channels, &out);
-    if (rc != NVH_OK) return rc;
-    if (!out.mapped()) return nvh_stream_synth_begin_planar(s, format, pcm_host, plane_stride, expected);
-    if (!pcm_host || !PcmOut::format_ok(format)) return NVH_ERR_ARGUMENT;
-    if (expected) *expected = 0;
-    if (plane_stride < s->pending.pcm_samples) return NVH_ERR_ARGUMENT;
-    return stream_synth_begin(s, out, pcm_host, plane_stride, expected);
-  });
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 1, out_channels, map, plane_stride};
+  return synth_begin_out(s, &d, pcm_host, expected, kNamedMap);
 }
 
 extern "C" int nvh_stream_synth_end(nvh_stream* s, int64_t* written) {
@@ -995,48 +994,50 @@ extern "C" int nvh_stream_kernels(const nvh_stream* s, char* buf, int cap) {
   return nvh_batch_kernels(s ? &s->scratch : nullptr, buf, cap);
 }
 
-extern "C" int nvh_batch_synth(nvh_batch* b, float* d_pcm, int64_t capacity) {
-  return nvh_batch_synth_pcm(b, NVH_PCM_F32, d_pcm, capacity);
-}
-
-// nvh_batch_synth_pcm / _planar: `capacity` in the unit of the batch's PCM in `out` (samples per channel for planar PCM)
-static int batch_synth(nvh_batch* b, const PcmOut& out, void* d_pcm, int64_t capacity) {
+// nvh_batch_synth_out: the resident batch into the destination the descriptor describes
+static int batch_out(nvh_batch* b, const nvh_pcm_out* d, void* d_pcm, NamedForm form = kDescriptor) {
   return nvh_guard([&]() -> int {
-    if (!b || !b->s || !PcmOut::format_ok(out.format) || !PcmOut::mix_ok(out.mix) || !out.dest_ok(d_pcm)) return NVH_ERR_ARGUMENT;
-    nvh_stream* s = b->s;
-    if (capacity < PcmShape(out, b->pcm_samples, s->setup.channels).len) return NVH_ERR_ARGUMENT;
-    if (b->pcm_samples > 0 && !d_pcm) return NVH_ERR_ARGUMENT;
+    nvh_stream* s = b ? b->s : nullptr;
+    PcmOut out;
+    const int rc = resolve_out(s, b, d, form, false, nullptr, d_pcm, nullptr, &out);
+    if (rc != NVH_OK) return rc;
     HIP_TRY(hipSetDevice(s->ctx->device));
     // the stream keeps the tail of the newest batch (written to its current carry buffer; the batch reads its own snapshot)
     return batch_launch(b, (const float*)b->carry_in.p, (float*)s->carry[s->carry_cur].p, d_pcm, false, nullptr, nullptr, out);
   });
 }
 
+extern "C" int nvh_batch_synth_out(nvh_batch* b, const nvh_pcm_out* out, void* d_pcm) { return batch_out(b, out, d_pcm); }
+
+extern "C" int nvh_batch_synth(nvh_batch* b, float* d_pcm, int64_t capacity) {
+  const nvh_pcm_out d{NVH_PCM_F32, NVH_MIX_NONE, 0, 0, nullptr, capacity};
+  return nvh_batch_synth_out(b, &d, d_pcm);
+}
+
 extern "C" int nvh_batch_synth_pcm(nvh_batch* b, int format, void* d_pcm, int64_t capacity) {
-  return batch_synth(b, PcmOut{format, 0}, d_pcm, capacity);
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 0, 0, nullptr, capacity};
+  return nvh_batch_synth_out(b, &d, d_pcm);
 }
 
 extern "C" int nvh_batch_synth_mix(nvh_batch* b, int format, int mix, void* d_pcm, int64_t capacity) {
-  if (!PcmOut::mix_ok(mix)) return NVH_ERR_ARGUMENT;
-  return batch_synth(b, mix_out(b ? b->s : nullptr, format, mix), d_pcm, capacity);
+  const nvh_pcm_out d{format, mix, 0, 0, nullptr, capacity};
+  return nvh_batch_synth_out(b, &d, d_pcm);
 }
 
 extern "C" int nvh_batch_synth_planar(nvh_batch* b, int format, void* d_pcm, int64_t plane_stride) {
-  return batch_synth(b, PcmOut{format, planar_launch_stride(plane_stride)}, d_pcm, plane_stride);
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 1, 0, nullptr, plane_stride};
+  return nvh_batch_synth_out(b, &d, d_pcm);
 }
 
-// ... and with a channel map (the identity map leaves `out` un-mapped: the calls above)
 extern "C" int nvh_batch_synth_map(nvh_batch* b, int format, const int32_t* map, int out_channels, void* d_pcm, int64_t capacity) {
-  PcmOut out{format, 0};
-  const int rc = map_out(b ? b->s : nullptr, map, out_channels, &out);
-  return rc != NVH_OK ? rc : batch_synth(b, out, d_pcm, capacity);
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 0, out_channels, map, capacity};
+  return batch_out(b, &d, d_pcm, kNamedMap);
 }
 
 extern "C" int nvh_batch_synth_planar_map(nvh_batch* b, int format, const int32_t* map, int out_channels, void* d_pcm,
                                           int64_t plane_stride) {
-  PcmOut out{format, planar_launch_stride(plane_stride)};
-  const int rc = map_out(b ? b->s : nullptr, map, out_channels, &out);
-  return rc != NVH_OK ? rc : batch_synth(b, out, d_pcm, plane_stride);
+  const nvh_pcm_out d{format, NVH_MIX_NONE, 1, out_channels, map, plane_stride};
+  return batch_out(b, &d, d_pcm, kNamedMap);
 }
 
 extern "C" int nvh_batch_time(nvh_batch* b, float* d_pcm, int64_t capacity, int iters, float* total_ms,

@@ -33,6 +33,12 @@ class NvhError(RuntimeError):
         super().__init__("%s failed: %d (%s)%s" % (where, code, _ERRNAMES.get(code, "?"), extra))
 
 
+class PcmOut(C.Structure):
+    """nvh_pcm_out: what a synthesis call writes -- sample format, down-mix, layout, channel map, and the destination's room."""
+    _fields_ = [("format", C.c_int32), ("mix", C.c_int32), ("planar", C.c_int32), ("out_channels", C.c_int32),
+                ("map", C.POINTER(C.c_int32)), ("extent", C.c_int64)]
+
+
 # symbol -> (restype, argtypes); also the list tests check against the header
 _u8p, _f32p, _i64p, _i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
 _vp, _vpp, _ip = C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)
@@ -91,6 +97,11 @@ SIGNATURES = {
     "nvh_stream_pending_slabs": (C.c_int, [_vp, _vp, C.c_int64, _i64p, _vp, C.c_int]),
     "nvh_stream_lattice_pool": (C.c_int, [_vp, _vp, C.c_int64, _i64p]),
     "nvh_stream_vq_pool": (C.c_int, [_vp, _vp, C.c_int64, _i64p]),
+    # the descriptor calls (what reader.py uses) ...
+    "nvh_stream_synth_out": (C.c_int, [_vp, C.POINTER(PcmOut), _vp, _vp, _i64p]),
+    "nvh_stream_synth_begin_out": (C.c_int, [_vp, C.POINTER(PcmOut), _vp, _i64p]),
+    "nvh_batch_synth_out": (C.c_int, [_vp, C.POINTER(PcmOut), _vp]),
+    # ... and the named calls, their shorthands
     "nvh_stream_synth_begin": (C.c_int, [_vp, _vp, C.c_int64, _i64p]),
     "nvh_stream_synth_end": (C.c_int, [_vp, _i64p]),
     "nvh_stream_synth": (C.c_int, [_vp, _vp, _vp, C.c_int64, _i64p]),

@@ -90,8 +90,18 @@ def _channel_map(channel_map, channels, mix=None):
     return m
 
 
-def _map_array(m):
-    return (C.c_int32 * len(m))(*m)
+def _pcm_out(dtype, planar, mix, channel_map, channels):
+    """The descriptor (native.PcmOut; the caller sets its extent) of a synthesis call on a stream of `channels` channels, after the
+    ValueError checks of _pcm_format, _mix and _channel_map in that order: (descriptor, numpy dtype, output channels = samples of
+    the output per sample time, whether the call's counts are per channel).  The descriptor keeps its map array alive."""
+    fmt, dt = _pcm_format(dtype)
+    mx = _mix(mix, planar)
+    cmap = _channel_map(channel_map, channels, mix)
+    d = native.PcmOut(format=fmt, mix=mx, planar=int(planar))
+    if cmap is not None:
+        d.out_channels, d.map = len(cmap), (C.c_int32 * len(cmap))(*cmap)  # (a ctypes structure holds on to what it points to)
+    och = len(cmap) if cmap is not None else channels if mx == native.MIX_NONE else 1
+    return d, dt, och, planar or mx != native.MIX_NONE
 
 
 def _ident_channels(packet):
@@ -365,24 +375,9 @@ class Batch:
         (capacity is then not used).  mix="mono": the channels' mean, self.samples samples (capacity counts those).
         channel_map (a sequence of ints, or "wave"): len(map) output channels, output slot j = source channel map[j], in either
         layout (capacity counts output samples); not together with mix."""
-        fmt, _ = _pcm_format(dtype)
-        mx = _mix(mix, plane_stride is not None)
-        cmap = _channel_map(channel_map, self._stream.channels, mix)
-        if cmap is not None:
-            if plane_stride is not None:
-                check(lib().nvh_batch_synth_planar_map(self._h, fmt, _map_array(cmap), len(cmap), C.c_void_p(d_pcm_ptr), int(plane_stride)),
-                      "nvh_batch_synth_planar_map")
-            else:
-                check(lib().nvh_batch_synth_map(self._h, fmt, _map_array(cmap), len(cmap), C.c_void_p(d_pcm_ptr), int(capacity)),
-                      "nvh_batch_synth_map")
-            return
-        if mx != native.MIX_NONE:
-            check(lib().nvh_batch_synth_mix(self._h, fmt, mx, C.c_void_p(d_pcm_ptr), int(capacity)), "nvh_batch_synth_mix")
-            return
-        if plane_stride is not None:
-            check(lib().nvh_batch_synth_planar(self._h, fmt, C.c_void_p(d_pcm_ptr), int(plane_stride)), "nvh_batch_synth_planar")
-            return
-        check(lib().nvh_batch_synth_pcm(self._h, fmt, C.c_void_p(d_pcm_ptr), int(capacity)), "nvh_batch_synth_pcm")
+        d, _, _, _ = _pcm_out(dtype, plane_stride is not None, mix, channel_map, self._stream.channels)
+        d.extent = int(capacity if plane_stride is None else plane_stride)
+        check(lib().nvh_batch_synth_out(self._h, C.byref(d), C.c_void_p(d_pcm_ptr)), "nvh_batch_synth_out")
 
     def time(self, d_pcm_ptr, capacity, iters, per_kernel=True):
         total = C.c_float(0)
@@ -676,13 +671,8 @@ class Stream:
         channel_map (a sequence of ints, or "wave" for the Vorbis-to-WAVE order): len(map) output channels, output slot j holding
         source channel map[j] -- exactly the samples the un-mapped call emits for that channel -- in either layout; not together
         with mix."""
-        fmt, dt = _pcm_format(dtype)
-        mx = _mix(mix, planar)
-        cmap = _channel_map(channel_map, self.channels, mix)
+        d, dt, ch, per_channel = _pcm_out(dtype, planar, mix, channel_map, self.channels)
         _, smp = self.pending()
-        ch = self.channels if mx == native.MIX_NONE else 1  # (samples of the output per sample time)
-        if cmap is not None:
-            ch = len(cmap)
         if out is None:
             shape = _host_shape(smp, ch, planar)
             n = int(np.prod(shape))
@@ -697,22 +687,9 @@ class Stream:
             if out.size == 0:
                 out = np.empty(1, dtype=dt)
         wr = C.c_int64(0)
-        if cmap is not None and planar:
-            where = "nvh_stream_synth_planar_map"
-            rc = lib().nvh_stream_synth_planar_map(self._h, fmt, _map_array(cmap), ch, out.ctypes.data, None, out.shape[1], C.byref(wr))
-        elif cmap is not None:
-            where = "nvh_stream_synth_map"
-            rc = lib().nvh_stream_synth_map(self._h, fmt, _map_array(cmap), ch, out.ctypes.data, None, out.size, C.byref(wr))
-        elif planar:
-            where = "nvh_stream_synth_planar"
-            rc = lib().nvh_stream_synth_planar(self._h, fmt, out.ctypes.data, None, out.shape[1], C.byref(wr))
-        elif mx != native.MIX_NONE:
-            where = "nvh_stream_synth_mix"
-            rc = lib().nvh_stream_synth_mix(self._h, fmt, mx, out.ctypes.data, None, out.size, C.byref(wr))
-        else:
-            where = "nvh_stream_synth_pcm"
-            rc = lib().nvh_stream_synth_pcm(self._h, fmt, out.ctypes.data, None, out.size, C.byref(wr))
-        self._note_parse_error(rc, wr.value, where, planar=planar or mx != native.MIX_NONE, channels=ch)
+        d.extent = out.shape[1] if planar else out.size
+        rc = lib().nvh_stream_synth_out(self._h, C.byref(d), out.ctypes.data, None, C.byref(wr))
+        self._note_parse_error(rc, wr.value, "nvh_stream_synth_out", planar=per_channel, channels=ch)
         return out[:, :wr.value] if planar else out[:wr.value]
 
     # ---- pipelined read-back (nvh_stream_synth_begin / _end) ----
@@ -721,35 +698,22 @@ class Stream:
         Two batches may be outstanding; synth_end() hands them back in order, each in the dtype of its begin (float32 / int16),
         and -- planar=True -- as a (channels, n) view of channel-planar PCM (the return value is then per channel too);
         mix="mono": the channels' mean, n samples.  channel_map: as in synth_host."""
-        fmt, dt = _pcm_format(dtype)
-        mx = _mix(mix, planar)
-        cmap = _channel_map(channel_map, self.channels, mix)
+        d, dt, och, per_channel = _pcm_out(dtype, planar, mix, channel_map, self.channels)
         if self._pipe_out >= 2:
             # refuse before touching a buffer: slot k is still the DMA destination of the oldest outstanding batch
             raise native.NvhError(native.ERR_ARGUMENT, "nvh_stream_synth_begin (two batches are outstanding: call synth_end first)")
-        och = len(cmap) if cmap is not None else self.channels if mx == native.MIX_NONE else 1
         shape = _host_shape(self.pending()[1], och, planar)
         n = int(np.prod(shape))
         k = self._pipe_next
         out = self._flight_bufs[k].get(n, dt)
         exp = C.c_int64(0)
-        if cmap is not None and planar:
-            check(lib().nvh_stream_synth_begin_planar_map(self._h, fmt, _map_array(cmap), och, out.ctypes.data, shape[1], C.byref(exp)),
-                  "nvh_stream_synth_begin_planar_map")
+        d.extent = shape[1] if planar else out.size
+        check(lib().nvh_stream_synth_begin_out(self._h, C.byref(d), out.ctypes.data, C.byref(exp)), "nvh_stream_synth_begin_out")
+        if planar:
             out = out[:n].reshape(shape)
-        elif cmap is not None:
-            check(lib().nvh_stream_synth_begin_map(self._h, fmt, _map_array(cmap), och, out.ctypes.data, out.size, C.byref(exp)),
-                  "nvh_stream_synth_begin_map")
-        elif planar:
-            check(lib().nvh_stream_synth_begin_planar(self._h, fmt, out.ctypes.data, shape[1], C.byref(exp)), "nvh_stream_synth_begin_planar")
-            out = out[:n].reshape(shape)
-        elif mx != native.MIX_NONE:
-            check(lib().nvh_stream_synth_begin_mix(self._h, fmt, mx, out.ctypes.data, out.size, C.byref(exp)), "nvh_stream_synth_begin_mix")
-        else:
-            check(lib().nvh_stream_synth_begin_pcm(self._h, fmt, out.ctypes.data, out.size, C.byref(exp)), "nvh_stream_synth_begin_pcm")
         # only a begin that succeeded occupies a slot
         self._flight_out[k] = out
-        self._flight_per_channel[k] = planar or mx != native.MIX_NONE  # (what the flight's counts mean)
+        self._flight_per_channel[k] = per_channel  # (what the flight's counts mean)
         self._flight_channels[k] = och
         self._pipe_next = k ^ 1
         self._pipe_out += 1
@@ -780,28 +744,11 @@ class Stream:
         written per channel (capacity is then not used).  mix="mono": the channels' mean (capacity and the return value count
         its samples, one per sample time).  channel_map: as in synth_host (capacity and the return value count output samples;
         a mapped destination need only be aligned to its samples)."""
-        fmt, _ = _pcm_format(dtype)
-        mx = _mix(mix, plane_stride is not None)
-        cmap = _channel_map(channel_map, self.channels, mix)
+        d, _, och, per_channel = _pcm_out(dtype, plane_stride is not None, mix, channel_map, self.channels)
+        d.extent = int(capacity if plane_stride is None else plane_stride)
         wr = C.c_int64(0)
-        if cmap is not None and plane_stride is not None:
-            rc = lib().nvh_stream_synth_planar_map(self._h, fmt, _map_array(cmap), len(cmap), None, C.c_void_p(d_ptr), int(plane_stride), C.byref(wr))
-            self._note_parse_error(rc, wr.value, "nvh_stream_synth_planar_map", planar=True)
-            return wr.value
-        if cmap is not None:
-            rc = lib().nvh_stream_synth_map(self._h, fmt, _map_array(cmap), len(cmap), None, C.c_void_p(d_ptr), int(capacity), C.byref(wr))
-            self._note_parse_error(rc, wr.value, "nvh_stream_synth_map", channels=len(cmap))
-            return wr.value
-        if mx != native.MIX_NONE:
-            rc = lib().nvh_stream_synth_mix(self._h, fmt, mx, None, C.c_void_p(d_ptr), int(capacity), C.byref(wr))
-            self._note_parse_error(rc, wr.value, "nvh_stream_synth_mix", planar=True)
-            return wr.value
-        if plane_stride is not None:
-            rc = lib().nvh_stream_synth_planar(self._h, fmt, None, C.c_void_p(d_ptr), int(plane_stride), C.byref(wr))
-            self._note_parse_error(rc, wr.value, "nvh_stream_synth_planar", planar=True)
-            return wr.value
-        rc = lib().nvh_stream_synth_pcm(self._h, fmt, None, C.c_void_p(d_ptr), int(capacity), C.byref(wr))
-        self._note_parse_error(rc, wr.value, "nvh_stream_synth_pcm")
+        rc = lib().nvh_stream_synth_out(self._h, C.byref(d), None, C.c_void_p(d_ptr), C.byref(wr))
+        self._note_parse_error(rc, wr.value, "nvh_stream_synth_out", planar=per_channel, channels=och)
         return wr.value
 
     def _note_parse_error(self, rc, written, where, planar=False, channels=None):

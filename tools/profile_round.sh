@@ -11,10 +11,13 @@ B="python bench.py --full --no-cpu-baseline --no-configs --no-unfused --c5-scale
 # (the counter passes serialise the launches: a shorter timed region there -- the counters are per launch, a few thousand launches are plenty)
 BP="python bench.py --full --no-cpu-baseline --no-configs --no-unfused --c5-scale 0 --steps 10 --warmup 2 --min-timed-ms 40 --streams 1 $3"
 BUILD=$(python -c "from nvorbis_amd import native; print(native.build_id())" 2>/dev/null | tail -1)
-rocprofv3 --kernel-trace --stats -d $OUT/trace -- $B > $OUT/trace.log 2>&1
-rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -- $BP > $OUT/fetch.log 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -- $BP > $OUT/write.log 2>&1
-rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES -d $OUT/insts -- $BP > $OUT/insts.log 2>&1
+# (each pass under a time limit of its own; a pass that fails or runs out of time ends the script: nothing more is started on the GPU)
+T="timeout -k 10 ${PROFILE_PASS_LIMIT:-420}"
+$T rocprofv3 --kernel-trace --stats -d $OUT/trace -- $B > $OUT/trace.log 2>&1 &&
+$T rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -- $BP > $OUT/fetch.log 2>&1 &&
+$T rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -- $BP > $OUT/write.log 2>&1 &&
+$T rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES -d $OUT/insts -- $BP > $OUT/insts.log 2>&1 ||
+  { rc=$?; echo "profile_round.sh: a pass failed (exit $rc); see $OUT/*.log"; tail -5 $OUT/*.log; exit $rc; }
 python tools/rocprof_summary.py --trace $(find $OUT/trace -name '*.db') --fetch $(find $OUT/fetch -name '*.db') \
   --write $(find $OUT/write -name '*.db') --insts $(find $OUT/insts -name '*.db') --out $OUT/summary \
   --note "$2" --traffic-out $OUT/traffic.json --build "$BUILD" --calibration-from profiles/traffic.json

@@ -74,6 +74,12 @@ namespace NVorbis.Hip
         [DllImport(Lib)] public static extern int nvh_stream_mode_info(IntPtr stream, int modeIndex, out int blockFlag, out int blockSize, out int mapping);
         [DllImport(Lib)] public static extern int nvh_stream_floor_info(IntPtr stream, int floorIndex, out int type, out int postCount, out int range);
         [DllImport(Lib)] public static extern int nvh_stream_pending(IntPtr stream, out int frames, out long samplesPerChannel);
+        /// <summary>A segment boundary: the packets since the last one end as nvh_stream_push_end ends a stream, the pending batch stays; align: a power of two up to 65536.</summary>
+        [DllImport(Lib)] public static extern int nvh_stream_next_segment(IntPtr stream, int align);
+        /// <summary>The pending batch's segments: number, begin and end (samples per channel of the batch's output) of each, the current one last.</summary>
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_pending_segments(IntPtr stream, long* index, long* begin, long* end, int cap, out int count);
+        /// <summary>The same table for the batch the last synthesis call consumed, as finally parsed (GPU-parse mode: after a packet the parser failed on).</summary>
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_segments(IntPtr stream, long* index, long* begin, long* end, int cap, out int count);
         /// <summary>[frames][8] ints: block size (0 = drained tail), start, valid, total, ... of every pending frame.</summary>
         [DllImport(Lib)] public static extern unsafe int nvh_stream_pending_geometry(IntPtr stream, int* geometry, int capFrames);
         /// <summary>Page table of one logical Ogg stream + IPacketProvider.SeekTo over it (Ogg/PacketProvider.cs:56-295), for hosts

@@ -246,6 +246,43 @@ int nvh_stream_push_end(nvh_stream *s);
  * emit_start, emit_count, overlap source frame (-1 none, -2 carried tail), overlap length. */
 int nvh_stream_pending_geometry(const nvh_stream *s, int32_t *out, int cap_frames);
 int nvh_stream_pending(const nvh_stream *s, int *frames, int64_t *pcm_samples_per_channel);
+/* ---- segments: many short runs of packets under one setup in one batch ----
+ * A segment is one independent run of audio packets decoded under the stream's setup: it decodes exactly as a freshly opened
+ * stream of the same three headers would decode it.  Several segments may share one pending batch (one upload, one parse, one
+ * set of launches); a segment may also run across batch boundaries, carried like any stream.
+ *
+ * nvh_stream_next_segment ends the current segment as nvh_stream_push_end would (the previous block's tail is drained unless
+ * an NVH_PKT_EOS packet ended the segment already) and puts the packet state machine into the state nvh_stream_reset leaves:
+ * previous block, position and end of stream forgotten, the next packet a first packet again.  It KEEPS the pending frames,
+ * the sticky HasClipped flag, ClipSamples, the parser choice and outstanding flights.  Then the batch's running output
+ * position (samples per channel) is rounded up to a multiple of `align`, a power of two in [1, 65536] (anything else, or no
+ * stream: NVH_ERR_ARGUMENT).  align = 4 is what the kernels' vector paths ask for (out_pos * channels in whole groups of
+ * four; out_pos itself for planar, mono and mapped PCM): with it a segment that ends on an odd sample does not push every
+ * later segment of the batch onto the per-frame fall-back.  Larger values are for callers who tile.  Segments are numbered
+ * from 0 since nvh_stream_open or the last nvh_stream_reset; two calls in a row make an empty segment.
+ *
+ * nvh_stream_pending_segments describes the pending batch -- read it before the synthesis call that consumes the batch: one
+ * entry per segment that was current while the batch was pending, in order.  The first is the segment that was open when the
+ * batch began (it may contribute nothing to this batch), the last is the current segment.  index[i] is the segment's number,
+ * [begin[i], end[i]) its range in the batch's output in samples per channel, the unit of nvh_stream_pending's count.  A stream
+ * that never calls nvh_stream_next_segment reports the one entry {0, 0, pending samples}.  *count is set even when `cap` is
+ * too small (NVH_ERR_ARGUMENT then).  Host state only: works on a host-only stream.
+ *
+ * nvh_stream_synth_segments is the same table for the batch the last synthesis call CONSUMED (nvh_stream_synth_* of any form;
+ * for a pipelined batch, from its nvh_stream_synth_end on), as that call finally parsed it.  It equals what
+ * nvh_stream_pending_segments said before the call -- except in GPU-parse mode for a batch with a packet the parser fails on
+ * (the call returns that error code together with *written > 0): the look-ahead counted the packet, the batch was parsed again
+ * without it, boundaries and gaps included, and the ranges behind it lie where THIS table says (each begin re-rounded to its
+ * align).  The rule below holds for these ranges.  No entries before the first synthesis call and after nvh_stream_reset.
+ *
+ * THE RULE.  For every output form, the samples of segment k in the batch outputs, taken over its ranges in batch order, are
+ * bit for bit the samples a fresh stream over the same headers and the same packets, granules and flags emits in that form.
+ * Samples in the gaps that `align` opens are zero.  *written, *expected and extents count gaps as samples.
+ * nvh_stream_position reports the current segment.  nvh_stream_parse_errors' samples_before stays an offset into the batch's
+ * output, gaps included.  HasClipped is the OR over every segment since the last reset. */
+int nvh_stream_next_segment(nvh_stream *s, int align);
+int nvh_stream_pending_segments(const nvh_stream *s, int64_t *index, int64_t *begin, int64_t *end, int cap, int *count);
+int nvh_stream_synth_segments(const nvh_stream *s, int64_t *index, int64_t *begin, int64_t *end, int cap, int *count);
 /* The pending frames in the form the synthesis kernels fetch (per-frame slabs: the integer half of Floor1.Apply --
  * UnwrapPosts and the walk over the sorted posts, Floor1.cs:196-297 -- as line segments, the vector writes of
  * Residue0.cs:132-175 / Residue2.cs:23-47 as chain-major records; the entry section in DIGIT form for setups whose residue books

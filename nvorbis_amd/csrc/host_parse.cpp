@@ -529,6 +529,27 @@ void StreamParser::begin_batch() {
   if (prev_frame_ >= 0) prev_frame_ = -2;
 }
 
+int StreamParser::next_segment(FrameBatch& out, int align) {
+  if (align < 1 || align > 65536 || (align & (align - 1)) != 0) return NVH_ERR_ARGUMENT;
+  if (!eos_found_) drain(out);  // push_end
+  out.closed_segments.push_back({segment_, out.segment_begin, out.pcm_samples});
+  // what `StreamParser(s_)` starts from (nvh_stream_reset): prev_frame_ = -1 and prev_end_ = 0 keep the next frame -- the first
+  // of the next batch, if the boundary falls on a batch boundary -- from naming an overlap source, carried tail included
+  has_prev_buf_ = false;
+  prev_start_ = prev_end_ = prev_stop_ = 0;
+  prev_frame_ = -1;
+  prev_n_ = 0;
+  prev_window_off_ = 0;
+  prev_exec_.clear();
+  has_position_ = eos_found_ = false;
+  position_ = emitted_ = 0;
+  ++segment_;
+  const int64_t at = (out.pcm_samples + align - 1) & ~(int64_t)(align - 1);
+  if (at > out.pcm_samples) out.gaps.push_back({out.pcm_samples, at - out.pcm_samples});
+  out.pcm_samples = out.segment_begin = at;
+  return NVH_OK;
+}
+
 int StreamParser::push_packet(const uint8_t* data, int len, int64_t granule, int flags, FrameBatch& out) {
   if (eos_found_) return NVH_OK;  // Read() stops pulling packets once _eosFound (StreamDecoder.cs:343-350)
   BitReader p(data, len);

@@ -63,7 +63,15 @@ struct FrameBatch {
   // frame's packet lies (parallel to `frames`; pseudo-frames carry an empty reference)
   PacketPool pkt_pool;
   std::vector<NvhPacketRef> pkt_refs;
-  int64_t pcm_samples = 0;      // per-channel samples the batch emits
+  int64_t pcm_samples = 0;      // per-channel samples the batch emits (the gaps between segments included)
+  // Segments (StreamParser::next_segment): the segments that ended inside this batch as {number, begin, end} in the batch's
+  // output (samples per channel), where the segment that is still open begins, and the gaps the boundaries' alignment opened
+  // as {position, length} (k_zero_gaps writes them).  clear() starts the next batch: the open segment continues at 0.
+  struct Segment { int64_t index, begin, end; };
+  struct Gap { int64_t pos, len; };
+  std::vector<Segment> closed_segments;
+  std::vector<Gap> gaps;
+  int64_t segment_begin = 0;
   bool sequential_ola = false;  // some overlap region reaches into a tail: apply overlaps in order
   bool clipped_unknown = true;
   void clear() {
@@ -71,6 +79,8 @@ struct FrameBatch {
     links_ok = true;
     pcm_samples = 0;
     sequential_ola = false;
+    closed_segments.clear(); gaps.clear();
+    segment_begin = 0;
   }
 };
 
@@ -91,6 +101,12 @@ class StreamParser {
   int push_end(FrameBatch& out);
   // Call after a batch was handed to synthesis: following frames refer to the carried tail.
   void begin_batch();
+  // A segment boundary: the current run of packets ends as push_end ends it (the previous block's tail is drained unless an
+  // end-of-stream packet was seen), the batch keeps its frames, and the state is a freshly constructed parser's again -- no
+  // previous block, no position, no end of stream; the next packet is a first packet.  The batch's output position is then
+  // rounded up to a multiple of `align` (a power of two in [1, 65536], else NVH_ERR_ARGUMENT); what that skips is a gap.
+  int next_segment(FrameBatch& out, int align);
+  int64_t segment() const { return segment_; }  // number of the current segment, from 0
 
   // IResidue.Decode on its own (Residue0.cs:119-178, fine-grained ABI): the bit-consuming half of one call, starting at
   // bit `bit_offset` of the packet, recorded as a single-frame batch whose only pass is this residue.
@@ -128,7 +144,8 @@ class StreamParser {
   std::vector<uint8_t> prev_exec_;  // per channel, of the previous decoded frame
   bool has_position_ = false, eos_found_ = false;
   int64_t position_ = 0;        // _currentPosition + bufferedSamples
-  int64_t emitted_ = 0;         // total samples emitted since open (per channel)
+  int64_t emitted_ = 0;         // total samples emitted since open (per channel); since the segment's start once there are segments
+  int64_t segment_ = 0;
 };
 
 }  // namespace nvh

@@ -1241,6 +1241,28 @@ k_expand_carry(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, fl
 }
 
 // ================================================================================================
+// Segments (host_parse.h: StreamParser::next_segment): the gaps their alignment opens in a batch's PCM are zeros
+// ================================================================================================
+
+// Workgroup (g, p) zeroes gap g -- gaps[2g] = position, gaps[2g + 1] = length, in samples per channel -- in plane p of the
+// destination: `width` samples of `sample_bytes` per sample time (the output channels of interleaved PCM, 1 for a plane),
+// planes `plane_stride` samples apart (one plane: gridDim.y == 1).  Samples are 2 or 4 bytes and aligned to their size at
+// least: 2-byte stores up to the first and behind the last 16-byte boundary of the gap, 16-byte stores between.
+extern "C" __global__ void __launch_bounds__(256)
+k_zero_gaps(const long long* __restrict__ gaps, unsigned char* __restrict__ dst, int sample_bytes, int width, long long plane_stride) {
+  const long long pos = gaps[2 * (long long)blockIdx.x], len = gaps[2 * (long long)blockIdx.x + 1];
+  unsigned char* p = dst + ((long long)blockIdx.y * plane_stride + pos * width) * sample_bytes;
+  const long long n = len * width * sample_bytes;
+  long long head = (long long)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u);
+  if (head > n) head = n;
+  const long long body = (n - head) & ~15ll;
+  for (long long i = 2 * (long long)threadIdx.x; i < head; i += 512) *(uint16_t*)(p + i) = 0;
+  uint4* q = (uint4*)(p + head);
+  for (long long i = threadIdx.x; i < body / 16; i += 256) q[i] = make_uint4(0u, 0u, 0u, 0u);
+  for (long long i = head + body + 2 * (long long)threadIdx.x; i < n; i += 512) *(uint16_t*)(p + i) = 0;
+}
+
+// ================================================================================================
 // Stand-alone mirrors of the remaining per-packet float loops (fine-grained ABI, unit parity)
 // ================================================================================================
 

@@ -438,6 +438,7 @@ extern "C" int nvh_stream_reset(nvh_stream* s) {
     s->pending.clear();
     s->replay.clear();
     s->replay_error = NVH_OK;
+    s->synth_segments.clear();
     s->parser.reset(new (std::nothrow) nvh::StreamParser(&s->setup));
     if (!s->parser) return NVH_ERR_NOMEM;
     s->parser->set_light(s->gpu_parse);
@@ -505,6 +506,46 @@ extern "C" int nvh_stream_push_end(nvh_stream* s) {
     if (!s) return NVH_ERR_ARGUMENT;
     replay_note(s, ReplayLog::kEnd, nullptr, 0, -1, 0);
     return s->parser->push_end(s->pending);
+  });
+}
+
+// A segment boundary (include/nvorbis_hip.h): the parser's state machine starts over, the pending batch stays.  The sticky
+// clipped flag, ClipSamples, the parser choice and outstanding flights are the stream's, not the state machine's: untouched.
+extern "C" int nvh_stream_next_segment(nvh_stream* s, int align) {
+  return nvh_guard([&]() -> int {
+    if (!s || align < 1 || align > 65536 || (align & (align - 1)) != 0) return NVH_ERR_ARGUMENT;
+    replay_note(s, ReplayLog::kSegment, nullptr, 0, -1, align);
+    return s->parser->next_segment(s->pending, align);
+  });
+}
+
+extern "C" int nvh_stream_pending_segments(const nvh_stream* s, int64_t* index, int64_t* begin, int64_t* end, int cap, int* count) {
+  return nvh_guard([&]() -> int {
+    if (!s || !count || cap < 0 || (cap > 0 && (!index || !begin || !end))) return NVH_ERR_ARGUMENT;
+    const std::vector<nvh::FrameBatch::Segment>& closed = s->pending.closed_segments;
+    const int n = (int)closed.size() + 1;
+    *count = n;
+    if (cap < n) return NVH_ERR_ARGUMENT;
+    for (int i = 0; i < n - 1; i++) {
+      index[i] = closed[(size_t)i].index; begin[i] = closed[(size_t)i].begin; end[i] = closed[(size_t)i].end;
+    }
+    index[n - 1] = s->parser->segment(); begin[n - 1] = s->pending.segment_begin; end[n - 1] = s->pending.pcm_samples;
+    return NVH_OK;
+  });
+}
+
+// The table of the batch the last synthesis call consumed, as that call finally parsed it: in GPU-parse mode a batch with a packet
+// the parser fails on is parsed again during the call, and this -- not the look-ahead's table -- says where its segments lie.
+extern "C" int nvh_stream_synth_segments(const nvh_stream* s, int64_t* index, int64_t* begin, int64_t* end, int cap, int* count) {
+  return nvh_guard([&]() -> int {
+    if (!s || !count || cap < 0 || (cap > 0 && (!index || !begin || !end))) return NVH_ERR_ARGUMENT;
+    const int n = (int)s->synth_segments.size();
+    *count = n;
+    if (cap < n) return NVH_ERR_ARGUMENT;
+    for (int i = 0; i < n; i++) {
+      index[i] = s->synth_segments[(size_t)i].index; begin[i] = s->synth_segments[(size_t)i].begin; end[i] = s->synth_segments[(size_t)i].end;
+    }
+    return NVH_OK;
   });
 }
 
@@ -637,6 +678,7 @@ static int synth_stage(nvh_stream* s, const PcmOut& out, int64_t capacity, DevBu
                     d_pcm ? out : P->staged(out));
   if (rc != NVH_OK) return rc;
   if (b->last_decoded >= 0) s->carry_cur ^= 1;  // the batch wrote its last block's tail into the other buffer
+  s->synth_segments = b->segments;  // (a pipelined batch: until its nvh_stream_synth_end puts the flight's copy back)
   return NVH_OK;
 }
 
@@ -701,6 +743,7 @@ static int stream_synth_begin(nvh_stream* s, const PcmOut& out, void* pcm_host, 
   F.need = 0;
   F.replay_error = NVH_OK;
   F.replay_errors.clear();
+  F.segments.clear();
   if (s->pending.frames.empty()) {  // nothing to do: an outstanding "batch" of zero samples keeps begin / end paired
     HIP_TRY(hipEventRecord(F.done, st));
     F.on = true;
@@ -723,6 +766,7 @@ static int stream_synth_begin(nvh_stream* s, const PcmOut& out, void* pcm_host, 
   F.need = P.len;  // (nvh_stream_synth_end reports it: samples per channel for a planar flight)
   F.replay_error = s->replay_error;
   F.replay_errors = s->replay_errors;
+  F.segments = s->synth_segments;
   F.on = true;
   s->flight_next ^= 1;
   if (expected) *expected = P.len;
@@ -904,6 +948,7 @@ extern "C" int nvh_stream_synth_end(nvh_stream* s, int64_t* written) {
     s->flight_first ^= 1;
     s->replay_error = F.replay_error;  // nvh_stream_parse_errors then describes THIS batch
     s->replay_errors = F.replay_errors;
+    s->synth_segments = F.segments;  // ... and nvh_stream_synth_segments
     if (F.need > 0) {
       const int* h = (const int*)s->h_flags2.p + 2 * slot;
       if (h[1]) s->has_clipped = 1;
@@ -935,10 +980,10 @@ extern "C" int nvh_batch_upload(nvh_stream* s, nvh_batch** out) {
     HIP_TRY(hipSetDevice(s->ctx->device));
     std::unique_ptr<nvh_batch> b(new (std::nothrow) nvh_batch());
     if (b && s && s->ctx) {
-      b->blob.pool = b->work.pool = b->carry_in.pool = b->slabs.pool = b->dev_copy.pool = b->slab3.pool = &s->ctx->pool;
+      b->blob.pool = b->work.pool = b->carry_in.pool = b->slabs.pool = b->dev_copy.pool = b->slab3.pool = b->gap_dev.pool = &s->ctx->pool;
       b->work.uncached = nvh_toggles().uncached_planes;
-      b->h_blob.host = true;
-      b->h_blob.pool = &s->ctx->hpool;
+      b->h_blob.host = b->gap_host.host = true;
+      b->h_blob.pool = b->gap_host.pool = &s->ctx->hpool;
     }
     if (!b) return NVH_ERR_NOMEM;
     // snapshot the tail this batch starts from so that repeated synthesis is idempotent

@@ -63,6 +63,7 @@ __global__ void k_parse_links(int nframes, int channels, NvhFrame* frames, NvhCh
                               uint32_t* carry_exec_out, int last_decoded, NvhParseResult* result, uint4* slabs, int stride_vecs);
 __global__ void k_inverse_couple(float* magnitude, float* angle, int cnt);
 __global__ void k_copy_f4(const float4* src, float4* dst, long long n4);
+__global__ void k_zero_gaps(const long long* gaps, unsigned char* dst, int sample_bytes, int width, long long plane_stride);
 __global__ void k_synth(NvhSynthArgs A NVH_DBG_PARAMS);
 __global__ void k_synth_g(NvhSynthArgs A NVH_DBG_PARAMS);     // + the general bin walk (Residue0, odd dimensions, several passes)
 __global__ void k_synth_tail(NvhSynthArgs A NVH_DBG_PARAMS);  // + the carried tail written in place (kernels_synth.hip: MODE 1)
@@ -349,13 +350,18 @@ struct nvh_batch {
   bool ola_all = false;          // GPU-parsed batch in which k_parse_links withdrew an emission candidate: k_ola_compact over every frame
   int ola_count = 0;             // entries of d_ola_list
   const int* d_ola_list = nullptr;  // inside the descriptor blob
+  // segments (host_parse.h: FrameBatch::gaps): the gaps the boundaries' alignment opened in this batch's output, as
+  // {position, length} pairs in samples per channel, for k_zero_gaps
+  std::vector<nvh::FrameBatch::Gap> gaps;
+  DevBuf gap_dev, gap_host;
+  std::vector<nvh::FrameBatch::Segment> segments;  // the batch's segment table as finally parsed (nvh_stream_synth_segments)
 };
 
 // GPU-parse mode: everything pushed since the last batch boundary, so that a batch in which k_parse found a packet the
 // reference would throw on can be replayed through the host parser (same frames kept, same state, same error code as in
 // host-parse mode) instead of being dropped.
 struct ReplayLog {
-  enum { kPacket = 0, kEnd = 1, kPosition = 2 };
+  enum { kPacket = 0, kEnd = 1, kPosition = 2, kSegment = 3 };  // kSegment: nvh_stream_next_segment, its align in `flags`
   struct Event { int kind; int64_t off, len, granule; int flags; };
   std::vector<uint8_t> bytes;
   std::vector<Event> events;
@@ -388,6 +394,7 @@ struct nvh_stream {
   ReplayLog replay;
   std::unique_ptr<nvh::StreamParser> replay_start;  // parser state at the first logged event
   int replay_error = NVH_OK;                         // first error of the last replay (reported by the synthesis call)
+  std::vector<nvh::FrameBatch::Segment> synth_segments;  // segment table of the batch the last synthesis call consumed, as finally parsed
   std::vector<std::pair<int, int64_t>> replay_errors;  // every error of it: (code, samples per channel the batch emits before that packet)
   // Pipelined read-back (nvh_stream_synth_begin / _end): the PCM of batch i travels to the host on a stream of its own while
   // batch i+1 is uploaded, parsed and synthesised.  Two batches may be outstanding, ended in the order they were begun.
@@ -397,6 +404,7 @@ struct nvh_stream {
     int64_t need = 0;
     int replay_error = NVH_OK;
     std::vector<std::pair<int, int64_t>> replay_errors;
+    std::vector<nvh::FrameBatch::Segment> segments;
   };
   hipStream_t copy_stream = nullptr;
   DevBuf pcm2[2];
@@ -419,6 +427,9 @@ struct nvh_stream {
     h_flags2.host = true;
     h_flags2.pool = c ? &c->hpool : nullptr;
     scratch.blob.pool = scratch.work.pool = scratch.carry_in.pool = scratch.slabs.pool = scratch.dev_copy.pool = scratch.slab3.pool = pool;
+    scratch.gap_dev.pool = pool;
+    scratch.gap_host.host = true;
+    scratch.gap_host.pool = c ? &c->hpool : nullptr;
     scratch.work.uncached = nvh_toggles().uncached_planes;
     h_pcm.host = scratch.h_blob.host = true;
     h_pcm.pool = scratch.h_blob.pool = c ? &c->hpool : nullptr;

@@ -8,6 +8,7 @@ static int collect_parse_result(nvh_stream* s, nvh_batch* b, const NvhParseResul
 static bool slab_shape_ok(const nvh_batch* b);
 static bool slab_size_ok(const nvh_batch* b);
 static void assign_emission(nvh_stream* s, nvh_batch* b, nvh::FrameBatch& P, int fpw, std::vector<int>& ola_list);
+static int batch_upload_frames(nvh_stream* s, nvh_batch* b);
 
 void replay_note(nvh_stream* s, int kind, const uint8_t* data, int len, int64_t granule, int flags) {
   if (!s->gpu_parse) return;
@@ -35,6 +36,7 @@ static int replay_on_host(nvh_stream* s) {
     int rc = NVH_OK;
     if (e.kind == ReplayLog::kEnd) rc = s->parser->push_end(s->pending);
     else if (e.kind == ReplayLog::kPosition) s->parser->set_position_state(e.flags != 0, e.granule);
+    else if (e.kind == ReplayLog::kSegment) rc = s->parser->next_segment(s->pending, e.flags);  // boundaries and gaps as they were
     else rc = s->parser->push_packet(e.len ? s->replay.bytes.data() + e.off : &empty, (int)e.len, e.granule, e.flags, s->pending);
     if (rc != NVH_OK) {
       if (first == NVH_OK) first = rc;
@@ -472,12 +474,34 @@ static void assign_emission(nvh_stream* s, nvh_batch* b, nvh::FrameBatch& P, int
   }
 }
 
+// The batch's gap list to the device (one small copy, on the stream, and only for a batch that has gaps)
+static int upload_gaps(nvh_stream* s, nvh_batch* b) {
+  if (b->gaps.empty()) return NVH_OK;
+  static_assert(sizeof(nvh::FrameBatch::Gap) == 2 * sizeof(long long), "k_zero_gaps reads {position, length} pairs");
+  const size_t bytes = b->gaps.size() * sizeof(nvh::FrameBatch::Gap);
+  int rc = b->gap_dev.reserve(bytes);
+  if (rc == NVH_OK) rc = b->gap_host.reserve(bytes);
+  if (rc != NVH_OK) return rc;
+  std::memcpy(b->gap_host.p, b->gaps.data(), bytes);
+  HIP_TRY(hipMemcpyAsync(b->gap_dev.p, b->gap_host.p, bytes, hipMemcpyHostToDevice, s->ctx->stream));
+  return NVH_OK;
+}
+
 int batch_upload(nvh_stream* s, nvh_batch* b) {
+  int rc = batch_upload_frames(s, b);
+  return rc != NVH_OK ? rc : upload_gaps(s, b);
+}
+
+static int batch_upload_frames(nvh_stream* s, nvh_batch* b) {
   nvh::FrameBatch& P = s->pending;
   b->s = s;
   b->nframes = (int)P.frames.size();
   b->chan_frames = (int)P.chans.size();
   b->pcm_samples = P.pcm_samples;
+  // segments: the batch's table as it is parsed NOW (a replayed batch comes through here again) and the gaps between them
+  b->segments = P.closed_segments;
+  b->segments.push_back({s->parser->segment(), P.segment_begin, P.pcm_samples});
+  b->gaps = P.gaps;
   b->sequential_ola = P.sequential_ola;
   b->last_decoded = -1;
   b->max_ops = b->max_ent = b->max_pass = 0;
@@ -521,7 +545,7 @@ int batch_upload(nvh_stream* s, nvh_batch* b) {
     }
     if ((rc = replay_on_host(s)) != NVH_OK) return rc;
     s->gpu_parse = false;  // this batch goes up as host-parsed descriptors
-    rc = batch_upload(s, b);
+    rc = batch_upload_frames(s, b);  // (takes the segments and gaps of this second parse)
     s->gpu_parse = true;
     s->replay.clear();
     return rc;
@@ -1135,6 +1159,15 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
     if (!compact && !b->block_only && b->last_decoded >= 0 && carry_out)
       HIP_TRY(hipMemcpyAsync(carry_out, (const uint8_t*)b->work.p + (size_t)b->last_decoded * plane_bytes, plane_bytes,
                              hipMemcpyDeviceToDevice, st));
+  }
+  // segments: the gaps between them are zeros in the destination, whatever its form -- gap x out_channels interleaved samples,
+  // or the gap in each plane (one plane for the mono mix).  One launch, and none for a batch without gaps.
+  if (!b->gaps.empty() && d_pcm && !b->block_only) {
+    const int oc = out.out_channels(ch);
+    const bool planes = planar || out.mono();
+    hipLaunchKernelGGL(k_zero_gaps, dim3((unsigned)b->gaps.size(), planar ? (unsigned)oc : 1u), dim3(256), 0, st,
+                       (const long long*)b->gap_dev.p, (unsigned char*)d_pcm, (int)out.sample_bytes(), planes ? 1 : oc,
+                       (long long)plane_stride);
   }
   if (timing) HIP_TRY(hipEventRecord(ev[4], st));
   HIP_TRY(hipGetLastError());

@@ -478,6 +478,31 @@ class Stream:
         check(lib().nvh_stream_pending(self._h, C.byref(fr), C.byref(smp)), "nvh_stream_pending")
         return fr.value, smp.value
 
+    def next_segment(self, align=1):
+        """A segment boundary (nvh_stream_next_segment): what was pushed since the last one ends as push_end ends a stream, the
+        next packet is a first packet again, and the pending batch stays.  The batch's output position is rounded up to a multiple
+        of `align` (a power of two up to 65536; 4 keeps the kernels' vector stores); the samples skipped are zeros in the output."""
+        check(lib().nvh_stream_next_segment(self._h, int(align)), "nvh_stream_next_segment")
+
+    def pending_segments(self):
+        """The pending batch's segments (nvh_stream_pending_segments), to be read before the synthesis call: an int64 array [n, 3]
+        of (segment number, begin, end) in samples per channel of the batch's output, the current segment last."""
+        return self._segments(lib().nvh_stream_pending_segments, "nvh_stream_pending_segments")
+
+    def synth_segments(self):
+        """The same table for the batch the last synthesis call (synth_host, synth_device, synth_end) consumed, as that call
+        finally parsed it (nvh_stream_synth_segments): in GPU-parse mode, where the segments of a batch lie after packets the
+        parser failed on (`parse_errors`) were left out.  [0, 3] before the first synthesis."""
+        return self._segments(lib().nvh_stream_synth_segments, "nvh_stream_synth_segments")
+
+    def _segments(self, fn, where):
+        n = C.c_int(0)
+        fn(self._h, None, None, None, 0, C.byref(n))
+        out = np.zeros((3, max(n.value, 1)), dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        check(fn(self._h, out[0].ctypes.data_as(i64), out[1].ctypes.data_as(i64), out[2].ctypes.data_as(i64), out.shape[1], C.byref(n)), where)
+        return np.ascontiguousarray(out[:, :n.value].T)
+
     def pending_geometry(self):
         fr, _ = self.pending()
         out = np.zeros((max(fr, 1), 8), dtype=np.int32)

@@ -76,6 +76,8 @@ namespace NVorbis.Hip
         [DllImport(Lib)] public static extern int nvh_stream_pending(IntPtr stream, out int frames, out long samplesPerChannel);
         /// <summary>A segment boundary: the packets since the last one end as nvh_stream_push_end ends a stream, the pending batch stays; align: a power of two up to 65536.</summary>
         [DllImport(Lib)] public static extern int nvh_stream_next_segment(IntPtr stream, int align);
+        /// <summary>The current segment's window, before its first packet: emit samples [skip, skip + take) of what the packets would emit (take -1: to the end); pitch &gt; 0: nvh_stream_next_segment pads the segment to pitch samples with zeros.</summary>
+        [DllImport(Lib)] public static extern int nvh_stream_segment_window(IntPtr stream, long skip, long take, long pitch);
         /// <summary>The pending batch's segments: number, begin and end (samples per channel of the batch's output) of each, the current one last.</summary>
         [DllImport(Lib)] public static extern unsafe int nvh_stream_pending_segments(IntPtr stream, long* index, long* begin, long* end, int cap, out int count);
         /// <summary>The same table for the batch the last synthesis call consumed, as finally parsed (GPU-parse mode: after a packet the parser failed on).</summary>

@@ -281,6 +281,46 @@ int nvh_stream_pending(const nvh_stream *s, int *frames, int64_t *pcm_samples_pe
  * nvh_stream_position reports the current segment.  nvh_stream_parse_errors' samples_before stays an offset into the batch's
  * output, gaps included.  HasClipped is the OR over every segment since the last reset. */
 int nvh_stream_next_segment(nvh_stream *s, int align);
+/* ---- windowed segments: crop and pad a segment into a fixed-length row ----
+ * nvh_stream_segment_window applies to the CURRENT segment and is legal only while that segment has seen no packet and no
+ * nvh_stream_push_end -- after nvh_stream_open, nvh_stream_reset or nvh_stream_next_segment; a second call before the first
+ * packet replaces the first.  NVH_ERR_ARGUMENT otherwise, and for: no stream, skip < 0, take < -1, pitch < 0, pitch > 0 with
+ * take < 0 or take > pitch.  nvh_stream_next_segment and nvh_stream_reset restore the default (0, -1, 0), with which
+ * everything is as without the call, bit for bit, the kernels launched included.
+ *
+ * THE RULE, windowed.  Number the samples per channel that a fresh stream over the same headers, packets, granules and flags
+ * emits from 0.  The segment emits exactly those with skip <= e < skip + take (take = -1: no upper end; fewer if the stream
+ * emits fewer), in every output form, bit for bit.  Its ranges in nvh_stream_pending_segments / nvh_stream_synth_segments
+ * cover emitted samples only; HasClipped follows the emitted samples.  nvh_stream_position: `position` keeps counting
+ * un-windowed stream time (the end-of-stream trim needs it), `emitted` counts what was emitted.
+ *
+ * Full window.  Once skip + take samples have been accounted for, the segment takes no more packets, as after an end-of-stream
+ * packet: nvh_stream_push_packet returns NVH_OK without parsing, nvh_stream_push_packets stops there (*consumed excludes such
+ * packets), and in GPU-parse mode they never reach the parser.  The packet that fills the window is parsed whole, only its
+ * emission is cut; the drain at the next boundary emits nothing.
+ *
+ * Pitch.  With pitch > 0, nvh_stream_next_segment -- before its `align` rounding -- advances the output position to the
+ * segment's first output position plus `pitch`: a pad of pitch minus everything the segment emitted, in this batch and in
+ * earlier ones.  The pad is a gap: zeros, outside the segment's range, counted in *written / *expected / extents (pads longer
+ * than a chunk are written by k_zero_rows, one bounded chunk per workgroup).  nvh_stream_push_end does not pad: the last row
+ * is closed with nvh_stream_next_segment.  An empty segment with a pitch is a row of zeros.  For a segment with a pitch the
+ * `align` rounding is applied to the pitch (the next segment begins pitch rounded up to `align` behind this one's first
+ * sample, also where that sample lies in an earlier batch at an odd position), so that with a pitch that `align` divides,
+ * the batch outputs of a run of rows, concatenated, ARE the dense [N, pitch] buffer.
+ *
+ * Two limits.  (1) A pending batch of pads alone (segments that emit nothing) is written by the nvh_stream_synth_* calls; the
+ * pipelined nvh_stream_synth_begin treats a batch without frames as empty, as before, and leaves the pads pending: they join the
+ * next batch that has frames, or are flushed by a synchronous synthesis call.  (2) GPU-parse mode, a segment with a bounded take
+ * that holds a packet the parser fails on: the look-ahead counts that packet's samples towards the window, so the window may be
+ * declared full one or more packets earlier than in host-parse mode; the replay emits nothing for the failing packet and the
+ * packets that were kept out are not there to fill the window: the segment comes out shorter than the host parser's (never
+ * different in the samples it has; nvh_stream_synth_segments tells its true range).  A caller who needs the host parser's
+ * count pushes such a clip with take = -1, or in host-parse mode.
+ *
+ * A frame whose emission the window cuts is emitted by the per-frame overlap kernel; a skip and a take in whole groups of four
+ * samples keep its vector paths, and with them every later frame of the row on paired emission (frame starts lie on multiples
+ * of 64 samples of stream time for blocks of 256 and more).  Python: Stream.segment_window, nv.decode_clip_rows. */
+int nvh_stream_segment_window(nvh_stream *s, int64_t skip, int64_t take, int64_t pitch);
 int nvh_stream_pending_segments(const nvh_stream *s, int64_t *index, int64_t *begin, int64_t *end, int cap, int *count);
 int nvh_stream_synth_segments(const nvh_stream *s, int64_t *index, int64_t *begin, int64_t *end, int cap, int *count);
 /* The pending frames in the form the synthesis kernels fetch (per-frame slabs: the integer half of Floor1.Apply --

@@ -5,16 +5,22 @@ identification and setup headers.  One stream per clip pays for its setup upload
 a read-back per clip; here every group of clips with the same setup is ONE stream, each clip a segment of it
 (Stream.next_segment, include/nvorbis_hip.h), and a batch of `batch_frames` frames -- however many clips that is -- goes
 through one upload, one parse and one set of launches.
+
+decode_clip_rows is the fixed-length form a dataset loader wants: a crop [start, start + length) of every clip, zero-padded
+where the clip is shorter, N rows in one tensor.  Every row is a WINDOWED segment (Stream.segment_window): only the packets the
+crop needs are pushed, the parser cuts the first and the last frame's emission, and the pad is written with the batch.
 """
+import ctypes as C
+
 import numpy as np
 
 from . import native
 from .reader import (Context, Stream, _channel_map, _layout, _mix, _pcm_out, _sample_format, demux_ogg_array)
 
 
-def _clip_error(index, err, where=None):
+def _clip_error(index, err, where=None, call="decode_clips"):
     """`err` (an NvhError) as the error of clip `index`."""
-    e = native.NvhError(err.code, "decode_clips: clip %d: %s" % (index, where or "decode"))
+    e = native.NvhError(err.code, "%s: clip %d: %s" % (call, index, where or "decode"))
     e.clip = index
     return e
 
@@ -174,3 +180,266 @@ def decode_clips(clips, ctx=None, device=0, batch_frames=4096, gpu_parse=True, s
         if own_ctx:
             ctx.close()
     return results
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# rows: crop and pad every clip into a fixed length
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def plan_clip_window(position_after, emitted_after, state_after, total, start, length):
+    """Which packets of a clip a row [start, start + length) needs, from Stream.index_packets' arrays over the clip's audio
+    packets (indices below count audio packets from 0).  Host arithmetic only.  Returns a dict:
+      valid         samples of the row that are the clip's: min(length, max(0, total - start))
+      lead          the lead-in packet, pushed first without granule or flags (it emits nothing: a first packet), or None: the
+                    run starts with the clip's first audio packet as a fresh stream does
+      has_position, position   the serial decoder's position state behind the lead-in (set_position_state), None without one
+      first, last   packets [first, last) follow with their granules and flags
+      skip          the window's skip: `start` minus what the serial decoder had emitted behind the lead-in
+    The first packet to emit is the first whose emitted_after exceeds `start`; the lead-in is the nearest packet before it that
+    decodes with its overlap out of its own tail (state bit 1, value 2: where plan_stream_chunks cuts); the last packet pushed is
+    the first whose emitted_after reaches start + length.  A row with valid == 0 needs no packet at all."""
+    em, state = np.asarray(emitted_after), np.asarray(state_after)
+    n = int(em.size)
+    valid = int(min(length, max(0, total - start)))
+    if valid == 0:
+        return {"valid": 0, "lead": None, "has_position": None, "position": None, "first": 0, "last": 0, "skip": 0}
+    f = int(np.searchsorted(em, start, side="right"))  # the first packet with emitted_after > start (n: only the final drain emits)
+    safe = np.nonzero(state[:f] & 2)[0]
+    lead = int(safe[-1]) if safe.size else None
+    reach = int(np.searchsorted(em, start + length, side="left"))  # the first packet with emitted_after >= start + length
+    last = min(reach + 1, n)
+    if lead is None:
+        return {"valid": valid, "lead": None, "has_position": None, "position": None, "first": 0, "last": last, "skip": int(start)}
+    return {"valid": valid, "lead": lead, "has_position": bool(state[lead] & 4), "position": int(position_after[lead]),
+            "first": lead + 1, "last": max(last, lead + 1), "skip": int(start - em[lead])}
+
+
+def push_clip_window(st, pa, plan, length, room=None, flush=None):
+    """Push one planned row into the current segment of `st` (the caller closes it with next_segment): the window, the lead-in,
+    the position state, the packets.  room() -> how many more frames the pending batch takes, flush() synthesises it; without
+    them everything is pushed at once.  `pa` is the clip's PacketArray (three headers first)."""
+    st.segment_window(plan["skip"], length, length)
+    if plan["valid"] == 0:
+        return
+    if plan["lead"] is not None:
+        if room is not None and room() <= 0:
+            flush()
+        st.push_packet(pa[3 + plan["lead"]], -1, 0)
+        st.set_position_state(plan["has_position"], plan["position"])
+    nxt, last = 3 + plan["first"], 3 + plan["last"]
+    while nxt < last:
+        take = last - nxt
+        if room is not None:
+            r = room()
+            if r <= 0:
+                flush()
+                continue
+            take = min(take, r)
+        took = st.push_packets(pa, nxt, take)
+        nxt += took
+        if took < take:
+            break  # the window is full, or the clip's end-of-stream packet: nothing behind it is pulled
+
+
+class _RowGroup:
+    """One setup's rows on one Stream, written into `buf` -- rows [row0, row0 + len(members)) of the dense buffer -- batch by
+    batch: every batch's destination is the buffer's base plus what the batches before it wrote."""
+
+    def __init__(self, ctx, members, packets, plans, opts, length):
+        self.members, self.packets, self.plans, self.opts, self.length = members, packets, plans, opts, length
+        pa = packets[members[0]]
+        self.stream = Stream(ctx, pa[0], pa[1], pa[2])
+        self.done = 0  # samples per channel written so far: whole rows and the part of the open one
+        self.dests = []  # the destination of every batch
+
+    def run(self, base_ptr, row0, rows_total):
+        """base_ptr: address of the dense buffer (device or host); rows_total: its rows (the planes' stride is rows_total * length)."""
+        o, st = self.opts, self.stream
+        self.base, self.row0, self.rows_total = base_ptr, row0, rows_total
+        if o["gpu_parse"]:
+            try:
+                st.set_gpu_parse(True)
+            except native.NvhError as e:
+                if e.code != native.ERR_UNSUPPORTED:
+                    raise
+        align = 4 if self.length % 4 == 0 else 1
+        # Batches end on row boundaries -- once batch_frames frames are pending and the next batch's destination is one the
+        # kernels take (interleaved 16-bit PCM: 16-byte aligned, which every eighth row boundary is at the latest) -- so that
+        # every row of a batch lies where the vector paths want it; only a row of more than batch_frames frames is cut inside.
+        och, isz = o["och"](st.channels), o["dtype"].itemsize
+        strict = isz == 2 and not o["planar"] and o["mix"] is None and o["map"](st.channels) is None
+        for i in self.members:
+            # a row is cut inside only after 2 * batch_frames frames of its own (what earlier rows left pending does not count
+            # against it; behind a cut inside the row the count starts again)
+            own = [st.pending()[0]]
+
+            def cut_inside():
+                self.flush()
+                own[0] = 0
+            try:
+                push_clip_window(st, self.packets[i], self.plans[i], self.length,
+                                 lambda: own[0] + 2 * o["batch_frames"] - st.pending()[0], cut_inside)
+            except native.NvhError as e:
+                if getattr(e, "clip", None) is not None:
+                    raise
+                raise _clip_error(i, e, "nvh_stream_push_packets", "decode_clip_rows")
+            st.next_segment(align)
+            frames, samples = st.pending()
+            if frames >= o["batch_frames"] and (not strict or (self.base + (self.row0 * self.length + self.done + samples) * och * isz) % 16 == 0):
+                self.flush()
+        self.flush()
+        if self.done != len(self.members) * self.length:
+            raise RuntimeError("decode_clip_rows: %d samples written, %d rows of %d planned" % (self.done, len(self.members), self.length))
+
+    def flush(self):
+        o, st = self.opts, self.stream
+        frames, samples = st.pending()
+        if not frames and not samples:
+            return
+        och, planar, isz = o["och"](st.channels), o["planar"], o["dtype"].itemsize
+        if self.done + samples > len(self.members) * self.length:  # (never write behind the group's rows)
+            raise RuntimeError("decode_clip_rows: a batch of %d samples behind %d does not fit %d rows of %d" %
+                               (samples, self.done, len(self.members), self.length))
+        stride = self.rows_total * self.length
+        at = self.row0 * self.length + self.done  # samples per channel in front of this batch
+        d, _, _, per = _pcm_out(o["dtype"], planar, o["mix"], o["map"](st.channels), st.channels)
+        if planar:
+            ptr, d.extent = self.base + at * isz, stride
+        else:
+            ptr, d.extent = self.base + at * och * isz, samples * och
+        self.dests.append(ptr)
+        wr = C.c_int64(0)
+        if o["device_out"]:
+            rc = native.lib().nvh_stream_synth_out(st._h, C.byref(d), None, C.c_void_p(ptr), C.byref(wr))
+        else:
+            rc = native.lib().nvh_stream_synth_out(st._h, C.byref(d), C.c_void_p(ptr), None, C.byref(wr))
+        st._note_parse_error(rc, wr.value, "nvh_stream_synth_out", planar=per, channels=och)
+        if st.parse_errors:  # GPU-parse mode: a packet of this batch made the parser fail; rows lie `length` apart
+            err, pos = st.parse_errors[0]
+            pos //= 1 if per else och
+            k = min((self.done + pos) // max(self.length, 1), len(self.members) - 1)
+            raise _clip_error(self.members[int(k)], err, "a packet the parser fails on", "decode_clip_rows")
+        self.done += wr.value if per else wr.value // och
+
+
+def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frames=4096, gpu_parse=True, sample_format="f32",
+                     layout="interleaved", mix=None, channel_map=None, device_out=False):
+    """Crop and pad a list of Ogg Vorbis clips (bytes or paths; logical stream 0 of each) into N rows of exactly `length` samples:
+    returns (rows, valid).  Row i holds samples [starts[i], starts[i] + length) of what VorbisReader(clips[i], <the same
+    options>).read_all() returns, per channel, bit for bit, and zeros behind the clip's end; valid[i] (an int64 numpy array) says
+    how many of the row's samples are the clip's -- 0 for a start at or beyond its end.  starts=None: 0 for every clip; starts
+    are ints >= 0, length >= 0.
+
+    Shapes: (N, length, channels) interleaved; (N, length) for mix="mono"; layout="planar": (N, channels, length), returned as a
+    PERMUTED VIEW of the (channels, N, length) buffer the planar kernels write (not contiguous: call .contiguous() /
+    np.ascontiguousarray where that matters).  channels = the output channels (len(channel_map) with a map).  device_out=True: a
+    torch tensor on the device, else a numpy array.  Clips whose output channel counts differ raise ValueError.
+
+    Only the packets a row needs are decoded: per clip the host plans (plan_clip_window, from Stream.index_packets) a one-packet
+    lead-in, the serial decoder's position state behind it and the packets up to the row's end, and pushes them as a windowed
+    segment (Stream.segment_window: skip, take = pitch = length).  Clips are grouped by setup as in decode_clips.  With one
+    group the kernels write the returned buffer itself, batch behind batch; with several, rows are written group by group and
+    returned through one gather.
+
+    Rows are aligned to 4 samples when length % 4 == 0 (else to 1).  Starts and lengths that are multiples of 4 keep the
+    kernels' vector paths and paired emission for the frames inside a row; any other start or length gives the same bits through
+    the per-frame fall-back, slower.
+
+    Batches end on row boundaries once `batch_frames` frames are pending; only a row of more than 2 * batch_frames frames of
+    its own is cut inside, every 2 * batch_frames frames.  LIMIT: such a cut falls on whatever sample the frames end on, and
+    interleaved 16-bit PCM asks for a 16-byte aligned destination (nvh_stream_synth_pcm's rule), so sample_format="s16" with
+    layout="interleaved" and rows that long can fail with NVH_ERR_ARGUMENT: raise batch_frames above half a row's frames
+    (length / 64 + 12 is an upper bound of a row's frames), or use the planar layout, which has no such rule.
+
+    A clip whose headers or packets make the library return an error raises NvhError with the clip's index in the message (and
+    as its `clip` attribute); there are no partial results."""
+    dtype = _sample_format(sample_format)
+    planar = _layout(layout)
+    _mix(mix, planar)
+    if channel_map is not None:
+        _channel_map(channel_map, None, mix)
+    if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0:
+        raise ValueError("length must be an int >= 0, not %r" % (length,))
+    length = int(length)
+    if int(batch_frames) < 1:
+        raise ValueError("batch_frames must be at least 1")
+    clips = list(clips)
+    if starts is None:
+        starts = [0] * len(clips)
+    starts = list(starts)
+    if len(starts) != len(clips):
+        raise ValueError("starts must name one start per clip (%d for %d clips)" % (len(starts), len(clips)))
+    for v in starts:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("starts must be ints >= 0, not %r" % (v,))
+    packets, plans, chans, groups = [], [], [], {}
+    for i, src in enumerate(clips):
+        if isinstance(src, (bytes, bytearray, memoryview)):
+            data = bytes(src)
+        else:
+            with open(src, "rb") as fh:
+                data = fh.read()
+        try:
+            pa = demux_ogg_array(data, 0)
+            if len(pa) < 3:
+                raise native.NvhError(native.ERR_NOT_VORBIS, "decode_clip_rows")
+            probe = Stream(None, pa[0], pa[1], pa[2])
+            try:
+                pos, em, state, total = probe.index_packets(pa, 3)
+                chans.append(_pcm_out(dtype, planar, mix, channel_map, probe.channels)[2])
+            finally:
+                probe.close()
+        except native.NvhError as e:
+            raise _clip_error(i, e, "headers", "decode_clip_rows")
+        packets.append(pa)
+        plans.append(plan_clip_window(pos, em, state, total, int(starts[i]), length))
+        groups.setdefault((pa[0], pa[2]), []).append(i)
+    if len(set(chans)) > 1:
+        raise ValueError("decode_clip_rows: the clips' output channel counts differ (%s)" % sorted(set(chans)))
+    n = len(clips)
+    och = chans[0] if chans else 1
+    valid = np.asarray([p["valid"] for p in plans], dtype=np.int64)
+    mono = mix is not None
+    shape = (och, n, length) if planar else (n, length) if mono else (n, length, och)
+    if device_out:
+        import torch
+        if ctx is not None:
+            device = ctx.device
+        buf = torch.empty(shape, dtype=torch.int16 if dtype == np.dtype(np.int16) else torch.float32, device="cuda:%d" % int(device))
+        base = buf.data_ptr()
+    else:
+        buf = np.empty(shape, dtype=dtype)
+        base = buf.ctypes.data
+    if n and length:
+        own_ctx = ctx is None
+        if own_ctx:
+            ctx = Context(device)
+        opts = {"batch_frames": int(batch_frames), "gpu_parse": bool(gpu_parse), "dtype": dtype, "planar": planar, "mix": mix,
+                "device_out": bool(device_out), "map": lambda ch: _channel_map(channel_map, ch, mix),
+                "och": lambda ch: _pcm_out(dtype, planar, mix, channel_map, ch)[2]}
+        try:
+            row0 = 0
+            for members in groups.values():
+                try:
+                    g = _RowGroup(ctx, members, packets, plans, opts, length)
+                except native.NvhError as e:
+                    raise _clip_error(members[0], e, "nvh_stream_open", "decode_clip_rows")
+                try:
+                    g.run(base, row0, n)
+                finally:
+                    g.stream.close()
+                row0 += len(members)
+        finally:
+            if own_ctx:
+                ctx.close()
+    if len(groups) > 1:  # rows lie group by group: one gather puts them into input order
+        order = np.empty(n, dtype=np.int64)
+        order[np.concatenate([np.asarray(m, dtype=np.int64) for m in groups.values()])] = np.arange(n)
+        if device_out:
+            import torch
+            buf = buf.index_select(1 if planar else 0, torch.as_tensor(order, device=buf.device))
+        else:
+            buf = np.take(buf, order, axis=1 if planar else 0)
+    if planar:
+        buf = buf.permute(1, 0, 2) if device_out else buf.transpose(1, 0, 2)
+    return buf, valid

@@ -480,24 +480,51 @@ int StreamParser::parse_residue(int residue_idx, const uint8_t* data, int len, i
 // stream state machine
 // ---------------------------------------------------------------------------------------------
 
+int StreamParser::set_window(int64_t skip, int64_t take, int64_t pitch) {
+  if (seg_touched_ || skip < 0 || take < -1 || pitch < 0 || (pitch > 0 && (take < 0 || take > pitch))) return NVH_ERR_ARGUMENT;
+  if (take >= 0 && skip > INT64_MAX - take) return NVH_ERR_ARGUMENT;
+  win_skip_ = skip;
+  win_take_ = take;
+  win_pitch_ = pitch;
+  return NVH_OK;
+}
+
+void StreamParser::window_cut(int cnt, int* lo, int* hi) {
+  const int64_t a = std::min<int64_t>(std::max<int64_t>(win_skip_ - raw_, 0), cnt);
+  const int64_t b = win_take_ < 0 ? cnt : std::min<int64_t>(std::max<int64_t>(win_skip_ + win_take_ - raw_, a), cnt);
+  *lo = (int)a;
+  *hi = (int)b;
+  raw_ += cnt;
+}
+
 void StreamParser::drain(FrameBatch& out) {
   // `_prevPacketEnd = _prevPacketStop` (StreamDecoder.cs:352-356): the previous block's windowed tail
   // is emitted as it is, with nothing overlapped onto it.
   int cnt = prev_stop_ - prev_start_;
   if (cnt > 0) {
-    if (prev_frame_ >= 0) {
-      out.frames[(size_t)prev_frame_].emit_count += cnt;
+    int lo, hi;
+    window_cut(cnt, &lo, &hi);  // (no window: 0, cnt)
+    const int kept = hi - lo;
+    if (kept <= 0) {
+      // the segment's window leaves nothing of the tail
+    } else if (prev_frame_ >= 0) {
+      NvhFrame& pf = out.frames[(size_t)prev_frame_];
+      if (pf.emit_count == 0) {  // its own part was cut away (or empty): the emission begins inside the drained part
+        pf.emit_start = prev_start_ + lo;
+        pf.out_pos = out.pcm_samples;
+      }
+      pf.emit_count += kept;
     } else if (prev_frame_ == -2) {
       NvhFrame f;
       std::memset(&f, 0, sizeof f);
       f.n = 0;  // no synthesis: emits the carried tail
       f.ov_frame = -2;
-      f.ov_src = prev_start_;
-      f.ov_len = cnt;
+      f.ov_src = prev_start_ + lo;
+      f.ov_len = kept;
       f.ov_n = prev_n_;
       f.ov_window_off = prev_window_off_;
       f.emit_start = 0;
-      f.emit_count = cnt;
+      f.emit_count = kept;
       f.out_pos = out.pcm_samples;
       f.chan_off = (uint32_t)out.chans.size();
       f.pass_begin = f.pass_end = (uint32_t)out.passes.size();
@@ -510,15 +537,18 @@ void StreamParser::drain(FrameBatch& out) {
       }
       out.frames.push_back(f);
     }
-    out.pcm_samples += cnt;
+    if (kept > 0) {
+      out.pcm_samples += kept;
+      emitted_ += kept;
+    }
     position_ += cnt;
-    emitted_ += cnt;
   }
   prev_end_ = prev_stop_;
   prev_start_ = prev_end_;
 }
 
 int StreamParser::push_end(FrameBatch& out) {
+  seg_touched_ = true;
   if (eos_found_) return NVH_OK;
   eos_found_ = true;  // GetNextPacket() == null (StreamDecoder.cs:472-475)
   drain(out);
@@ -527,6 +557,7 @@ int StreamParser::push_end(FrameBatch& out) {
 
 void StreamParser::begin_batch() {
   if (prev_frame_ >= 0) prev_frame_ = -2;
+  seg_carried_ = emitted_;  // what the open segment emitted into the batches before the next one
 }
 
 int StreamParser::next_segment(FrameBatch& out, int align) {
@@ -542,16 +573,26 @@ int StreamParser::next_segment(FrameBatch& out, int align) {
   prev_window_off_ = 0;
   prev_exec_.clear();
   has_position_ = eos_found_ = false;
+  // The window's pitch: the next segment begins `pitch` behind this one's first output position -- which may lie in an earlier
+  // batch: row0 is that position in this batch's coordinates, below zero then.  The rounding to `align` is then applied to the
+  // pitch, not to the batch position: a row that crossed a batch boundary on an odd sample must not move the rows behind it out
+  // of the dense [N, pitch] buffer the batch outputs add up to.
+  const int64_t row0 = out.segment_begin - seg_carried_;
+  const int64_t pitch = win_pitch_;
   position_ = emitted_ = 0;
+  win_skip_ = win_pitch_ = raw_ = seg_carried_ = 0;
+  win_take_ = -1;
+  seg_touched_ = false;
   ++segment_;
-  const int64_t at = (out.pcm_samples + align - 1) & ~(int64_t)(align - 1);
+  const int64_t at = pitch > 0 ? row0 + ((pitch + align - 1) & ~(int64_t)(align - 1)) : (out.pcm_samples + align - 1) & ~(int64_t)(align - 1);
   if (at > out.pcm_samples) out.gaps.push_back({out.pcm_samples, at - out.pcm_samples});
   out.pcm_samples = out.segment_begin = at;
   return NVH_OK;
 }
 
 int StreamParser::push_packet(const uint8_t* data, int len, int64_t granule, int flags, FrameBatch& out) {
-  if (eos_found_) return NVH_OK;  // Read() stops pulling packets once _eosFound (StreamDecoder.cs:343-350)
+  seg_touched_ = true;
+  if (eos_found_ || window_full()) return NVH_OK;  // Read() stops pulling packets once _eosFound (StreamDecoder.cs:343-350); a full window likewise
   BitReader p(data, len);
   const bool is_eos = (flags & NVH_PKT_EOS) != 0;
   if (flags & NVH_PKT_RESYNC) has_position_ = false;  // StreamDecoder.cs:481-484
@@ -635,13 +676,15 @@ int StreamParser::push_packet(const uint8_t* data, int len, int64_t granule, int
     rollback();
     return NVH_ERR_RUNTIME;
   }
+  int lo, hi;
+  window_cut(cnt, &lo, &hi);  // (no window: 0, cnt)
   f.valid = valid;
-  f.emit_start = prev_start_;
-  f.emit_count = cnt;
+  f.emit_start = prev_start_ + lo;
+  f.emit_count = hi - lo;
   f.out_pos = out.pcm_samples;
-  out.pcm_samples += cnt;
+  out.pcm_samples += hi - lo;
   position_ += cnt;
-  emitted_ += cnt;
+  emitted_ += hi - lo;
   prev_start_ = prev_end_;
   prev_frame_ = idx;
   prev_n_ = f.n;

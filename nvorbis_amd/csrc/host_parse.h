@@ -107,6 +107,16 @@ class StreamParser {
   // rounded up to a multiple of `align` (a power of two in [1, 65536], else NVH_ERR_ARGUMENT); what that skips is a gap.
   int next_segment(FrameBatch& out, int align);
   int64_t segment() const { return segment_; }  // number of the current segment, from 0
+  // The current segment's window (include/nvorbis_hip.h, nvh_stream_segment_window).  Number the samples per channel the
+  // segment's packets emit from 0: only those in [skip, skip + take) are emitted (take = -1: no upper end); every frame keeps
+  // its other fields, its emission -- one contiguous range of its block, the frame's own part followed by a drained tail -- is
+  // intersected with the window, and out_pos is where its first emitted sample goes.  Once skip + take samples are accounted
+  // for the segment takes no more packets (window_full).  pitch > 0: next_segment advances the output position to the segment's
+  // first output position + pitch, counted over every batch the segment ran through; the pad is a gap.  Legal only while the
+  // segment has seen neither a packet nor push_end (else, and for arguments outside the header's rules, NVH_ERR_ARGUMENT);
+  // next_segment restores (0, -1, 0).
+  int set_window(int64_t skip, int64_t take, int64_t pitch);
+  bool window_full() const { return win_take_ >= 0 && raw_ >= win_skip_ + win_take_; }
 
   // IResidue.Decode on its own (Residue0.cs:119-178, fine-grained ABI): the bit-consuming half of one call, starting at
   // bit `bit_offset` of the packet, recorded as a single-frame batch whose only pass is this residue.
@@ -130,6 +140,8 @@ class StreamParser {
   int decode_floor(int floor_idx, BitReader& p, FrameBatch& out, NvhChan& ch, bool* energy);
   int decode_residue(int residue_idx, BitReader& p, int block_size, FrameBatch& out, NvhResPass& pass, uint32_t frame_op_begin);
   void drain(FrameBatch& out);
+  // [raw_, raw_ + cnt) intersected with the window, as offsets [lo, hi) into the cnt samples; raw_ moves on
+  void window_cut(int cnt, int* lo, int* hi);
 
   const Setup* s_;
   bool light_ = false;
@@ -146,6 +158,10 @@ class StreamParser {
   int64_t position_ = 0;        // _currentPosition + bufferedSamples
   int64_t emitted_ = 0;         // total samples emitted since open (per channel); since the segment's start once there are segments
   int64_t segment_ = 0;
+  // the segment's window: raw_ counts what the segment would have emitted without one
+  int64_t win_skip_ = 0, win_take_ = -1, win_pitch_ = 0, raw_ = 0;
+  int64_t seg_carried_ = 0;     // of emitted_: what went into batches before the pending one (begin_batch)
+  bool seg_touched_ = false;    // the segment has seen a packet or push_end
 };
 
 }  // namespace nvh

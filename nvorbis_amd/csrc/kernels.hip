@@ -1262,6 +1262,26 @@ k_zero_gaps(const long long* __restrict__ gaps, unsigned char* __restrict__ dst,
   for (long long i = head + body + 2 * (long long)threadIdx.x; i < n; i += 512) *(uint16_t*)(p + i) = 0;
 }
 
+// The long gaps -- the pad behind a windowed segment, up to its pitch: a whole row of a [N, T] buffer, and in interleaved PCM
+// `width` times that -- are cut into chunks on the host (nvh_launch.hip: upload_gaps), so that one short clip among long rows
+// does not leave ONE workgroup writing megabytes behind the emitting kernels.  Workgroup (k, p) zeroes chunk k --
+// chunks[2k] = position, chunks[2k + 1] = length, in samples per channel, the length bounded -- in plane p, as k_zero_gaps
+// zeroes a gap: 2-byte stores up to the first and behind the last 16-byte boundary, between them 16-byte streaming stores
+// (pcm_store4's: the zeros are written once and read by nobody on the device).
+extern "C" __global__ void __launch_bounds__(256)
+k_zero_rows(const long long* __restrict__ chunks, unsigned char* __restrict__ dst, int sample_bytes, int width, long long plane_stride) {
+  const long long pos = chunks[2 * (long long)blockIdx.x], len = chunks[2 * (long long)blockIdx.x + 1];
+  unsigned char* p = dst + ((long long)blockIdx.y * plane_stride + pos * width) * sample_bytes;
+  const long long n = len * width * sample_bytes;
+  long long head = (long long)((16u - (unsigned)((uintptr_t)p & 15u)) & 15u);
+  if (head > n) head = n;
+  const long long body = (n - head) & ~15ll;
+  for (long long i = 2 * (long long)threadIdx.x; i < head; i += 512) *(uint16_t*)(p + i) = 0;
+  float4* q = (float4*)(p + head);
+  for (long long i = threadIdx.x; i < body / 16; i += 256) pcm_store4(q + i, 0.0f, 0.0f, 0.0f, 0.0f);
+  for (long long i = head + body + 2 * (long long)threadIdx.x; i < n; i += 512) *(uint16_t*)(p + i) = 0;
+}
+
 // ================================================================================================
 // Stand-alone mirrors of the remaining per-packet float loops (fine-grained ABI, unit parity)
 // ================================================================================================

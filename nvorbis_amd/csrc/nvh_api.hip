@@ -44,6 +44,7 @@ const NvhToggles& nvh_toggles() {
     x.no_sleep_wait = on("NVH_NO_SLEEP_WAIT");
     x.no_parse_sort = on("NVH_NO_PARSE_SORT");
     x.ola_segs = num("NVH_OLA_SEGS");
+    x.zero_chunk_kib = num("NVH_ZERO_CHUNK_KIB");
     x.phase_mask = std::getenv("NVH_DEBUG_SPECTRUM_MASK") ? num("NVH_DEBUG_SPECTRUM_MASK") : 15;
     return x;
   }();
@@ -472,6 +473,7 @@ extern "C" int nvh_stream_push_packet(nvh_stream* s, const uint8_t* data, int le
   return nvh_guard([&]() -> int {
     if (!s || (!data && len > 0) || len < 0) return NVH_ERR_ARGUMENT;
     static const uint8_t empty = 0;
+    if (s->parser->window_full()) return s->parser->push_packet(&empty, 0, -1, 0, s->pending);  // (not parsed, not logged: NVH_OK)
     replay_note(s, ReplayLog::kPacket, data, len, granule, flags);
     return s->parser->push_packet(data ? data : &empty, len, granule, flags, s->pending);
   });
@@ -485,7 +487,8 @@ extern "C" int nvh_stream_push_packets(nvh_stream* s, const uint8_t* bytes, cons
     int i = 0;
     // the look-ahead loop of a batched caller: stop when the quota is used up or once the stream has seen its
     // end-of-stream packet (StreamDecoder.cs:343-350: no more packets are pulled after _eosFound)
-    for (; i < n && i < max_packets && !s->parser->eos(); i++) {
+    // ... or once the segment's window is full (nvh_stream_segment_window): such packets are not consumed
+    for (; i < n && i < max_packets && !s->parser->eos() && !s->parser->window_full(); i++) {
       const int64_t len = offsets[i + 1] - offsets[i];
       if (len < 0 || len > 0x7FFFFFFF) return NVH_ERR_ARGUMENT;
       replay_note(s, ReplayLog::kPacket, bytes + offsets[i], (int)len, granules ? granules[i] : -1, flags ? (int)flags[i] : 0);
@@ -516,6 +519,18 @@ extern "C" int nvh_stream_next_segment(nvh_stream* s, int align) {
     if (!s || align < 1 || align > 65536 || (align & (align - 1)) != 0) return NVH_ERR_ARGUMENT;
     replay_note(s, ReplayLog::kSegment, nullptr, 0, -1, align);
     return s->parser->next_segment(s->pending, align);
+  });
+}
+
+// The current segment's window (include/nvorbis_hip.h): the parser's integer state machine cuts every frame's emission to it.
+extern "C" int nvh_stream_segment_window(nvh_stream* s, int64_t skip, int64_t take, int64_t pitch) {
+  return nvh_guard([&]() -> int {
+    if (!s) return NVH_ERR_ARGUMENT;
+    // (noted after the call: a refused window leaves no event; the replay's snapshot then already holds the window, and setting it
+    // again before the segment's first packet is legal)
+    const int rc = s->parser->set_window(skip, take, pitch);
+    if (rc == NVH_OK) replay_note_window(s, skip, take, pitch);
+    return rc;
   });
 }
 
@@ -689,7 +704,7 @@ static int stream_synth(nvh_stream* s, const PcmOut& out, void* pcm_host, void* 
   if (s->flight[0].on || s->flight[1].on) return NVH_ERR_ARGUMENT;  // pipelined batches outstanding: end them first
   HIP_TRY(hipSetDevice(s->ctx->device));
   const int ch = s->setup.channels;
-  if (s->pending.frames.empty()) return NVH_OK;
+  if (s->pending.frames.empty() && s->pending.pcm_samples == 0) return NVH_OK;  // (pads alone are a batch: rows of zeros)
   if (s->pending.pcm_samples > 0 && !pcm_host && !d_pcm) return NVH_ERR_ARGUMENT;
   if (capacity < PcmShape(out, s->pending.pcm_samples, ch).len) return NVH_ERR_ARGUMENT;
   PcmShape P(out, 0, ch);

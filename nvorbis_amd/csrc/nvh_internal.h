@@ -64,6 +64,7 @@ __global__ void k_parse_links(int nframes, int channels, NvhFrame* frames, NvhCh
 __global__ void k_inverse_couple(float* magnitude, float* angle, int cnt);
 __global__ void k_copy_f4(const float4* src, float4* dst, long long n4);
 __global__ void k_zero_gaps(const long long* gaps, unsigned char* dst, int sample_bytes, int width, long long plane_stride);
+__global__ void k_zero_rows(const long long* chunks, unsigned char* dst, int sample_bytes, int width, long long plane_stride);
 __global__ void k_synth(NvhSynthArgs A NVH_DBG_PARAMS);
 __global__ void k_synth_g(NvhSynthArgs A NVH_DBG_PARAMS);     // + the general bin walk (Residue0, odd dimensions, several passes)
 __global__ void k_synth_tail(NvhSynthArgs A NVH_DBG_PARAMS);  // + the carried tail written in place (kernels_synth.hip: MODE 1)
@@ -174,6 +175,7 @@ struct NvhToggles {
   bool no_parse_sub;  // NVH_NO_PARSE_SUB: k_parse_slab_f finds long codes by scanning their groups instead of through the second-level tables (A/B aid)
   bool no_parse_uni;  // NVH_NO_PARSE_UNI: one-packet-per-wavefront batches through k_parse_slab instead of k_parse_slab_u (A/B aid)
   int ola_segs;   // NVH_OLA_SEGS: workgroups per frame in k_ola_compact (default: by frame size)
+  int zero_chunk_kib;  // NVH_ZERO_CHUNK_KIB: k_zero_rows' chunk in KiB of a 4-byte plane (measurement aid; default kZeroChunkSamples)
   int phase_mask;  // debug build only (NVH_DEBUG_SPECTRUM_MASK)
 };
 const NvhToggles& nvh_toggles();
@@ -354,6 +356,10 @@ struct nvh_batch {
   // {position, length} pairs in samples per channel, for k_zero_gaps
   std::vector<nvh::FrameBatch::Gap> gaps;
   DevBuf gap_dev, gap_host;
+  // ... and the long ones -- a windowed segment's pad can be a whole row -- cut into chunks of at most zero_chunk_samples()
+  // samples per channel, {position, length} pairs as well, behind the gaps in gap_dev: one workgroup of k_zero_rows per
+  // (chunk, plane).  `gaps` then holds only the gaps of at most one chunk.
+  std::vector<nvh::FrameBatch::Gap> row_chunks;
   std::vector<nvh::FrameBatch::Segment> segments;  // the batch's segment table as finally parsed (nvh_stream_synth_segments)
 };
 
@@ -361,7 +367,8 @@ struct nvh_batch {
 // reference would throw on can be replayed through the host parser (same frames kept, same state, same error code as in
 // host-parse mode) instead of being dropped.
 struct ReplayLog {
-  enum { kPacket = 0, kEnd = 1, kPosition = 2, kSegment = 3 };  // kSegment: nvh_stream_next_segment, its align in `flags`
+  // kSegment: nvh_stream_next_segment, its align in `flags`; kWindow: nvh_stream_segment_window, skip / take / pitch in off / len / granule
+  enum { kPacket = 0, kEnd = 1, kPosition = 2, kSegment = 3, kWindow = 4 };
   struct Event { int kind; int64_t off, len, granule; int flags; };
   std::vector<uint8_t> bytes;
   std::vector<Event> events;
@@ -506,3 +513,4 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
                  hipEvent_t* ext_ev = nullptr, PcmOut out = PcmOut());  // nvh_launch.hip
 int collect_flags(nvh_stream* s);                                // nvh_launch.hip
 void replay_note(nvh_stream* s, int kind, const uint8_t* data, int len, int64_t granule, int flags);  // nvh_launch.hip
+void replay_note_window(nvh_stream* s, int64_t skip, int64_t take, int64_t pitch);                    // nvh_launch.hip

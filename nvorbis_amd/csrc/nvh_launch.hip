@@ -18,6 +18,13 @@ void replay_note(nvh_stream* s, int kind, const uint8_t* data, int len, int64_t 
   s->replay.events.push_back(e);
 }
 
+// nvh_stream_segment_window's event: skip / take / pitch in off / len / granule, no bytes
+void replay_note_window(nvh_stream* s, int64_t skip, int64_t take, int64_t pitch) {
+  if (!s->gpu_parse) return;
+  if (s->replay.events.empty()) s->replay_start.reset(new nvh::StreamParser(*s->parser));
+  s->replay.events.push_back(ReplayLog::Event{ReplayLog::kWindow, skip, take, pitch, 0});
+}
+
 // k_parse found a packet the managed decoder would throw on.  The host parser in light mode has already walked past the
 // whole look-ahead batch, so: back to the state at the batch boundary, and the logged packets once more through the full
 // host parser.  The throwing packet(s) are consumed and leave no frame -- exactly what a caller of the host-parse mode
@@ -37,6 +44,7 @@ static int replay_on_host(nvh_stream* s) {
     if (e.kind == ReplayLog::kEnd) rc = s->parser->push_end(s->pending);
     else if (e.kind == ReplayLog::kPosition) s->parser->set_position_state(e.flags != 0, e.granule);
     else if (e.kind == ReplayLog::kSegment) rc = s->parser->next_segment(s->pending, e.flags);  // boundaries and gaps as they were
+    else if (e.kind == ReplayLog::kWindow) rc = s->parser->set_window(e.off, e.len, e.granule);  // ... and windows and pads
     else rc = s->parser->push_packet(e.len ? s->replay.bytes.data() + e.off : &empty, (int)e.len, e.granule, e.flags, s->pending);
     if (rc != NVH_OK) {
       if (first == NVH_OK) first = rc;
@@ -475,14 +483,34 @@ static void assign_emission(nvh_stream* s, nvh_batch* b, nvh::FrameBatch& P, int
 }
 
 // The batch's gap list to the device (one small copy, on the stream, and only for a batch that has gaps)
+// k_zero_rows' chunk in samples per channel: 16 KiB of a 4-byte plane (8 KiB of 16-bit samples; times the output channels in
+// interleaved PCM).  The timings of 4, 16 and 64 KiB (tools/time_clip_rows.py --chunks) are in profiles/clip_rows_rates.txt.
+static const int64_t kZeroChunkSamples = 4096;
+static int64_t zero_chunk_samples() {
+  const int kib = nvh_toggles().zero_chunk_kib;
+  return kib > 0 ? (int64_t)kib * 256 : kZeroChunkSamples;
+}
+
 static int upload_gaps(nvh_stream* s, nvh_batch* b) {
-  if (b->gaps.empty()) return NVH_OK;
+  // gaps longer than a chunk (the pads of windowed segments) leave the list for the chunk table: whole chunks, then the rest.
+  // A chunk is a multiple of 8 samples, so that every chunk of a gap begins as far from a 16-byte boundary as the gap does.
+  b->row_chunks.clear();
+  const int64_t chunk = zero_chunk_samples();
+  size_t keep = 0;
+  for (const nvh::FrameBatch::Gap& g : b->gaps) {
+    if (g.len <= chunk) { b->gaps[keep++] = g; continue; }
+    for (int64_t at = 0; at < g.len; at += chunk) b->row_chunks.push_back({g.pos + at, std::min(chunk, g.len - at)});
+  }
+  b->gaps.resize(keep);
+  if (b->gaps.empty() && b->row_chunks.empty()) return NVH_OK;
   static_assert(sizeof(nvh::FrameBatch::Gap) == 2 * sizeof(long long), "k_zero_gaps reads {position, length} pairs");
-  const size_t bytes = b->gaps.size() * sizeof(nvh::FrameBatch::Gap);
+  const size_t gap_bytes = b->gaps.size() * sizeof(nvh::FrameBatch::Gap), row_bytes = b->row_chunks.size() * sizeof(nvh::FrameBatch::Gap);
+  const size_t bytes = gap_bytes + row_bytes;
   int rc = b->gap_dev.reserve(bytes);
   if (rc == NVH_OK) rc = b->gap_host.reserve(bytes);
   if (rc != NVH_OK) return rc;
-  std::memcpy(b->gap_host.p, b->gaps.data(), bytes);
+  if (gap_bytes) std::memcpy(b->gap_host.p, b->gaps.data(), gap_bytes);
+  if (row_bytes) std::memcpy((uint8_t*)b->gap_host.p + gap_bytes, b->row_chunks.data(), row_bytes);
   HIP_TRY(hipMemcpyAsync(b->gap_dev.p, b->gap_host.p, bytes, hipMemcpyHostToDevice, s->ctx->stream));
   return NVH_OK;
 }
@@ -495,6 +523,20 @@ int batch_upload(nvh_stream* s, nvh_batch* b) {
 static int batch_upload_frames(nvh_stream* s, nvh_batch* b) {
   nvh::FrameBatch& P = s->pending;
   b->s = s;
+  if (P.frames.empty()) {
+    // a batch of pads alone (windowed segments that emit nothing: rows of zeros): no descriptors, only the tables
+    b->nframes = b->chan_frames = 0;
+    b->pcm_samples = P.pcm_samples;
+    b->segments = P.closed_segments;
+    b->segments.push_back({s->parser->segment(), P.segment_begin, P.pcm_samples});
+    b->gaps = P.gaps;
+    b->last_decoded = -1;
+    b->ola_count = 0;
+    s->replay.clear();
+    P.clear();
+    s->parser->begin_batch();
+    return NVH_OK;
+  }
   b->nframes = (int)P.frames.size();
   b->chan_frames = (int)P.chans.size();
   b->pcm_samples = P.pcm_samples;
@@ -809,12 +851,42 @@ static auto with_unmapped_twins(PcmOut out, F&& f) {
   __builtin_unreachable();
 }
 
+// Segments: the gaps between them are zeros in the destination, whatever its form -- gap x out_channels interleaved samples, or
+// the gap in each plane (one plane for the mono mix).  One launch of k_zero_gaps, and none for a batch without gaps.  The long
+// gaps -- a windowed segment's pad up to its pitch -- go through k_zero_rows, one workgroup per (chunk, plane) of the chunk table
+// behind the gap list, and only then is that kernel named (behind the fourth slot's name).  `out` as batch_launch adjusted it.
+static void launch_gap_fill(nvh_batch* b, const PcmOut& out, void* d_pcm, hipStream_t st) {
+  if (b->gaps.empty() && b->row_chunks.empty()) return;
+  const int oc = out.out_channels(b->s->setup.channels);
+  const bool planar = out.planar(), planes = planar || out.mono();
+  if (!b->gaps.empty())
+    hipLaunchKernelGGL(k_zero_gaps, dim3((unsigned)b->gaps.size(), planar ? (unsigned)oc : 1u), dim3(256), 0, st,
+                       (const long long*)b->gap_dev.p, (unsigned char*)d_pcm, (int)out.sample_bytes(), planes ? 1 : oc,
+                       (long long)out.plane_stride);
+  if (!b->row_chunks.empty()) {
+    hipLaunchKernelGGL(k_zero_rows, dim3((unsigned)b->row_chunks.size(), planar ? (unsigned)oc : 1u), dim3(256), 0, st,
+                       (const long long*)b->gap_dev.p + 2 * b->gaps.size(), (unsigned char*)d_pcm, (int)out.sample_bytes(),
+                       planes ? 1 : oc, (long long)out.plane_stride);
+    const std::string was = b->slot_name[3];
+    b->slot_name_buf[3] = was == "-" ? std::string("k_zero_rows") : was + "+k_zero_rows";
+    b->slot_name[3] = b->slot_name_buf[3].c_str();
+  }
+}
+
 int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms, hipEvent_t* ext_ev,
                  PcmOut out) {
   nvh_stream* s = b->s;
   hipStream_t st = s->ctx->stream;
-  if (b->nframes == 0) return NVH_OK;
   const int ch = s->setup.channels;
+  if (b->nframes == 0) {
+    // no frames: nothing to synthesise -- but a batch of windowed segments may still hold pads (rows of zeros)
+    if (b->gaps.empty() && b->row_chunks.empty()) return NVH_OK;
+    for (int k = 0; k < 4; k++) b->slot_name[k] = "-";
+    if (ch == 1 && !out.mapped()) out.plane_stride = 0, out.mix = NVH_MIX_NONE;
+    if (d_pcm && !b->block_only) launch_gap_fill(b, out, d_pcm, st);
+    HIP_TRY(hipGetLastError());
+    return NVH_OK;
+  }
   // Channel-planar output: the _planar twins.  One channel is the same bytes either way: mono takes the interleaved kernels.
   // The twins' vector stores need every plane's first sample of a frame on a 16-byte boundary: an aligned base, a plane stride in
   // whole groups of four samples (below 2^31: NvhSynthArgs::plane_stride) and a frame position in whole groups of four
@@ -1160,15 +1232,7 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       HIP_TRY(hipMemcpyAsync(carry_out, (const uint8_t*)b->work.p + (size_t)b->last_decoded * plane_bytes, plane_bytes,
                              hipMemcpyDeviceToDevice, st));
   }
-  // segments: the gaps between them are zeros in the destination, whatever its form -- gap x out_channels interleaved samples,
-  // or the gap in each plane (one plane for the mono mix).  One launch, and none for a batch without gaps.
-  if (!b->gaps.empty() && d_pcm && !b->block_only) {
-    const int oc = out.out_channels(ch);
-    const bool planes = planar || out.mono();
-    hipLaunchKernelGGL(k_zero_gaps, dim3((unsigned)b->gaps.size(), planar ? (unsigned)oc : 1u), dim3(256), 0, st,
-                       (const long long*)b->gap_dev.p, (unsigned char*)d_pcm, (int)out.sample_bytes(), planes ? 1 : oc,
-                       (long long)plane_stride);
-  }
+  if (d_pcm && !b->block_only) launch_gap_fill(b, out, d_pcm, st);
   if (timing) HIP_TRY(hipEventRecord(ev[4], st));
   HIP_TRY(hipGetLastError());
   if (timing && !ext_ev) {

@@ -94,6 +94,7 @@ SIGNATURES = {
     "nvh_stream_push_end": (C.c_int, [_vp]),
     "nvh_stream_pending": (C.c_int, [_vp, _ip, _i64p]),
     "nvh_stream_next_segment": (C.c_int, [_vp, C.c_int]),
+    "nvh_stream_segment_window": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64]),
     "nvh_stream_pending_segments": (C.c_int, [_vp, _i64p, _i64p, _i64p, C.c_int, _ip]),
     "nvh_stream_synth_segments": (C.c_int, [_vp, _i64p, _i64p, _i64p, C.c_int, _ip]),
     "nvh_stream_pending_geometry": (C.c_int, [_vp, _vp, C.c_int]),

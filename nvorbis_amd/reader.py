@@ -484,6 +484,13 @@ class Stream:
         of `align` (a power of two up to 65536; 4 keeps the kernels' vector stores); the samples skipped are zeros in the output."""
         check(lib().nvh_stream_next_segment(self._h, int(align)), "nvh_stream_next_segment")
 
+    def segment_window(self, skip=0, take=-1, pitch=0):
+        """The current segment's window (nvh_stream_segment_window), before the segment's first packet: of the samples per channel
+        the segment's packets emit, numbered from 0, only [skip, skip + take) are emitted (take=-1: to the end), and once they are
+        the segment takes no more packets.  pitch > 0: next_segment pads the segment with zeros to `pitch` samples, so that rows
+        begin `pitch` apart.  next_segment and reset restore (0, -1, 0)."""
+        check(lib().nvh_stream_segment_window(self._h, int(skip), int(take), int(pitch)), "nvh_stream_segment_window")
+
     def pending_segments(self):
         """The pending batch's segments (nvh_stream_pending_segments), to be read before the synthesis call: an int64 array [n, 3]
         of (segment number, begin, end) in samples per channel of the batch's output, the current segment last."""

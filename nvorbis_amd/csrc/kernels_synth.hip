@@ -1079,8 +1079,9 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const unsigned idx = 4u * (unsigned)jj + (unsigned)k;  // position in the half's interleaved floats
-        // (idx < 2^16, oc <= 8: exact -- but for a divisor of 1 the magic number is 2^32, which does not fit: a map may keep ONE channel)
-        const unsigned tt = MAP && oc == 1 ? idx : __umulhi(idx, ch_magic), c = idx - tt * (unsigned)oc;
+        // (idx < 2^16, oc <= 8: exact -- but for a divisor of 1 the magic number is 2^32, which does not fit: a map may keep ONE
+        // channel, and a mono stream with blocks of 4096 samples has one)
+        const unsigned tt = oc == 1 ? idx : __umulhi(idx, ch_magic), c = idx - tt * (unsigned)oc;
         float x = sr[c * (unsigned)RUN + tt];
         if (A.clip) x = clip_value(x, &clipped);
         e[k] = x;

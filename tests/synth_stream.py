@@ -415,6 +415,53 @@ def _longcode_config(name, books):
                 modes=[(0, 0), (1, 1)])
 
 
+BLOCK_SIZES = (64, 128, 256, 512, 1024, 2048, 4096, 8192)
+
+
+def grid_name(ch, b0, b1):
+    return "grid_%dch_%d_%d" % (ch, b0, b1)
+
+
+def grid_cell(name):
+    """(channels, block0, block1) of a grid name."""
+    ch, b0, b1 = name[len("grid_"):].split("_")
+    ch, b0, b1 = int(ch[:-2]), int(b0), int(b1)
+    if ch not in (1, 2) or b0 not in BLOCK_SIZES or b1 not in BLOCK_SIZES or b0 > b1:
+        raise KeyError(name)
+    return ch, b0, b1
+
+
+# every pair block0 <= block1 that Vorbis I allows, mono and stereo: 72 setups of one recipe (tests/test_block_grid.py).  Kept
+# out of CONFIG_NAMES: the tests parametrised over that list would each grow by 72.
+GRID_NAMES = [grid_name(ch, b0, b1) for ch in (1, 2) for b0 in BLOCK_SIZES for b1 in BLOCK_SIZES if b0 <= b1]
+
+
+def _grid_config(name):
+    """One recipe for every block-size pair: config()'s books; two Floor1 with X lists scaled to the block (two partitions below
+    64 bins, else three for the short and five for the long block); a per-channel Residue1 over the whole short block; a long
+    residue from bin 8 in partitions of 32 up to the last whole partition -- Residue1 for mono, a Residue2 over both channels for
+    stereo --; stereo couples (0, 1) in short and (1, 0) in long blocks.  With block0 == block1 both modes stay: one frame size
+    reached through either block flag."""
+    ch, b0, b1 = grid_cell(name)
+
+    def floor(n, long_block):
+        half = n // 2
+        return _floor1_long(0, 1, max(ilog(half - 1), 5), 2 if half < 64 else (5 if long_block else 3))
+
+    ps0 = 8 if b0 // 2 < 64 else 16
+    e0 = b0 // 2 // ps0 * ps0
+    e1 = (b1 // 2 - 8) // 32 * 32 + 8
+    rtype1, end1 = (1, e1) if ch == 1 else (2, 2 * e1 - 8)
+    cpl = (lambda pair: []) if ch == 1 else (lambda pair: [pair])
+    return dict(channels=ch, block0=b0, block1=b1,
+                floors=[floor(b0, False), floor(b1, True)],
+                residues=[lambda w: write_residue(w, 1, 0, e0, ps0, 2, [1, 2, 7, 0], [3, 4, 3, 4, 5]),
+                          lambda w: write_residue(w, rtype1, 8, end1, 32, 2, [3, 1, 4, 6], [3, 4, 5, 5, 4, 3])],
+                mappings=[lambda w: write_mapping(w, ch, 1, cpl((0, 1)), None, [(0, 0)]),
+                          lambda w: write_mapping(w, ch, 1, cpl((1, 0)), None, [(1, 1)])],
+                modes=[(0, 0), (1, 1)])
+
+
 def config(name):
     # common books: 0 = 1-bit scalar (masterbook / class word helper), 1 = 2-bit scalar (floor posts 0..3),
     # 2 = 4-bit classbook (dim 2, 4 classes), 3 = VQ dim2 16 entries lattice, 4 = VQ dim4 256 entries lattice,
@@ -620,6 +667,8 @@ def config(name):
                  modes=[(0, 0), (1, 1)])
     elif name in LONGCODE_NAMES:
         c.update(_longcode_config(name, books))
+    elif name.startswith("grid_"):
+        c.update(_grid_config(name))
     else:
         raise KeyError(name)
     return c

@@ -82,6 +82,7 @@ namespace NVorbis.Hip
         [DllImport(Lib)] public static extern unsafe int nvh_stream_pending_segments(IntPtr stream, long* index, long* begin, long* end, int cap, out int count);
         /// <summary>The same table for the batch the last synthesis call consumed, as finally parsed (GPU-parse mode: after a packet the parser failed on).</summary>
         [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_segments(IntPtr stream, long* index, long* begin, long* end, int cap, out int count);
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_segments_clipped(IntPtr stream, int* clipped, int cap, out int count);
         /// <summary>[frames][8] ints: block size (0 = drained tail), start, valid, total, ... of every pending frame.</summary>
         [DllImport(Lib)] public static extern unsafe int nvh_stream_pending_geometry(IntPtr stream, int* geometry, int capFrames);
         /// <summary>Page table of one logical Ogg stream + IPacketProvider.SeekTo over it (Ogg/PacketProvider.cs:56-295), for hosts

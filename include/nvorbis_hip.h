@@ -279,7 +279,24 @@ int nvh_stream_pending(const nvh_stream *s, int *frames, int64_t *pcm_samples_pe
  * bit for bit the samples a fresh stream over the same headers and the same packets, granules and flags emits in that form.
  * Samples in the gaps that `align` opens are zero.  *written, *expected and extents count gaps as samples.
  * nvh_stream_position reports the current segment.  nvh_stream_parse_errors' samples_before stays an offset into the batch's
- * output, gaps included.  HasClipped is the OR over every segment since the last reset. */
+ * output, gaps included.  HasClipped has two calls: nvh_stream_has_clipped is the sticky OR over every segment since the last
+ * reset, nvh_stream_synth_segments_clipped says which segments of the last batch set it.
+ *
+ * THE RULE, HasClipped.  For the batch the last synthesis call consumed, entry i of nvh_stream_synth_segments_clipped belongs
+ * to entry i of nvh_stream_synth_segments.  It is 1 exactly when ClipSamples clamped at least one of the samples THIS BATCH
+ * emitted inside that segment's range, in the output form of the call; otherwise 0.  ORed over the batches a segment runs
+ * through, it is the HasClipped a fresh stream over the same headers, packets, granules and flags reports after emitting the
+ * same samples in the same form.  With NVH_MIX_MONO the mix decides the flag; with a channel map only the emitted channels
+ * count; with a window only the emitted samples count; gaps and pads never set a flag; with ClipSamples off every entry is 0.
+ * In GPU-parse mode a batch that was parsed again reports by the table as finally parsed.  nvh_stream_has_clipped keeps its
+ * meaning and its value in every case (it is the OR of every entry since the last reset).
+ * The call follows nvh_stream_synth_segments' conventions: *count is set even when `cap` is too small (NVH_ERR_ARGUMENT
+ * then); no entries before the first synthesis call and after nvh_stream_reset; host state only once the synthesis call has
+ * returned (works on a host-only stream: no entries); for a pipelined batch valid from that batch's nvh_stream_synth_end on.
+ * A batch of one segment -- every stream that never calls nvh_stream_next_segment -- launches exactly what it launched before
+ * there was this call: its one entry is what the batch added to the sticky flag.  Resident batches (nvh_batch_*) have no
+ * table: they are launched repeatedly and report through nvh_stream_has_clipped alone.
+ * Python: Stream.synth_segments_clipped, decode_clips(..., return_clipped=True). */
 int nvh_stream_next_segment(nvh_stream *s, int align);
 /* ---- windowed segments: crop and pad a segment into a fixed-length row ----
  * nvh_stream_segment_window applies to the CURRENT segment and is legal only while that segment has seen no packet and no
@@ -323,6 +340,7 @@ int nvh_stream_next_segment(nvh_stream *s, int align);
 int nvh_stream_segment_window(nvh_stream *s, int64_t skip, int64_t take, int64_t pitch);
 int nvh_stream_pending_segments(const nvh_stream *s, int64_t *index, int64_t *begin, int64_t *end, int cap, int *count);
 int nvh_stream_synth_segments(const nvh_stream *s, int64_t *index, int64_t *begin, int64_t *end, int cap, int *count);
+int nvh_stream_synth_segments_clipped(const nvh_stream *s, int32_t *clipped, int cap, int *count);
 /* The pending frames in the form the synthesis kernels fetch (per-frame slabs: the integer half of Floor1.Apply --
  * UnwrapPosts and the walk over the sorted posts, Floor1.cs:196-297 -- as line segments, the vector writes of
  * Residue0.cs:132-175 / Residue2.cs:23-47 as chain-major records; the entry section in DIGIT form for setups whose residue books

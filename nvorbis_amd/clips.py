@@ -18,6 +18,19 @@ from . import native
 from .reader import (Context, Stream, _channel_map, _layout, _mix, _pcm_out, _sample_format, demux_ogg_array)
 
 
+def _return_clipped(value):
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError("return_clipped must be True or False, not %r" % (value,))
+    return bool(value)
+
+
+def _note_clipped(st, members, clipped):
+    """OR the last batch's per-segment flags (Stream.synth_segments_clipped) into `clipped`, segment k being clip members[k]."""
+    for k, hit in zip(st.synth_segments()[:, 0], st.synth_segments_clipped()):
+        if hit:
+            clipped[members[int(k)]] = True
+
+
 def _clip_error(index, err, where=None, call="decode_clips"):
     """`err` (an NvhError) as the error of clip `index`."""
     e = native.NvhError(err.code, "%s: clip %d: %s" % (call, index, where or "decode"))
@@ -34,6 +47,7 @@ class _Group:
         pa = packets[first]
         self.stream = Stream(ctx, pa[0], pa[1], pa[2])
         self.pieces = {i: [] for i in members}
+        self.clipped = opts.get("clipped")  # the caller's bool array over all clips, or None: not asked for
 
     def run(self):
         o, st = self.opts, self.stream
@@ -89,6 +103,8 @@ class _Group:
             row = inside[0] if inside.size else max(int(np.searchsorted(table[:, 1], at, side="right")) - 1, 0)
             k = int(table[row, 0])
             raise _clip_error(self.members[k], err, "a packet the parser fails on")
+        if self.clipped is not None:
+            _note_clipped(st, self.members, self.clipped)
         for k, b, e in table:
             if e > b:
                 piece = out[:, b:e] if planar else out[b * och:e * och]
@@ -113,7 +129,7 @@ class _Group:
 
 
 def decode_clips(clips, ctx=None, device=0, batch_frames=4096, gpu_parse=True, sample_format="f32", layout="interleaved", mix=None,
-                 channel_map=None, align=4, device_out=False):
+                 channel_map=None, align=4, device_out=False, return_clipped=False):
     """Decode a list of Ogg Vorbis clips (bytes or paths; logical stream 0 of each) and return one array per clip, in input
     order: what VorbisReader(clip, <the same options>).read_all() returns for it, bit for bit.
 
@@ -125,11 +141,16 @@ def decode_clips(clips, ctx=None, device=0, batch_frames=4096, gpu_parse=True, s
     Host results are numpy arrays: (T * channels,) interleaved, (channels, T) for layout="planar", (T,) for mix="mono".
     device_out=True: torch tensors on the device instead -- views of the batch outputs for clips that lie inside one batch.
 
+    return_clipped=True: returns (results, clipped) instead, `clipped` a numpy bool array with one entry per clip: that clip's
+    VorbisReader.HasClipped after read_all() in the same output form (the per-segment flags of every batch the clip ran through,
+    ORed: Stream.synth_segments_clipped).
+
     A clip whose headers or packets make the library return an error raises NvhError with the clip's index in the message (and
     as its `clip` attribute); there are no partial results."""
     dtype = _sample_format(sample_format)
     planar = _layout(layout)
     _mix(mix, planar)
+    return_clipped = _return_clipped(return_clipped)
     if channel_map is not None:
         _channel_map(channel_map, None, mix)
     if isinstance(align, bool) or not isinstance(align, (int, np.integer)) or align < 1 or align > 65536 or align & (align - 1):
@@ -165,6 +186,9 @@ def decode_clips(clips, ctx=None, device=0, batch_frames=4096, gpu_parse=True, s
         "och": lambda ch: _pcm_out(dtype, planar, mix, channel_map, ch)[2],
     }
     results = [None] * len(packets)
+    clipped = np.zeros(len(packets), dtype=bool)
+    if return_clipped:
+        opts["clipped"] = clipped
     try:
         for members in groups.values():
             try:
@@ -179,7 +203,7 @@ def decode_clips(clips, ctx=None, device=0, batch_frames=4096, gpu_parse=True, s
     finally:
         if own_ctx:
             ctx.close()
-    return results
+    return (results, clipped) if return_clipped else results
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -250,6 +274,7 @@ class _RowGroup:
         pa = packets[members[0]]
         self.stream = Stream(ctx, pa[0], pa[1], pa[2])
         self.done = 0  # samples per channel written so far: whole rows and the part of the open one
+        self.clipped = opts.get("clipped")  # the caller's bool array over all rows, or None: not asked for
         self.dests = []  # the destination of every batch
 
     def run(self, base_ptr, row0, rows_total):
@@ -319,11 +344,13 @@ class _RowGroup:
             pos //= 1 if per else och
             k = min((self.done + pos) // max(self.length, 1), len(self.members) - 1)
             raise _clip_error(self.members[int(k)], err, "a packet the parser fails on", "decode_clip_rows")
+        if self.clipped is not None:
+            _note_clipped(st, self.members, self.clipped)
         self.done += wr.value if per else wr.value // och
 
 
 def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frames=4096, gpu_parse=True, sample_format="f32",
-                     layout="interleaved", mix=None, channel_map=None, device_out=False):
+                     layout="interleaved", mix=None, channel_map=None, device_out=False, return_clipped=False):
     """Crop and pad a list of Ogg Vorbis clips (bytes or paths; logical stream 0 of each) into N rows of exactly `length` samples:
     returns (rows, valid).  Row i holds samples [starts[i], starts[i] + length) of what VorbisReader(clips[i], <the same
     options>).read_all() returns, per channel, bit for bit, and zeros behind the clip's end; valid[i] (an int64 numpy array) says
@@ -345,6 +372,10 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
     kernels' vector paths and paired emission for the frames inside a row; any other start or length gives the same bits through
     the per-frame fall-back, slower.
 
+    return_clipped=True: returns ((rows, valid), clipped) instead, `clipped` a numpy bool array with one entry per row: whether
+    ClipSamples clamped one of the samples the row holds (HasClipped of a reader that emitted exactly those samples in the same
+    output form; the pad never counts).
+
     Batches end on row boundaries once `batch_frames` frames are pending; only a row of more than 2 * batch_frames frames of
     its own is cut inside, every 2 * batch_frames frames.  LIMIT: such a cut falls on whatever sample the frames end on, and
     interleaved 16-bit PCM asks for a 16-byte aligned destination (nvh_stream_synth_pcm's rule), so sample_format="s16" with
@@ -356,6 +387,7 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
     dtype = _sample_format(sample_format)
     planar = _layout(layout)
     _mix(mix, planar)
+    return_clipped = _return_clipped(return_clipped)
     if channel_map is not None:
         _channel_map(channel_map, None, mix)
     if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0:
@@ -400,6 +432,7 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
     och = chans[0] if chans else 1
     valid = np.asarray([p["valid"] for p in plans], dtype=np.int64)
     mono = mix is not None
+    clipped = np.zeros(n, dtype=bool)
     shape = (och, n, length) if planar else (n, length) if mono else (n, length, och)
     if device_out:
         import torch
@@ -417,6 +450,8 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
         opts = {"batch_frames": int(batch_frames), "gpu_parse": bool(gpu_parse), "dtype": dtype, "planar": planar, "mix": mix,
                 "device_out": bool(device_out), "map": lambda ch: _channel_map(channel_map, ch, mix),
                 "och": lambda ch: _pcm_out(dtype, planar, mix, channel_map, ch)[2]}
+        if return_clipped:
+            opts["clipped"] = clipped
         try:
             row0 = 0
             for members in groups.values():
@@ -442,4 +477,4 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
             buf = np.take(buf, order, axis=1 if planar else 0)
     if planar:
         buf = buf.permute(1, 0, 2) if device_out else buf.transpose(1, 0, 2)
-    return buf, valid
+    return ((buf, valid), clipped) if return_clipped else (buf, valid)

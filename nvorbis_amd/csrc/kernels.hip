@@ -628,7 +628,7 @@ k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const 
       if (clip) m = clip_value(m, &clipped);
       pcm_store1(out + t, m);
     }
-    report_clipped(clipped, clipped_flag);
+    report_clipped(clipped, clipped_flag, f);
     return;
   }
   for (int o = threadIdx.x; o < total; o += NVH_THREADS) {
@@ -648,7 +648,7 @@ k_ola_emit(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, const 
     if constexpr (PLANAR) pcm_store1(out + c * pstride + t, v);
     else pcm_store1(out + o, v);
   }
-  report_clipped(clipped, clipped_flag);
+  report_clipped(clipped, clipped_flag, f);
 }
 
 // Sequential form: one workgroup walks the frames in order and performs the adds in place, exactly
@@ -663,9 +663,9 @@ k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const fl
   const NvhChanMap cm = pcm_map_of(plane_stride);  // (k_ola_emit: slot c, source sc; the adds in place cover every channel)
   const long long pstride = pcm_stride_of(plane_stride);
   const int oc = MAP ? cm.oc : ch;
-  int clipped = 0;
   for (int f = 0; f < Bt.nframes; ++f) {
     const NvhFrame fr = Bt.frames[f];
+    int clipped = 0;  // per frame: the frame's segment takes the flag (kernels_common.h: report_clipped)
     float* cur = work + (long long)f * ch * S.block1;
     const float* prev = nullptr;
     if (fr.ov_len > 0) prev = (fr.ov_frame == -2) ? carry : (fr.ov_frame >= 0 ? work + (long long)fr.ov_frame * ch * S.block1 : nullptr);
@@ -699,9 +699,9 @@ k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* __restrict__ work, const fl
       if constexpr (PLANAR) pcm_store1(out + c * pstride + t, v);
       else pcm_store1(out + o, v);
     }
+    report_clipped(clipped, clipped_flag, f);
     __syncthreads();
   }
-  report_clipped(clipped, clipped_flag);
 }
 #define NVH_OLA_EMIT_TWINS(PCM, LAYOUT, SFX)                                                                                    \
   template __global__ void k_ola_emit<PCM, LAYOUT>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,   \
@@ -1083,7 +1083,7 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
       else
       clipped = psym ? ola_sym_planar<PCM>(S, fr, cur, prev, w, wp, out, pstride, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS)
                      : ola_vec_planar<PCM>(S, fr, cur, prev, prev_full, w, wp, out, pstride, ch, clip, NVH_OLA_TID, NVH_OLA_THREADS);
-      report_clipped(clipped, clipped_flag);
+      report_clipped(clipped, clipped_flag, f);
       return;
     }
   }
@@ -1123,7 +1123,7 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
         pcm_store1(out + t, m);
       }
     }
-    report_clipped(clipped, clipped_flag);
+    report_clipped(clipped, clipped_flag, f);
     return;
   }
   const bool sym = vec && prev && !prev_full && fr.ov_n == fr.n && fr.start == 0 && fr.emit_start == 0 && fr.emit_count == (fr.n >> 1) &&
@@ -1147,7 +1147,7 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
         default: NVH_OLA_MAP_CASE(8)
       }
 #undef NVH_OLA_MAP_CASE
-      report_clipped(clipped, clipped_flag);
+      report_clipped(clipped, clipped_flag, f);
       return;
     }
   } else {
@@ -1163,7 +1163,7 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
       case 7: clipped = ola_sym_lds<7, PCM>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
       default: clipped = ola_sym_lds<8, PCM>(S, fr, cur, prev, w, wp, out, clip, s_run); break;
     }
-    report_clipped(clipped, clipped_flag);
+    report_clipped(clipped, clipped_flag, f);
     return;
   }
   if (sym) {
@@ -1177,7 +1177,7 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
       case 7: clipped = ola_sym<7, PCM>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
       default: clipped = ola_sym<8, PCM>(S, fr, cur, prev, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
     }
-    report_clipped(clipped, clipped_flag);
+    report_clipped(clipped, clipped_flag, f);
     return;
   }
   if (vec) {
@@ -1191,7 +1191,7 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
       case 7: clipped = ola_vec<7, PCM>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
       default: clipped = ola_vec<8, PCM>(S, fr, cur, prev, prev_full, w, wp, out, clip, NVH_OLA_TID, NVH_OLA_THREADS); break;
     }
-    report_clipped(clipped, clipped_flag);
+    report_clipped(clipped, clipped_flag, f);
     return;
   }
   }
@@ -1218,7 +1218,7 @@ k_ola_compact(NvhDevSetup S, NvhDevBatch Bt, const float* __restrict__ work, con
     if constexpr (PLANAR) pcm_store1(out + c * pstride + t, v);
     else pcm_store1(out + o, v);
   }
-  report_clipped(clipped, clipped_flag);
+  report_clipped(clipped, clipped_flag, f);
 }
 #define NVH_OLA_COMPACT_TWINS(PCM, LAYOUT, SFX)                                                                                     \
   template __global__ void k_ola_compact<PCM, LAYOUT>(NvhDevSetup, NvhDevBatch, const float*, const float*, PCM*, int, int*,    \

@@ -248,15 +248,17 @@ __device__ __forceinline__ float4 stream_load4(const float* p) {
 
 // Utils.cs:30-43, without branches (two compares, two selects; the flag is an OR of the compare masks): the early-return form
 // compiles to two exec-mask regions per sample.  A NaN compares false twice and passes through, as in the reference.
-__device__ __forceinline__ float clip_value(float v, int* clipped) {
+// `bit`: what a clamped sample ORs into the lane's flag.  A lane that emits for more than one frame gives each frame a bit of its
+// own (report_clipped<NB>: bit k belongs to frame + k), so that the flag still costs one select and one OR per sample.
+__device__ __forceinline__ float clip_value(float v, int* clipped, int bit = 1) {
   const bool hi = v > .99999994f, lo = v < -.99999994f;
-  *clipped |= (int)(hi | lo);
+  *clipped |= (hi | lo) ? bit : 0;
   return hi ? 0.99999994f : (lo ? -0.99999994f : v);
 }
 
-__device__ __forceinline__ void clip_value4(float4& v, int* clipped) {
-  v.x = clip_value(v.x, clipped); v.y = clip_value(v.y, clipped);
-  v.z = clip_value(v.z, clipped); v.w = clip_value(v.w, clipped);
+__device__ __forceinline__ void clip_value4(float4& v, int* clipped, int bit = 1) {
+  v.x = clip_value(v.x, clipped, bit); v.y = clip_value(v.y, clipped, bit);
+  v.z = clip_value(v.z, clipped, bit); v.w = clip_value(v.w, clipped, bit);
 }
 
 // ---- the symmetric overlap-add tail ------------------------------------------------------------------------------------------
@@ -312,15 +314,15 @@ __device__ __forceinline__ float4 compact_value4(const float* __restrict__ plane
 // kernels (at most two channels, k_synth_emit at its 64-VGPR cap) spell the stereo case out as a multiply by 0.5f.
 __device__ __forceinline__ float mono_scale(float s, int nch) { return s / (float)nch; }
 // the narrow emission's eight values per half (sample time k of channel c at v[2 k + c], nch <= 2) -> the four mixed sample times
-__device__ __forceinline__ float4 mono_mix2(const float (&v)[8], int nch, int clip, int* clipped) {
+__device__ __forceinline__ float4 mono_mix2(const float (&v)[8], int nch, int clip, int* clipped, int bit = 1) {
   float4 m = nch == 2 ? make_float4((v[0] + v[1]) * 0.5f, (v[2] + v[3]) * 0.5f, (v[4] + v[5]) * 0.5f, (v[6] + v[7]) * 0.5f)
                       : make_float4(v[0], v[2], v[4], v[6]);
-  if (clip) clip_value4(m, clipped);
+  if (clip) clip_value4(m, clipped, bit);
   return m;
 }
 // CH channels per lane (sample time k of channel c at v[k * CH + c]) -> the four mixed sample times
 template <int CH>
-__device__ __forceinline__ float4 mono_mix(const float (&v)[4 * CH], int clip, int* clipped) {
+__device__ __forceinline__ float4 mono_mix(const float (&v)[4 * CH], int clip, int* clipped, int bit = 1) {
   float m[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -330,17 +332,43 @@ __device__ __forceinline__ float4 mono_mix(const float (&v)[4 * CH], int clip, i
     m[k] = s / (float)CH;
   }
   float4 r = make_float4(m[0], m[1], m[2], m[3]);
-  if (clip) clip_value4(r, clipped);
+  if (clip) clip_value4(r, clipped, bit);
   return r;
 }
 
 // HasClipped (StreamDecoder.cs:728) is sticky: one lane per wavefront that clipped looks at the flag and only sets it
 // while it is still clear.  A stream that clips everywhere (loud material; Floor0 curves on random bits) otherwise
 // serialises one atomic per lane -- or still 8192 per launch with one per wavefront, ~35 us -- on a single address.
+__device__ __forceinline__ void set_clipped_word(int* w) {
+  if (__atomic_load_n(w, __ATOMIC_RELAXED) == 0) atomicOr(w, 1);
+}
+// (the stand-alone form: a flag word of the caller's, nothing behind it -- k_copy_buffer)
 __device__ __forceinline__ void report_clipped(int clipped, int* __restrict__ clipped_flag) {
   const unsigned long long any = __ballot(clipped != 0);
-  if (any && (int)(threadIdx.x & 63u) == __ffsll((long long)any) - 1) {
-    if (__atomic_load_n(clipped_flag, __ATOMIC_RELAXED) == 0) atomicOr(clipped_flag, 1);
+  if (any && (int)(threadIdx.x & 63u) == __ffsll((long long)any) - 1) set_clipped_word(clipped_flag);
+}
+// The emitting kernels of a batch: `clipped_flag` is word 1 of the stream's flag block (nvh_internal.h: nvh_stream::flags), and
+// words 2-3 of that block hold the device address of the batch's segment-flag table, or null (a batch of one segment, a resident
+// batch: the sticky word alone, which is then that segment's flag).  The table is one int32 per frame -- the index, from the
+// table's base, of the flag word of the segment the frame's PCM belongs to -- followed by those flag words, zeroed at upload.
+// `frame` is uniform over the wavefront, and bit k of a lane's `clipped << shift` says that the lane clamped a sample of
+// frame + k (`shift`: for a lane whose every sample belongs to one frame, known without a bit of its own; applied behind `any`).
+// Everything new is behind `any`: a wavefront that did not clip executes what it executed before.  The segment words keep the
+// sticky word's discipline (one lane per wavefront and frame, a load in front of the atomic).
+template <int NB = 1>
+__device__ __forceinline__ void report_clipped(int clipped, int* __restrict__ clipped_flag, int frame, int shift = 0) {
+  const unsigned long long any = __ballot(clipped != 0);
+  if (any) {
+    const int lane = (int)(threadIdx.x & 63u);
+    if (lane == __ffsll((long long)any) - 1) set_clipped_word(clipped_flag);
+    int* tab = *reinterpret_cast<int* const*>(clipped_flag + 1);
+    if (tab) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+        const unsigned long long m = NB == 1 ? any : __ballot((((clipped << shift) >> k) & 1) != 0);
+        if (m && lane == __ffsll((long long)m) - 1) set_clipped_word(tab + tab[frame + k]);
+      }
+    }
   }
 }
 #endif

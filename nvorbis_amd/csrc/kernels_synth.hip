@@ -693,7 +693,7 @@ __device__ __forceinline__ void synth_carry_out(const NvhSynthArgs& A, const flo
 // its registers.
 template <int NT, typename PCM = float, int LAYOUT = NVH_LAYOUT_INTERLEAVED>
 __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const float* spec, int n, int nch, unsigned window_off,
-                                              unsigned out_pos, int tid, int cstride = 0) {
+                                              unsigned out_pos, int tid, int frame, int cstride = 0) {
   const int half = n >> 1;
   if (cstride == 0) cstride = half;  // floats between the channels' first quarters
   constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;  // (MONO: kernels_common.h: mono_mix2)
@@ -754,7 +754,7 @@ __device__ __forceinline__ void synth_self_carry(const NvhSynthArgs& A, const fl
       pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + ((n >> 3) - 1 - g), mir[0], mir[2], mir[4], mir[6]);
     }
   }
-  if (A.clip) report_clipped(clipped, A.clipped_flag);
+  if (A.clip) report_clipped(clipped, A.clipped_flag, frame);
 }
 
 // ---- paired emission (nvh_format.h: NVH_EMIT_*) ---------------------------------------------------------------------------
@@ -851,15 +851,19 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
   __syncthreads();  // drains the staging DMA (vmcnt(0) in front of the barrier): all four quarters of every channel are in LDS
   EM_T(17);
   if (carry_out) synth_carry_out<NT>(A, planes, n, nch, exec_mask, w_self, tid);  // (such a frame has no NEXT: its plane was written)
-  if (self_carry) synth_self_carry<NT, PCM, LAYOUT>(A, spec, n, nch, w_self, out_self, tid);    // the batch's first frame
+  if (self_carry) synth_self_carry<NT, PCM, LAYOUT>(A, spec, n, nch, w_self, out_self, tid, (int)frame);    // the batch's first frame
   // ---- overlap-add + interleave + clip, every lane of the workgroup: lane task = (overlap, group of four compact indices i0);
   // it produces sample times i0 .. i0 + 3 and n/2 - 4 - i0 .. n/2 - 1 - i0 of every channel (kernels.hip: ola_sym) ----
   int clipped = 0;
   const int groups = n >> 4;  // per overlap
+  // n <= 2048: with 256 threads a lane has at most one of the 2 * groups tasks, and which overlap that is follows from tid -- the
+  // lane's flag needs no bit per overlap (this kernel has no register to spare for one)
+  constexpr bool ONE_TASK = NT >= 256;
   // One task: NX = which overlap (a wave-uniform value when a wavefront's 64 tasks lie inside one overlap, i.e. n >= 1024: the
   // window / output / LDS bases are then scalar selects instead of per-lane 64-bit arithmetic).
   auto task = [&](const bool nx, const int g) {
     const int i0 = 4 * g;
+    const int cbit = ONE_TASK ? 1 : (nx ? 2 : 1);  // SELF is this frame's PCM, NEXT the next frame's (report_clipped<2>)
     const float* __restrict__ w = A.windows + (nx ? w_next : w_self);
     const float* __restrict__ wp = A.windows + (nx ? wp_next : wp_self);
     // (fetching these in front of the barrier above, next to the staging DMA, was tried: the kernel sits at its 64-VGPR cap and
@@ -892,10 +896,10 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
         // (a pre-test on the task's largest |x| in front of the compares and selects was tried twice: a wavefront's 1024 samples
         // of loud material nearly always hold one that clips, so the slow path runs anyway)
         if (!MONO && A.clip) {  // (the mono form clips the mix)
-          v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
-          v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
-          u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
-          u.z = clip_value(u.z, &clipped); u.w = clip_value(u.w, &clipped);
+          v.x = clip_value(v.x, &clipped, cbit); v.y = clip_value(v.y, &clipped, cbit);
+          v.z = clip_value(v.z, &clipped, cbit); v.w = clip_value(v.w, &clipped, cbit);
+          u.x = clip_value(u.x, &clipped, cbit); u.y = clip_value(u.y, &clipped, cbit);
+          u.z = clip_value(u.z, &clipped, cbit); u.w = clip_value(u.w, &clipped, cbit);
         }
 #endif
         if constexpr (PLANAR) {  // channel-planar: the channel leaves at once (nothing is held for an interleave)
@@ -916,7 +920,7 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
     if constexpr (PLANAR) {
       // (stored per channel above)
     } else if constexpr (MONO) {  // the mean of the channels, clipped once: one vector per half
-      pcm_store_plane(out, g, (n >> 3) - 1 - g, mono_mix2(fwd, nch, A.clip, &clipped), mono_mix2(mir, nch, A.clip, &clipped));
+      pcm_store_plane(out, g, (n >> 3) - 1 - g, mono_mix2(fwd, nch, A.clip, &clipped, cbit), mono_mix2(mir, nch, A.clip, &clipped, cbit));
     } else if (nch == 2) {
       pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
       pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
@@ -948,7 +952,7 @@ __device__ __forceinline__ void synth_emit(const NvhSynthArgs& A, float* smem, f
       if (nx ? emit_next : do_self) task(nx, nx ? t - groups : t);
     }
   }
-  if (A.clip) report_clipped(clipped, A.clipped_flag);
+  if (A.clip) report_clipped<2>(clipped, A.clipped_flag, (int)frame, ONE_TASK ? (int)(tid >= groups) : 0);
   EM_T(18);
 #undef EM_T
 }
@@ -984,6 +988,7 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
   for (int ov = 0; ov < 2; ++ov) {
     if (ov == 0 ? !(ef & NVH_EMIT_SELF) : !(ef & NVH_EMIT_NEXT)) continue;  // uniform
     const NvhFrame* fr = A.frames + frame + ov;  // the frame whose PCM this overlap is
+    const int cbit = 1 << ov;                    // ... and whose segment its clamped samples flag (report_clipped<2>)
     const bool from_carry = ov == 0 && (ef & NVH_EMIT_SELF_CARRY);  // the batch's first frame over the carried tail (stored windowed)
     const float* cur = A.work + (long long)(frame + ov) * nch * A.block1;  // the later block: its first quarter
     const float* prev = from_carry ? A.carry : A.work + (long long)(frame + ov - 1) * nch * A.block1;  // the earlier block
@@ -1030,10 +1035,10 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
         if constexpr (PLANAR) {
           // channel-planar: straight from the lane to the channel's plane (consecutive lanes, consecutive groups of one plane)
           if (A.clip) {
-            v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
-            v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
-            u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
-            u.z = clip_value(u.z, &clipped); u.w = clip_value(u.w, &clipped);
+            v.x = clip_value(v.x, &clipped, cbit); v.y = clip_value(v.y, &clipped, cbit);
+            v.z = clip_value(v.z, &clipped, cbit); v.w = clip_value(v.w, &clipped, cbit);
+            u.x = clip_value(u.x, &clipped, cbit); u.y = clip_value(u.y, &clipped, cbit);
+            u.z = clip_value(u.z, &clipped, cbit); u.w = clip_value(u.w, &clipped, cbit);
           }
           pcm4_t<PCM>* pc = reinterpret_cast<pcm4_t<PCM>*>(out + (long long)cc[k] * A.plane_stride);
           pcm_store4(pc + gl[k], v.x, v.y, v.z, v.w);
@@ -1061,7 +1066,7 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
           m.x = m.x + x.x; m.y = m.y + x.y; m.z = m.z + x.z; m.w = m.w + x.w;
         }
         m = make_float4(mono_scale(m.x, nch), mono_scale(m.y, nch), mono_scale(m.z, nch), mono_scale(m.w, nch));
-        if (A.clip) clip_value4(m, &clipped);
+        if (A.clip) clip_value4(m, &clipped, cbit);
         pcm_store4((mir ? oM1 : oF1) + jj, m.x, m.y, m.z, m.w);
       }
       __syncthreads();
@@ -1083,14 +1088,14 @@ __device__ __forceinline__ void synth_emit8(const NvhSynthArgs& A, float* s_run,
         // channel, and a mono stream with blocks of 4096 samples has one)
         const unsigned tt = oc == 1 ? idx : __umulhi(idx, ch_magic), c = idx - tt * (unsigned)oc;
         float x = sr[c * (unsigned)RUN + tt];
-        if (A.clip) x = clip_value(x, &clipped);
+        if (A.clip) x = clip_value(x, &clipped, cbit);
         e[k] = x;
       }
       pcm_store4((mir ? oM : oF) + jj, e[0], e[1], e[2], e[3]);
     }
     __syncthreads();
   }
-  if (A.clip) report_clipped(clipped, A.clipped_flag);
+  if (A.clip) report_clipped<2>(clipped, A.clipped_flag, (int)frame);
 }
 
 // NVH_EMIT_CARRY_OUT for wide frames: the block that becomes the carried tail of the next batch, fully windowed, from the frame's
@@ -1160,6 +1165,7 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
   int clipped = 0;
   auto task = [&](const bool nx, const int g, const bool whole_wave) {
     const int i0 = 4 * g;
+    const int cbit = nx ? 2 : 1;  // SELF is this frame's PCM, NEXT the next frame's (report_clipped<2>)
     const float* __restrict__ w = A.windows + (nx ? w_next : w_self);
     const float* __restrict__ wp = A.windows + (nx ? wp_next : wp_self);
     const float4 wf = *reinterpret_cast<const float4*>(w + i0);
@@ -1192,10 +1198,10 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
       const float4 r = make_float4(b.w * pm.x, b.z * pm.y, b.y * pm.z, b.x * pm.w);
       u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
       if (!MONO && A.clip) {  // (the mono form clips the mix)
-        v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
-        v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
-        u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
-        u.z = clip_value(u.z, &clipped); u.w = clip_value(u.w, &clipped);
+        v.x = clip_value(v.x, &clipped, cbit); v.y = clip_value(v.y, &clipped, cbit);
+        v.z = clip_value(v.z, &clipped, cbit); v.w = clip_value(v.w, &clipped, cbit);
+        u.x = clip_value(u.x, &clipped, cbit); u.y = clip_value(u.y, &clipped, cbit);
+        u.z = clip_value(u.z, &clipped, cbit); u.w = clip_value(u.w, &clipped, cbit);
       }
       fwd[0 * CH + c] = v.x; fwd[1 * CH + c] = v.y; fwd[2 * CH + c] = v.z; fwd[3 * CH + c] = v.w;
       mir[0 * CH + c] = u.x; mir[1 * CH + c] = u.y; mir[2 * CH + c] = u.z; mir[3 * CH + c] = u.w;
@@ -1217,7 +1223,7 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
       // the mono down-mix: the lane holds every channel of its sample times -- one vector per half of the one plane; a store
       // instruction's 64 lanes (consecutive groups) write whole lines, as in the planar form
       pcm4_t<PCM>* p = reinterpret_cast<pcm4_t<PCM>*>(reinterpret_cast<PCM*>(A.pcm) + (nx ? o_next : o_self));
-      const float4 mf = mono_mix<CH>(fwd, A.clip, &clipped), mm = mono_mix<CH>(mir, A.clip, &clipped);
+      const float4 mf = mono_mix<CH>(fwd, A.clip, &clipped, cbit), mm = mono_mix<CH>(mir, A.clip, &clipped, cbit);
       pcm_store4(p + g, mf.x, mf.y, mf.z, mf.w);
       pcm_store4(p + ((n >> 3) - 1 - g), mm.x, mm.y, mm.z, mm.w);
       return;
@@ -1330,7 +1336,7 @@ __device__ __forceinline__ void synth_emit8_direct(const NvhSynthArgs& A, float*
       task(nx, nx ? t - groups : t, false);
     }
   }
-  if (A.clip) report_clipped(clipped, A.clipped_flag);
+  if (A.clip) report_clipped<2>(clipped, A.clipped_flag, (int)frame);
 }
 
 // The float side of one frame up to its spectra: residue adds (+ inverse coupling and the floor multiply inside the walk where the
@@ -2065,7 +2071,7 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
     if (cout_k[k])  // the block that becomes the next batch's carried tail (its whole plane was written above)
       synth_carry_out<NT>(A, A.work + (long long)(fa + k) * nch * A.block1, nn[k], nch, (w0[k] >> 16) & 0xFFu, cwin[k], tid);
   if (self_carry)  // the batch's first frame
-    synth_self_carry<NT, PCM, LAYOUT>(A, slice0, nn[0], nch, __builtin_amdgcn_readfirstlane(otab[0]), __builtin_amdgcn_readfirstlane(otab[2]), tid, slice_words);
+    synth_self_carry<NT, PCM, LAYOUT>(A, slice0, nn[0], nch, __builtin_amdgcn_readfirstlane(otab[0]), __builtin_amdgcn_readfirstlane(otab[2]), tid, fa, slice_words);
 
   // ---- overlap-add + interleave + clip: lane task = (overlap j, group of four compact indices i0); it produces sample times
   // i0 .. i0 + 3 and n/2 - 4 - i0 .. n/2 - 1 - i0 of every channel (kernels.hip: ola_sym) ----
@@ -2083,6 +2089,7 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
     for (int jj = 1; jj <= FPW; ++jj) g = j == jj ? t - cnt[jj] : g;
     const uint4 r0 = reinterpret_cast<const uint4*>(otab)[2 * j], r1 = reinterpret_cast<const uint4*>(otab)[2 * j + 1];
     const int n = (int)r0.w, half = n >> 1, i0 = 4 * g;  // (n: the overlap's m)
+    const int cbit = 1 << j;  // overlap j is the PCM of frame fa + j (report_clipped<FPW + 1>)
     const float* __restrict__ w = A.windows + r0.x;
     const float* __restrict__ wp = A.windows + r0.y;
     const float4 wf = *reinterpret_cast<const float4*>(w + i0);
@@ -2102,10 +2109,10 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
         const float4 r = make_float4(b.w * pm.x, b.z * pm.y, b.y * pm.z, b.x * pm.w);
         u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
         if (!MONO && A.clip) {  // (the mono form clips the mix)
-          v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
-          v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
-          u.x = clip_value(u.x, &clipped); u.y = clip_value(u.y, &clipped);
-          u.z = clip_value(u.z, &clipped); u.w = clip_value(u.w, &clipped);
+          v.x = clip_value(v.x, &clipped, cbit); v.y = clip_value(v.y, &clipped, cbit);
+          v.z = clip_value(v.z, &clipped, cbit); v.w = clip_value(v.w, &clipped, cbit);
+          u.x = clip_value(u.x, &clipped, cbit); u.y = clip_value(u.y, &clipped, cbit);
+          u.z = clip_value(u.z, &clipped, cbit); u.w = clip_value(u.w, &clipped, cbit);
         }
         if constexpr (PLANAR) {  // channel-planar: the channel leaves at once (nothing is held for an interleave)
           pcm_store_plane(reinterpret_cast<PCM*>(A.pcm) + (long long)r0.z + (long long)c * A.plane_stride, g, (n >> 3) - 1 - g, v, u);
@@ -2119,7 +2126,7 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
     if constexpr (PLANAR) {
       // (stored per channel above)
     } else if constexpr (MONO) {  // the mean of the channels, clipped once: one vector per half
-      pcm_store_plane(out, g, (n >> 3) - 1 - g, mono_mix2(fwd, nch, A.clip, &clipped), mono_mix2(mir, nch, A.clip, &clipped));
+      pcm_store_plane(out, g, (n >> 3) - 1 - g, mono_mix2(fwd, nch, A.clip, &clipped, cbit), mono_mix2(mir, nch, A.clip, &clipped, cbit));
     } else if (nch == 2) {
       pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
       pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
@@ -2153,6 +2160,7 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
     const uint4 r0 = reinterpret_cast<const uint4*>(otab)[2 * (FPW + 1 + k)], r1 = reinterpret_cast<const uint4*>(otab)[2 * (FPW + 1 + k) + 1];
     const int n = (int)r0.z, q1 = (int)(r1.y >> 2);
     const bool second = g >= q1;
+    const int cbit = 1 << k;  // frame fa + k's own PCM
     const int idx0 = second ? (n >> 1) + 4 * (g - q1) : (int)r1.x + 4 * g;
     const float4 wv4 = *reinterpret_cast<const float4*>(A.windows + r0.x + idx0);
     // first half: y[idx] = -A[n/2 - 1 - idx] (idx >= n/4); second half: y[idx] = B[idx - n/2] (idx < 3n/4); B lies behind A in the slice
@@ -2165,8 +2173,8 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
         float4 v = second ? make_float4(x.x * wv4.x, x.y * wv4.y, x.z * wv4.z, x.w * wv4.w)
                           : make_float4(-x.w * wv4.x, -x.z * wv4.y, -x.y * wv4.z, -x.x * wv4.w);
         if (!MONO && A.clip) {
-          v.x = clip_value(v.x, &clipped); v.y = clip_value(v.y, &clipped);
-          v.z = clip_value(v.z, &clipped); v.w = clip_value(v.w, &clipped);
+          v.x = clip_value(v.x, &clipped, cbit); v.y = clip_value(v.y, &clipped, cbit);
+          v.z = clip_value(v.z, &clipped, cbit); v.w = clip_value(v.w, &clipped, cbit);
         }
         if constexpr (PLANAR)
           pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(reinterpret_cast<PCM*>(A.pcm) + ((long long)r0.y + (idx0 - (int)r1.w)) +
@@ -2180,7 +2188,7 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
     if constexpr (PLANAR) {
       // (stored per channel above)
     } else if constexpr (MONO) {
-      const float4 m = mono_mix2(o, nch, A.clip, &clipped);
+      const float4 m = mono_mix2(o, nch, A.clip, &clipped, cbit);
       pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out), m.x, m.y, m.z, m.w);
     } else if (nch == 2) {
       if constexpr (std::is_same<PCM, int16_t>::value) {
@@ -2193,7 +2201,7 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
       pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out), o[0], o[2], o[4], o[6]);
     }
   }
-  if (A.clip && emit) report_clipped(clipped, A.clipped_flag);
+  if (A.clip && emit) report_clipped<FPW + 1>(clipped, A.clipped_flag, fa);
   GR_T(7);
 #undef GR_T
 }

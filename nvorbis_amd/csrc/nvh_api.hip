@@ -243,8 +243,8 @@ extern "C" int nvh_stream_open(nvh_ctx* c, const uint8_t* id_pkt, int id_len, co
       if ((rc = s->carry[k].reserve(plane)) != NVH_OK) return rc;
       HIP_TRY(hipMemsetAsync(s->carry[k].p, 0, plane, c->stream));
     }
-    if ((rc = s->flags.reserve(2 * sizeof(int))) != NVH_OK) return rc;
-    HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), c->stream));
+    if ((rc = s->flags.reserve(4 * sizeof(int))) != NVH_OK) return rc;  // (nvh_internal.h: two flag words, one device address)
+    HIP_TRY(hipMemsetAsync(s->flags.p, 0, 4 * sizeof(int), c->stream));
     if ((rc = s->carry_exec.reserve(2 * sizeof(uint32_t))) != NVH_OK) return rc;
     HIP_TRY(hipMemsetAsync(s->carry_exec.p, 0, 2 * sizeof(uint32_t), c->stream));
     if (nvh_toggles().gpu_parse_default && s->shared->gpu_parse_ok) {  // opt-in default for whole test runs
@@ -440,6 +440,7 @@ extern "C" int nvh_stream_reset(nvh_stream* s) {
     s->replay.clear();
     s->replay_error = NVH_OK;
     s->synth_segments.clear();
+    s->synth_clipped.clear();
     s->parser.reset(new (std::nothrow) nvh::StreamParser(&s->setup));
     if (!s->parser) return NVH_ERR_NOMEM;
     s->parser->set_light(s->gpu_parse);
@@ -564,6 +565,19 @@ extern "C" int nvh_stream_synth_segments(const nvh_stream* s, int64_t* index, in
   });
 }
 
+// Entry i: whether the batch the last synthesis call consumed clamped a sample of entry i of nvh_stream_synth_segments (the rule
+// is in the public header).  Host state: the flags came back with the batch's PCM.
+extern "C" int nvh_stream_synth_segments_clipped(const nvh_stream* s, int32_t* clipped, int cap, int* count) {
+  return nvh_guard([&]() -> int {
+    if (!s || !count || cap < 0 || (cap > 0 && !clipped)) return NVH_ERR_ARGUMENT;
+    const int n = (int)s->synth_clipped.size();
+    *count = n;
+    if (cap < n) return NVH_ERR_ARGUMENT;
+    for (int i = 0; i < n; i++) clipped[i] = s->synth_clipped[(size_t)i];
+    return NVH_OK;
+  });
+}
+
 extern "C" int nvh_stream_pending_geometry(const nvh_stream* s, int32_t* out, int cap_frames) {
   return nvh_guard([&]() -> int {
     if (!s || !out) return NVH_ERR_ARGUMENT;
@@ -671,6 +685,31 @@ static bool host_pinned(const void* p) {
   return false;
 }
 
+// Per-segment HasClipped of the batch synth_stage has just launched: queue the read-back of its table's flag words (a batch
+// of two or more segments; nvh_launch.hip: upload_seg_table) into `h`, behind the kernels on the launch stream.  Returns the
+// number of words on their way, 0 for a batch without a table.
+static int seg_flags_readback(nvh_stream* s, DevBuf& h, int* words) {
+  const nvh_batch* b = &s->scratch;
+  *words = 0;
+  if (!b->seg_table) return NVH_OK;
+  const size_t n = b->segments.size();
+  int rc = h.reserve(n * sizeof(int32_t));
+  if (rc != NVH_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(h.p, b->seg_flags_dev(), n * sizeof(int32_t), hipMemcpyDeviceToHost, s->ctx->stream));
+  *words = (int)n;
+  return NVH_OK;
+}
+// ... and, once they have landed, the table nvh_stream_synth_segments_clipped reports, aligned with s->synth_segments.  Without a
+// table the batch's sticky word is the flag of its one segment (segments that emit nothing have none to set).
+static void seg_flags_take(nvh_stream* s, const DevBuf& h, int words, int sticky) {
+  s->synth_clipped.assign(s->synth_segments.size(), 0);
+  if (words > 0) {
+    for (int i = 0; i < words && i < (int)s->synth_clipped.size(); i++) s->synth_clipped[(size_t)i] = ((const int32_t*)h.p)[i] != 0;
+  } else if (s->synth_clipped.size() == 1) {
+    s->synth_clipped[0] = sticky != 0;
+  }
+}
+
 // The head the synchronous and the pipelined path share: upload the pending batch, size its PCM in the layout of `out`, launch the
 // kernels -- into d_pcm where the caller has a device destination, else into `staging` -- and flip the carried tail.  *P: the
 // batch's shape; *dst: where its PCM lies on the device.  `capacity` in the unit of *written.
@@ -723,7 +762,10 @@ static int stream_synth(nvh_stream* s, const PcmOut& out, void* pcm_host, void* 
   int* h_flags = (int*)((uint8_t*)s->h_pcm.p + bounce);
   if (pcm_host) HIP_TRY(planar_readback(direct ? pcm_host : s->h_pcm.p, direct ? P.stride : P.len, dst, P.stage, P.len, P.planes, sb, st));
   HIP_TRY(hipMemcpyAsync(h_flags, s->flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  int seg_words = 0;
+  if ((rc = seg_flags_readback(s, s->h_seg_flags[0], &seg_words)) != NVH_OK) return rc;
   HIP_TRY(nvh_wait_stream(s->ctx, st));
+  seg_flags_take(s, s->h_seg_flags[0], seg_words, h_flags[1]);
   if (bounce)
     for (int c = 0; c < P.planes; c++)
       std::memcpy((uint8_t*)pcm_host + (size_t)c * (size_t)P.stride * sb, (const uint8_t*)s->h_pcm.p + (size_t)c * plane_bytes, plane_bytes);
@@ -759,6 +801,7 @@ static int stream_synth_begin(nvh_stream* s, const PcmOut& out, void* pcm_host, 
   F.replay_error = NVH_OK;
   F.replay_errors.clear();
   F.segments.clear();
+  F.seg_flag_words = 0;
   if (s->pending.frames.empty()) {  // nothing to do: an outstanding "batch" of zero samples keeps begin / end paired
     HIP_TRY(hipEventRecord(F.done, st));
     F.on = true;
@@ -774,6 +817,7 @@ static int stream_synth_begin(nvh_stream* s, const PcmOut& out, void* pcm_host, 
   // this batch's flag words, then a clean pair for the next one (all on the launch stream, in order)
   HIP_TRY(hipMemcpyAsync((int*)s->h_flags2.p + 2 * slot, s->flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemsetAsync(s->flags.p, 0, 2 * sizeof(int), st));
+  if ((rc = seg_flags_readback(s, s->h_seg_flags[slot], &F.seg_flag_words)) != NVH_OK) return rc;  // (in front of F.kernels: F.done covers it)
   HIP_TRY(hipEventRecord(F.kernels, st));
   HIP_TRY(hipStreamWaitEvent(s->copy_stream, F.kernels, 0));
   HIP_TRY(planar_readback(pcm_host, P.stride, dst, P.stage, P.len, P.planes, out.sample_bytes(), s->copy_stream));
@@ -964,6 +1008,7 @@ extern "C" int nvh_stream_synth_end(nvh_stream* s, int64_t* written) {
     s->replay_error = F.replay_error;  // nvh_stream_parse_errors then describes THIS batch
     s->replay_errors = F.replay_errors;
     s->synth_segments = F.segments;  // ... and nvh_stream_synth_segments
+    seg_flags_take(s, s->h_seg_flags[slot], F.seg_flag_words, F.need > 0 ? ((const int*)s->h_flags2.p)[2 * slot + 1] : 0);
     if (F.need > 0) {
       const int* h = (const int*)s->h_flags2.p + 2 * slot;
       if (h[1]) s->has_clipped = 1;

@@ -361,6 +361,16 @@ struct nvh_batch {
   // (chunk, plane).  `gaps` then holds only the gaps of at most one chunk.
   std::vector<nvh::FrameBatch::Gap> row_chunks;
   std::vector<nvh::FrameBatch::Segment> segments;  // the batch's segment table as finally parsed (nvh_stream_synth_segments)
+  // Per-segment HasClipped (nvh_stream_synth_segments_clipped; kernels_common.h: report_clipped).  Only the stream's own batch
+  // asks for it (want_seg_flags), and only a batch of two or more segments with frames has a table: seg_image is its host
+  // image in page-locked memory -- 8 bytes holding the device address of the table, then one int32 per frame (the index, from
+  // the table's base, of the flag word of the segment the frame emits into), then one zeroed flag word per segment -- and
+  // seg_dev the copy the kernels reach through the stream's flag block.  No table: the batch's sticky word is its one flag.
+  bool want_seg_flags = false;
+  bool seg_table = false;
+  DevBuf seg_dev, seg_image;
+  int* seg_table_dev() const { return seg_table ? (int*)((uint8_t*)seg_dev.p + 8) : nullptr; }
+  int* seg_flags_dev() const { return seg_table ? seg_table_dev() + nframes : nullptr; }
 };
 
 // GPU-parse mode: everything pushed since the last batch boundary, so that a batch in which k_parse found a packet the
@@ -390,7 +400,9 @@ struct nvh_stream {
   nvh::SlabBatch slab_build;  // scratch of host_slab.cpp, reused from batch to batch
   DevBuf carry[2];  // [ch][block1] windowed block of the last decoded frame (ping-pong: read one, write the other)
   int carry_cur = 0;
-  DevBuf flags;  // int[2]: device error word, clipped flag
+  DevBuf flags;  // int[4]: device error word, clipped flag, and (8 bytes) the device address of the running batch's segment-flag
+                 // table or null (nvh_batch::seg_table_dev; the emitting kernels read it behind the clipped flag)
+  int* seg_table_set = nullptr;  // what those 8 bytes hold once everything queued has run
   DevBuf pcm;    // staging for host-destination synth
   DevBuf h_pcm;  // pinned bounce buffer behind it (+ 2 ints: the flag words), read back asynchronously
   int clip = 1;
@@ -402,6 +414,8 @@ struct nvh_stream {
   std::unique_ptr<nvh::StreamParser> replay_start;  // parser state at the first logged event
   int replay_error = NVH_OK;                         // first error of the last replay (reported by the synthesis call)
   std::vector<nvh::FrameBatch::Segment> synth_segments;  // segment table of the batch the last synthesis call consumed, as finally parsed
+  std::vector<int32_t> synth_clipped;  // ... and, entry for entry, whether that batch clamped a sample of the segment
+  DevBuf h_seg_flags[2];   // pinned: the segment flag words of a batch on their way back (a pipelined batch: its flight's slot)
   std::vector<std::pair<int, int64_t>> replay_errors;  // every error of it: (code, samples per channel the batch emits before that packet)
   // Pipelined read-back (nvh_stream_synth_begin / _end): the PCM of batch i travels to the host on a stream of its own while
   // batch i+1 is uploaded, parsed and synthesised.  Two batches may be outstanding, ended in the order they were begun.
@@ -412,6 +426,7 @@ struct nvh_stream {
     int replay_error = NVH_OK;
     std::vector<std::pair<int, int64_t>> replay_errors;
     std::vector<nvh::FrameBatch::Segment> segments;
+    int seg_flag_words = 0;  // flag words of the batch's table in h_seg_flags[slot]; 0: the sticky word is the one segment's flag
   };
   hipStream_t copy_stream = nullptr;
   DevBuf pcm2[2];
@@ -433,6 +448,10 @@ struct nvh_stream {
     carry[0].pool = carry[1].pool = flags.pool = pcm.pool = carry_exec.pool = pcm2[0].pool = pcm2[1].pool = pool;
     h_flags2.host = true;
     h_flags2.pool = c ? &c->hpool : nullptr;
+    h_seg_flags[0].host = h_seg_flags[1].host = scratch.seg_image.host = true;
+    h_seg_flags[0].pool = h_seg_flags[1].pool = scratch.seg_image.pool = c ? &c->hpool : nullptr;
+    scratch.seg_dev.pool = pool;
+    scratch.want_seg_flags = true;
     scratch.blob.pool = scratch.work.pool = scratch.carry_in.pool = scratch.slabs.pool = scratch.dev_copy.pool = scratch.slab3.pool = pool;
     scratch.gap_dev.pool = pool;
     scratch.gap_host.host = true;

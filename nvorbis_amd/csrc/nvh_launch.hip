@@ -515,9 +515,46 @@ static int upload_gaps(nvh_stream* s, nvh_batch* b) {
   return NVH_OK;
 }
 
+// The batch's segment-flag table (nvh_internal.h: nvh_batch::seg_image) to the device, flag words zeroed: one small copy, on
+// the stream, and only for a batch of two or more segments.  batch_upload_frames filled the image while it had the frames.
+static int upload_seg_table(nvh_stream* s, nvh_batch* b) {
+  if (!b->seg_table) return NVH_OK;
+  const size_t bytes = 8 + ((size_t)b->nframes + b->segments.size()) * sizeof(int32_t);
+  int rc = b->seg_dev.reserve(bytes);
+  if (rc != NVH_OK) return rc;
+  int* table = b->seg_table_dev();
+  std::memcpy(b->seg_image.p, &table, sizeof table);
+  HIP_TRY(hipMemcpyAsync(b->seg_dev.p, b->seg_image.p, bytes, hipMemcpyHostToDevice, s->ctx->stream));
+  return NVH_OK;
+}
+
+// Which segment of the batch's table each frame emits into: frames and segments both run in output order, a frame that emits
+// lies inside exactly one segment's [begin, end), and a frame that emits nothing is never reported (slot 0).
+static int build_seg_table(nvh_batch* b, const nvh::FrameBatch& P) {
+  b->seg_table = false;
+  if (!b->want_seg_flags || b->segments.size() < 2 || P.frames.empty()) return NVH_OK;
+  const size_t nf = P.frames.size(), ns = b->segments.size();
+  int rc = b->seg_image.reserve(8 + (nf + ns) * sizeof(int32_t));
+  if (rc != NVH_OK) return rc;
+  int32_t* idx = (int32_t*)((uint8_t*)b->seg_image.p + 8);
+  size_t slot = 0;
+  for (size_t f = 0; f < nf; f++) {
+    const NvhFrame& fr = P.frames[f];
+    if (fr.emit_count > 0) {
+      while (slot + 1 < ns && (int64_t)fr.out_pos >= b->segments[slot].end) slot++;
+      if ((int64_t)fr.out_pos < b->segments[slot].begin || (int64_t)fr.out_pos + fr.emit_count > b->segments[slot].end) return NVH_ERR_RUNTIME;
+    }
+    idx[f] = (int32_t)(nf + (fr.emit_count > 0 ? slot : 0));
+  }
+  std::memset(idx + nf, 0, ns * sizeof(int32_t));
+  b->seg_table = true;
+  return NVH_OK;
+}
+
 int batch_upload(nvh_stream* s, nvh_batch* b) {
   int rc = batch_upload_frames(s, b);
-  return rc != NVH_OK ? rc : upload_gaps(s, b);
+  if (rc == NVH_OK) rc = upload_gaps(s, b);
+  return rc != NVH_OK ? rc : upload_seg_table(s, b);
 }
 
 static int batch_upload_frames(nvh_stream* s, nvh_batch* b) {
@@ -529,6 +566,7 @@ static int batch_upload_frames(nvh_stream* s, nvh_batch* b) {
     b->pcm_samples = P.pcm_samples;
     b->segments = P.closed_segments;
     b->segments.push_back({s->parser->segment(), P.segment_begin, P.pcm_samples});
+    b->seg_table = false;
     b->gaps = P.gaps;
     b->last_decoded = -1;
     b->ola_count = 0;
@@ -543,6 +581,7 @@ static int batch_upload_frames(nvh_stream* s, nvh_batch* b) {
   // segments: the batch's table as it is parsed NOW (a replayed batch comes through here again) and the gaps between them
   b->segments = P.closed_segments;
   b->segments.push_back({s->parser->segment(), P.segment_begin, P.pcm_samples});
+  if (int rc = build_seg_table(b, P); rc != NVH_OK) return rc;
   b->gaps = P.gaps;
   b->sequential_ola = P.sequential_ola;
   b->last_decoded = -1;
@@ -915,6 +954,13 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
   };
   float* work = (float*)b->work.p;
   int* flags = (int*)s->flags.p;
+  // the segment-flag table the emitting kernels find behind the clipped flag: this batch's, or none (every batch of one segment,
+  // every resident batch) -- written only when it changes, so a plain stream queues nothing here
+  if (int* table = b->seg_table_dev(); table != s->seg_table_set) {
+    if (table) HIP_TRY(hipMemcpyAsync(flags + 2, b->seg_image.p, sizeof table, hipMemcpyHostToDevice, st));
+    else HIP_TRY(hipMemsetAsync(flags + 2, 0, sizeof table, st));
+    s->seg_table_set = table;
+  }
   const size_t lds = (size_t)s->setup.block1 * sizeof(float);
   ScopedEvent sev[5];
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};

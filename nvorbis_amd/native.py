@@ -97,6 +97,7 @@ SIGNATURES = {
     "nvh_stream_segment_window": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64]),
     "nvh_stream_pending_segments": (C.c_int, [_vp, _i64p, _i64p, _i64p, C.c_int, _ip]),
     "nvh_stream_synth_segments": (C.c_int, [_vp, _i64p, _i64p, _i64p, C.c_int, _ip]),
+    "nvh_stream_synth_segments_clipped": (C.c_int, [_vp, _ip, C.c_int, _ip]),
     "nvh_stream_pending_geometry": (C.c_int, [_vp, _vp, C.c_int]),
     "nvh_stream_pending_slabs": (C.c_int, [_vp, _vp, C.c_int64, _i64p, _vp, C.c_int]),
     "nvh_stream_lattice_pool": (C.c_int, [_vp, _vp, C.c_int64, _i64p]),

@@ -502,6 +502,17 @@ class Stream:
         parser failed on (`parse_errors`) were left out.  [0, 3] before the first synthesis."""
         return self._segments(lib().nvh_stream_synth_segments, "nvh_stream_synth_segments")
 
+    def synth_segments_clipped(self):
+        """Per-segment HasClipped of the batch the last synthesis call consumed (nvh_stream_synth_segments_clipped): a bool array,
+        entry i for row i of `synth_segments()` -- whether ClipSamples clamped a sample this batch emitted inside that segment,
+        in the call's output form.  OR it over the batches a segment runs through; `has_clipped()` stays the OR of everything."""
+        n = C.c_int(0)
+        lib().nvh_stream_synth_segments_clipped(self._h, None, 0, C.byref(n))
+        out = np.zeros(max(n.value, 1), dtype=np.int32)
+        check(lib().nvh_stream_synth_segments_clipped(self._h, out.ctypes.data_as(C.POINTER(C.c_int)), out.shape[0], C.byref(n)),
+              "nvh_stream_synth_segments_clipped")
+        return out[:n.value] != 0
+
     def _segments(self, fn, where):
         n = C.c_int(0)
         fn(self._h, None, None, None, 0, C.byref(n))

@@ -10,6 +10,12 @@ per clip.  DIR is a checkout of the parent commit with its library built: the ba
 sequentially and on 16 threads with a context each -- in a process of its own; decode_clips runs in this tree.  Parent and
 branch alternate, `--runs` runs each; the table reports clips/s and frames/s as min - max.
 
+    python tools/clip_rates.py --flags --parent-tree DIR [--clips 2048] [--runs 3] [--out profiles/segment_clipped_rates.txt]
+
+--flags: what per-segment HasClipped costs.  The same workload through nv.decode_clips in the parent tree (clips_plain), in this
+tree without the keyword (clips_plain) and with return_clipped=True (clips_flags), and the headline of `python bench.py` in both
+trees; parent and branch alternate.
+
 Every measurement is a child process (this script with --child): a fresh HIP runtime each time, nothing shared between runs."""
 import argparse
 import json
@@ -133,6 +139,18 @@ def child(mode, workload, length, batch_frames):
             dt = time.perf_counter() - t0
         for c in ctxs:
             c.close()
+    elif mode in ("clips_plain", "clips_flags"):
+        kw = {"return_clipped": True} if mode == "clips_flags" else {}
+        ctx = nv.Context(0)
+        nv.decode_clips(files[:32], ctx=ctx, batch_frames=batch_frames, **kw)
+        t0 = time.perf_counter()
+        res = nv.decode_clips(files, ctx=ctx, batch_frames=batch_frames, gpu_parse=True, align=4, **kw)
+        dt = time.perf_counter() - t0
+        if kw:
+            res, clipped = res
+            out["clipped_clips"] = int(clipped.sum())
+        out["samples"] = sum(r.size for r in res)
+        ctx.close()
     else:
         ctx = nv.Context(0)
         nv.decode_clips(files[:32], ctx=ctx, batch_frames=batch_frames)
@@ -159,13 +177,59 @@ def run_child(tree, mode, workload, length, batch_frames):
     return json.loads(lines[-1][len("CLIP_RATES "):])
 
 
+def bench_headline(tree):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` in `tree`: the headline (frames/s) of its one JSON line."""
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], cwd=tree,
+                       env=dict(os.environ, PYTHONPATH=tree), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    if p.returncode != 0 or not lines:
+        raise SystemExit("bench.py in %s failed (exit %d):\n%s" % (tree, p.returncode, p.stdout[-2000:]))
+    return float(json.loads(lines[-1])["value"])
+
+
+def flags_main(a, parent):
+    """--flags: profiles/segment_clipped_rates.txt"""
+    workdir = tempfile.mkdtemp(prefix="clip_rates_")
+    workload = os.path.join(workdir, "workload.pkl")
+    make_workload(a.clips, workload)
+    bench, rows = {"parent": [], "branch": []}, {}
+    for _ in range(a.runs):  # parent and branch alternate
+        for who, tree in (("parent", parent), ("branch", ROOT)):
+            bench[who].append(bench_headline(tree))
+            print("bench %s %.1f M frames/s" % (who, bench[who][-1] / 1e6), flush=True)
+    for length in (40, 8):
+        for _ in range(a.runs):
+            for who, tree, mode in (("parent", parent, "clips_plain"), ("branch", ROOT, "clips_plain"), ("branch", ROOT, "clips_flags")):
+                r = run_child(tree, mode, workload, length, a.batch_frames)
+                rows.setdefault((length, who, mode), []).append(r)
+                print(who, json.dumps(r), flush=True)
+    with open(a.out, "w") as fh:
+        fh.write("# tools/clip_rates.py --flags: parent commit against this tree, alternating, %d runs each; min - max over the runs.\n" % a.runs)
+        fh.write("# python bench.py --gpus 1 --steps 20 --warmup 5, the headline (frames/s, kernel only):\n")
+        for who in ("parent", "branch"):
+            fh.write("%-8s %12.0f - %-12.0f  (%s)\n" % (who, min(bench[who]), max(bench[who]),
+                                                       ", ".join("%.1f M" % (v / 1e6) for v in bench[who])))
+        fh.write("# nv.decode_clips: %d clips per length cut from 3test.ogg, one context, GPU packet parser, f32 interleaved to the host,\n"
+                 "# batch_frames %d, align 4.  clips_plain: without the keyword; clips_flags: return_clipped=True.\n" % (a.clips, a.batch_frames))
+        fh.write("%-8s %-8s %-12s %-25s %-27s\n" % ("packets", "tree", "mode", "clips/s", "frames/s"))
+        for (length, who, mode), rs in rows.items():
+            c, f = [r["clips_per_s"] for r in rs], [r["frames_per_s"] for r in rs]
+            fh.write("%-8d %-8s %-12s %10.0f - %-12.0f %11.0f - %-13.0f\n" % (length, who, mode, min(c), max(c), min(f), max(f)))
+        for (length, who, mode), rs in rows.items():
+            if mode == "clips_flags":
+                fh.write("# %d packets per clip: %d of %d clips flagged\n" % (length, rs[-1]["clipped_clips"], rs[-1]["clips"]))
+    print(open(a.out).read())
+    shutil.rmtree(workdir, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-tree")
+    ap.add_argument("--flags", action="store_true")
     ap.add_argument("--clips", type=int, default=2048)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--batch-frames", type=int, default=4096)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "clip_batch_rates.txt"))
+    ap.add_argument("--out")
     ap.add_argument("--child")
     ap.add_argument("--workload")
     ap.add_argument("--length", type=int, default=40)
@@ -175,6 +239,9 @@ def main():
     if not a.parent_tree:
         raise SystemExit("--parent-tree: a checkout of the parent commit with its library built")
     parent = os.path.abspath(a.parent_tree)
+    a.out = a.out or os.path.join(ROOT, "profiles", "segment_clipped_rates.txt" if a.flags else "clip_batch_rates.txt")
+    if a.flags:
+        return flags_main(a, parent)
     workdir = tempfile.mkdtemp(prefix="clip_rates_")
     workload = os.path.join(workdir, "workload.pkl")  # (the clips, for the child processes)
     make_workload(a.clips, workload)

@@ -605,6 +605,59 @@ int nvh_ogg_index_page(const nvh_ogg_index *ix, int page, int64_t *granule, int 
 int nvh_ogg_seek(const nvh_ogg_index *ix, const nvh_stream *s, int64_t granule_pos, int pre_roll, int64_t *packet_index,
                  int64_t *granule_out);
 
+/* ---- rows at one sample rate: a stateless polyphase resampler over rows of f32 samples ----
+ * Every output row is a pure function of a window of source samples; nothing is carried from call to call, and no synthesis
+ * call, emitting kernel or parser takes part.  THE RULE (a dozen lines of numpy reproduce it bit for bit):
+ *   Ratio and width.  Source rate fi, target rate fo, g = gcd(fi, fo), L = fo / g (up), M = fi / g (down).
+ *     half = 16 when L >= M, else (16 * M + L - 1) / L in integers; W = 16 * max(1, M / L) and sc = 0.94 * min(1, L / M) in reals.
+ *   Taps.  A table h[L][2 * half] of f32: tap k of phase p lies at t = (k - half + 1) - p / L, with u = t / W, and
+ *     h = sc * sinc(sc * t) * I0(9 * sqrt(1 - u * u)) / I0(9) for |u| < 1, else 0; sinc(x) = sin(pi x) / (pi x), 1 at 0; I0 by its
+ *     power series to convergence.  Everything in double on the host, rounded once to f32.
+ *   Output sample J of a clip (J counts from 0 in the clip resampled as a whole): n = J * M in 64 bits, c = n div L, p = n mod L;
+ *     acc = +0.0f; for k = 0 .. 2 * half - 1 in this order: acc = fl(acc + fl(x[c - half + 1 + k] * h[p][k])) -- product and sum
+ *     rounded separately, one accumulator.  x is the clip's f32 sample in the requested output form (after the mono mix or the
+ *     channel map, after ClipSamples' clip, per output channel) and 0 outside [0, total).  (Skipping the terms whose x lies
+ *     outside the clip gives the same bits.)
+ *   Clip and format.  The result goes through ClipSamples' clip again (a band-limited filter overshoots), then, for NVH_PCM_S16,
+ *     through the 16-bit conversion of nvh_stream_synth_pcm.
+ *   Length.  total_out = (total * L + M - 1) / M.  A row [start, start + T) counts target-rate samples;
+ *     valid = clamp(total_out - start, 0, T); the samples at and behind `valid` are zeros, as pads are, not filter ringing.
+ *   Limits.  NVH_ERR_ARGUMENT for a rate below 1; NVH_ERR_UNSUPPORTED for L > 4096 or L * 2 * half > 262144.
+ *
+ * nvh_resample_plan: *up = L, *down = M, *half, *tap_count = L * 2 * half.  Host only; every output pointer is required.
+ * nvh_resample_taps: the table exactly as the kernel uses it, phase after phase.  Host only.  *count is set even when `cap` is
+ *   too small (NVH_ERR_ARGUMENT then).
+ * nvh_resample_rows: `rows` rows of `length` (T) output samples per channel, asynchronous on the context's HIP stream.
+ *   Element (row i, sample time e, channel c) of the source lies at d_src + i * src_row_stride + e * src_time_stride +
+ *   c * src_chan_stride (f32), for e in [0, src_length); of the destination at d_dst + dst_row[i] * dst_row_stride + t *
+ *   dst_time_stride + c * dst_chan_stride in elements of `format` -- interleaved, planar (C, N, T) and mono are stride choices.
+ *   origin[i]: the source-sample index that element 0 of source row i holds; reads outside the row are 0.  start[i], valid[i]: as
+ *   in the rule (0 <= valid[i] <= length; the row's samples from valid[i] on are written as zeros).  dst_row: the destination
+ *   row of row i, or NULL for i.  d_clipped: NULL, or one int32 per DESTINATION row, zeroed by the caller; word dst_row[i]
+ *   becomes non-zero when the second clip clamped a sample of that row (one lane per wavefront looks and sets, as HasClipped's
+ *   word is set).  The four per-row arrays are host arrays, read during the call and uploaded in one copy; the device tap table
+ *   is cached per context and (L, M).  Errors, before any device is touched: NVH_ERR_ARGUMENT for no descriptor, a rate below 1,
+ *   rows / length / src_length below 0, channels below 1, an unknown format, a missing array or buffer with rows and length
+ *   above 0, a start or an origin below 0 or with start + length above 2^48, a valid outside [0, length], a dst_row below 0;
+ *   NVH_ERR_UNSUPPORTED as nvh_resample_plan; NVH_ERR_NO_GPU for no context.  The kernel owns NVH_RESAMPLE_TILE consecutive
+ *   outputs of one (row, channel) per workgroup step. */
+#define NVH_RESAMPLE_TILE 512
+typedef struct nvh_resample_desc {
+  int32_t in_rate, out_rate;
+  int32_t rows;     /* N */
+  int32_t channels; /* output channels per row (1 for the mono mix) */
+  int32_t format;   /* NVH_PCM_* of the destination; the source is f32 */
+  int32_t reserved; /* 0 */
+  int64_t length;     /* T: output samples per row and channel */
+  int64_t src_length; /* source samples per row and channel */
+  int64_t src_row_stride, src_time_stride, src_chan_stride; /* in f32 elements */
+  int64_t dst_row_stride, dst_time_stride, dst_chan_stride; /* in elements of `format` */
+} nvh_resample_desc;
+int nvh_resample_plan(int in_rate, int out_rate, int *up, int *down, int *half, int64_t *tap_count);
+int nvh_resample_taps(int in_rate, int out_rate, float *taps, int64_t cap, int64_t *count);
+int nvh_resample_rows(nvh_ctx *ctx, const nvh_resample_desc *desc, const float *d_src, void *d_dst, const int64_t *origin,
+                      const int64_t *start, const int64_t *valid, const int32_t *dst_row, int32_t *d_clipped);
+
 /* ---- multi-GPU: the gather of the file-parallel corpus transcode (SURVEY 8 e) ----
  * StreamDecoder holds per-stream state only (StreamDecoder.cs:35-39), so a corpus shards by file: every process decodes its
  * files on its own GPU (one nvh_ctx per process) and the PCM is gathered on one of them -- the path's one collective, through

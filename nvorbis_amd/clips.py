@@ -241,8 +241,9 @@ def plan_clip_window(position_after, emitted_after, state_after, total, start, l
 def push_clip_window(st, pa, plan, length, room=None, flush=None):
     """Push one planned row into the current segment of `st` (the caller closes it with next_segment): the window, the lead-in,
     the position state, the packets.  room() -> how many more frames the pending batch takes, flush() synthesises it; without
-    them everything is pushed at once.  `pa` is the clip's PacketArray (three headers first)."""
-    st.segment_window(plan["skip"], length, length)
+    them everything is pushed at once.  `pa` is the clip's PacketArray (three headers first).  A plan with a "take" emits that
+    many samples at most and pads the row to `length` (the resampler's source rows: a window of the row's own)."""
+    st.segment_window(plan["skip"], plan.get("take", length), length)
     if plan["valid"] == 0:
         return
     if plan["lead"] is not None:
@@ -349,8 +350,128 @@ class _RowGroup:
         self.done += wr.value if per else wr.value // och
 
 
+def resample_plan(in_rate, out_rate):
+    """(L, M, half, tap_count) of nvh_resample_plan for a source and a target rate; ValueError for a pair outside its limits."""
+    up, down, half, count = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+    rc = native.lib().nvh_resample_plan(int(in_rate), int(out_rate), C.byref(up), C.byref(down), C.byref(half), C.byref(count))
+    if rc in (native.ERR_UNSUPPORTED, native.ERR_ARGUMENT):
+        raise ValueError("no resampler from %d Hz to %d Hz: the ratio is outside the limits (include/nvorbis_hip.h)" % (in_rate, out_rate))
+    native.check(rc, "nvh_resample_plan")
+    return up.value, down.value, half.value, count.value
+
+
+def resample_taps(in_rate, out_rate):
+    """The tap table of nvh_resample_taps as a float32 array (L, 2 * half): exactly what k_resample_rows reads."""
+    L, _, half, count = resample_plan(in_rate, out_rate)
+    h = np.zeros(count, np.float32)
+    got = C.c_int64(0)
+    native.check(native.lib().nvh_resample_taps(int(in_rate), int(out_rate), h.ctypes.data, count, C.byref(got)), "nvh_resample_taps")
+    return h.reshape(L, 2 * half)
+
+
+def _sample_rate(value):
+    if value is None:
+        return None
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 1 or value > 2 ** 31 - 1:
+        raise ValueError("sample_rate must be None or an int in [1, 2**31), not %r" % (value,))
+    return int(value)
+
+
+def _run_row_groups(ctx, members, packets, plans, opts, length, base, rows_total):
+    """Clips `members` as rows [0, len(members)) of the buffer at `base` (of rows_total rows), grouped by setup, one _RowGroup
+    after the other.  Returns the clips in the order of their rows."""
+    groups = {}
+    for i in members:
+        groups.setdefault((packets[i][0], packets[i][2]), []).append(i)
+    placed, row0 = [], 0
+    for group in groups.values():
+        try:
+            g = _RowGroup(ctx, group, packets, plans, opts, length)
+        except native.NvhError as e:
+            raise _clip_error(group[0], e, "nvh_stream_open", "decode_clip_rows")
+        try:
+            g.run(base, row0, rows_total)
+        finally:
+            g.stream.close()
+        row0 += len(group)
+        placed += group
+    return placed, len(groups)
+
+
+def _resampled_rows(ctx, device, packets, index, rates, plans, starts, length, sample_rate, och, dtype, planar, mono, opts, clipped):
+    """decode_clip_rows with at least one clip at another rate than `sample_rate`: (buf, valid) on the device, rows in input
+    order.  Clips at the target rate go through the row path as they are and are copied to their rows; the others are classed by
+    source rate, every class decodes f32 source rows [origin, origin + S) into a temporary buffer through the same row path,
+    and k_resample_rows writes the class's rows of the returned buffer."""
+    import torch
+    n = len(packets)
+    dev = "cuda:%d" % int(device)
+    tdt = torch.int16 if dtype == np.dtype(np.int16) else torch.float32
+    row_axis = 1 if planar else 0
+
+    def shape_of(rows, t):
+        return (och, rows, t) if planar else (rows, t) if mono else (rows, t, och)
+
+    def strides_of(rows, t):  # (row, sample time, channel) in elements
+        return (t, 1, rows * t) if planar else (t, 1, 0) if mono else (t * och, och, 1)
+    buf = torch.empty(shape_of(n, length), dtype=tdt, device=dev)
+    flags = torch.zeros(n, dtype=torch.int32, device=dev) if clipped is not None else None
+    valid = np.asarray([p["valid"] for p in plans], dtype=np.int64)
+    same = [i for i in range(n) if rates[i] == sample_rate]
+    classes = {}
+    for i in range(n):
+        if rates[i] != sample_rate:
+            classes.setdefault(rates[i], []).append(i)
+    keep = []  # the temporaries, until the context's stream has run
+    setups = {}
+    for i in same:
+        setups.setdefault((packets[i][0], packets[i][2]), []).append(i)
+    for group in setups.values():  # (a buffer per setup: every group begins on an allocation's alignment, whatever the length)
+        tmp = torch.empty(shape_of(len(group), length), dtype=tdt, device=dev)
+        placed, _ = _run_row_groups(ctx, group, packets, plans, opts, length, tmp.data_ptr(), len(group))
+        buf.index_copy_(row_axis, torch.as_tensor(placed, dtype=torch.int64, device=dev), tmp)
+        keep.append(tmp)
+    f32 = dict(opts, dtype=np.dtype(np.float32))
+    for rate, members in classes.items():
+        L, M, half, _ = resample_plan(rate, sample_rate)
+        origin, take = {}, {}
+        for i in members:
+            total = index[i][3]
+            total_out = (total * L + M - 1) // M
+            valid[i] = min(length, max(0, total_out - starts[i]))
+            origin[i] = take[i] = 0  # (nothing of the clip in the row: no packet is decoded, the source row is a pad)
+            if valid[i]:
+                c_first, c_last = (starts[i] * M) // L, ((starts[i] + int(valid[i]) - 1) * M) // L
+                origin[i] = max(0, c_first - half + 1) & ~3
+                take[i] = (c_last + half + 1 - origin[i] + 3) & ~3
+        S = max(4, max(take.values()))  # the source rows' pitch; row i holds source samples [origin, origin + take) and a pad
+        src_plans = {}
+        for i in members:
+            pos, em, state, total = index[i]
+            src_plans[i] = plan_clip_window(pos, em, state, total, origin[i] if take[i] else total, take[i])
+            if take[i]:
+                src_plans[i]["take"] = take[i]
+        tmp = torch.empty(shape_of(len(members), S), dtype=torch.float32, device=dev)
+        placed, _ = _run_row_groups(ctx, members, packets, src_plans, f32, S, tmp.data_ptr(), len(members))
+        torch.cuda.current_stream(dev).synchronize()  # (the flag words are zeroed on torch's stream)
+        sr, st, sc = strides_of(len(members), S)
+        dr, dt, dc = strides_of(n, length)
+        desc = native.ResampleDesc(in_rate=rate, out_rate=sample_rate, rows=len(members), channels=och,
+                                   format=native.PCM_S16 if tdt == torch.int16 else native.PCM_F32, length=length, src_length=S,
+                                   src_row_stride=sr, src_time_stride=st, src_chan_stride=sc, dst_row_stride=dr,
+                                   dst_time_stride=dt, dst_chan_stride=dc)
+        ctx.resample_rows(desc, tmp.data_ptr(), buf.data_ptr(), [origin[i] for i in placed], [starts[i] for i in placed],
+                          [valid[i] for i in placed], placed, None if flags is None else flags.data_ptr())
+        keep.append(tmp)
+    ctx.synchronize()
+    if flags is not None:
+        clipped |= flags.cpu().numpy() != 0
+    del keep
+    return buf, valid
+
+
 def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frames=4096, gpu_parse=True, sample_format="f32",
-                     layout="interleaved", mix=None, channel_map=None, device_out=False, return_clipped=False):
+                     layout="interleaved", mix=None, channel_map=None, device_out=False, return_clipped=False, sample_rate=None):
     """Crop and pad a list of Ogg Vorbis clips (bytes or paths; logical stream 0 of each) into N rows of exactly `length` samples:
     returns (rows, valid).  Row i holds samples [starts[i], starts[i] + length) of what VorbisReader(clips[i], <the same
     options>).read_all() returns, per channel, bit for bit, and zeros behind the clip's end; valid[i] (an int64 numpy array) says
@@ -376,6 +497,20 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
     ClipSamples clamped one of the samples the row holds (HasClipped of a reader that emitted exactly those samples in the same
     output form; the pad never counts).
 
+    sample_rate=R: every row at R Hz.  None, or a clip whose own rate is R: that clip's row is what it is without the keyword,
+    bit for bit, and if every clip is at R so are the launches.  A clip at another rate is resampled by the rule of
+    include/nvorbis_hip.h (nvh_resample_rows: a polyphase filter of 2 * half taps per output, reproducible bit for bit): `starts`,
+    `length` and `valid` then count samples at R -- valid = clamp(ceil(total * R / rate) - start, 0, length) -- and the row holds
+    outputs [start, start + length) of the clip resampled as a whole, zeros from `valid` on.  Such clips are classed by source
+    rate; per class the row path above decodes f32 SOURCE rows into a temporary device buffer in the requested mix, map and
+    layout -- the source window of a row is what its outputs read, which includes up to `half` samples of margin on each side:
+    [origin, origin + take) with origin = max(0, c_first - half + 1) rounded down and take rounded up to a multiple of 4 samples, so
+    that paired emission is kept, c_first = start * M div L -- and k_resample_rows writes the rows into the
+    returned buffer at their final indices, clipping again and converting to 16 bits there for sample_format="s16".  Host
+    results are that device buffer read back.  return_clipped: a resampled row's flag is the decode stage's flag for its source
+    window, margins included, ORed with the resampler's.  ValueError for a rate that is no int >= 1 and for a pair of rates
+    outside the resampler's limits (up factor above 4096, or more than 262144 taps), before any device is touched.
+
     Batches end on row boundaries once `batch_frames` frames are pending; only a row of more than 2 * batch_frames frames of
     its own is cut inside, every 2 * batch_frames frames.  LIMIT: such a cut falls on whatever sample the frames end on, and
     interleaved 16-bit PCM asks for a 16-byte aligned destination (nvh_stream_synth_pcm's rule), so sample_format="s16" with
@@ -388,6 +523,7 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
     planar = _layout(layout)
     _mix(mix, planar)
     return_clipped = _return_clipped(return_clipped)
+    sample_rate = _sample_rate(sample_rate)
     if channel_map is not None:
         _channel_map(channel_map, None, mix)
     if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0:
@@ -404,7 +540,8 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
     for v in starts:
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
             raise ValueError("starts must be ints >= 0, not %r" % (v,))
-    packets, plans, chans, groups = [], [], [], {}
+    starts = [int(v) for v in starts]
+    packets, plans, chans, index, rates = [], [], [], [], []
     for i, src in enumerate(clips):
         if isinstance(src, (bytes, bytearray, memoryview)):
             data = bytes(src)
@@ -419,13 +556,16 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
             try:
                 pos, em, state, total = probe.index_packets(pa, 3)
                 chans.append(_pcm_out(dtype, planar, mix, channel_map, probe.channels)[2])
+                rates.append(probe.sample_rate)
             finally:
                 probe.close()
         except native.NvhError as e:
             raise _clip_error(i, e, "headers", "decode_clip_rows")
         packets.append(pa)
-        plans.append(plan_clip_window(pos, em, state, total, int(starts[i]), length))
-        groups.setdefault((pa[0], pa[2]), []).append(i)
+        if sample_rate is not None and rates[i] != sample_rate:
+            resample_plan(rates[i], sample_rate)  # (ValueError for a pair outside the limits: before any device)
+        index.append((pos, em, state, total))
+        plans.append(plan_clip_window(pos, em, state, total, starts[i], length))
     if len(set(chans)) > 1:
         raise ValueError("decode_clip_rows: the clips' output channel counts differ (%s)" % sorted(set(chans)))
     n = len(clips)
@@ -434,6 +574,28 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
     mono = mix is not None
     clipped = np.zeros(n, dtype=bool)
     shape = (och, n, length) if planar else (n, length) if mono else (n, length, och)
+    resampling = sample_rate is not None and n and length and any(r != sample_rate for r in rates)
+    opts = {"batch_frames": int(batch_frames), "gpu_parse": bool(gpu_parse), "dtype": dtype, "planar": planar, "mix": mix,
+            "device_out": bool(device_out), "map": lambda ch: _channel_map(channel_map, ch, mix),
+            "och": lambda ch: _pcm_out(dtype, planar, mix, channel_map, ch)[2]}
+    if return_clipped:
+        opts["clipped"] = clipped
+    if resampling:
+        own_ctx = ctx is None
+        if own_ctx:
+            ctx = Context(device)
+        try:
+            opts["device_out"] = True
+            buf, valid = _resampled_rows(ctx, ctx.device, packets, index, rates, plans, starts, length, sample_rate, och, dtype, planar,
+                                         mono, opts, clipped if return_clipped else None)
+        finally:
+            if own_ctx:
+                ctx.close()
+        if not device_out:
+            buf = buf.cpu().numpy()
+        if planar:
+            buf = buf.permute(1, 0, 2) if device_out else buf.transpose(1, 0, 2)
+        return ((buf, valid), clipped) if return_clipped else (buf, valid)
     if device_out:
         import torch
         if ctx is not None:
@@ -443,33 +605,21 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
     else:
         buf = np.empty(shape, dtype=dtype)
         base = buf.ctypes.data
+    placed, groups = list(range(n)), 1
     if n and length:
         own_ctx = ctx is None
         if own_ctx:
             ctx = Context(device)
-        opts = {"batch_frames": int(batch_frames), "gpu_parse": bool(gpu_parse), "dtype": dtype, "planar": planar, "mix": mix,
-                "device_out": bool(device_out), "map": lambda ch: _channel_map(channel_map, ch, mix),
-                "och": lambda ch: _pcm_out(dtype, planar, mix, channel_map, ch)[2]}
-        if return_clipped:
-            opts["clipped"] = clipped
         try:
-            row0 = 0
-            for members in groups.values():
-                try:
-                    g = _RowGroup(ctx, members, packets, plans, opts, length)
-                except native.NvhError as e:
-                    raise _clip_error(members[0], e, "nvh_stream_open", "decode_clip_rows")
-                try:
-                    g.run(base, row0, n)
-                finally:
-                    g.stream.close()
-                row0 += len(members)
+            placed, groups = _run_row_groups(ctx, range(n), packets, plans, opts, length, base, n)
         finally:
             if own_ctx:
                 ctx.close()
-    if len(groups) > 1:  # rows lie group by group: one gather puts them into input order
+    elif n:
+        groups = len(set((pa[0], pa[2]) for pa in packets))
+    if groups > 1:  # rows lie group by group: one gather puts them into input order
         order = np.empty(n, dtype=np.int64)
-        order[np.concatenate([np.asarray(m, dtype=np.int64) for m in groups.values()])] = np.arange(n)
+        order[np.asarray(placed, dtype=np.int64)] = np.arange(n)
         if device_out:
             import torch
             buf = buf.index_select(1 if planar else 0, torch.as_tensor(order, device=buf.device))

@@ -114,6 +114,10 @@ extern "C" void nvh_ctx_destroy(nvh_ctx* c) {
       (void)hipFree(kv.second.br);
       (void)hipFree(kv.second.tw);
     }
+    for (auto& kv : c->resample_cache) (void)hipFree(kv.second.taps);
+    if (c->resample_copied) (void)hipEventDestroy(c->resample_copied);
+    c->resample_rows_host.release();  // (back into the pools that are cleared below)
+    c->resample_rows_dev.release();
     c->setup_cache.clear();  // streams must have been closed: they share these entries and return their buffers here
     c->pool.clear();
     c->hpool.clear();

@@ -26,6 +26,7 @@
 #include "host_slab.h"
 #include "kernels_common.h"
 #include "nvh_parse_format.h"
+#include "resample_dev.h"
 
 extern "C" {
 __global__ void k_mdct_reverse(float* buf, int n, long long stride, const float* A, const float* B, const float* C,
@@ -115,6 +116,12 @@ __global__ void k_ola_emit_seq(NvhDevSetup S, NvhDevBatch Bt, float* work, const
                                                               pcm_stride_t<LAYOUT>);
 NVH_FOR_PCM_TWINS(NVH_OLA_DECL)
 NVH_FOR_PCM_MAP_TWINS(NVH_OLA_DECL)
+
+// ... and the row resampler (kernels_resample.hip), once per sample type
+template <typename PCM>
+__global__ void k_resample_rows(NvhResampleArgs A);
+extern template __global__ void k_resample_rows<float>(NvhResampleArgs);
+extern template __global__ void k_resample_rows<int16_t>(NvhResampleArgs);
 
 extern thread_local int g_last_hip_error;
 
@@ -262,6 +269,11 @@ struct MdctDev {
   uint16_t* br = nullptr;
 };
 
+struct ResampleDev {  // the tap table of one ratio (nvh_resample.hip), [L][2 * half] floats in device memory
+  int L = 0, M = 0, half = 0;
+  float* taps = nullptr;
+};
+
 // Everything derived from a stream's headers: parsed tables on the host, their device image, kernel-selection
 // flags.  Immutable once built, so streams with byte-identical identification + setup packets (the normal case
 // inside one corpus: same encoder, same settings) share one entry per context.
@@ -299,6 +311,12 @@ struct nvh_ctx {
   bool synth_lds_attr_set = false;  // k_synth8's 160 KB dynamic-LDS opt-in was made on this context's device
   bool parse_lds_attr_set = false;  // k_parse's 80 KB dynamic-LDS opt-in was made on this context's device
   int parse_lanes = 0;              // nvh_ctx_set_parse_lanes: packets per wavefront of the GPU parser, 0 = automatic
+  // nvh_resample_rows: the tap tables by (L, M), like the per-n IMDCT tables; the per-row block's staging and device copy, and
+  // the event behind the last copy out of the staging
+  std::map<std::pair<int, int>, ResampleDev> resample_cache;
+  bool resample_lds_attr_set = false;  // k_resample_rows' 80 KB dynamic-LDS opt-in was made on this context's device
+  DevBuf resample_rows_host, resample_rows_dev;
+  hipEvent_t resample_copied = nullptr;
 };
 
 // Wait for the context's stream.  A context of a worker pool (nvh_ctx_set_parse_lanes > 0: one of many host threads, each waiting

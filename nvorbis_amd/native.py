@@ -39,6 +39,16 @@ class PcmOut(C.Structure):
                 ("map", C.POINTER(C.c_int32)), ("extent", C.c_int64)]
 
 
+class ResampleDesc(C.Structure):
+    """nvh_resample_desc: rates, shape, destination format and the element strides of source and destination."""
+    _fields_ = [("in_rate", C.c_int32), ("out_rate", C.c_int32), ("rows", C.c_int32), ("channels", C.c_int32),
+                ("format", C.c_int32), ("reserved", C.c_int32), ("length", C.c_int64), ("src_length", C.c_int64),
+                ("src_row_stride", C.c_int64), ("src_time_stride", C.c_int64), ("src_chan_stride", C.c_int64),
+                ("dst_row_stride", C.c_int64), ("dst_time_stride", C.c_int64), ("dst_chan_stride", C.c_int64)]
+
+
+RESAMPLE_TILE = 512  # NVH_RESAMPLE_TILE: consecutive outputs of one (row, channel) per workgroup step of k_resample_rows
+
 # symbol -> (restype, argtypes); also the list tests check against the header
 _u8p, _f32p, _i64p, _i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
 _vp, _vpp, _ip = C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)
@@ -144,6 +154,10 @@ SIGNATURES = {
     "nvh_ogg_seek": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _i64p, _i64p]),
     "nvh_ogg_demux_stream": (C.c_int, [_vp, C.c_size_t, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, C.c_int, _ip, _i64p, _ip]),
     "nvh_ogg_index_packets": (C.c_int, [_vp, C.c_size_t, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, C.c_int, _ip, _i64p, _i64p, _ip]),
+    # rows at one sample rate (nvh_resample.hip)
+    "nvh_resample_plan": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _ip, _i64p]),
+    "nvh_resample_taps": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int64, _i64p]),
+    "nvh_resample_rows": (C.c_int, [_vp, C.POINTER(ResampleDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # the corpus gather through RCCL's C API (nvh_comm.hip): what a host without torch.distributed binds to
     "nvh_comm_unique_id": (C.c_int, [_vp]),
     "nvh_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),

@@ -333,6 +333,18 @@ class Context:
         """One inverse square-polar coupling step over two device vectors, in place (Mapping.cs:150-178)."""
         check(lib().nvh_inverse_couple(self._h, C.c_void_p(d_magnitude), C.c_void_p(d_angle), int(count)), "nvh_inverse_couple")
 
+    def resample_rows(self, desc, d_src, d_dst, origin, start, valid, dst_row=None, d_clipped=None):
+        """nvh_resample_rows: `desc` a native.ResampleDesc, d_src / d_dst / d_clipped device addresses, the per-row arrays host
+        sequences of desc.rows ints.  Asynchronous on the context's stream (synchronize() waits for it)."""
+        n = int(desc.rows)
+        o, s, v = (np.ascontiguousarray(a, dtype=np.int64) for a in (origin, start, valid))
+        r = None if dst_row is None else np.ascontiguousarray(dst_row, dtype=np.int32)
+        if any(a.shape != (n,) for a in (o, s, v)) or (r is not None and r.shape != (n,)):
+            raise ValueError("resample_rows: the per-row arrays hold one entry per row (%d)" % n)
+        check(lib().nvh_resample_rows(self._h, C.byref(desc), C.c_void_p(d_src), C.c_void_p(d_dst), o.ctypes.data, s.ctypes.data,
+                                      v.ctypes.data, None if r is None else r.ctypes.data,
+                                      None if d_clipped is None else C.c_void_p(d_clipped)), "nvh_resample_rows")
+
     def close(self):
         if self._h:
             lib().nvh_ctx_destroy(self._h)

@@ -1,13 +1,14 @@
 #!/usr/bin/env python
 """The compiler's resource report of the PCM-emitting kernels (everything that calls report_clipped), as one table.
 
-    python tools/kernel_resources.py [--tree DIR] [--label TEXT] [--reports FILE ...]
+    python tools/kernel_resources.py [--tree DIR] [--label TEXT] [--reports FILE ...] [--files NAME ...] [--match REGEX]
 
 Compiles kernels_synth.hip and kernels.hip of DIR (default: this checkout) for gfx950 with the flags of nvorbis_amd/build.py plus
 -Rpass-analysis=kernel-resource-usage, and prints per kernel: VGPRs, AGPRs, SGPRs, scratch bytes per lane, the occupancy the
 compiler states (waves per SIMD), spilled SGPRs and VGPRs and static LDS bytes.  Needs hipcc, no GPU.  Two runs -- one on an export of the parent commit, one on
 the checkout -- put side by side are profiles/segment_clipped_resources.txt.  --reports: the compiler's saved remarks (its
-standard error) instead of compiling again.
+standard error) instead of compiling again.  --files / --match: other files of csrc/ and the kernels to list from them, e.g.
+--files kernels_resample.hip --match k_resample_rows (profiles/resample_rows_resources.txt).
 """
 import argparse
 import os
@@ -35,10 +36,10 @@ def short(name):
     return m.group(1) if m else name
 
 
-def report(tree, reports=None):
+def report(tree, reports=None, files=FILES, match=EMITTING):
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize"]
     rows = {}
-    for f in reports or FILES:
+    for f in reports or files:
         if reports:
             text = open(f).read()
         else:
@@ -58,7 +59,7 @@ def report(tree, reports=None):
                     cur[key] = int(m.group(1))
     names = list(rows)
     nice = [short(n) for n in demangle(names)]
-    return [(nn, rows[n]) for n, nn in zip(names, nice) if EMITTING.match(nn)]
+    return [(nn, rows[n]) for n, nn in zip(names, nice) if match.match(nn)]
 
 
 def main():
@@ -66,8 +67,10 @@ def main():
     ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--label", default="")
     ap.add_argument("--reports", nargs="*")
+    ap.add_argument("--files", nargs="*", default=list(FILES))
+    ap.add_argument("--match", default=None)
     a = ap.parse_args()
-    rows = report(os.path.abspath(a.tree), a.reports)
+    rows = report(os.path.abspath(a.tree), a.reports, a.files, re.compile(a.match) if a.match else EMITTING)
     print("# %s" % (a.label or a.tree))
     print("%-32s %5s %5s %5s %8s %4s %7s %7s %6s" % ("kernel", "VGPR", "AGPR", "SGPR", "scratch", "occ", "s-spill", "v-spill", "LDS"))
     for name, r in rows:

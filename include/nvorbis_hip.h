@@ -658,6 +658,83 @@ int nvh_resample_taps(int in_rate, int out_rate, float *taps, int64_t cap, int64
 int nvh_resample_rows(nvh_ctx *ctx, const nvh_resample_desc *desc, const float *d_src, void *d_dst, const int64_t *origin,
                       const int64_t *start, const int64_t *valid, const int32_t *dst_row, int32_t *d_clipped);
 
+/* ---- log-mel features of rows: a short-time transform, a mel filter bank and a logarithm over rows of f32 samples ----
+ * Rows in, features out: every value is a pure function of one frame of one (row, channel); nothing is carried from call to
+ * call, and no synthesis call, emitting kernel, parser or the resampler takes part.  Everything on the device is f32 with
+ * separately rounded operations (fl(.) below; no fused multiply-add, IEEE division); every table is computed in double on the
+ * host and rounded once to f32 (fl32(.)).  THE RULE (about 60 lines of numpy reproduce it bit for bit):
+ *   Parameters.  rate R >= 1; n_fft N a power of two in [64, 4096]; win_length W in [1, N]; hop H in [1, 65536]; n_mels B in
+ *     [1, 256]; doubles 0 <= f_min < f_max <= R / 2; mel_scale NVH_MEL_HTK or NVH_MEL_SLANEY; norm NVH_MEL_NORM_NONE or
+ *     NVH_MEL_NORM_SLANEY; scale NVH_MEL_POWER, NVH_MEL_LN or NVH_MEL_DB; floor an f32 >= 2^-126 (1e-10 is the usual one);
+ *     frames F >= 0; first an int64 that may be negative.  NVH_ERR_ARGUMENT for anything outside these (and, so that f * H +
+ *     first stays inside 64 bits, for F above 2^40 or |first| above 2^60); there is no NVH_ERR_UNSUPPORTED case.
+ *   Tables.  tw[k] = (cos(2 pi k / N), sin(2 pi k / N)) for k = 0 .. N/2.  win[n] = 0.5 - 0.5 cos(2 pi n / W) for n < W, the
+ *     periodic Hann window (W = 1: the one sample is 0, taken as it is).  fb[b][k], b < B, k = 0 .. N/2: B + 2 points
+ *     pt[i] = hz(m_lo + (m_hi - m_lo) * i / (B + 1)), equally spaced on the mel scale between m_lo = mel(f_min) and m_hi =
+ *     mel(f_max); with l = pt[b], c = pt[b+1], r = pt[b+2] and f = k * R / N: fb = max(0, min((f - l) / (c - l), (r - f) /
+ *     (r - c))), times 2 / (r - l) for NVH_MEL_NORM_SLANEY.  HTK: mel(f) = 2595 log10(1 + f / 700), hz(m) = 700 (10^(m / 2595)
+ *     - 1).  Slaney: mel(f) = 3 f / 200 below 1000 Hz, 15 + ln(f / 1000) / (ln(6.4) / 27) from there on, hz its inverse.  A
+ *     band that no bin falls into has an all-zero row: its value is 0, the floor in the log scales; that is not an error.
+ *   Frame f of a (row, channel).  u = N zeros, then u[(N - W) div 2 + n] = fl(x[f * H + first + n] * win[n]) for n < W, x the
+ *     row's f32 sample and 0 outside [0, valid) of the row.
+ *   Transform.  z[n] = u[2n] + i u[2n+1], n < N/2, through an N/2-point radix-2 decimation-in-time FFT: input in bit-reversed
+ *     order, then stages with half = 1, 2, .., N/4; in each the pair (a, b) at distance `half`, a at index j inside its group
+ *     of 2 * half, takes (c, s) = tw[j * N / (2 * half)]:  tr = fl(fl(br c) + fl(bi s)), ti = fl(fl(bi c) - fl(br s)),
+ *     a' = (fl(ar + tr), fl(ai + ti)), b' = (fl(ar - tr), fl(ai - ti)).
+ *   Split, k = 0 .. N/2.  a = Z[k mod N/2], b = conj(Z[(N/2 - k) mod N/2]); er = fl(ar + br), ei = fl(ai + bi), dr = fl(ar -
+ *     br), di = fl(ai - bi); with (c, s) = tw[k]: tr = fl(fl(c di) - fl(s dr)), ti = -fl(fl(c dr) + fl(s di)), xr = fl(er +
+ *     tr), xi = fl(ei + ti); P[k] = fl(0.25 fl(fl(xr xr) + fl(xi xi))) -- the power of bin k of the frame's N-point transform.
+ *   Mel.  m[b]: acc = +0; for k rising over the bins with fb[b][k] != 0: acc = fl(acc + fl(P[k] fb[b][k])).  One accumulator.
+ *     (The non-zero bins of a band are consecutive; the kernel reads them as first bin, count and weights.)
+ *   Scale.  NVH_MEL_POWER: m.  NVH_MEL_LN: ln_r(max(m, floor)).  NVH_MEL_DB: fl(ln_r(max(m, floor)) * fl32(10 / ln 10)).
+ *     ln_r(v), the rule's own logarithm (a device library's logf is not reproducible): v = g 2^e with g in [0.5, 1); if g <
+ *     fl32(0.70710678) then g = 2 g, e = e - 1; s = fl(fl(g - 1) / fl(g + 1)), z = fl(s s); p = fl32(1/11), then for c in
+ *     fl32(1/9), fl32(1/7), fl32(1/5), fl32(1/3), 1: p = fl(fl(p z) + c); ln_r = fl(fl(float(e) * fl32(0.6931471805599453)) +
+ *     fl(fl(s + s) * p)).  Within 4 ulp of the logarithm over [1e-10, 1e8] (tests/test_mel_plan.py).
+ *
+ * nvh_mel_plan: validates the parameters and returns the table sizes: *twiddle_count = 2 * (N/2 + 1), *window_count = W,
+ *   *bank_count = B * (N/2 + 1).  Host only; every pointer is required.
+ * nvh_mel_tables: the tables exactly as the kernel uses their values -- twiddles as (cos, sin) pairs, the window, the bank
+ *   dense, band after band.  Host only.  The three counts are set even when a cap is too small (NVH_ERR_ARGUMENT then); a
+ *   table whose pointer is NULL with cap 0 is left out.
+ * nvh_mel_rows: `rows` rows of `channels` channels, F frames each, asynchronous on the context's HIP stream.  Element (row i,
+ *   sample time e, channel c) of the source lies at d_src + i * src_row_stride + e * src_time_stride + c * src_chan_stride
+ *   (f32), for e in [0, src_length) -- interleaved, planar and mono are stride choices, as in nvh_resample_desc; value (row i,
+ *   channel c, frame f, band b) is written to d_dst + i * dst_row_stride + c * dst_chan_stride + f * dst_frame_stride + b *
+ *   dst_band_stride (f32), so that [N, C, F, B] and [N, C, B, F] are stride choices too.  valid: NULL (every row counts
+ *   src_length samples), or a host array of one int64 per row in [0, src_length], read during the call and uploaded in one
+ *   copy: reads at and behind valid[i] are 0.  The device tables are cached per context and parameter set.  Errors, before
+ *   any device is touched: NVH_ERR_ARGUMENT for no descriptor, a parameter outside the rule's, rows / src_length below 0,
+ *   channels outside [1, 65535], a missing buffer with rows and F above 0, a valid[i] outside [0, src_length]; then
+ *   NVH_ERR_NO_GPU for no context.  The kernel: one wavefront per frame, NVH_MEL_FRAMES consecutive frames of one (row,
+ *   channel) per workgroup. */
+#define NVH_MEL_HTK 0
+#define NVH_MEL_SLANEY 1
+#define NVH_MEL_NORM_NONE 0
+#define NVH_MEL_NORM_SLANEY 1
+#define NVH_MEL_POWER 0
+#define NVH_MEL_LN 1
+#define NVH_MEL_DB 2
+#define NVH_MEL_FRAMES 4
+typedef struct nvh_mel_desc {
+  int32_t rate, n_fft, win_length, hop, n_mels;
+  int32_t mel_scale, norm, scale; /* NVH_MEL_* */
+  float floor;
+  int32_t rows;     /* N */
+  int32_t channels; /* channels per row (1 for the mono mix) */
+  int32_t reserved; /* 0 */
+  double f_min, f_max;
+  int64_t frames; /* F: frames per row and channel */
+  int64_t first;  /* frame f begins at sample f * hop + first of its row */
+  int64_t src_length; /* source samples per row and channel */
+  int64_t src_row_stride, src_time_stride, src_chan_stride;                    /* in f32 elements */
+  int64_t dst_row_stride, dst_chan_stride, dst_frame_stride, dst_band_stride; /* in f32 elements */
+} nvh_mel_desc;
+int nvh_mel_plan(const nvh_mel_desc *desc, int64_t *twiddle_count, int64_t *window_count, int64_t *bank_count);
+int nvh_mel_tables(const nvh_mel_desc *desc, float *twiddle, float *window, float *bank, int64_t twiddle_cap, int64_t window_cap,
+                   int64_t bank_cap, int64_t *twiddle_count, int64_t *window_count, int64_t *bank_count);
+int nvh_mel_rows(nvh_ctx *ctx, const nvh_mel_desc *desc, const float *d_src, float *d_dst, const int64_t *valid);
+
 /* ---- multi-GPU: the gather of the file-parallel corpus transcode (SURVEY 8 e) ----
  * StreamDecoder holds per-stream state only (StreamDecoder.cs:35-39), so a corpus shards by file: every process decodes its
  * files on its own GPU (one nvh_ctx per process) and the PCM is gathered on one of them -- the path's one collective, through

@@ -628,3 +628,196 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
     if planar:
         buf = buf.permute(1, 0, 2) if device_out else buf.transpose(1, 0, 2)
     return ((buf, valid), clipped) if return_clipped else (buf, valid)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# features: log-mel spectrograms of the rows
+# ---------------------------------------------------------------------------------------------------------------------------
+
+_MEL_SCALES = {"htk": native.MEL_HTK, "slaney": native.MEL_SLANEY}
+_MEL_NORMS = {None: native.MEL_NORM_NONE, "slaney": native.MEL_NORM_SLANEY}
+_MEL_OUT = {"power": native.MEL_POWER, "ln": native.MEL_LN, "db": native.MEL_DB}
+
+
+def _int_in(name, value, lo, hi):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < lo or value > hi:
+        raise ValueError("%s must be an int in [%d, %d], not %r" % (name, lo, hi, value))
+    return int(value)
+
+
+def mel_desc(rate, n_fft=512, win_length=400, hop=160, n_mels=80, f_min=0.0, f_max=None, mel_scale="htk", norm=None, scale="ln",
+             floor=1e-10):
+    """A native.MelDesc with the rule's parameters filled in (include/nvorbis_hip.h: nvh_mel_rows), checked on the host: ValueError
+    for anything outside the rule's limits.  f_max=None: rate / 2.  Shape and strides are left 0 for the caller."""
+    rate = _int_in("the sample rate", rate, 1, 2 ** 31 - 1)
+    n_fft = _int_in("n_fft", n_fft, 64, 4096)
+    if n_fft & (n_fft - 1):
+        raise ValueError("n_fft must be a power of two in [64, 4096], not %r (other transforms are out of scope)" % (n_fft,))
+    win_length = _int_in("win_length", win_length, 1, n_fft)
+    hop = _int_in("hop", hop, 1, 65536)
+    n_mels = _int_in("n_mels", n_mels, 1, 256)
+    if not isinstance(mel_scale, str) or mel_scale not in _MEL_SCALES:
+        raise ValueError("mel_scale must be 'htk' or 'slaney', not %r" % (mel_scale,))
+    if norm is not None and (not isinstance(norm, str) or norm not in _MEL_NORMS):
+        raise ValueError("norm must be None or 'slaney', not %r" % (norm,))
+    if not isinstance(scale, str) or scale not in _MEL_OUT:
+        raise ValueError("scale must be 'power', 'ln' or 'db', not %r" % (scale,))
+    reals = []
+    for name, v in (("f_min", f_min), ("f_max", rate / 2.0 if f_max is None else f_max), ("floor", floor)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError("%s must be a finite number, not %r" % (name, v))
+        reals.append(float(v))
+    f_min, f_max, floor = reals
+    if not 0.0 <= f_min < f_max <= rate / 2.0:
+        raise ValueError("f_min and f_max must satisfy 0 <= f_min < f_max <= rate / 2 (%r, %r at %d Hz)" % (f_min, f_max, rate))
+    with np.errstate(over="ignore"):
+        floor32 = np.float32(floor)
+    if not np.isfinite(floor32) or floor32 < np.float32(2.0 ** -126):
+        raise ValueError("floor must be an f32 >= 2**-126, not %r" % (floor,))
+    d = native.MelDesc(rate=rate, n_fft=n_fft, win_length=win_length, hop=hop, n_mels=n_mels, mel_scale=_MEL_SCALES[mel_scale],
+                       norm=_MEL_NORMS[norm], scale=_MEL_OUT[scale], floor=float(floor32), f_min=f_min, f_max=f_max)
+    counts = [C.c_int64(0) for _ in range(3)]
+    rc = native.lib().nvh_mel_plan(C.byref(d), *[C.byref(c) for c in counts])
+    if rc == native.ERR_ARGUMENT:
+        raise ValueError("the mel parameters are outside the rule's limits (include/nvorbis_hip.h)")
+    native.check(rc, "nvh_mel_plan")
+    return d
+
+
+def mel_tables(rate, n_fft=512, win_length=400, n_mels=80, f_min=0.0, f_max=None, mel_scale="htk", norm=None):
+    """The tables of nvh_mel_tables as float32 arrays, exactly the values k_mel_rows uses: (twiddles (n_fft / 2 + 1, 2) as (cos,
+    sin), window (win_length,), bank (n_mels, n_fft / 2 + 1))."""
+    d = mel_desc(rate, n_fft, win_length, 1, n_mels, f_min, f_max, mel_scale, norm)
+    bins = n_fft // 2 + 1
+    tw, win, fb = np.zeros(2 * bins, np.float32), np.zeros(win_length, np.float32), np.zeros(n_mels * bins, np.float32)
+    counts = [C.c_int64(0) for _ in range(3)]
+    native.check(native.lib().nvh_mel_tables(C.byref(d), tw.ctypes.data, win.ctypes.data, fb.ctypes.data, tw.size, win.size, fb.size,
+                                             *[C.byref(c) for c in counts]), "nvh_mel_tables")
+    return tw.reshape(bins, 2), win, fb.reshape(n_mels, bins)
+
+
+def _clip_probe(clips, mix, channel_map, sample_rate):
+    """(sample rates, output channel counts) of the clips, from their headers (host only), with decode_clip_rows' ValueErrors for
+    a map that does not fit a clip and for a rate the resampler does not take to `sample_rate`."""
+    rates, chans = [], []
+    f32 = np.dtype(np.float32)
+    for i, src in enumerate(clips):
+        if isinstance(src, (bytes, bytearray, memoryview)):
+            data = bytes(src)
+        else:
+            with open(src, "rb") as fh:
+                data = fh.read()
+        try:
+            pa = demux_ogg_array(data, 0)
+            if len(pa) < 3:
+                raise native.NvhError(native.ERR_NOT_VORBIS, "decode_clip_features")
+            probe = Stream(None, pa[0], pa[1], pa[2])
+            try:
+                rates.append(probe.sample_rate)
+                chans.append(_pcm_out(f32, mix is None, mix, channel_map, probe.channels)[2])
+            finally:
+                probe.close()
+        except native.NvhError as e:
+            raise _clip_error(i, e, "headers", "decode_clip_features")
+        if sample_rate is not None and rates[i] != sample_rate:
+            resample_plan(rates[i], sample_rate)
+    return rates, chans
+
+
+def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=512, win_length=400, hop=160, n_mels=80, f_min=0.0,
+                         f_max=None, mel_scale="htk", norm=None, scale="ln", floor=1e-10, center=True, band_major=True, mix=None,
+                         channel_map=None, ctx=None, device=0, batch_frames=4096, gpu_parse=True, device_out=True,
+                         return_clipped=False):
+    """Log-mel features of fixed-length rows: decode_clip_rows(clips, length, starts, sample_format="f32", layout="planar",
+    device_out=True, sample_rate=sample_rate, ...) as it is, then nvh_mel_rows over the buffer the planar kernels wrote (the one
+    plane of mix="mono").  Returns (features, valid, valid_frames); with return_clipped=True ((features, valid, valid_frames),
+    clipped), `clipped` being decode_clip_rows' per-row flags.
+
+    features: float32, (N, C, n_mels, F), or (N, C, F, n_mels) with band_major=False; the C axis is absent with mix="mono".  A
+    torch tensor on the device, or a numpy array with device_out=False.  Every value follows the rule of include/nvorbis_hip.h
+    (nvh_mel_rows) bit for bit: a periodic Hann window of win_length samples centred in n_fft, the power spectrum, a triangular
+    mel bank (mel_scale "htk" or "slaney", norm None or "slaney", f_max=None: half the rate), then scale "power", "ln" or "db"
+    of max(value, floor).  Samples outside [0, valid[i]) of a row count as zeros.
+
+    center=True is torch.stft's center=True with pad_mode="constant": frame f is centred on sample f * hop, F = length // hop + 1.
+    center=False: frame f begins at sample f * hop, F = (length - n_fft) // hop + 1; ValueError for length < n_fft.  Reflect
+    padding is out of scope.  n_fft must be a power of two in [64, 4096]: other transform lengths are out of scope (Whisper's
+    own 400-point bins, for example, are not what n_fft=512, win_length=400 gives).
+
+    valid: decode_clip_rows' valid.  valid_frames[i] (int64): how many of the row's frames have one of their win_length samples
+    inside [0, valid[i]).  Without sample_rate all clips must share one rate (ValueError otherwise); with it, clips at other
+    rates are resampled as decode_clip_rows does.  Every keyword is checked, with ValueError, before any device is touched."""
+    for name, v in (("center", center), ("band_major", band_major), ("device_out", device_out)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("%s must be True or False, not %r" % (name, v))
+    return_clipped = _return_clipped(return_clipped)
+    sample_rate = _sample_rate(sample_rate)
+    _mix(mix, False)
+    if channel_map is not None:
+        _channel_map(channel_map, None, mix)
+    if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0:
+        raise ValueError("length must be an int >= 0, not %r" % (length,))
+    length = int(length)
+    if int(batch_frames) < 1:
+        raise ValueError("batch_frames must be at least 1")
+    clips = list(clips)
+    if starts is not None:
+        starts = list(starts)
+        if len(starts) != len(clips):
+            raise ValueError("starts must name one start per clip (%d for %d clips)" % (len(starts), len(clips)))
+        for v in starts:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError("starts must be ints >= 0, not %r" % (v,))
+    rates, chans = _clip_probe(clips, mix, channel_map, sample_rate)
+    if len(set(chans)) > 1:
+        raise ValueError("decode_clip_features: the clips' output channel counts differ (%s)" % sorted(set(chans)))
+    rate = sample_rate
+    if rate is None:
+        if len(set(rates)) != 1:
+            raise ValueError("decode_clip_features: without sample_rate all clips must share one rate (found %s)" % sorted(set(rates)))
+        rate = rates[0]
+    desc = mel_desc(rate, n_fft, win_length, hop, n_mels, f_min, f_max, mel_scale, norm, scale, floor)
+    N_, W, H, B = desc.n_fft, desc.win_length, desc.hop, desc.n_mels
+    if center:
+        first, F = (N_ - W) // 2 - N_ // 2, length // H + 1
+    else:
+        if length < N_:
+            raise ValueError("center=False needs length >= n_fft (%d < %d)" % (length, N_))
+        first, F = (N_ - W) // 2, (length - N_) // H + 1
+    import torch
+    own_ctx = ctx is None
+    if own_ctx:
+        ctx = Context(device)
+    try:
+        out = decode_clip_rows(clips, length, starts, ctx=ctx, batch_frames=batch_frames, gpu_parse=gpu_parse, sample_format="f32",
+                               layout="interleaved" if mix is not None else "planar", mix=mix, channel_map=channel_map,
+                               device_out=True, return_clipped=return_clipped, sample_rate=sample_rate)
+        (rows, valid), clipped = out if return_clipped else (out, None)
+        mono = mix is not None
+        n = rows.shape[0]
+        och = 1 if mono else rows.shape[1]
+        shape = (n, och, B, F) if band_major else (n, och, F, B)
+        feats = torch.empty(shape, dtype=torch.float32, device=rows.device)
+        if n and och:
+            desc.rows, desc.channels, desc.frames, desc.first, desc.src_length = n, och, F, first, length
+            if length:
+                desc.src_row_stride, desc.src_time_stride = rows.stride(0), rows.stride(-1)
+                desc.src_chan_stride = 0 if mono else rows.stride(1)
+            else:  # no samples at all: every frame is the transform of zeros (the source is never read)
+                rows = torch.zeros(1, dtype=torch.float32, device=rows.device)
+            desc.dst_row_stride, desc.dst_chan_stride = feats.stride(0), feats.stride(1)
+            desc.dst_band_stride, desc.dst_frame_stride = (feats.stride(2), feats.stride(3)) if band_major else (feats.stride(3), feats.stride(2))
+            torch.cuda.current_stream(rows.device).synchronize()  # (a gather of several setups' rows runs on torch's stream)
+            ctx.mel_rows(desc, rows.data_ptr(), feats.data_ptr(), valid)
+            ctx.synchronize()
+    finally:
+        if own_ctx:
+            ctx.close()
+    begins = np.arange(F, dtype=np.int64) * H + first
+    valid_frames = (np.maximum(begins, 0)[None, :] < np.minimum(begins[None, :] + W, valid[:, None])).sum(axis=1).astype(np.int64)
+    if mono:
+        feats = feats[:, 0]
+    if not device_out:
+        feats = feats.cpu().numpy()
+    res = (feats, valid, valid_frames)
+    return (res, clipped) if return_clipped else res

@@ -1,0 +1,43 @@
+// mel_dev.h -- what k_mel_rows (kernels_mel.hip) and its launcher (nvh_mel.hip) share: the kernel's argument block and its LDS
+// geometry.  include/nvorbis_hip.h states the rule (nvh_mel_rows).
+#pragma once
+#include <stdint.h>
+
+#define NVH_MEL_WAVES 4        // wavefronts per workgroup, one frame each: NVH_MEL_FRAMES of the ABI
+#define NVH_MEL_THREADS (64 * NVH_MEL_WAVES)
+#define NVH_MEL_MAX_BANDS 256
+#define NVH_MEL_OUT_STRIDE (NVH_MEL_MAX_BANDS + 1)  // floats per frame of the workgroup's output tile (odd: band-major reads spread over the banks)
+#define NVH_MEL_LDS_BYTES 81920  // a workgroup's LDS budget: two workgroups per CU (160 KB)
+
+// Floats of one wavefront's transform slice: N/2 complex points at float2 slot c + 8 * (c >> 6), the padded layout of imdct_wave.h.
+static inline constexpr int nvh_mel_slice_floats(int n_fft) { return 2 * ((n_fft >> 1) + (((n_fft >> 1) >> 6) << 3)); }
+// float2 slots of the staged twiddles: pair k at slot k + (k >> 4), so that a pass's lanes, which read pairs a power of two
+// apart, spread over the banks.
+static inline constexpr int nvh_mel_tw_pad(int k) { return k + (k >> 4); }
+static inline constexpr int nvh_mel_tw_slots(int n_fft) { return nvh_mel_tw_pad(n_fft >> 1) + 1; }
+// The workgroup's LDS in floats: the four slices, the output tile, then (staged tables) the twiddles, the band records, the
+// sparse weights, the window and the source span of the four frames.
+static inline constexpr int nvh_mel_fixed_floats(int n_fft) { return NVH_MEL_WAVES * nvh_mel_slice_floats(n_fft) + NVH_MEL_WAVES * NVH_MEL_OUT_STRIDE; }
+
+struct NvhMelArgs {
+  const float* tw;    // [N/2 + 1] (cos, sin) pairs
+  const float* win;   // [W]
+  const float* fbw;   // the sparse bank's weights, band after band
+  const int* band;    // [B][3]: first bin, bin count, offset of the band's weights in fbw
+  const float* src;
+  float* dst;
+  const long long* valid;  // one per row (the per-row block, one upload), or null: src_length
+  long long src_length, first, frames;
+  long long src_row_stride, src_time_stride, src_chan_stride;
+  long long dst_row_stride, dst_chan_stride, dst_frame_stride, dst_band_stride;
+  long long groups;  // ceil(frames / NVH_MEL_WAVES)
+  long long total;   // rows * channels * groups: the workgroups' work items
+  int channels;
+  int n_fft, ld;     // N = 1 << ld
+  int win_length, hop, n_mels;
+  int scale;
+  float floor;
+  int weights;       // floats of fbw
+  int span;          // floats of the four frames' source span in LDS (3 * hop + W), 0: every frame reads the row through L2
+  int band_fast;     // the band stride is the smaller one: a frame's bands are stored side by side, else a band's four frames
+};

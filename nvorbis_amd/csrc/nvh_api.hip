@@ -118,6 +118,15 @@ extern "C" void nvh_ctx_destroy(nvh_ctx* c) {
     if (c->resample_copied) (void)hipEventDestroy(c->resample_copied);
     c->resample_rows_host.release();  // (back into the pools that are cleared below)
     c->resample_rows_dev.release();
+    for (auto& kv : c->mel_cache) {
+      (void)hipFree(kv.second.tw);
+      (void)hipFree(kv.second.win);
+      (void)hipFree(kv.second.fbw);
+      (void)hipFree(kv.second.band);
+    }
+    if (c->mel_copied) (void)hipEventDestroy(c->mel_copied);
+    c->mel_rows_host.release();
+    c->mel_rows_dev.release();
     c->setup_cache.clear();  // streams must have been closed: they share these entries and return their buffers here
     c->pool.clear();
     c->hpool.clear();

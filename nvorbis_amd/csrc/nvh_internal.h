@@ -17,6 +17,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/nvorbis_hip.h"
@@ -26,6 +27,7 @@
 #include "host_slab.h"
 #include "kernels_common.h"
 #include "nvh_parse_format.h"
+#include "mel_dev.h"
 #include "resample_dev.h"
 
 extern "C" {
@@ -122,6 +124,12 @@ template <typename PCM>
 __global__ void k_resample_rows(NvhResampleArgs A);
 extern template __global__ void k_resample_rows<float>(NvhResampleArgs);
 extern template __global__ void k_resample_rows<int16_t>(NvhResampleArgs);
+
+// ... and the log-mel features of rows (kernels_mel.hip), with the tables staged in LDS or read through L2
+template <bool STAGED>
+__global__ void k_mel_rows(NvhMelArgs A);
+extern template __global__ void k_mel_rows<true>(NvhMelArgs);
+extern template __global__ void k_mel_rows<false>(NvhMelArgs);
 
 extern thread_local int g_last_hip_error;
 
@@ -274,6 +282,14 @@ struct ResampleDev {  // the tap table of one ratio (nvh_resample.hip), [L][2 * 
   float* taps = nullptr;
 };
 
+struct MelDev {  // the device tables of one parameter set (nvh_mel.hip): twiddles, window, the sparse bank
+  float *tw = nullptr, *win = nullptr, *fbw = nullptr;
+  int* band = nullptr;
+  int weights = 0;
+};
+// (rate, n_fft, win_length, n_mels, mel_scale, norm, f_min, f_max): what the tables depend on
+typedef std::tuple<int, int, int, int, int, int, double, double> MelKey;
+
 // Everything derived from a stream's headers: parsed tables on the host, their device image, kernel-selection
 // flags.  Immutable once built, so streams with byte-identical identification + setup packets (the normal case
 // inside one corpus: same encoder, same settings) share one entry per context.
@@ -317,6 +333,11 @@ struct nvh_ctx {
   bool resample_lds_attr_set = false;  // k_resample_rows' 80 KB dynamic-LDS opt-in was made on this context's device
   DevBuf resample_rows_host, resample_rows_dev;
   hipEvent_t resample_copied = nullptr;
+  // nvh_mel_rows: the tables by parameter set, and the per-row block's staging, device copy and event as above
+  std::map<MelKey, MelDev> mel_cache;
+  bool mel_lds_attr_set = false;  // k_mel_rows' 80 KB dynamic-LDS opt-in was made on this context's device
+  DevBuf mel_rows_host, mel_rows_dev;
+  hipEvent_t mel_copied = nullptr;
 };
 
 // Wait for the context's stream.  A context of a worker pool (nvh_ctx_set_parse_lanes > 0: one of many host threads, each waiting

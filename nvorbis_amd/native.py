@@ -49,6 +49,24 @@ class ResampleDesc(C.Structure):
 
 RESAMPLE_TILE = 512  # NVH_RESAMPLE_TILE: consecutive outputs of one (row, channel) per workgroup step of k_resample_rows
 
+
+class MelDesc(C.Structure):
+    """nvh_mel_desc: the rule's parameters, the shape, and the element strides of source (row, time, channel) and destination
+    (row, channel, frame, band)."""
+    _fields_ = [("rate", C.c_int32), ("n_fft", C.c_int32), ("win_length", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32),
+                ("mel_scale", C.c_int32), ("norm", C.c_int32), ("scale", C.c_int32), ("floor", C.c_float), ("rows", C.c_int32),
+                ("channels", C.c_int32), ("reserved", C.c_int32), ("f_min", C.c_double), ("f_max", C.c_double),
+                ("frames", C.c_int64), ("first", C.c_int64), ("src_length", C.c_int64),
+                ("src_row_stride", C.c_int64), ("src_time_stride", C.c_int64), ("src_chan_stride", C.c_int64),
+                ("dst_row_stride", C.c_int64), ("dst_chan_stride", C.c_int64), ("dst_frame_stride", C.c_int64),
+                ("dst_band_stride", C.c_int64)]
+
+
+MEL_HTK, MEL_SLANEY = 0, 1              # NVH_MEL_HTK / _SLANEY
+MEL_NORM_NONE, MEL_NORM_SLANEY = 0, 1   # NVH_MEL_NORM_*
+MEL_POWER, MEL_LN, MEL_DB = 0, 1, 2     # NVH_MEL_POWER / _LN / _DB
+MEL_FRAMES = 4  # NVH_MEL_FRAMES: consecutive frames of one (row, channel) per workgroup of k_mel_rows
+
 # symbol -> (restype, argtypes); also the list tests check against the header
 _u8p, _f32p, _i64p, _i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
 _vp, _vpp, _ip = C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)
@@ -158,6 +176,10 @@ SIGNATURES = {
     "nvh_resample_plan": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _ip, _i64p]),
     "nvh_resample_taps": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int64, _i64p]),
     "nvh_resample_rows": (C.c_int, [_vp, C.POINTER(ResampleDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # log-mel features of rows (nvh_mel.hip)
+    "nvh_mel_plan": (C.c_int, [C.POINTER(MelDesc), _i64p, _i64p, _i64p]),
+    "nvh_mel_tables": (C.c_int, [C.POINTER(MelDesc), _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p, _i64p]),
+    "nvh_mel_rows": (C.c_int, [_vp, C.POINTER(MelDesc), _vp, _vp, _vp]),
     # the corpus gather through RCCL's C API (nvh_comm.hip): what a host without torch.distributed binds to
     "nvh_comm_unique_id": (C.c_int, [_vp]),
     "nvh_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),

@@ -345,6 +345,17 @@ class Context:
                                       v.ctypes.data, None if r is None else r.ctypes.data,
                                       None if d_clipped is None else C.c_void_p(d_clipped)), "nvh_resample_rows")
 
+    def mel_rows(self, desc, d_src, d_dst, valid=None):
+        """nvh_mel_rows: `desc` a native.MelDesc, d_src / d_dst device addresses, `valid` None or a host sequence of desc.rows
+        ints.  Asynchronous on the context's stream (synchronize() waits for it)."""
+        v = None
+        if valid is not None:
+            v = np.ascontiguousarray(valid, dtype=np.int64)
+            if v.shape != (int(desc.rows),):
+                raise ValueError("mel_rows: valid holds one entry per row (%d)" % int(desc.rows))
+        check(lib().nvh_mel_rows(self._h, C.byref(desc), C.c_void_p(d_src), C.c_void_p(d_dst), None if v is None else v.ctypes.data),
+              "nvh_mel_rows")
+
     def close(self):
         if self._h:
             lib().nvh_ctx_destroy(self._h)

@@ -735,6 +735,69 @@ int nvh_mel_tables(const nvh_mel_desc *desc, float *twiddle, float *window, floa
                    int64_t bank_cap, int64_t *twiddle_count, int64_t *window_count, int64_t *bank_count);
 int nvh_mel_rows(nvh_ctx *ctx, const nvh_mel_desc *desc, const float *d_src, float *d_dst, const int64_t *valid);
 
+/* ---- per-row normalisation of features: mean, variance or peak of each (row, channel), and the fill of its padded frames ----
+ * Features in, features out: every value is a pure function of one (row, channel) of the input and of that row's frame count;
+ * nothing is carried from call to call, and nvh_mel_rows takes no part.  (fnorm: NVH_MEL_NORM_* is the bank's normalisation.)
+ * Everything on the device is f32 with separately rounded operations (fl(.) below; no fused multiply-add); division and square
+ * root are the correctly rounded ones.  THE RULE (about 40 lines of numpy reproduce it bit for bit):
+ *   Input.  x[i, c, f, b] for row i < rows, channel c < channels, frame f < F, band b < B, and vf[i] in [0, F], the number of
+ *     counted frames of row i: valid_frames[i], or F for every row when valid_frames is NULL.  B in [1, 256], F in [0, 2^24],
+ *     channels in [1, 65535], rows >= 0.  Inputs are finite or +-inf; a NaN makes the values of its group unspecified (it is
+ *     not an error, and nothing faults).
+ *   sum64(v[0 .. n)), the one summation.  64 partials p[l] = +0; for e = l, l + 64, l + 128, .. < n, rising: p[l] = fl(p[l] +
+ *     v[e]); then for d = 32, 16, 8, 4, 2, 1: p[l] = fl(p[l] + p[l + d]) for every l < d; the result is p[0].  (numpy: pad to a
+ *     multiple of 64 with zeros, reshape to (-1, 64), add the rows in order, then six halvings.)  Within (ceil(n / 64) + 6) *
+ *     2^-24 * sum |v| of the exact sum (tests/test_fnorm_plan.py).
+ *   Groups, by axis.  NVH_FNORM_PER_BAND: one group per (i, c, b); S1 = sum64 over f < vf[i] of x[i, c, f, b], n = vf[i].
+ *     NVH_FNORM_ALL: one group per (i, c); the per-band sum64 results S_b are added in rising b into one accumulator, acc = +0,
+ *     acc = fl(acc + S_b); S1 = acc, n = vf[i] * B.  (The order does not depend on the memory layout.)
+ *   Modes.  mean = fl(S1 / fl32(n)), fl32(n) the integer rounded to nearest.
+ *     NVH_FNORM_NONE: y = x.  NVH_FNORM_MEAN: y = fl(x - mean).
+ *     NVH_FNORM_MEAN_VAR: d = fl(x - mean), q = fl(d d); S2 the same sums over q (per band, and for NVH_FNORM_ALL the bands'
+ *       results added in rising b); var = fl(S2 / fl32(n)), the population variance; sd = sqrt(fl(var + eps)); y = fl(d / sd).
+ *       eps is an f32 >= 2^-126.
+ *     NVH_FNORM_PEAK: the group is (i, c) whatever the axis.  mx = the maximum of x over the counted frames and all bands
+ *       (exact: its order is free); t = fl(mx - range); y = fl(fl(max(x, t) + offset) * gain).  range an f32 >= 0 or +inf,
+ *       offset and gain finite.  On dB features range = 80, offset = 40, gain = fl32(1 / 40) is Whisper's normalisation.
+ *   Pad.  Every (i, c, f >= vf[i], b) gets pad_value, a finite f32; a row with vf = 0 is all pad_value.
+ *
+ * nvh_fnorm_check: NVH_OK or NVH_ERR_ARGUMENT for the descriptor's numbers (below).  Host only.
+ * nvh_fnorm_rows: asynchronous on the context's HIP stream.  x[i, c, f, b] lies at d_src + i * src_row_stride + c *
+ *   src_chan_stride + f * src_frame_stride + b * src_band_stride, y at d_dst with the dst strides (f32 elements): [N, C, B, F]
+ *   and [N, C, F, B] are stride choices, on each side independently.  d_dst == d_src with identical strides is the in-place
+ *   form (only the last pass writes); any other overlap of the two is the caller's error and gives unspecified values.
+ *   valid_frames: NULL, or a host array of one int64 per row, read during the call and uploaded in one copy.  Errors, before any
+ *   device is touched: NVH_ERR_ARGUMENT for no descriptor; a mode or axis that is none of the constants (the axis is checked in
+ *   every mode); rows, channels, F or B outside the limits above; a pad_value that is not finite (in every mode, with or without
+ *   valid_frames); in NVH_FNORM_MEAN_VAR an eps that is not a finite f32 >= 2^-126; in NVH_FNORM_PEAK a range that is negative or
+ *   NaN, an offset or gain that is not finite (a field its mode does not use is not looked at); a missing buffer with rows and F
+ *   above 0; a valid_frames[i] outside [0, F].  Then NVH_ERR_NO_GPU for no context.  There is no NVH_ERR_UNSUPPORTED case.
+ *   The kernel: a workgroup per (row, channel), a wavefront per band, partial p[l] in lane l.  A (row, channel) of at most
+ *   NVH_FNORM_RESIDENT_FLOATS floats, counted as (F | 1) * B, is read once and normalised out of LDS; a larger one re-reads its
+ *   source for the second sum and for the last pass. */
+#define NVH_FNORM_NONE 0
+#define NVH_FNORM_MEAN 1
+#define NVH_FNORM_MEAN_VAR 2
+#define NVH_FNORM_PEAK 3
+#define NVH_FNORM_PER_BAND 0
+#define NVH_FNORM_ALL 1
+#define NVH_FNORM_RESIDENT_FLOATS 19952
+typedef struct nvh_fnorm_desc {
+  int32_t mode, axis; /* NVH_FNORM_* */
+  int32_t rows;       /* N */
+  int32_t channels;   /* channels per row */
+  int32_t frames;     /* F: frames per row and channel */
+  int32_t bands;      /* B */
+  float eps;          /* NVH_FNORM_MEAN_VAR */
+  float pad_value;
+  float range, offset, gain; /* NVH_FNORM_PEAK */
+  int32_t reserved;          /* 0 */
+  int64_t src_row_stride, src_chan_stride, src_frame_stride, src_band_stride; /* in f32 elements */
+  int64_t dst_row_stride, dst_chan_stride, dst_frame_stride, dst_band_stride; /* in f32 elements */
+} nvh_fnorm_desc;
+int nvh_fnorm_check(const nvh_fnorm_desc *desc);
+int nvh_fnorm_rows(nvh_ctx *ctx, const nvh_fnorm_desc *desc, const float *d_src, float *d_dst, const int64_t *valid_frames);
+
 /* ---- multi-GPU: the gather of the file-parallel corpus transcode (SURVEY 8 e) ----
  * StreamDecoder holds per-stream state only (StreamDecoder.cs:35-39), so a corpus shards by file: every process decodes its
  * files on its own GPU (one nvh_ctx per process) and the PCM is gathered on one of them -- the path's one collective, through

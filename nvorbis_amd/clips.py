@@ -696,6 +696,57 @@ def mel_tables(rate, n_fft=512, win_length=400, n_mels=80, f_min=0.0, f_max=None
     return tw.reshape(bins, 2), win, fb.reshape(n_mels, bins)
 
 
+_FNORM_MODES = {None: native.FNORM_NONE, "mean": native.FNORM_MEAN, "mean_var": native.FNORM_MEAN_VAR, "peak": native.FNORM_PEAK}
+_FNORM_AXES = {"band": native.FNORM_PER_BAND, "all": native.FNORM_ALL}
+
+
+class _DefaultPad(float):
+    """decode_clip_features' pad_value default: 0.0, and an object of its own, so that `pad_value=0.0` given by the caller is not it."""
+    __slots__ = ()
+
+    def __repr__(self):
+        return "0.0"
+
+
+_PAD_DEFAULT = _DefaultPad(0.0)
+
+
+def fnorm_desc(normalize=None, normalize_axis="band", norm_eps=1e-5, pad_value=0.0, peak_range=80.0, peak_offset=40.0, peak_gain=1 / 40,
+               frames=0, bands=1):
+    """A native.FnormDesc with the rule's numbers filled in (include/nvorbis_hip.h: nvh_fnorm_rows), checked on the host: ValueError
+    for anything outside the rule's limits.  Every number is checked whatever the mode (the C call looks only at those its mode
+    uses).  rows, channels and the strides are left 0 for the caller."""
+    if normalize is not None and (not isinstance(normalize, str) or normalize not in _FNORM_MODES):
+        raise ValueError("normalize must be None, 'mean', 'mean_var' or 'peak', not %r" % (normalize,))
+    if not isinstance(normalize_axis, str) or normalize_axis not in _FNORM_AXES:
+        raise ValueError("normalize_axis must be 'band' or 'all', not %r" % (normalize_axis,))
+    frames = _int_in("frames", frames, 0, 2 ** 24)
+    bands = _int_in("bands", bands, 1, 256)
+    vals = {}
+    for name, v in (("norm_eps", norm_eps), ("pad_value", pad_value), ("peak_range", peak_range), ("peak_offset", peak_offset),
+                    ("peak_gain", peak_gain)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or np.isnan(v):
+            raise ValueError("%s must be a number, not %r" % (name, v))
+        with np.errstate(over="ignore"):
+            vals[name] = np.float32(v)
+    if not np.isfinite(vals["norm_eps"]) or vals["norm_eps"] < np.float32(2.0 ** -126):
+        raise ValueError("norm_eps must be an f32 >= 2**-126, not %r" % (norm_eps,))
+    if not vals["peak_range"] >= 0:
+        raise ValueError("peak_range must be >= 0 (inf: no clamp), not %r" % (peak_range,))
+    for name in ("pad_value", "peak_offset", "peak_gain"):
+        if not np.isfinite(vals[name]):
+            raise ValueError("%s must be a finite f32, not %r" % (name, {"pad_value": pad_value, "peak_offset": peak_offset, "peak_gain": peak_gain}[name]))
+    d = native.FnormDesc(mode=_FNORM_MODES[normalize], axis=_FNORM_AXES[normalize_axis], frames=frames, bands=bands, channels=1,
+                         eps=float(vals["norm_eps"]), pad_value=float(vals["pad_value"]), range=float(vals["peak_range"]),
+                         offset=float(vals["peak_offset"]), gain=float(vals["peak_gain"]))
+    rc = native.lib().nvh_fnorm_check(C.byref(d))
+    if rc == native.ERR_ARGUMENT:
+        raise ValueError("the normalisation parameters are outside the rule's limits (include/nvorbis_hip.h)")
+    native.check(rc, "nvh_fnorm_check")
+    d.channels = 0
+    return d
+
+
 def _clip_probe(clips, mix, channel_map, sample_rate):
     """(sample rates, output channel counts) of the clips, from their headers (host only), with decode_clip_rows' ValueErrors for
     a map that does not fit a clip and for a rate the resampler does not take to `sample_rate`."""
@@ -727,7 +778,8 @@ def _clip_probe(clips, mix, channel_map, sample_rate):
 def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=512, win_length=400, hop=160, n_mels=80, f_min=0.0,
                          f_max=None, mel_scale="htk", norm=None, scale="ln", floor=1e-10, center=True, band_major=True, mix=None,
                          channel_map=None, ctx=None, device=0, batch_frames=4096, gpu_parse=True, device_out=True,
-                         return_clipped=False):
+                         return_clipped=False, normalize=None, normalize_axis="band", norm_eps=1e-5, pad_value=_PAD_DEFAULT,
+                         peak_range=80.0, peak_offset=40.0, peak_gain=1 / 40, mask_padding=True):
     """Log-mel features of fixed-length rows: decode_clip_rows(clips, length, starts, sample_format="f32", layout="planar",
     device_out=True, sample_rate=sample_rate, ...) as it is, then nvh_mel_rows over the buffer the planar kernels wrote (the one
     plane of mix="mono").  Returns (features, valid, valid_frames); with return_clipped=True ((features, valid, valid_frames),
@@ -746,7 +798,19 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
 
     valid: decode_clip_rows' valid.  valid_frames[i] (int64): how many of the row's frames have one of their win_length samples
     inside [0, valid[i]).  Without sample_rate all clips must share one rate (ValueError otherwise); with it, clips at other
-    rates are resampled as decode_clip_rows does.  Every keyword is checked, with ValueError, before any device is touched."""
+    rates are resampled as decode_clip_rows does.  Every keyword is checked, with ValueError, before any device is touched.
+
+    normalize: the last stage, nvh_fnorm_rows in place on the features (include/nvorbis_hip.h states its rule).  "mean": the mean
+    over the row's counted frames is subtracted, per band with normalize_axis="band" (utterance CMVN, NeMo's per_feature) or one
+    mean of all bands with "all" (all_features).  "mean_var": then divided by sqrt(population variance + norm_eps).  "peak":
+    (max(x, peak - peak_range) + peak_offset) * peak_gain, `peak` the maximum over the row's counted frames and all bands
+    (normalize_axis is not used); with scale="db" the defaults 80, 40, 1/40 are Whisper's.  mask_padding=True: the counted frames
+    of row i are its first valid_frames[i] ones, and every frame behind them is set to pad_value.  mask_padding=False: every frame
+    counts and none is filled (the exact Whisper form).
+    With normalize=None the stage runs only as the fill-only form, which needs mask_padding=True and a pad_value GIVEN BY THE
+    CALLER: the default of pad_value is a marker object equal to 0.0, and the stage is told to run by `pad_value is not that
+    object`, so that pad_value=0.0 written out fills with zeros while leaving the keyword away keeps today's frames (ln(floor) and
+    the like) and launches nothing new.  normalize=None with mask_padding=False has nothing to do and launches nothing either."""
     for name, v in (("center", center), ("band_major", band_major), ("device_out", device_out)):
         if not isinstance(v, (bool, np.bool_)):
             raise ValueError("%s must be True or False, not %r" % (name, v))
@@ -778,12 +842,20 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
         rate = rates[0]
     desc = mel_desc(rate, n_fft, win_length, hop, n_mels, f_min, f_max, mel_scale, norm, scale, floor)
     N_, W, H, B = desc.n_fft, desc.win_length, desc.hop, desc.n_mels
+    if not isinstance(mask_padding, (bool, np.bool_)):
+        raise ValueError("mask_padding must be True or False, not %r" % (mask_padding,))
+    pad_given = pad_value is not _PAD_DEFAULT
+    ndesc = fnorm_desc(normalize, normalize_axis, norm_eps, pad_value, peak_range, peak_offset, peak_gain, 0, B)
+    run_fnorm = normalize is not None or (bool(mask_padding) and pad_given)
     if center:
         first, F = (N_ - W) // 2 - N_ // 2, length // H + 1
     else:
         if length < N_:
             raise ValueError("center=False needs length >= n_fft (%d < %d)" % (length, N_))
         first, F = (N_ - W) // 2, (length - N_) // H + 1
+    if run_fnorm and F > 2 ** 24:
+        raise ValueError("normalize takes at most 2**24 frames per row (%d)" % F)
+    begins = np.arange(F, dtype=np.int64) * H + first
     import torch
     own_ctx = ctx is None
     if own_ctx:
@@ -809,12 +881,19 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
             desc.dst_band_stride, desc.dst_frame_stride = (feats.stride(2), feats.stride(3)) if band_major else (feats.stride(3), feats.stride(2))
             torch.cuda.current_stream(rows.device).synchronize()  # (a gather of several setups' rows runs on torch's stream)
             ctx.mel_rows(desc, rows.data_ptr(), feats.data_ptr(), valid)
+        valid_frames = (np.maximum(begins, 0)[None, :] < np.minimum(begins[None, :] + W, valid[:, None])).sum(axis=1).astype(np.int64)
+        if n and och:
+            if run_fnorm:  # behind k_mel_rows on the context's stream, in place
+                ndesc.rows, ndesc.channels, ndesc.frames = n, och, F
+                ndesc.src_row_stride = ndesc.dst_row_stride = desc.dst_row_stride
+                ndesc.src_chan_stride = ndesc.dst_chan_stride = desc.dst_chan_stride
+                ndesc.src_frame_stride = ndesc.dst_frame_stride = desc.dst_frame_stride
+                ndesc.src_band_stride = ndesc.dst_band_stride = desc.dst_band_stride
+                ctx.fnorm_rows(ndesc, feats.data_ptr(), feats.data_ptr(), valid_frames if mask_padding else None)
             ctx.synchronize()
     finally:
         if own_ctx:
             ctx.close()
-    begins = np.arange(F, dtype=np.int64) * H + first
-    valid_frames = (np.maximum(begins, 0)[None, :] < np.minimum(begins[None, :] + W, valid[:, None])).sum(axis=1).astype(np.int64)
     if mono:
         feats = feats[:, 0]
     if not device_out:

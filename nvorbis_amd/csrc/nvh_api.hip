@@ -127,6 +127,9 @@ extern "C" void nvh_ctx_destroy(nvh_ctx* c) {
     if (c->mel_copied) (void)hipEventDestroy(c->mel_copied);
     c->mel_rows_host.release();
     c->mel_rows_dev.release();
+    if (c->fnorm_copied) (void)hipEventDestroy(c->fnorm_copied);
+    c->fnorm_rows_host.release();
+    c->fnorm_rows_dev.release();
     c->setup_cache.clear();  // streams must have been closed: they share these entries and return their buffers here
     c->pool.clear();
     c->hpool.clear();

@@ -27,6 +27,7 @@
 #include "host_slab.h"
 #include "kernels_common.h"
 #include "nvh_parse_format.h"
+#include "fnorm_dev.h"
 #include "mel_dev.h"
 #include "resample_dev.h"
 
@@ -130,6 +131,12 @@ template <bool STAGED>
 __global__ void k_mel_rows(NvhMelArgs A);
 extern template __global__ void k_mel_rows<true>(NvhMelArgs);
 extern template __global__ void k_mel_rows<false>(NvhMelArgs);
+
+// ... and the per-row normalisation of features (kernels_fnorm.hip), out of LDS or re-reading its source
+template <bool RESIDENT>
+__global__ void k_fnorm_rows(NvhFnormArgs A);
+extern template __global__ void k_fnorm_rows<true>(NvhFnormArgs);
+extern template __global__ void k_fnorm_rows<false>(NvhFnormArgs);
 
 extern thread_local int g_last_hip_error;
 
@@ -338,6 +345,10 @@ struct nvh_ctx {
   bool mel_lds_attr_set = false;  // k_mel_rows' 80 KB dynamic-LDS opt-in was made on this context's device
   DevBuf mel_rows_host, mel_rows_dev;
   hipEvent_t mel_copied = nullptr;
+  // nvh_fnorm_rows: the per-row block's staging, device copy and event as above
+  bool fnorm_lds_attr_set = false;  // k_fnorm_rows' 80 KB dynamic-LDS opt-in was made on this context's device
+  DevBuf fnorm_rows_host, fnorm_rows_dev;
+  hipEvent_t fnorm_copied = nullptr;
 };
 
 // Wait for the context's stream.  A context of a worker pool (nvh_ctx_set_parse_lanes > 0: one of many host threads, each waiting

@@ -67,6 +67,23 @@ MEL_NORM_NONE, MEL_NORM_SLANEY = 0, 1   # NVH_MEL_NORM_*
 MEL_POWER, MEL_LN, MEL_DB = 0, 1, 2     # NVH_MEL_POWER / _LN / _DB
 MEL_FRAMES = 4  # NVH_MEL_FRAMES: consecutive frames of one (row, channel) per workgroup of k_mel_rows
 
+
+
+class FnormDesc(C.Structure):
+    """nvh_fnorm_desc: mode and axis, the shape, the rule's numbers, and the element strides of source and destination (row, channel,
+    frame, band)."""
+    _fields_ = [("mode", C.c_int32), ("axis", C.c_int32), ("rows", C.c_int32), ("channels", C.c_int32), ("frames", C.c_int32),
+                ("bands", C.c_int32), ("eps", C.c_float), ("pad_value", C.c_float), ("range", C.c_float), ("offset", C.c_float),
+                ("gain", C.c_float), ("reserved", C.c_int32),
+                ("src_row_stride", C.c_int64), ("src_chan_stride", C.c_int64), ("src_frame_stride", C.c_int64),
+                ("src_band_stride", C.c_int64), ("dst_row_stride", C.c_int64), ("dst_chan_stride", C.c_int64),
+                ("dst_frame_stride", C.c_int64), ("dst_band_stride", C.c_int64)]
+
+
+FNORM_NONE, FNORM_MEAN, FNORM_MEAN_VAR, FNORM_PEAK = 0, 1, 2, 3  # NVH_FNORM_NONE / _MEAN / _MEAN_VAR / _PEAK
+FNORM_PER_BAND, FNORM_ALL = 0, 1                                 # NVH_FNORM_PER_BAND / _ALL
+FNORM_RESIDENT_FLOATS = 19952  # NVH_FNORM_RESIDENT_FLOATS: (F | 1) * B up to here is normalised out of LDS
+
 # symbol -> (restype, argtypes); also the list tests check against the header
 _u8p, _f32p, _i64p, _i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
 _vp, _vpp, _ip = C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)
@@ -180,6 +197,9 @@ SIGNATURES = {
     "nvh_mel_plan": (C.c_int, [C.POINTER(MelDesc), _i64p, _i64p, _i64p]),
     "nvh_mel_tables": (C.c_int, [C.POINTER(MelDesc), _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p, _i64p]),
     "nvh_mel_rows": (C.c_int, [_vp, C.POINTER(MelDesc), _vp, _vp, _vp]),
+    # per-row normalisation of features (nvh_fnorm.hip)
+    "nvh_fnorm_check": (C.c_int, [C.POINTER(FnormDesc)]),
+    "nvh_fnorm_rows": (C.c_int, [_vp, C.POINTER(FnormDesc), _vp, _vp, _vp]),
     # the corpus gather through RCCL's C API (nvh_comm.hip): what a host without torch.distributed binds to
     "nvh_comm_unique_id": (C.c_int, [_vp]),
     "nvh_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),

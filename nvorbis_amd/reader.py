@@ -356,6 +356,18 @@ class Context:
         check(lib().nvh_mel_rows(self._h, C.byref(desc), C.c_void_p(d_src), C.c_void_p(d_dst), None if v is None else v.ctypes.data),
               "nvh_mel_rows")
 
+    def fnorm_rows(self, desc, d_src, d_dst, valid_frames=None):
+        """nvh_fnorm_rows: `desc` a native.FnormDesc, d_src / d_dst device addresses (the same address with the same strides: in
+        place), `valid_frames` None or a host sequence of desc.rows ints.  Asynchronous on the context's stream (synchronize()
+        waits for it)."""
+        v = None
+        if valid_frames is not None:
+            v = np.ascontiguousarray(valid_frames, dtype=np.int64)
+            if v.shape != (int(desc.rows),):
+                raise ValueError("fnorm_rows: valid_frames holds one entry per row (%d)" % int(desc.rows))
+        check(lib().nvh_fnorm_rows(self._h, C.byref(desc), C.c_void_p(d_src), C.c_void_p(d_dst), None if v is None else v.ctypes.data),
+              "nvh_fnorm_rows")
+
     def close(self):
         if self._h:
             lib().nvh_ctx_destroy(self._h)

@@ -10,18 +10,134 @@ decode_clip_rows is the fixed-length form a dataset loader wants: a crop [start,
 where the clip is shorter, N rows in one tensor.  Every row is a WINDOWED segment (Stream.segment_window): only the packets the
 crop needs are pushed, the parser cuts the first and the last frame's emission, and the pad is written with the batch.
 """
+import collections
+import contextlib
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
 from . import native
-from .reader import (Context, Stream, _channel_map, _layout, _mix, _pcm_out, _sample_format, demux_ogg_array)
+from .reader import (Context, Stream, _channel_map, _enable_gpu_parse, _layout, _mix, _pcm_format, _pcm_out, _sample_format,
+                     demux_ogg_array)
 
 
 def _return_clipped(value):
     if not isinstance(value, (bool, np.bool_)):
         raise ValueError("return_clipped must be True or False, not %r" % (value,))
     return bool(value)
+
+
+def _length(value):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 0:
+        raise ValueError("length must be an int >= 0, not %r" % (value,))
+    return int(value)
+
+
+def _batch_frames(value):
+    if int(value) < 1:
+        raise ValueError("batch_frames must be at least 1")
+    return int(value)
+
+
+def _starts(starts, n):
+    """One start per clip as a list of ints; None: 0 for every clip."""
+    if starts is None:
+        return [0] * n
+    starts = list(starts)
+    if len(starts) != n:
+        raise ValueError("starts must name one start per clip (%d for %d clips)" % (len(starts), n))
+    for v in starts:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("starts must be ints >= 0, not %r" % (v,))
+    return [int(v) for v in starts]
+
+
+@contextlib.contextmanager
+def _context(ctx, device):
+    """The caller's Context, or one of its own on `device` that is closed on every way out of the block."""
+    if ctx is not None:
+        yield ctx
+        return
+    ctx = Context(device)
+    try:
+        yield ctx
+    finally:
+        ctx.close()
+
+
+@dataclasses.dataclass
+class _Form:
+    """The output form of one public call: what every batch is synthesised as and where it goes."""
+    dtype: np.dtype  # of a sample: float32 or int16
+    planar: bool
+    mix: object
+    channel_map: object
+    batch_frames: int
+    gpu_parse: bool
+    device_out: bool
+    device: int
+    align: int = None  # clip batches only
+    clipped: object = None  # the caller's bool array over all clips or rows, or None: not asked for
+
+    def map(self, ch):
+        """The map of a stream of `ch` channels ("wave" depends on the count)."""
+        return _channel_map(self.channel_map, ch, self.mix)
+
+    def och(self, ch):
+        """The samples per sample time that a stream of `ch` channels leaves."""
+        return _pcm_out(self.dtype, self.planar, self.mix, self.channel_map, ch)[2]
+
+    def torch_dtype(self):
+        import torch
+        return torch.int16 if self.dtype == np.dtype(np.int16) else torch.float32
+
+    def row_shape(self, rows, t, och):
+        return (och, rows, t) if self.planar else (rows, t) if self.mix is not None else (rows, t, och)
+
+    def row_strides(self, rows, t, och):
+        """(row, sample time, channel) in elements."""
+        return (t, 1, rows * t) if self.planar else (t, 1, 0) if self.mix is not None else (t * och, och, 1)
+
+    def f32(self):
+        """The same form in float32: the resampler's source rows."""
+        return dataclasses.replace(self, dtype=np.dtype(np.float32))
+
+
+_Clip = collections.namedtuple("_Clip", "packets key channels rate index")
+
+
+def _load_clips(clips, call, sample_rate=None, want_index=False, form=None):
+    """One _Clip per clip (bytes or a path), on the host: its PacketArray, its setup key (identification and setup packet), the
+    stream's channels and rate, and with want_index what Stream.index_packets says of its audio packets (else None).  Clip by
+    clip, before the next one is looked at: NvhError for its headers as clip i of `call`, then, with a form, ValueError for a
+    channel map that does not fit it, then ValueError for a rate the resampler does not take to `sample_rate`."""
+    recs = []
+    for i, src in enumerate(clips):
+        if isinstance(src, (bytes, bytearray, memoryview)):
+            data = bytes(src)
+        else:
+            with open(src, "rb") as fh:
+                data = fh.read()
+        try:
+            pa = demux_ogg_array(data, 0)
+            if len(pa) < 3:
+                raise native.NvhError(native.ERR_NOT_VORBIS, call)
+            # every clip's own three headers are looked at, on the host (a setup seen before on this thread is not parsed again)
+            key = (pa[0], pa[2])
+            probe = Stream(None, key[0], pa[1], key[1])
+            try:
+                rec = _Clip(pa, key, probe.channels, probe.sample_rate, probe.index_packets(pa, 3) if want_index else None)
+            finally:
+                probe.close()
+        except native.NvhError as e:
+            raise _clip_error(i, e, "headers", call)
+        if form is not None:
+            form.och(rec.channels)
+        if sample_rate is not None and rec.rate != sample_rate:
+            resample_plan(rec.rate, sample_rate)
+        recs.append(rec)
+    return recs
 
 
 def _note_clipped(st, members, clipped):
@@ -42,25 +158,20 @@ class _Group:
     """One setup's clips on one Stream: pushes them as segments, synthesises whenever batch_frames frames are pending and
     routes every batch through its segment table."""
 
-    def __init__(self, ctx, first, members, packets, opts):
-        self.members, self.packets, self.opts = members, packets, opts
-        pa = packets[first]
+    def __init__(self, ctx, members, recs, form):
+        self.members, self.recs, self.form = members, recs, form
+        pa = recs[members[0]].packets
         self.stream = Stream(ctx, pa[0], pa[1], pa[2])
         self.pieces = {i: [] for i in members}
-        self.clipped = opts.get("clipped")  # the caller's bool array over all clips, or None: not asked for
 
     def run(self):
-        o, st = self.opts, self.stream
-        if o["gpu_parse"]:  # stream shapes outside the GPU parser's limits keep the host parser, as in VorbisReader
-            try:
-                st.set_gpu_parse(True)
-            except native.NvhError as e:
-                if e.code != native.ERR_UNSUPPORTED:
-                    raise
+        o, st = self.form, self.stream
+        if o.gpu_parse:
+            _enable_gpu_parse(st)
         for i in self.members:
-            pa, nxt = self.packets[i], 3
+            pa, nxt = self.recs[i].packets, 3
             while nxt < len(pa):
-                room = o["batch_frames"] - st.pending()[0]
+                room = o.batch_frames - st.pending()[0]
                 if room <= 0:
                     self.flush()
                     continue
@@ -71,60 +182,58 @@ class _Group:
                 nxt += took
                 if took < room and nxt < len(pa):
                     break  # the clip's end-of-stream packet: nothing behind it is pulled
-            st.next_segment(o["align"])
+            st.next_segment(o.align)
         self.flush()
 
     def flush(self):
-        o, st = self.opts, self.stream
+        o, st = self.form, self.stream
         frames, samples = st.pending()
         if not frames:
             return
         table = st.pending_segments()
-        och, planar = o["och"](st.channels), o["planar"]
-        if o["device_out"]:
+        och, planar = o.och(st.channels), o.planar
+        if o.device_out:
             import torch
-            dev = "cuda:%d" % o["device"]
-            tdt = torch.int16 if o["dtype"] == np.dtype(np.int16) else torch.float32
+            dev = "cuda:%d" % o.device
             if planar:
                 stride = max((samples + 3) & ~3, 4)
-                out = torch.empty((och, stride), dtype=tdt, device=dev)
-                st.synth_device(out.data_ptr(), 0, dtype=o["dtype"], plane_stride=stride, channel_map=o["map"](st.channels))
+                out = torch.empty((och, stride), dtype=o.torch_dtype(), device=dev)
+                st.synth_device(out.data_ptr(), 0, dtype=o.dtype, plane_stride=stride, channel_map=o.map(st.channels))
             else:
-                out = torch.empty(max(samples * och, 1), dtype=tdt, device=dev)
-                st.synth_device(out.data_ptr(), out.numel(), dtype=o["dtype"], mix=o["mix"], channel_map=o["map"](st.channels))
+                out = torch.empty(max(samples * och, 1), dtype=o.torch_dtype(), device=dev)
+                st.synth_device(out.data_ptr(), out.numel(), dtype=o.dtype, mix=o.mix, channel_map=o.map(st.channels))
         else:
-            out = st.synth_host(pinned=True, dtype=o["dtype"], planar=planar, mix=o["mix"], channel_map=o["map"](st.channels))
+            out = st.synth_host(pinned=True, dtype=o.dtype, planar=planar, mix=o.mix, channel_map=o.map(st.channels))
         if st.parse_errors:  # GPU-parse mode: a packet of this batch made the parser fail; positions up to it are the table's
             err, at = st.parse_errors[0]
-            at //= 1 if (planar or o["mix"] is not None) else och
+            at //= 1 if (planar or o.mix is not None) else och
             # the segment whose range holds the position; a packet that leaves no samples there (a clip's first): the first
             # non-empty segment that begins at it, else the last one that begins before it
             inside = np.nonzero((table[:, 1] <= at) & (at < table[:, 2]))[0]
             row = inside[0] if inside.size else max(int(np.searchsorted(table[:, 1], at, side="right")) - 1, 0)
             k = int(table[row, 0])
             raise _clip_error(self.members[k], err, "a packet the parser fails on")
-        if self.clipped is not None:
-            _note_clipped(st, self.members, self.clipped)
+        if o.clipped is not None:
+            _note_clipped(st, self.members, o.clipped)
         for k, b, e in table:
             if e > b:
                 piece = out[:, b:e] if planar else out[b * och:e * och]
                 # (a host batch lies in the stream's page-locked buffer, which the next batch overwrites)
-                self.pieces[self.members[int(k)]].append(piece if o["device_out"] else piece.copy())
+                self.pieces[self.members[int(k)]].append(piece if o.device_out else piece.copy())
 
     def results(self, into):
-        o, st = self.opts, self.stream
-        och = o["och"](st.channels)
+        o, st = self.form, self.stream
+        och = o.och(st.channels)
         for i in self.members:
             ps = self.pieces[i]
-            if o["device_out"]:
+            if o.device_out:
                 import torch
                 if not ps:
-                    tdt = torch.int16 if o["dtype"] == np.dtype(np.int16) else torch.float32
-                    ps = [torch.empty((och, 0) if o["planar"] else (0,), dtype=tdt, device="cuda:%d" % o["device"])]
+                    ps = [torch.empty((och, 0) if o.planar else (0,), dtype=o.torch_dtype(), device="cuda:%d" % o.device)]
                 into[i] = ps[0] if len(ps) == 1 else torch.cat(ps, dim=-1)  # (a clip inside one batch: a view of that batch's output)
             else:
                 if not ps:
-                    ps = [np.zeros((och, 0) if o["planar"] else (0,), dtype=o["dtype"])]
+                    ps = [np.zeros((och, 0) if o.planar else (0,), dtype=o.dtype)]
                 into[i] = ps[0] if len(ps) == 1 else np.concatenate(ps, axis=-1)
 
 
@@ -155,54 +264,28 @@ def decode_clips(clips, ctx=None, device=0, batch_frames=4096, gpu_parse=True, s
         _channel_map(channel_map, None, mix)
     if isinstance(align, bool) or not isinstance(align, (int, np.integer)) or align < 1 or align > 65536 or align & (align - 1):
         raise ValueError("align must be a power of two in [1, 65536], not %r" % (align,))
-    if int(batch_frames) < 1:
-        raise ValueError("batch_frames must be at least 1")
-    packets, groups = [], {}
-    for i, src in enumerate(clips):
-        if isinstance(src, (bytes, bytearray, memoryview)):
-            data = bytes(src)
-        else:
-            with open(src, "rb") as fh:
-                data = fh.read()
-        try:
-            pa = demux_ogg_array(data, 0)
-            if len(pa) < 3:
-                raise native.NvhError(native.ERR_NOT_VORBIS, "decode_clips")
-            key = (pa[0], pa[2])
-            # every clip's own three headers are looked at, on the host (a setup seen before on this thread is not parsed again)
-            Stream(None, pa[0], pa[1], pa[2]).close()
-        except native.NvhError as e:
-            raise _clip_error(i, e, "headers")
-        packets.append(pa)
-        groups.setdefault(key, []).append(i)
-    own_ctx = ctx is None and bool(groups)
-    if own_ctx:
-        ctx = Context(device)
-    opts = {
-        "batch_frames": int(batch_frames), "gpu_parse": bool(gpu_parse), "dtype": dtype, "planar": planar, "mix": mix,
-        "align": int(align), "device_out": bool(device_out), "device": ctx.device if ctx is not None else int(device),
-        # the map of a stream of `ch` channels ("wave" depends on the count), and the samples per sample time it leaves
-        "map": lambda ch: _channel_map(channel_map, ch, mix),
-        "och": lambda ch: _pcm_out(dtype, planar, mix, channel_map, ch)[2],
-    }
-    results = [None] * len(packets)
-    clipped = np.zeros(len(packets), dtype=bool)
+    form = _Form(dtype, planar, mix, channel_map, _batch_frames(batch_frames), bool(gpu_parse), bool(device_out),
+                 int(device) if ctx is None else ctx.device, int(align))
+    recs = _load_clips(clips, "decode_clips")
+    groups = {}
+    for i, r in enumerate(recs):
+        groups.setdefault(r.key, []).append(i)
+    results = [None] * len(recs)
+    clipped = np.zeros(len(recs), dtype=bool)
     if return_clipped:
-        opts["clipped"] = clipped
-    try:
-        for members in groups.values():
-            try:
-                g = _Group(ctx, members[0], members, packets, opts)
-            except native.NvhError as e:
-                raise _clip_error(members[0], e, "nvh_stream_open")
-            try:
-                g.run()
-                g.results(results)
-            finally:
-                g.stream.close()
-    finally:
-        if own_ctx:
-            ctx.close()
+        form.clipped = clipped
+    if groups:
+        with _context(ctx, device) as ctx:
+            for members in groups.values():
+                try:
+                    g = _Group(ctx, members, recs, form)
+                except native.NvhError as e:
+                    raise _clip_error(members[0], e, "nvh_stream_open")
+                try:
+                    g.run()
+                    g.results(results)
+                finally:
+                    g.stream.close()
     return (results, clipped) if return_clipped else results
 
 
@@ -270,30 +353,25 @@ class _RowGroup:
     """One setup's rows on one Stream, written into `buf` -- rows [row0, row0 + len(members)) of the dense buffer -- batch by
     batch: every batch's destination is the buffer's base plus what the batches before it wrote."""
 
-    def __init__(self, ctx, members, packets, plans, opts, length):
-        self.members, self.packets, self.plans, self.opts, self.length = members, packets, plans, opts, length
-        pa = packets[members[0]]
+    def __init__(self, ctx, members, recs, plans, form, length):
+        self.members, self.recs, self.plans, self.form, self.length = members, recs, plans, form, length
+        pa = recs[members[0]].packets
         self.stream = Stream(ctx, pa[0], pa[1], pa[2])
         self.done = 0  # samples per channel written so far: whole rows and the part of the open one
-        self.clipped = opts.get("clipped")  # the caller's bool array over all rows, or None: not asked for
         self.dests = []  # the destination of every batch
 
     def run(self, base_ptr, row0, rows_total):
         """base_ptr: address of the dense buffer (device or host); rows_total: its rows (the planes' stride is rows_total * length)."""
-        o, st = self.opts, self.stream
+        o, st = self.form, self.stream
         self.base, self.row0, self.rows_total = base_ptr, row0, rows_total
-        if o["gpu_parse"]:
-            try:
-                st.set_gpu_parse(True)
-            except native.NvhError as e:
-                if e.code != native.ERR_UNSUPPORTED:
-                    raise
+        if o.gpu_parse:
+            _enable_gpu_parse(st)
         align = 4 if self.length % 4 == 0 else 1
         # Batches end on row boundaries -- once batch_frames frames are pending and the next batch's destination is one the
         # kernels take (interleaved 16-bit PCM: 16-byte aligned, which every eighth row boundary is at the latest) -- so that
         # every row of a batch lies where the vector paths want it; only a row of more than batch_frames frames is cut inside.
-        och, isz = o["och"](st.channels), o["dtype"].itemsize
-        strict = isz == 2 and not o["planar"] and o["mix"] is None and o["map"](st.channels) is None
+        och, isz = o.och(st.channels), o.dtype.itemsize
+        strict = isz == 2 and not o.planar and o.mix is None and o.map(st.channels) is None
         for i in self.members:
             # a row is cut inside only after 2 * batch_frames frames of its own (what earlier rows left pending does not count
             # against it; behind a cut inside the row the count starts again)
@@ -303,39 +381,39 @@ class _RowGroup:
                 self.flush()
                 own[0] = 0
             try:
-                push_clip_window(st, self.packets[i], self.plans[i], self.length,
-                                 lambda: own[0] + 2 * o["batch_frames"] - st.pending()[0], cut_inside)
+                push_clip_window(st, self.recs[i].packets, self.plans[i], self.length,
+                                 lambda: own[0] + 2 * o.batch_frames - st.pending()[0], cut_inside)
             except native.NvhError as e:
                 if getattr(e, "clip", None) is not None:
                     raise
                 raise _clip_error(i, e, "nvh_stream_push_packets", "decode_clip_rows")
             st.next_segment(align)
             frames, samples = st.pending()
-            if frames >= o["batch_frames"] and (not strict or (self.base + (self.row0 * self.length + self.done + samples) * och * isz) % 16 == 0):
+            if frames >= o.batch_frames and (not strict or (self.base + (self.row0 * self.length + self.done + samples) * och * isz) % 16 == 0):
                 self.flush()
         self.flush()
         if self.done != len(self.members) * self.length:
             raise RuntimeError("decode_clip_rows: %d samples written, %d rows of %d planned" % (self.done, len(self.members), self.length))
 
     def flush(self):
-        o, st = self.opts, self.stream
+        o, st = self.form, self.stream
         frames, samples = st.pending()
         if not frames and not samples:
             return
-        och, planar, isz = o["och"](st.channels), o["planar"], o["dtype"].itemsize
+        och, planar, isz = o.och(st.channels), o.planar, o.dtype.itemsize
         if self.done + samples > len(self.members) * self.length:  # (never write behind the group's rows)
             raise RuntimeError("decode_clip_rows: a batch of %d samples behind %d does not fit %d rows of %d" %
                                (samples, self.done, len(self.members), self.length))
         stride = self.rows_total * self.length
         at = self.row0 * self.length + self.done  # samples per channel in front of this batch
-        d, _, _, per = _pcm_out(o["dtype"], planar, o["mix"], o["map"](st.channels), st.channels)
+        d, _, _, per = _pcm_out(o.dtype, planar, o.mix, o.map(st.channels), st.channels)
         if planar:
             ptr, d.extent = self.base + at * isz, stride
         else:
             ptr, d.extent = self.base + at * och * isz, samples * och
         self.dests.append(ptr)
         wr = C.c_int64(0)
-        if o["device_out"]:
+        if o.device_out:
             rc = native.lib().nvh_stream_synth_out(st._h, C.byref(d), None, C.c_void_p(ptr), C.byref(wr))
         else:
             rc = native.lib().nvh_stream_synth_out(st._h, C.byref(d), C.c_void_p(ptr), None, C.byref(wr))
@@ -345,8 +423,8 @@ class _RowGroup:
             pos //= 1 if per else och
             k = min((self.done + pos) // max(self.length, 1), len(self.members) - 1)
             raise _clip_error(self.members[int(k)], err, "a packet the parser fails on", "decode_clip_rows")
-        if self.clipped is not None:
-            _note_clipped(st, self.members, self.clipped)
+        if o.clipped is not None:
+            _note_clipped(st, self.members, o.clipped)
         self.done += wr.value if per else wr.value // och
 
 
@@ -377,16 +455,24 @@ def _sample_rate(value):
     return int(value)
 
 
-def _run_row_groups(ctx, members, packets, plans, opts, length, base, rows_total):
+def _output_channels(recs, form, call):
+    """The one output channel count of the clips in `form` (1 without clips); ValueError of `call` if they differ."""
+    ochs = sorted(set(form.och(ch) for ch in set(r.channels for r in recs)))
+    if len(ochs) > 1:
+        raise ValueError("%s: the clips' output channel counts differ (%s)" % (call, ochs))
+    return ochs[0] if ochs else 1
+
+
+def _run_row_groups(ctx, members, recs, plans, form, length, base, rows_total):
     """Clips `members` as rows [0, len(members)) of the buffer at `base` (of rows_total rows), grouped by setup, one _RowGroup
     after the other.  Returns the clips in the order of their rows."""
     groups = {}
     for i in members:
-        groups.setdefault((packets[i][0], packets[i][2]), []).append(i)
+        groups.setdefault(recs[i].key, []).append(i)
     placed, row0 = [], 0
     for group in groups.values():
         try:
-            g = _RowGroup(ctx, group, packets, plans, opts, length)
+            g = _RowGroup(ctx, group, recs, plans, form, length)
         except native.NvhError as e:
             raise _clip_error(group[0], e, "nvh_stream_open", "decode_clip_rows")
         try:
@@ -398,45 +484,35 @@ def _run_row_groups(ctx, members, packets, plans, opts, length, base, rows_total
     return placed, len(groups)
 
 
-def _resampled_rows(ctx, device, packets, index, rates, plans, starts, length, sample_rate, och, dtype, planar, mono, opts, clipped):
+def _resampled_rows(ctx, recs, plans, starts, length, sample_rate, form):
     """decode_clip_rows with at least one clip at another rate than `sample_rate`: (buf, valid) on the device, rows in input
     order.  Clips at the target rate go through the row path as they are and are copied to their rows; the others are classed by
     source rate, every class decodes f32 source rows [origin, origin + S) into a temporary buffer through the same row path,
-    and k_resample_rows writes the class's rows of the returned buffer."""
+    and k_resample_rows writes the class's rows of the returned buffer.  `form`: the call's, with device_out set."""
     import torch
-    n = len(packets)
-    dev = "cuda:%d" % int(device)
-    tdt = torch.int16 if dtype == np.dtype(np.int16) else torch.float32
-    row_axis = 1 if planar else 0
-
-    def shape_of(rows, t):
-        return (och, rows, t) if planar else (rows, t) if mono else (rows, t, och)
-
-    def strides_of(rows, t):  # (row, sample time, channel) in elements
-        return (t, 1, rows * t) if planar else (t, 1, 0) if mono else (t * och, och, 1)
-    buf = torch.empty(shape_of(n, length), dtype=tdt, device=dev)
-    flags = torch.zeros(n, dtype=torch.int32, device=dev) if clipped is not None else None
+    n = len(recs)
+    dev = "cuda:%d" % form.device
+    tdt, och = form.torch_dtype(), form.och(recs[0].channels)
+    buf = torch.empty(form.row_shape(n, length, och), dtype=tdt, device=dev)
+    flags = torch.zeros(n, dtype=torch.int32, device=dev) if form.clipped is not None else None
     valid = np.asarray([p["valid"] for p in plans], dtype=np.int64)
-    same = [i for i in range(n) if rates[i] == sample_rate]
-    classes = {}
-    for i in range(n):
-        if rates[i] != sample_rate:
-            classes.setdefault(rates[i], []).append(i)
+    classes, setups = {}, {}
+    for i, r in enumerate(recs):
+        if r.rate != sample_rate:
+            classes.setdefault(r.rate, []).append(i)
+        else:
+            setups.setdefault(r.key, []).append(i)
     keep = []  # the temporaries, until the context's stream has run
-    setups = {}
-    for i in same:
-        setups.setdefault((packets[i][0], packets[i][2]), []).append(i)
     for group in setups.values():  # (a buffer per setup: every group begins on an allocation's alignment, whatever the length)
-        tmp = torch.empty(shape_of(len(group), length), dtype=tdt, device=dev)
-        placed, _ = _run_row_groups(ctx, group, packets, plans, opts, length, tmp.data_ptr(), len(group))
-        buf.index_copy_(row_axis, torch.as_tensor(placed, dtype=torch.int64, device=dev), tmp)
+        tmp = torch.empty(form.row_shape(len(group), length, och), dtype=tdt, device=dev)
+        placed, _ = _run_row_groups(ctx, group, recs, plans, form, length, tmp.data_ptr(), len(group))
+        buf.index_copy_(1 if form.planar else 0, torch.as_tensor(placed, dtype=torch.int64, device=dev), tmp)
         keep.append(tmp)
-    f32 = dict(opts, dtype=np.dtype(np.float32))
     for rate, members in classes.items():
         L, M, half, _ = resample_plan(rate, sample_rate)
         origin, take = {}, {}
         for i in members:
-            total = index[i][3]
+            total = recs[i].index[3]
             total_out = (total * L + M - 1) // M
             valid[i] = min(length, max(0, total_out - starts[i]))
             origin[i] = take[i] = 0  # (nothing of the clip in the row: no packet is decoded, the source row is a pad)
@@ -447,17 +523,17 @@ def _resampled_rows(ctx, device, packets, index, rates, plans, starts, length, s
         S = max(4, max(take.values()))  # the source rows' pitch; row i holds source samples [origin, origin + take) and a pad
         src_plans = {}
         for i in members:
-            pos, em, state, total = index[i]
+            pos, em, state, total = recs[i].index
             src_plans[i] = plan_clip_window(pos, em, state, total, origin[i] if take[i] else total, take[i])
             if take[i]:
                 src_plans[i]["take"] = take[i]
-        tmp = torch.empty(shape_of(len(members), S), dtype=torch.float32, device=dev)
-        placed, _ = _run_row_groups(ctx, members, packets, src_plans, f32, S, tmp.data_ptr(), len(members))
+        tmp = torch.empty(form.row_shape(len(members), S, och), dtype=torch.float32, device=dev)
+        placed, _ = _run_row_groups(ctx, members, recs, src_plans, form.f32(), S, tmp.data_ptr(), len(members))
         torch.cuda.current_stream(dev).synchronize()  # (the flag words are zeroed on torch's stream)
-        sr, st, sc = strides_of(len(members), S)
-        dr, dt, dc = strides_of(n, length)
+        sr, st, sc = form.row_strides(len(members), S, och)
+        dr, dt, dc = form.row_strides(n, length, och)
         desc = native.ResampleDesc(in_rate=rate, out_rate=sample_rate, rows=len(members), channels=och,
-                                   format=native.PCM_S16 if tdt == torch.int16 else native.PCM_F32, length=length, src_length=S,
+                                   format=_pcm_format(form.dtype)[0], length=length, src_length=S,
                                    src_row_stride=sr, src_time_stride=st, src_chan_stride=sc, dst_row_stride=dr,
                                    dst_time_stride=dt, dst_chan_stride=dc)
         ctx.resample_rows(desc, tmp.data_ptr(), buf.data_ptr(), [origin[i] for i in placed], [starts[i] for i in placed],
@@ -465,7 +541,7 @@ def _resampled_rows(ctx, device, packets, index, rates, plans, starts, length, s
         keep.append(tmp)
     ctx.synchronize()
     if flags is not None:
-        clipped |= flags.cpu().numpy() != 0
+        form.clipped |= flags.cpu().numpy() != 0
     del keep
     return buf, valid
 
@@ -526,108 +602,51 @@ def decode_clip_rows(clips, length, starts=None, ctx=None, device=0, batch_frame
     sample_rate = _sample_rate(sample_rate)
     if channel_map is not None:
         _channel_map(channel_map, None, mix)
-    if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0:
-        raise ValueError("length must be an int >= 0, not %r" % (length,))
-    length = int(length)
-    if int(batch_frames) < 1:
-        raise ValueError("batch_frames must be at least 1")
+    length = _length(length)
+    batch_frames = _batch_frames(batch_frames)
     clips = list(clips)
-    if starts is None:
-        starts = [0] * len(clips)
-    starts = list(starts)
-    if len(starts) != len(clips):
-        raise ValueError("starts must name one start per clip (%d for %d clips)" % (len(starts), len(clips)))
-    for v in starts:
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
-            raise ValueError("starts must be ints >= 0, not %r" % (v,))
-    starts = [int(v) for v in starts]
-    packets, plans, chans, index, rates = [], [], [], [], []
-    for i, src in enumerate(clips):
-        if isinstance(src, (bytes, bytearray, memoryview)):
-            data = bytes(src)
-        else:
-            with open(src, "rb") as fh:
-                data = fh.read()
-        try:
-            pa = demux_ogg_array(data, 0)
-            if len(pa) < 3:
-                raise native.NvhError(native.ERR_NOT_VORBIS, "decode_clip_rows")
-            probe = Stream(None, pa[0], pa[1], pa[2])
-            try:
-                pos, em, state, total = probe.index_packets(pa, 3)
-                chans.append(_pcm_out(dtype, planar, mix, channel_map, probe.channels)[2])
-                rates.append(probe.sample_rate)
-            finally:
-                probe.close()
-        except native.NvhError as e:
-            raise _clip_error(i, e, "headers", "decode_clip_rows")
-        packets.append(pa)
-        if sample_rate is not None and rates[i] != sample_rate:
-            resample_plan(rates[i], sample_rate)  # (ValueError for a pair outside the limits: before any device)
-        index.append((pos, em, state, total))
-        plans.append(plan_clip_window(pos, em, state, total, starts[i], length))
-    if len(set(chans)) > 1:
-        raise ValueError("decode_clip_rows: the clips' output channel counts differ (%s)" % sorted(set(chans)))
-    n = len(clips)
-    och = chans[0] if chans else 1
+    starts = _starts(starts, len(clips))
+    form = _Form(dtype, planar, mix, channel_map, batch_frames, bool(gpu_parse), bool(device_out),
+                 int(device) if ctx is None else ctx.device, clipped=np.zeros(len(clips), dtype=bool) if return_clipped else None)
+    recs = _load_clips(clips, "decode_clip_rows", sample_rate, True, form)
+    return _clip_rows(ctx, recs, starts, length, sample_rate, form)
+
+
+def _clip_rows(ctx, recs, starts, length, sample_rate, form):
+    """decode_clip_rows behind its argument checks and the load: `recs` from _load_clips with the index, `form` with the
+    `clipped` array of return_clipped (what is returned says so: ((rows, valid), clipped))."""
+    n, och = len(recs), _output_channels(recs, form, "decode_clip_rows")
+    plans = [plan_clip_window(*r.index, starts[i], length) for i, r in enumerate(recs)]
     valid = np.asarray([p["valid"] for p in plans], dtype=np.int64)
-    mono = mix is not None
-    clipped = np.zeros(n, dtype=bool)
-    shape = (och, n, length) if planar else (n, length) if mono else (n, length, och)
-    resampling = sample_rate is not None and n and length and any(r != sample_rate for r in rates)
-    opts = {"batch_frames": int(batch_frames), "gpu_parse": bool(gpu_parse), "dtype": dtype, "planar": planar, "mix": mix,
-            "device_out": bool(device_out), "map": lambda ch: _channel_map(channel_map, ch, mix),
-            "och": lambda ch: _pcm_out(dtype, planar, mix, channel_map, ch)[2]}
-    if return_clipped:
-        opts["clipped"] = clipped
-    if resampling:
-        own_ctx = ctx is None
-        if own_ctx:
-            ctx = Context(device)
-        try:
-            opts["device_out"] = True
-            buf, valid = _resampled_rows(ctx, ctx.device, packets, index, rates, plans, starts, length, sample_rate, och, dtype, planar,
-                                         mono, opts, clipped if return_clipped else None)
-        finally:
-            if own_ctx:
-                ctx.close()
-        if not device_out:
+    if sample_rate is not None and n and length and any(r.rate != sample_rate for r in recs):
+        with _context(ctx, form.device) as ctx:
+            buf, valid = _resampled_rows(ctx, recs, plans, starts, length, sample_rate, dataclasses.replace(form, device_out=True))
+        if not form.device_out:
             buf = buf.cpu().numpy()
-        if planar:
-            buf = buf.permute(1, 0, 2) if device_out else buf.transpose(1, 0, 2)
-        return ((buf, valid), clipped) if return_clipped else (buf, valid)
-    if device_out:
-        import torch
-        if ctx is not None:
-            device = ctx.device
-        buf = torch.empty(shape, dtype=torch.int16 if dtype == np.dtype(np.int16) else torch.float32, device="cuda:%d" % int(device))
-        base = buf.data_ptr()
     else:
-        buf = np.empty(shape, dtype=dtype)
-        base = buf.ctypes.data
-    placed, groups = list(range(n)), 1
-    if n and length:
-        own_ctx = ctx is None
-        if own_ctx:
-            ctx = Context(device)
-        try:
-            placed, groups = _run_row_groups(ctx, range(n), packets, plans, opts, length, base, n)
-        finally:
-            if own_ctx:
-                ctx.close()
-    elif n:
-        groups = len(set((pa[0], pa[2]) for pa in packets))
-    if groups > 1:  # rows lie group by group: one gather puts them into input order
-        order = np.empty(n, dtype=np.int64)
-        order[np.asarray(placed, dtype=np.int64)] = np.arange(n)
-        if device_out:
+        if form.device_out:
             import torch
-            buf = buf.index_select(1 if planar else 0, torch.as_tensor(order, device=buf.device))
+            buf = torch.empty(form.row_shape(n, length, och), dtype=form.torch_dtype(), device="cuda:%d" % form.device)
+            base = buf.data_ptr()
         else:
-            buf = np.take(buf, order, axis=1 if planar else 0)
-    if planar:
-        buf = buf.permute(1, 0, 2) if device_out else buf.transpose(1, 0, 2)
-    return ((buf, valid), clipped) if return_clipped else (buf, valid)
+            buf = np.empty(form.row_shape(n, length, och), dtype=form.dtype)
+            base = buf.ctypes.data
+        placed, groups = list(range(n)), 1
+        if n and length:
+            with _context(ctx, form.device) as ctx:
+                placed, groups = _run_row_groups(ctx, range(n), recs, plans, form, length, base, n)
+        elif n:
+            groups = len(set(r.key for r in recs))
+        if groups > 1:  # rows lie group by group: one gather puts them into input order
+            order = np.empty(n, dtype=np.int64)
+            order[np.asarray(placed, dtype=np.int64)] = np.arange(n)
+            if form.device_out:
+                buf = buf.index_select(1 if form.planar else 0, torch.as_tensor(order, device=buf.device))
+            else:
+                buf = np.take(buf, order, axis=1 if form.planar else 0)
+    if form.planar:
+        buf = buf.permute(1, 0, 2) if form.device_out else buf.transpose(1, 0, 2)
+    return ((buf, valid), form.clipped) if form.clipped is not None else (buf, valid)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -643,6 +662,14 @@ def _int_in(name, value, lo, hi):
     if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < lo or value > hi:
         raise ValueError("%s must be an int in [%d, %d], not %r" % (name, lo, hi, value))
     return int(value)
+
+
+def _real(name, value, finite):
+    """`value` if it is a real number: no bool, no NaN and, with `finite`, no infinity."""
+    if (isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating))
+            or (not np.isfinite(value) if finite else np.isnan(value))):
+        raise ValueError("%s must be a %s, not %r" % (name, "finite number" if finite else "number", value))
+    return value
 
 
 def mel_desc(rate, n_fft=512, win_length=400, hop=160, n_mels=80, f_min=0.0, f_max=None, mel_scale="htk", norm=None, scale="ln",
@@ -662,12 +689,8 @@ def mel_desc(rate, n_fft=512, win_length=400, hop=160, n_mels=80, f_min=0.0, f_m
         raise ValueError("norm must be None or 'slaney', not %r" % (norm,))
     if not isinstance(scale, str) or scale not in _MEL_OUT:
         raise ValueError("scale must be 'power', 'ln' or 'db', not %r" % (scale,))
-    reals = []
-    for name, v in (("f_min", f_min), ("f_max", rate / 2.0 if f_max is None else f_max), ("floor", floor)):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-            raise ValueError("%s must be a finite number, not %r" % (name, v))
-        reals.append(float(v))
-    f_min, f_max, floor = reals
+    f_min, f_max, floor = (float(_real(name, v, True)) for name, v in
+                           (("f_min", f_min), ("f_max", rate / 2.0 if f_max is None else f_max), ("floor", floor)))
     if not 0.0 <= f_min < f_max <= rate / 2.0:
         raise ValueError("f_min and f_max must satisfy 0 <= f_min < f_max <= rate / 2 (%r, %r at %d Hz)" % (f_min, f_max, rate))
     with np.errstate(over="ignore"):
@@ -725,10 +748,8 @@ def fnorm_desc(normalize=None, normalize_axis="band", norm_eps=1e-5, pad_value=0
     vals = {}
     for name, v in (("norm_eps", norm_eps), ("pad_value", pad_value), ("peak_range", peak_range), ("peak_offset", peak_offset),
                     ("peak_gain", peak_gain)):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or np.isnan(v):
-            raise ValueError("%s must be a number, not %r" % (name, v))
         with np.errstate(over="ignore"):
-            vals[name] = np.float32(v)
+            vals[name] = np.float32(_real(name, v, False))
     if not np.isfinite(vals["norm_eps"]) or vals["norm_eps"] < np.float32(2.0 ** -126):
         raise ValueError("norm_eps must be an f32 >= 2**-126, not %r" % (norm_eps,))
     if not vals["peak_range"] >= 0:
@@ -745,34 +766,6 @@ def fnorm_desc(normalize=None, normalize_axis="band", norm_eps=1e-5, pad_value=0
     native.check(rc, "nvh_fnorm_check")
     d.channels = 0
     return d
-
-
-def _clip_probe(clips, mix, channel_map, sample_rate):
-    """(sample rates, output channel counts) of the clips, from their headers (host only), with decode_clip_rows' ValueErrors for
-    a map that does not fit a clip and for a rate the resampler does not take to `sample_rate`."""
-    rates, chans = [], []
-    f32 = np.dtype(np.float32)
-    for i, src in enumerate(clips):
-        if isinstance(src, (bytes, bytearray, memoryview)):
-            data = bytes(src)
-        else:
-            with open(src, "rb") as fh:
-                data = fh.read()
-        try:
-            pa = demux_ogg_array(data, 0)
-            if len(pa) < 3:
-                raise native.NvhError(native.ERR_NOT_VORBIS, "decode_clip_features")
-            probe = Stream(None, pa[0], pa[1], pa[2])
-            try:
-                rates.append(probe.sample_rate)
-                chans.append(_pcm_out(f32, mix is None, mix, channel_map, probe.channels)[2])
-            finally:
-                probe.close()
-        except native.NvhError as e:
-            raise _clip_error(i, e, "headers", "decode_clip_features")
-        if sample_rate is not None and rates[i] != sample_rate:
-            resample_plan(rates[i], sample_rate)
-    return rates, chans
 
 
 def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=512, win_length=400, hop=160, n_mels=80, f_min=0.0,
@@ -819,26 +812,20 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
     _mix(mix, False)
     if channel_map is not None:
         _channel_map(channel_map, None, mix)
-    if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0:
-        raise ValueError("length must be an int >= 0, not %r" % (length,))
-    length = int(length)
-    if int(batch_frames) < 1:
-        raise ValueError("batch_frames must be at least 1")
+    length = _length(length)
+    batch_frames = _batch_frames(batch_frames)
     clips = list(clips)
-    if starts is not None:
-        starts = list(starts)
-        if len(starts) != len(clips):
-            raise ValueError("starts must name one start per clip (%d for %d clips)" % (len(starts), len(clips)))
-        for v in starts:
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
-                raise ValueError("starts must be ints >= 0, not %r" % (v,))
-    rates, chans = _clip_probe(clips, mix, channel_map, sample_rate)
-    if len(set(chans)) > 1:
-        raise ValueError("decode_clip_features: the clips' output channel counts differ (%s)" % sorted(set(chans)))
+    starts = _starts(starts, len(clips))
+    # the rows' form: f32 on the device, the planes of the planar kernels or the one plane of the mix
+    form = _Form(np.dtype(np.float32), mix is None, mix, channel_map, batch_frames, bool(gpu_parse), True,
+                 int(device) if ctx is None else ctx.device, clipped=np.zeros(len(clips), dtype=bool) if return_clipped else None)
+    recs = _load_clips(clips, "decode_clip_features", sample_rate, True, form)  # (every clip is read once per call)
+    _output_channels(recs, form, "decode_clip_features")
     rate = sample_rate
     if rate is None:
-        if len(set(rates)) != 1:
-            raise ValueError("decode_clip_features: without sample_rate all clips must share one rate (found %s)" % sorted(set(rates)))
+        rates = sorted(set(r.rate for r in recs))
+        if len(rates) != 1:
+            raise ValueError("decode_clip_features: without sample_rate all clips must share one rate (found %s)" % rates)
         rate = rates[0]
     desc = mel_desc(rate, n_fft, win_length, hop, n_mels, f_min, f_max, mel_scale, norm, scale, floor)
     N_, W, H, B = desc.n_fft, desc.win_length, desc.hop, desc.n_mels
@@ -857,13 +844,8 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
         raise ValueError("normalize takes at most 2**24 frames per row (%d)" % F)
     begins = np.arange(F, dtype=np.int64) * H + first
     import torch
-    own_ctx = ctx is None
-    if own_ctx:
-        ctx = Context(device)
-    try:
-        out = decode_clip_rows(clips, length, starts, ctx=ctx, batch_frames=batch_frames, gpu_parse=gpu_parse, sample_format="f32",
-                               layout="interleaved" if mix is not None else "planar", mix=mix, channel_map=channel_map,
-                               device_out=True, return_clipped=return_clipped, sample_rate=sample_rate)
+    with _context(ctx, device) as ctx:
+        out = _clip_rows(ctx, recs, starts, length, sample_rate, form)
         (rows, valid), clipped = out if return_clipped else (out, None)
         mono = mix is not None
         n = rows.shape[0]
@@ -891,9 +873,6 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
                 ndesc.src_band_stride = ndesc.dst_band_stride = desc.dst_band_stride
                 ctx.fnorm_rows(ndesc, feats.data_ptr(), feats.data_ptr(), valid_frames if mask_padding else None)
             ctx.synchronize()
-    finally:
-        if own_ctx:
-            ctx.close()
     if mono:
         feats = feats[:, 0]
     if not device_out:

@@ -293,6 +293,16 @@ class Comm:
             self._h = C.c_void_p()
 
 
+def _row_array(call, what, a, rows, dtype=np.int64):
+    """`a` (None stays None) as a contiguous `dtype` array with one entry per row; ValueError of `call` for any other shape."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.shape != (int(rows),):
+        raise ValueError("%s: %s one entry per row (%d)" % (call, what, int(rows)))
+    return a
+
+
 class Context:
     """nvh_ctx: one GPU + one HIP stream."""
 
@@ -336,11 +346,8 @@ class Context:
     def resample_rows(self, desc, d_src, d_dst, origin, start, valid, dst_row=None, d_clipped=None):
         """nvh_resample_rows: `desc` a native.ResampleDesc, d_src / d_dst / d_clipped device addresses, the per-row arrays host
         sequences of desc.rows ints.  Asynchronous on the context's stream (synchronize() waits for it)."""
-        n = int(desc.rows)
-        o, s, v = (np.ascontiguousarray(a, dtype=np.int64) for a in (origin, start, valid))
-        r = None if dst_row is None else np.ascontiguousarray(dst_row, dtype=np.int32)
-        if any(a.shape != (n,) for a in (o, s, v)) or (r is not None and r.shape != (n,)):
-            raise ValueError("resample_rows: the per-row arrays hold one entry per row (%d)" % n)
+        o, s, v = (_row_array("resample_rows", "the per-row arrays hold", a, desc.rows) for a in (origin, start, valid))
+        r = _row_array("resample_rows", "the per-row arrays hold", dst_row, desc.rows, np.int32)
         check(lib().nvh_resample_rows(self._h, C.byref(desc), C.c_void_p(d_src), C.c_void_p(d_dst), o.ctypes.data, s.ctypes.data,
                                       v.ctypes.data, None if r is None else r.ctypes.data,
                                       None if d_clipped is None else C.c_void_p(d_clipped)), "nvh_resample_rows")
@@ -348,11 +355,7 @@ class Context:
     def mel_rows(self, desc, d_src, d_dst, valid=None):
         """nvh_mel_rows: `desc` a native.MelDesc, d_src / d_dst device addresses, `valid` None or a host sequence of desc.rows
         ints.  Asynchronous on the context's stream (synchronize() waits for it)."""
-        v = None
-        if valid is not None:
-            v = np.ascontiguousarray(valid, dtype=np.int64)
-            if v.shape != (int(desc.rows),):
-                raise ValueError("mel_rows: valid holds one entry per row (%d)" % int(desc.rows))
+        v = _row_array("mel_rows", "valid holds", valid, desc.rows)
         check(lib().nvh_mel_rows(self._h, C.byref(desc), C.c_void_p(d_src), C.c_void_p(d_dst), None if v is None else v.ctypes.data),
               "nvh_mel_rows")
 
@@ -360,11 +363,7 @@ class Context:
         """nvh_fnorm_rows: `desc` a native.FnormDesc, d_src / d_dst device addresses (the same address with the same strides: in
         place), `valid_frames` None or a host sequence of desc.rows ints.  Asynchronous on the context's stream (synchronize()
         waits for it)."""
-        v = None
-        if valid_frames is not None:
-            v = np.ascontiguousarray(valid_frames, dtype=np.int64)
-            if v.shape != (int(desc.rows),):
-                raise ValueError("fnorm_rows: valid_frames holds one entry per row (%d)" % int(desc.rows))
+        v = _row_array("fnorm_rows", "valid_frames holds", valid_frames, desc.rows)
         check(lib().nvh_fnorm_rows(self._h, C.byref(desc), C.c_void_p(d_src), C.c_void_p(d_dst), None if v is None else v.ctypes.data),
               "nvh_fnorm_rows")
 
@@ -869,6 +868,15 @@ class Stream:
             pass
 
 
+def _enable_gpu_parse(stream):
+    """Have k_parse parse the stream's packets; a stream shape outside its limits silently keeps the host parser."""
+    try:
+        stream.set_gpu_parse(True)
+    except native.NvhError as e:
+        if e.code != native.ERR_UNSUPPORTED:
+            raise
+
+
 class StreamDecoder:
     """IStreamDecoder-shaped object (Contracts/IStreamDecoder.cs:9-105) over a packet list."""
 
@@ -899,12 +907,8 @@ class StreamDecoder:
                 raise native.NvhError(native.ERR_NOT_VORBIS, "StreamDecoder")
             self._channel_map = _channel_map(channel_map, ident)
         self._stream = Stream(ctx, packets[0], packets[1], packets[2])
-        if gpu_parse:  # packets parsed by k_parse; stream shapes outside its limits silently keep the host parser
-            try:
-                self._stream.set_gpu_parse(True)
-            except native.NvhError as e:
-                if e.code != native.ERR_UNSUPPORTED:
-                    raise
+        if gpu_parse:
+            _enable_gpu_parse(self._stream)
         self._ctx = ctx
         self._gpu_parse = bool(gpu_parse)
         self._index = None

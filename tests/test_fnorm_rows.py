@@ -106,12 +106,17 @@ def test_kernel_alone(gpu_ctx, shape):
     and destination band-major and frame-major in all four pairings, out of place and (same layout) in place; row and channel
     strides with gaps that keep their sentinel, behind the end as well; and valid_frames = NULL.  (130, 256) and (250, 80) take the
     re-reading path, every other shape the LDS-resident one; (249, 80) and (250, 80) lie on the two sides of that boundary."""
-    torch = _torch()
     F, B = shape
     assert takes_lds_path(F, B) == (shape not in ((130, 256), (250, 80)))
     if shape not in _KERNEL_CASES:
         _KERNEL_CASES[shape] = kernel_case(F, B)
-    X, vf, R, R_all = _KERNEL_CASES[shape]
+    check_kernel_case(gpu_ctx, _KERNEL_CASES[shape])
+
+
+def check_kernel_case(gpu_ctx, case, null_rows=(3, 5)):
+    """The launches and assertions of test_kernel_alone over one kernel_case(F, B); R_all holds rows null_rows[0]:null_rows[1]."""
+    torch = _torch()
+    X, vf, R, R_all = case
     d_src = {}
     for bm in (True, False):
         buf, rs, cs = pack(X, bm, GAP)
@@ -141,7 +146,7 @@ def test_kernel_alone(gpu_ctx, shape):
     for bm in (True, False):
         assert same_bits(d_src[bm][0].cpu().numpy(), pack(X, bm, GAP)[0])
     # valid_frames = NULL: every frame of rows 3 and 4 counts, nothing is filled
-    sub = np.ascontiguousarray(X[3:5])
+    sub = np.ascontiguousarray(X[null_rows[0]:null_rows[1]])
     for (mode, axis), want in R_all.items():
         for src_bm, dst_bm in ((True, False), (False, False), (True, True)):
             buf, rs, cs = pack(sub, src_bm, GAP)

@@ -77,13 +77,17 @@ def test_kernel_alone(gpu_ctx, cfg, frames):
     """nvh_mel_rows on synthetic rows -- noise, a 1 kHz tone, zeros, valid = 0, a row that ends inside frame 2, a unit impulse --
     with interleaved, planar and mono source strides, band-major and frame-major destinations whose row and channel strides leave
     gaps, and the three scales: every value equals the numpy rule, the gaps and the tail keep their sentinel."""
-    torch = _torch()
-    from nvorbis_amd import native
-    rate, N, W, H, B = cfg
     key = (cfg, frames)
     if key not in _KERNEL_CASES:
         _KERNEL_CASES[key] = kernel_case(cfg, frames)
-    first, S, valid, X, R = _KERNEL_CASES[key]
+    check_kernel_case(gpu_ctx, cfg, frames, _KERNEL_CASES[key])
+
+
+def check_kernel_case(gpu_ctx, cfg, frames, case):
+    """The launches and assertions of test_kernel_alone over one kernel_case(cfg, frames)."""
+    torch = _torch()
+    rate, N, W, H, B = cfg
+    first, S, valid, X, R = case
     rows = X.shape[0]
     for layout in ("interleaved", "planar", "mono"):
         C_ = 1 if layout == "mono" else 2

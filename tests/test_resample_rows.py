@@ -94,13 +94,19 @@ def test_kernel_alone(gpu_ctx, fi, fo, T):
     row equals the numpy rule, the flag words equal the reference's, rows and tiles behind `valid` are zeros, the destination row
     nobody names and the tail behind the buffer keep their sentinel.  Row 4 starts at 2**33 (a 32-bit J * M goes wrong there),
     row 1 reads in front of its source row and the longest row behind it, row 5 is a unit impulse."""
-    torch = _torch()
     from nvorbis_amd import native
     T = 3 * native.RESAMPLE_TILE + 17 if isinstance(T, str) else T
     key = (fi, fo, T)
     if key not in _KERNEL_CASES:
         _KERNEL_CASES[key] = kernel_case(fi, fo, T)
-    rows, X, R, hit = _KERNEL_CASES[key]
+    check_kernel_case(gpu_ctx, fi, fo, T, _KERNEL_CASES[key])
+
+
+def check_kernel_case(gpu_ctx, fi, fo, T, case):
+    """The launches and assertions of test_kernel_alone over one kernel_case(fi, fo, T)."""
+    torch = _torch()
+    from nvorbis_amd import native
+    rows, X, R, hit = case
     N, S = len(rows), X.shape[2]
     assert hit.any(axis=1).any() and not hit.any(axis=1).all()
     dst_row = np.asarray([3, 0, 6, 1, 5, 2], np.int32)  # destination row 4 is nobody's

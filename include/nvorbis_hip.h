@@ -735,6 +735,76 @@ int nvh_mel_tables(const nvh_mel_desc *desc, float *twiddle, float *window, floa
                    int64_t bank_cap, int64_t *twiddle_count, int64_t *window_count, int64_t *bank_count);
 int nvh_mel_rows(nvh_ctx *ctx, const nvh_mel_desc *desc, const float *d_src, float *d_dst, const int64_t *valid);
 
+/* ---- the front of a frame: DC removal, pre-emphasis, other windows, reflect padding, triangles linear in mel ----
+ * The front of a frame is everything between the row's samples and u[0 .. N) of nvh_mel_rows' rule; a second descriptor,
+ * nvh_mel_front, chooses it.  Every field at today's value (NVH_WIN_HANN, NVH_TRI_HZ, NVH_PAD_ZERO, remove_dc 0, preemphasis 0,
+ * gain 1), or no nvh_mel_front at all, is nvh_mel_rows' rule and nvh_mel_rows' kernel.  As there: every operation is a separately
+ * rounded f32 instruction (fl(.)), every table is computed in double and rounded once (fl32(.)).  THE RULE OF THE FRONT (about 40
+ * more lines of numpy):
+ *   Parameters.  window one of NVH_WIN_*; triangles NVH_TRI_HZ or NVH_TRI_MEL; pad_mode NVH_PAD_ZERO or NVH_PAD_REFLECT; remove_dc
+ *     0 or 1; preemphasis p a finite f32 in [0, 1] (0: none); gain g a finite f32 > 0 (1: none); reserved 0.  NVH_ERR_ARGUMENT
+ *     for anything else.
+ *   Tables.  win[n], n < W.  NVH_WIN_HANN: nvh_mel_rows' periodic Hann, 0.5 - 0.5 cos(2 pi n / W).  The others are symmetric, with
+ *     the denominator D = W - 1 (W = 1: D = 1): NVH_WIN_HANN_SYM 0.5 - 0.5 cos(2 pi n / D); NVH_WIN_HAMMING 0.54 - 0.46 cos(2 pi n
+ *     / D); NVH_WIN_POVEY (0.5 - 0.5 cos(2 pi n / D))^0.85, the power taken in double on the host; NVH_WIN_RECT 1.
+ *     fb[b][k] under NVH_TRI_MEL: B + 2 points pm[i] = m_lo + (m_hi - m_lo) * i / (B + 1), equally spaced on the mel scale
+ *     between m_lo = mel(f_min) and m_hi = mel(f_max) and NOT mapped back to Hz; with l = pm[b], c = pm[b+1], r = pm[b+2] and m =
+ *     mel(k * R / N): fb = max(0, min((m - l) / (c - l), (r - m) / (r - c))), times 2 / (hz(r) - hz(l)) for NVH_MEL_NORM_SLANEY
+ *     (the normalisation keeps its Hz definition).  mel and hz are those of mel_scale.  The non-zero bins of a band are
+ *     consecutive here too.  NVH_TRI_HZ: nvh_mel_rows' bank.  The twiddles do not depend on the front.
+ *   Frame f of a (row, channel).  For n < W, t = f * H + first + n is mapped first:
+ *     NVH_PAD_REFLECT, with L = src_length: t < 0 -> -t; t >= L -> 2 (L - 1) - t.  One reflection must be enough for every frame
+ *       of the call: L >= 2, -first <= L - 1 and (F - 1) H + first + W - 1 <= 2 (L - 1), else NVH_ERR_ARGUMENT (a call with F = 0
+ *       has no frame and passes).  NVH_PAD_ZERO: t stays.
+ *     x[n] = the row's f32 sample at the mapped t, and 0 where the mapped t lies outside [0, valid) of the row: the zeroing comes
+ *       after the reflection, so a reflected read can land in the zeros behind `valid`.
+ *     s[n] = fl(x[n] * g); with g == 1, s[n] = x[n] (which is the same bits).
+ *     remove_dc: mean = fl(sum64(s[0 .. W)) / fl32(W)), then s[n] = fl(s[n] - mean) for every n < W.  sum64 is the summation of
+ *       nvh_fnorm_rows' rule below: 64 partials, element e into partial e mod 64 in rising e, then the six halvings.
+ *     y[n] = s[n] with p == 0.  With p > 0: y[n] = fl(s[n] - fl(p * s[n-1])) for 1 <= n < W, and y[0] = fl(s[0] - fl(p * s[0]))
+ *       -- Kaldi's pre-emphasis.  It reads the values s (after the DC removal), never y: it is not recursive.
+ *     u = N zeros, then u[(N - W) div 2 + n] = fl(y[n] * win[n]) for n < W.  (The window stays centred in N; Kaldi puts it at the
+ *     start of the buffer, which changes the phase of the transform and not its power.)
+ *   Transform, Split, Mel and Scale are nvh_mel_rows' text, unchanged.
+ *   Kaldi's fbank (dither 0, no energy column) is: g = 32768, remove_dc, p = 0.97, NVH_WIN_POVEY, NVH_TRI_MEL with NVH_MEL_HTK
+ *   (Kaldi's 1127 ln(1 + f / 700) is the HTK scale, and the bank holds only ratios of mel differences), NVH_MEL_LN with floor =
+ *   2^-23, first = 0 and F = (L - W) div H + 1.  torch.stft's default padding and Whisper's front end are NVH_PAD_REFLECT with
+ *   first = (N - W) div 2 - N div 2.
+ *
+ * nvh_mel_front_check: NVH_OK or NVH_ERR_ARGUMENT for the pair (desc's rule parameters as nvh_mel_plan checks them, the front's
+ *   fields, and under NVH_PAD_REFLECT with F > 0 the three conditions above from desc's src_length, first, frames, hop and
+ *   win_length).  front == NULL checks desc alone.  Host only.
+ * nvh_mel_tables_front: nvh_mel_tables with the front's window and triangles (front == NULL: nvh_mel_tables).  Host only.
+ * nvh_mel_rows_front: nvh_mel_rows with the front.  front == NULL or a front with every field at today's value IS nvh_mel_rows:
+ *   the same kernel instance, LDS, grid and bits.  Errors as nvh_mel_rows, nvh_mel_front_check's among the argument errors, all
+ *   before NVH_ERR_NO_GPU.  The kernel: a front variant of k_mel_rows; the span staging applies the reflection, the zeroing and
+ *   the gain, the frame's wavefront sums its mean (partial l in lane l, the halvings across lanes) and the window step recomputes
+ *   s[n-1] from the span.  No LDS is added, so a parameter set is staged with a front exactly when it is without. */
+#define NVH_WIN_HANN 0
+#define NVH_WIN_HANN_SYM 1
+#define NVH_WIN_HAMMING 2
+#define NVH_WIN_POVEY 3
+#define NVH_WIN_RECT 4
+#define NVH_TRI_HZ 0
+#define NVH_TRI_MEL 1
+#define NVH_PAD_ZERO 0
+#define NVH_PAD_REFLECT 1
+typedef struct nvh_mel_front {
+  int32_t window;      /* NVH_WIN_* */
+  int32_t triangles;   /* NVH_TRI_* */
+  int32_t pad_mode;    /* NVH_PAD_* */
+  int32_t remove_dc;   /* 0 | 1 */
+  float preemphasis;   /* p, a finite f32 in [0, 1]; 0: none */
+  float gain;          /* g, a finite f32 > 0; 1: none */
+  int32_t reserved[2]; /* 0 */
+} nvh_mel_front;
+int nvh_mel_front_check(const nvh_mel_desc *desc, const nvh_mel_front *front);
+int nvh_mel_tables_front(const nvh_mel_desc *desc, const nvh_mel_front *front, float *twiddle, float *window, float *bank,
+                         int64_t twiddle_cap, int64_t window_cap, int64_t bank_cap, int64_t *twiddle_count, int64_t *window_count,
+                         int64_t *bank_count);
+int nvh_mel_rows_front(nvh_ctx *ctx, const nvh_mel_desc *desc, const nvh_mel_front *front, const float *d_src, float *d_dst,
+                       const int64_t *valid);
+
 /* ---- per-row normalisation of features: mean, variance or peak of each (row, channel), and the fill of its padded frames ----
  * Features in, features out: every value is a pure function of one (row, channel) of the input and of that row's frame count;
  * nothing is carried from call to call, and nvh_mel_rows takes no part.  (fnorm: NVH_MEL_NORM_* is the bank's normalisation.)

@@ -707,16 +707,79 @@ def mel_desc(rate, n_fft=512, win_length=400, hop=160, n_mels=80, f_min=0.0, f_m
     return d
 
 
-def mel_tables(rate, n_fft=512, win_length=400, n_mels=80, f_min=0.0, f_max=None, mel_scale="htk", norm=None):
-    """The tables of nvh_mel_tables as float32 arrays, exactly the values k_mel_rows uses: (twiddles (n_fft / 2 + 1, 2) as (cos,
-    sin), window (win_length,), bank (n_mels, n_fft / 2 + 1))."""
+_MEL_WINDOWS = {"hann": native.WIN_HANN, "hann_symmetric": native.WIN_HANN_SYM, "hamming": native.WIN_HAMMING, "povey": native.WIN_POVEY,
+                "rectangular": native.WIN_RECT}
+_MEL_TRIANGLES = {"hz": native.TRI_HZ, "mel": native.TRI_MEL}
+_MEL_PADS = {"constant": native.PAD_ZERO, "reflect": native.PAD_REFLECT}
+
+
+def mel_front(window="hann", mel_triangles="hz", pad_mode="constant", remove_dc=False, preemphasis=0.0, sample_gain=1.0):
+    """A native.MelFront (include/nvorbis_hip.h: nvh_mel_front), checked on the host with ValueError -- or None where every
+    argument has today's value: the caller then goes through nvh_mel_rows itself."""
+    if not isinstance(window, str) or window not in _MEL_WINDOWS:
+        raise ValueError("window must be one of %s, not %r" % (", ".join(repr(k) for k in _MEL_WINDOWS), window))
+    if not isinstance(mel_triangles, str) or mel_triangles not in _MEL_TRIANGLES:
+        raise ValueError("mel_triangles must be 'hz' or 'mel', not %r" % (mel_triangles,))
+    if not isinstance(pad_mode, str) or pad_mode not in _MEL_PADS:
+        raise ValueError("pad_mode must be 'constant' or 'reflect', not %r" % (pad_mode,))
+    if not isinstance(remove_dc, (bool, np.bool_)):
+        raise ValueError("remove_dc must be True or False, not %r" % (remove_dc,))
+    with np.errstate(over="ignore"):
+        p32 = np.float32(_real("preemphasis", preemphasis, False))
+        g32 = np.float32(_real("sample_gain", sample_gain, False))
+    if not 0.0 <= p32 <= 1.0:
+        raise ValueError("preemphasis must be in [0, 1], not %r" % (preemphasis,))
+    if not np.isfinite(g32) or not g32 > 0:
+        raise ValueError("sample_gain must be a finite f32 > 0, not %r" % (sample_gain,))
+    f = native.MelFront(_MEL_WINDOWS[window], _MEL_TRIANGLES[mel_triangles], _MEL_PADS[pad_mode], int(bool(remove_dc)), float(p32), float(g32))
+    if (f.window, f.triangles, f.pad_mode, f.remove_dc) == (native.WIN_HANN, native.TRI_HZ, native.PAD_ZERO, 0) and p32 == 0 and g32 == 1:
+        return None
+    return f
+
+
+def mel_tables(rate, n_fft=512, win_length=400, n_mels=80, f_min=0.0, f_max=None, mel_scale="htk", norm=None, window="hann",
+               mel_triangles="hz"):
+    """The tables of nvh_mel_tables (nvh_mel_tables_front with a window or triangles of one's own) as float32 arrays, exactly the
+    values k_mel_rows uses: (twiddles (n_fft / 2 + 1, 2) as (cos, sin), window (win_length,), bank (n_mels, n_fft / 2 + 1))."""
     d = mel_desc(rate, n_fft, win_length, 1, n_mels, f_min, f_max, mel_scale, norm)
+    front = mel_front(window, mel_triangles)
     bins = n_fft // 2 + 1
     tw, win, fb = np.zeros(2 * bins, np.float32), np.zeros(win_length, np.float32), np.zeros(n_mels * bins, np.float32)
     counts = [C.c_int64(0) for _ in range(3)]
-    native.check(native.lib().nvh_mel_tables(C.byref(d), tw.ctypes.data, win.ctypes.data, fb.ctypes.data, tw.size, win.size, fb.size,
-                                             *[C.byref(c) for c in counts]), "nvh_mel_tables")
+    if front is None:
+        native.check(native.lib().nvh_mel_tables(C.byref(d), tw.ctypes.data, win.ctypes.data, fb.ctypes.data, tw.size, win.size, fb.size,
+                                                 *[C.byref(c) for c in counts]), "nvh_mel_tables")
+    else:
+        native.check(native.lib().nvh_mel_tables_front(C.byref(d), C.byref(front), tw.ctypes.data, win.ctypes.data, fb.ctypes.data, tw.size,
+                                                       win.size, fb.size, *[C.byref(c) for c in counts]), "nvh_mel_tables_front")
     return tw.reshape(bins, 2), win, fb.reshape(n_mels, bins)
+
+
+def kaldi_fbank_keywords(rate, frame_length_ms=25.0, frame_shift_ms=10.0, num_mel_bins=80, low_freq=20.0, high_freq=0.0, preemphasis=0.97,
+                         remove_dc=True, window="povey"):
+    """The keywords that make decode_clip_features compute Kaldi's fbank (compute-fbank-feats, torchaudio.compliance.kaldi.fbank)
+    at `rate` Hz, under Kaldi's own option names: decode_clip_features(clips, length, sample_rate=rate,
+    **kaldi_fbank_keywords(rate)).  win_length and hop are the milliseconds in samples (truncated, as Kaldi does), n_fft the next
+    power of two (at least 64: round_to_power_of_two), f_min = low_freq, f_max = high_freq, or rate / 2 + high_freq for high_freq
+    <= 0; mel_scale="htk" with mel_triangles="mel" (Kaldi's bank), scale="ln" with floor = the f32 epsilon, center=False with
+    frame_count="window" (snip_edges) and sample_gain=32768 (Kaldi reads 16-bit sample values).  What differs from Kaldi: the
+    window is centred in n_fft, not at its start (the power spectrum is the same), and the arithmetic is the rule's f32
+    (tests/test_mel_front_plan.py measures the distance).  Dither (dither=0 in Kaldi's terms) and the energy column (use_energy)
+    are out of scope; so is snip_edges=false.  The dict does not hold sample_rate: pass it beside the dict where the clips are
+    at other rates."""
+    rate = _int_in("rate", rate, 1, 2 ** 31 - 1)
+    for name, v in (("frame_length_ms", frame_length_ms), ("frame_shift_ms", frame_shift_ms), ("low_freq", low_freq), ("high_freq", high_freq)):
+        _real(name, v, True)
+    win_length, hop = int(rate * 0.001 * frame_length_ms), int(rate * 0.001 * frame_shift_ms)
+    if win_length < 1 or win_length > 4096 or hop < 1:
+        raise ValueError("frame_length_ms and frame_shift_ms must give a window in [1, 4096] samples and a hop >= 1 (%d, %d)" % (win_length, hop))
+    n_fft = 64
+    while n_fft < win_length:
+        n_fft *= 2
+    return dict(n_fft=n_fft, win_length=win_length, hop=hop, n_mels=num_mel_bins, f_min=float(low_freq),
+                f_max=float(high_freq) if high_freq > 0 else rate / 2.0 + float(high_freq), mel_scale="htk", mel_triangles="mel",
+                scale="ln", floor=float(np.finfo(np.float32).eps), center=False, frame_count="window", sample_gain=32768.0,
+                preemphasis=preemphasis, remove_dc=remove_dc, window=window)
 
 
 _FNORM_MODES = {None: native.FNORM_NONE, "mean": native.FNORM_MEAN, "mean_var": native.FNORM_MEAN_VAR, "peak": native.FNORM_PEAK}
@@ -772,7 +835,8 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
                          f_max=None, mel_scale="htk", norm=None, scale="ln", floor=1e-10, center=True, band_major=True, mix=None,
                          channel_map=None, ctx=None, device=0, batch_frames=4096, gpu_parse=True, device_out=True,
                          return_clipped=False, normalize=None, normalize_axis="band", norm_eps=1e-5, pad_value=_PAD_DEFAULT,
-                         peak_range=80.0, peak_offset=40.0, peak_gain=1 / 40, mask_padding=True):
+                         peak_range=80.0, peak_offset=40.0, peak_gain=1 / 40, mask_padding=True, window="hann", remove_dc=False,
+                         preemphasis=0.0, sample_gain=1.0, pad_mode="constant", mel_triangles="hz", frame_count="n_fft"):
     """Log-mel features of fixed-length rows: decode_clip_rows(clips, length, starts, sample_format="f32", layout="planar",
     device_out=True, sample_rate=sample_rate, ...) as it is, then nvh_mel_rows over the buffer the planar kernels wrote (the one
     plane of mix="mono").  Returns (features, valid, valid_frames); with return_clipped=True ((features, valid, valid_frames),
@@ -785,12 +849,27 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
     of max(value, floor).  Samples outside [0, valid[i]) of a row count as zeros.
 
     center=True is torch.stft's center=True with pad_mode="constant": frame f is centred on sample f * hop, F = length // hop + 1.
-    center=False: frame f begins at sample f * hop, F = (length - n_fft) // hop + 1; ValueError for length < n_fft.  Reflect
-    padding is out of scope.  n_fft must be a power of two in [64, 4096]: other transform lengths are out of scope (Whisper's
-    own 400-point bins, for example, are not what n_fft=512, win_length=400 gives).
+    center=False: frame f begins at sample f * hop, F = (length - n_fft) // hop + 1; ValueError for length < n_fft.  n_fft must
+    be a power of two in [64, 4096]: other transform lengths are out of scope (Whisper's own 400-point bins, for example, are
+    not what n_fft=512, win_length=400 gives).
+
+    The front of a frame (include/nvorbis_hip.h: nvh_mel_front; with every keyword of this paragraph left away the call goes
+    through nvh_mel_rows exactly as before).  window: "hann" (periodic), "hann_symmetric", "hamming", "povey" or "rectangular".
+    sample_gain: every sample is multiplied by it first (32768: 16-bit sample values).  remove_dc: the mean of the frame's
+    win_length samples is subtracted.  preemphasis p in [0, 1]: y[n] = s[n] - p s[n-1], y[0] = s[0] - p s[0] (Kaldi's).
+    mel_triangles="mel": the bank's triangles are linear in mel, not in Hz (Kaldi's bank).  pad_mode="reflect" (torch.stft's
+    default, Whisper's front end) needs center=True: samples in front of the row and behind `length` are the row mirrored at
+    its first and last sample; ValueError unless one reflection is enough for every frame (length >= 2, n_fft // 2 -
+    (n_fft - win_length) // 2 <= length - 1, and the last frame's last sample at most 2 (length - 1)).  The mirror is at
+    `length`, not at valid[i]: samples at and behind valid[i] are zeros, and a mirrored read can land in them.
+    frame_count="window" (Kaldi's snip_edges) needs center=False: frame f begins at sample f * hop, F = (length - win_length)
+    // hop + 1; ValueError for length < win_length.  kaldi_fbank_keywords() returns the whole Kaldi set.
 
     valid: decode_clip_rows' valid.  valid_frames[i] (int64): how many of the row's frames have one of their win_length samples
-    inside [0, valid[i]).  Without sample_rate all clips must share one rate (ValueError otherwise); with it, clips at other
+    inside [0, valid[i]) -- under pad_mode="reflect" too, where the formula looks at the UNREFLECTED positions (a frame counts by
+    where its window lies, not by what the mirror shows it: with valid[i] == length - win_length / 2 and hop dividing length, the
+    frame behind the last counted one reads one counted sample through the mirror; the counted frames stay a prefix).  Without
+    sample_rate all clips must share one rate (ValueError otherwise); with it, clips at other
     rates are resampled as decode_clip_rows does.  Every keyword is checked, with ValueError, before any device is touched.
 
     normalize: the last stage, nvh_fnorm_rows in place on the features (include/nvorbis_hip.h states its rule).  "mean": the mean
@@ -829,6 +908,13 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
         rate = rates[0]
     desc = mel_desc(rate, n_fft, win_length, hop, n_mels, f_min, f_max, mel_scale, norm, scale, floor)
     N_, W, H, B = desc.n_fft, desc.win_length, desc.hop, desc.n_mels
+    front = mel_front(window, mel_triangles, pad_mode, remove_dc, preemphasis, sample_gain)
+    if not isinstance(frame_count, str) or frame_count not in ("n_fft", "window"):
+        raise ValueError("frame_count must be 'n_fft' or 'window', not %r" % (frame_count,))
+    if frame_count == "window" and center:
+        raise ValueError("frame_count='window' needs center=False")
+    if pad_mode == "reflect" and not center:
+        raise ValueError("pad_mode='reflect' needs center=True")
     if not isinstance(mask_padding, (bool, np.bool_)):
         raise ValueError("mask_padding must be True or False, not %r" % (mask_padding,))
     pad_given = pad_value is not _PAD_DEFAULT
@@ -836,6 +922,13 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
     run_fnorm = normalize is not None or (bool(mask_padding) and pad_given)
     if center:
         first, F = (N_ - W) // 2 - N_ // 2, length // H + 1
+        if pad_mode == "reflect" and (length < 2 or -first > length - 1 or (F - 1) * H + first + W - 1 > 2 * (length - 1)):
+            raise ValueError("pad_mode='reflect' needs one reflection to be enough for every frame: length >= 2, %d <= length - 1 and "
+                             "%d <= 2 * (length - 1) (length %d)" % (-first, (F - 1) * H + first + W - 1, length))
+    elif frame_count == "window":
+        if length < W:
+            raise ValueError("frame_count='window' needs length >= win_length (%d < %d)" % (length, W))
+        first, F = 0, (length - W) // H + 1
     else:
         if length < N_:
             raise ValueError("center=False needs length >= n_fft (%d < %d)" % (length, N_))
@@ -862,7 +955,7 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
             desc.dst_row_stride, desc.dst_chan_stride = feats.stride(0), feats.stride(1)
             desc.dst_band_stride, desc.dst_frame_stride = (feats.stride(2), feats.stride(3)) if band_major else (feats.stride(3), feats.stride(2))
             torch.cuda.current_stream(rows.device).synchronize()  # (a gather of several setups' rows runs on torch's stream)
-            ctx.mel_rows(desc, rows.data_ptr(), feats.data_ptr(), valid)
+            ctx.mel_rows(desc, rows.data_ptr(), feats.data_ptr(), valid, front)
         valid_frames = (np.maximum(begins, 0)[None, :] < np.minimum(begins[None, :] + W, valid[:, None])).sum(axis=1).astype(np.int64)
         if n and och:
             if run_fnorm:  # behind k_mel_rows on the context's stream, in place

@@ -16,6 +16,9 @@
 // apart), the sparse bank (first bin, bin count, weights' offset per band -- never the dense table), the window and the source span
 // the four frames share (3 H + W samples, zeros outside [0, valid)) lie in LDS, staged once per workgroup resp. per work item;
 // otherwise (N = 4096, or a hop far beyond the window: the slices leave no room) they are read through L2.
+// FRONT (the front of nvh_mel_front, stated under it in the header): the span staging also mirrors a sample time outside the row
+// and applies the gain, the frame's wavefront sums its mean as the rule's sum64 (partial l in lane l, the halvings across lanes),
+// and the window step reads s[n] and s[n-1], subtracts the mean from both and pre-emphasises.  No LDS of its own.
 // Every operation of the rule is one f32 instruction: the build has -ffp-contract=off, and nothing here calls fmaf or a library
 // logarithm.
 #include <hip/hip_runtime.h>
@@ -101,9 +104,36 @@ __device__ __forceinline__ float mel_ln(float v) {
   return hi + lo;
 }
 
+// s of the front's rule at sample time t of the row: the reflection (one is enough for every frame of the call: the launcher has
+// checked it; a dead frame of the last group may map outside the row and reads 0), the zeroing at and behind `valid`, the gain
+__device__ __forceinline__ float front_sample(const NvhMelArgs& A, const float* __restrict__ src, long long valid, long long t) {
+  if (A.reflect) {
+    if (t < 0) t = -t;
+    else if (t >= A.src_length) t = 2 * (A.src_length - 1) - t;
+  }
+  float x = (t >= 0 && t < valid) ? src[t * A.src_time_stride] : 0.0f;
+  if (A.gain != 1.0f) x = x * A.gain;
+  return x;
+}
+
+// the frame's mean by the rule's sum64: partial l in lane l over the elements l, l + 64, .. in rising order, the six halvings
+// (lane l < d takes p[l + d]), the division in lane 0's value; every lane returns it
+template <bool STAGED>
+__device__ __forceinline__ float front_mean(const NvhMelArgs& A, const float* __restrict__ span, const float* __restrict__ src,
+                                            long long valid, long long t_frame, int W, int lane) {
+  float p = 0.0f;
+#pragma unroll 1
+  for (int e = lane; e < W; e += 64) p = p + (STAGED ? span[e] : front_sample(A, src, valid, t_frame + e));
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) p = p + __shfl_down(p, d, 64);
+  return __shfl(p / (float)W, 0, 64);
+}
+
 }  // namespace
 
-template <bool STAGED>
+// FRONT: the front of nvh_mel_front (reflection, gain, DC removal, pre-emphasis) between the row and the window; the instances
+// without it are nvh_mel_rows' own and read none of the front's arguments.
+template <bool STAGED, bool FRONT>
 __global__ void __launch_bounds__(NVH_MEL_THREADS) k_mel_rows(NvhMelArgs A) {
   extern __shared__ float mel_lds[];
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -140,7 +170,8 @@ __global__ void __launch_bounds__(NVH_MEL_THREADS) k_mel_rows(NvhMelArgs A) {
     if (STAGED) {
       for (int e = tid; e < A.span; e += NVH_MEL_THREADS) {
         const long long t = t_group + e;
-        l_span[e] = (t >= 0 && t < valid) ? src[t * A.src_time_stride] : 0.0f;
+        if (FRONT) l_span[e] = front_sample(A, src, valid, t);
+        else l_span[e] = (t >= 0 && t < valid) ? src[t * A.src_time_stride] : 0.0f;
       }
     }
     __syncthreads();  // the span (and, the first time, the tables) are staged; the item before is done with the output tile
@@ -148,6 +179,8 @@ __global__ void __launch_bounds__(NVH_MEL_THREADS) k_mel_rows(NvhMelArgs A) {
     if (live) {
       // ---- window: z[n] = (u[2n], u[2n+1]) at the bit-reversed index ----
       const long long t_frame = t_group + (long long)wave * A.hop;
+      float mean = 0.0f;
+      if (FRONT && A.remove_dc) mean = front_mean<STAGED>(A, l_span + wave * A.hop, src, valid, t_frame, W, lane);
 #pragma unroll 1
       for (int n = lane; n < points; n += 64) {
         float u[2];
@@ -157,7 +190,27 @@ __global__ void __launch_bounds__(NVH_MEL_THREADS) k_mel_rows(NvhMelArgs A) {
           float v = 0.0f;
           if (i >= 0 && i < W) {
             float x, w;
-            if (STAGED) {
+            if (FRONT) {  // x: s[i]; xp: s[i-1], recomputed (s[0] under window sample 0)
+              const int ip = i > 0 ? i - 1 : 0;
+              float xp;
+              if (STAGED) {
+                x = l_span[wave * A.hop + i];
+                xp = l_span[wave * A.hop + ip];
+                w = l_win[i];
+              } else {
+                x = front_sample(A, src, valid, t_frame + i);
+                xp = front_sample(A, src, valid, t_frame + ip);
+                w = A.win[i];
+              }
+              if (A.remove_dc) {
+                x = x - mean;
+                xp = xp - mean;
+              }
+              if (A.preemphasis > 0.0f) {
+                const float q = A.preemphasis * xp;
+                x = x - q;
+              }
+            } else if (STAGED) {
               x = l_span[wave * A.hop + i];
               w = l_win[i];
             } else {
@@ -252,5 +305,7 @@ __global__ void __launch_bounds__(NVH_MEL_THREADS) k_mel_rows(NvhMelArgs A) {
   }
 }
 
-template __global__ void k_mel_rows<true>(NvhMelArgs);
-template __global__ void k_mel_rows<false>(NvhMelArgs);
+template __global__ void k_mel_rows<true, false>(NvhMelArgs);
+template __global__ void k_mel_rows<false, false>(NvhMelArgs);
+template __global__ void k_mel_rows<true, true>(NvhMelArgs);
+template __global__ void k_mel_rows<false, true>(NvhMelArgs);

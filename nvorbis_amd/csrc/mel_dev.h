@@ -1,5 +1,5 @@
 // mel_dev.h -- what k_mel_rows (kernels_mel.hip) and its launcher (nvh_mel.hip) share: the kernel's argument block and its LDS
-// geometry.  include/nvorbis_hip.h states the rule (nvh_mel_rows).
+// geometry.  include/nvorbis_hip.h states the rule (nvh_mel_rows; nvh_mel_front for the front of a frame).
 #pragma once
 #include <stdint.h>
 
@@ -40,4 +40,10 @@ struct NvhMelArgs {
   int weights;       // floats of fbw
   int span;          // floats of the four frames' source span in LDS (3 * hop + W), 0: every frame reads the row through L2
   int band_fast;     // the band stride is the smaller one: a frame's bands are stored side by side, else a band's four frames
+  // the front (nvh_mel_front), read by the FRONT instances of the kernel only; it takes no LDS of its own: the mean lives in
+  // registers, so the staged layout above and the launcher's route choice are the same with and without it
+  int reflect;       // NVH_PAD_REFLECT: a sample time outside [0, src_length) is mirrored once
+  int remove_dc;
+  float preemphasis; // p, 0: none
+  float gain;        // g, 1: none
 };

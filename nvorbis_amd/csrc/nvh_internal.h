@@ -127,10 +127,13 @@ extern template __global__ void k_resample_rows<float>(NvhResampleArgs);
 extern template __global__ void k_resample_rows<int16_t>(NvhResampleArgs);
 
 // ... and the log-mel features of rows (kernels_mel.hip), with the tables staged in LDS or read through L2
-template <bool STAGED>
+// (FRONT: with the front of nvh_mel_front between the row and the window)
+template <bool STAGED, bool FRONT>
 __global__ void k_mel_rows(NvhMelArgs A);
-extern template __global__ void k_mel_rows<true>(NvhMelArgs);
-extern template __global__ void k_mel_rows<false>(NvhMelArgs);
+extern template __global__ void k_mel_rows<true, false>(NvhMelArgs);
+extern template __global__ void k_mel_rows<false, false>(NvhMelArgs);
+extern template __global__ void k_mel_rows<true, true>(NvhMelArgs);
+extern template __global__ void k_mel_rows<false, true>(NvhMelArgs);
 
 // ... and the per-row normalisation of features (kernels_fnorm.hip), out of LDS or re-reading its source
 template <bool RESIDENT>
@@ -294,8 +297,8 @@ struct MelDev {  // the device tables of one parameter set (nvh_mel.hip): twiddl
   int* band = nullptr;
   int weights = 0;
 };
-// (rate, n_fft, win_length, n_mels, mel_scale, norm, f_min, f_max): what the tables depend on
-typedef std::tuple<int, int, int, int, int, int, double, double> MelKey;
+// (rate, n_fft, win_length, n_mels, mel_scale, norm, f_min, f_max, window, triangles): what the tables depend on
+typedef std::tuple<int, int, int, int, int, int, double, double, int, int> MelKey;
 
 // Everything derived from a stream's headers: parsed tables on the host, their device image, kernel-selection
 // flags.  Immutable once built, so streams with byte-identical identification + setup packets (the normal case

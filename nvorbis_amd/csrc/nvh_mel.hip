@@ -1,5 +1,6 @@
-// nvh_mel.hip -- log-mel features of rows (include/nvorbis_hip.h: nvh_mel_plan / _tables / _rows): the parameter check, the tables
-// in double on the host, the per-context cache of device tables, and the launch of k_mel_rows (kernels_mel.hip).
+// nvh_mel.hip -- log-mel features of rows (include/nvorbis_hip.h: nvh_mel_plan / _tables / _rows and their _front forms): the
+// parameter check, the tables in double on the host, the per-context cache of device tables, and the launch of k_mel_rows
+// (kernels_mel.hip).
 #include <cmath>
 
 #include "nvh_internal.h"
@@ -45,24 +46,60 @@ void mel_twiddles(const nvh_mel_desc& D, float* tw) {
   }
 }
 
-void mel_window(const nvh_mel_desc& D, float* win) {
-  for (int n = 0; n < D.win_length; ++n) win[n] = (float)(0.5 - 0.5 * std::cos(2.0 * kPi * (double)n / (double)D.win_length));
+// The front's fields (nvh_mel_front) and, under NVH_PAD_REFLECT, that one reflection is enough for every frame of D.
+int front_check(const nvh_mel_desc& D, const nvh_mel_front& Fr) {
+  if (Fr.window < NVH_WIN_HANN || Fr.window > NVH_WIN_RECT || (Fr.triangles != NVH_TRI_HZ && Fr.triangles != NVH_TRI_MEL)) return NVH_ERR_ARGUMENT;
+  if ((Fr.pad_mode != NVH_PAD_ZERO && Fr.pad_mode != NVH_PAD_REFLECT) || (Fr.remove_dc != 0 && Fr.remove_dc != 1)) return NVH_ERR_ARGUMENT;
+  if (!(Fr.preemphasis >= 0.0f) || !(Fr.preemphasis <= 1.0f)) return NVH_ERR_ARGUMENT;  // (NaN fails each)
+  if (!(Fr.gain > 0.0f) || !(Fr.gain <= 3.40282347e+38f)) return NVH_ERR_ARGUMENT;
+  if (Fr.reserved[0] != 0 || Fr.reserved[1] != 0) return NVH_ERR_ARGUMENT;
+  if (Fr.pad_mode == NVH_PAD_REFLECT && D.frames > 0) {  // (mel_check has bounded frames, hop and first: no overflow below)
+    const int64_t L = D.src_length;
+    if (L < 2 || -D.first > L - 1) return NVH_ERR_ARGUMENT;
+    const int64_t last = (D.frames - 1) * D.hop + D.first + D.win_length - 1;  // below 2^61
+    if (L - 1 < ((int64_t)1 << 61) && last > 2 * (L - 1)) return NVH_ERR_ARGUMENT;
+  }
+  return NVH_OK;
 }
 
-// the dense bank, [B][N/2 + 1]
-void mel_bank(const nvh_mel_desc& D, float* fb) {
+// every field at today's value: the front that is nvh_mel_rows itself
+bool front_is_default(const nvh_mel_front* Fr) {
+  return !Fr || (Fr->window == NVH_WIN_HANN && Fr->triangles == NVH_TRI_HZ && Fr->pad_mode == NVH_PAD_ZERO && Fr->remove_dc == 0 &&
+                 Fr->preemphasis == 0.0f && Fr->gain == 1.0f);
+}
+
+void mel_window(const nvh_mel_desc& D, int kind, float* win) {
+  const int W = D.win_length;
+  const double den = kind == NVH_WIN_HANN ? (double)W : (W > 1 ? (double)(W - 1) : 1.0);
+  for (int n = 0; n < W; ++n) {
+    const double c = std::cos(2.0 * kPi * (double)n / den);
+    double v = 0.5 - 0.5 * c;  // NVH_WIN_HANN (periodic), NVH_WIN_HANN_SYM
+    if (kind == NVH_WIN_HAMMING) v = 0.54 - 0.46 * c;
+    else if (kind == NVH_WIN_POVEY) v = std::pow(v, 0.85);
+    else if (kind == NVH_WIN_RECT) v = 1.0;
+    win[n] = (float)v;
+  }
+}
+
+// the dense bank, [B][N/2 + 1]; triangles linear in Hz (NVH_TRI_HZ) or in mel (NVH_TRI_MEL)
+void mel_bank(const nvh_mel_desc& D, int triangles, float* fb) {
   const int bins = D.n_fft / 2 + 1, B = D.n_mels;
   const double m_lo = hz_to_mel(D.f_min, D.mel_scale), m_hi = hz_to_mel(D.f_max, D.mel_scale);
-  std::vector<double> pt((size_t)B + 2);
-  for (int i = 0; i < B + 2; ++i) pt[(size_t)i] = mel_to_hz(m_lo + (m_hi - m_lo) * (double)i / (double)(B + 1), D.mel_scale);
+  std::vector<double> pt((size_t)B + 2), hz((size_t)B + 2);
+  for (int i = 0; i < B + 2; ++i) {
+    const double m = m_lo + (m_hi - m_lo) * (double)i / (double)(B + 1);
+    hz[(size_t)i] = mel_to_hz(m, D.mel_scale);
+    pt[(size_t)i] = triangles == NVH_TRI_MEL ? m : hz[(size_t)i];
+  }
   for (int b = 0; b < B; ++b) {
     const double l = pt[(size_t)b], c = pt[(size_t)b + 1], r = pt[(size_t)b + 2];
     for (int k = 0; k < bins; ++k) {
-      const double f = (double)k * (double)D.rate / (double)D.n_fft;
+      double f = (double)k * (double)D.rate / (double)D.n_fft;
+      if (triangles == NVH_TRI_MEL) f = hz_to_mel(f, D.mel_scale);
       const double up = (f - l) / (c - l), down = (r - f) / (r - c);
       double v = up < down ? up : down;
       if (!(v > 0.0)) v = 0.0;
-      if (D.norm == NVH_MEL_NORM_SLANEY) v *= 2.0 / (r - l);
+      if (D.norm == NVH_MEL_NORM_SLANEY) v *= 2.0 / (hz[(size_t)b + 2] - hz[(size_t)b]);
       fb[(size_t)b * bins + k] = (float)v;
     }
   }
@@ -79,8 +116,8 @@ int upload(void** dst, const void* src, size_t bytes) {
   return NVH_OK;
 }
 
-int get_mel(nvh_ctx* c, const nvh_mel_desc& D, MelDev** out) {
-  const MelKey key(D.rate, D.n_fft, D.win_length, D.n_mels, D.mel_scale, D.norm, D.f_min, D.f_max);
+int get_mel(nvh_ctx* c, const nvh_mel_desc& D, int window, int triangles, MelDev** out) {
+  const MelKey key(D.rate, D.n_fft, D.win_length, D.n_mels, D.mel_scale, D.norm, D.f_min, D.f_max, window, triangles);
   auto it = c->mel_cache.find(key);
   if (it != c->mel_cache.end()) {
     *out = &it->second;
@@ -89,8 +126,8 @@ int get_mel(nvh_ctx* c, const nvh_mel_desc& D, MelDev** out) {
   const int bins = D.n_fft / 2 + 1, B = D.n_mels;
   std::vector<float> tw((size_t)2 * bins), win((size_t)D.win_length), fb((size_t)B * bins), wts;
   mel_twiddles(D, tw.data());
-  mel_window(D, win.data());
-  mel_bank(D, fb.data());
+  mel_window(D, window, win.data());
+  mel_bank(D, triangles, fb.data());
   // the sparse bank: per band its first non-zero bin, the bins up to its last non-zero one, and where their weights begin
   std::vector<int> band((size_t)3 * B);
   for (int b = 0; b < B; ++b) {
@@ -137,28 +174,52 @@ extern "C" int nvh_mel_plan(const nvh_mel_desc* desc, int64_t* twiddle_count, in
   });
 }
 
+extern "C" int nvh_mel_front_check(const nvh_mel_desc* desc, const nvh_mel_front* front) {
+  return nvh_guard([&]() -> int {
+    if (!desc) return NVH_ERR_ARGUMENT;
+    int ld = 0;
+    const int rc = mel_check(*desc, &ld);
+    if (rc != NVH_OK || !front) return rc;
+    return front_check(*desc, *front);
+  });
+}
+
 extern "C" int nvh_mel_tables(const nvh_mel_desc* desc, float* twiddle, float* window, float* bank, int64_t twiddle_cap,
                               int64_t window_cap, int64_t bank_cap, int64_t* twiddle_count, int64_t* window_count, int64_t* bank_count) {
+  return nvh_mel_tables_front(desc, nullptr, twiddle, window, bank, twiddle_cap, window_cap, bank_cap, twiddle_count, window_count, bank_count);
+}
+
+extern "C" int nvh_mel_tables_front(const nvh_mel_desc* desc, const nvh_mel_front* front, float* twiddle, float* window, float* bank,
+                                    int64_t twiddle_cap, int64_t window_cap, int64_t bank_cap, int64_t* twiddle_count,
+                                    int64_t* window_count, int64_t* bank_count) {
   return nvh_guard([&]() -> int {
     if (twiddle_cap < 0 || window_cap < 0 || bank_cap < 0 || (twiddle_cap > 0 && !twiddle) || (window_cap > 0 && !window) || (bank_cap > 0 && !bank))
       return NVH_ERR_ARGUMENT;
-    const int rc = nvh_mel_plan(desc, twiddle_count, window_count, bank_count);
+    int rc = nvh_mel_plan(desc, twiddle_count, window_count, bank_count);
+    if (rc == NVH_OK && front) rc = front_check(*desc, *front);
     if (rc != NVH_OK) return rc;
     if ((twiddle && *twiddle_count > twiddle_cap) || (window && *window_count > window_cap) || (bank && *bank_count > bank_cap)) return NVH_ERR_ARGUMENT;
     if (twiddle) mel_twiddles(*desc, twiddle);
-    if (window) mel_window(*desc, window);
-    if (bank) mel_bank(*desc, bank);
+    if (window) mel_window(*desc, front ? front->window : NVH_WIN_HANN, window);
+    if (bank) mel_bank(*desc, front ? front->triangles : NVH_TRI_HZ, bank);
     return NVH_OK;
   });
 }
 
 extern "C" int nvh_mel_rows(nvh_ctx* c, const nvh_mel_desc* desc, const float* d_src, float* d_dst, const int64_t* valid) {
+  return nvh_mel_rows_front(c, desc, nullptr, d_src, d_dst, valid);
+}
+
+extern "C" int nvh_mel_rows_front(nvh_ctx* c, const nvh_mel_desc* desc, const nvh_mel_front* front, const float* d_src, float* d_dst,
+                                  const int64_t* valid) {
   return nvh_guard([&]() -> int {
     if (!desc) return NVH_ERR_ARGUMENT;
     const nvh_mel_desc& D = *desc;
     int ld = 0;
     int rc = mel_check(D, &ld);
+    if (rc == NVH_OK && front) rc = front_check(D, *front);
     if (rc != NVH_OK) return rc;
+    if (front_is_default(front)) front = nullptr;  // nvh_mel_rows itself: its kernel instances, its LDS, its grid
     if (D.rows < 0 || D.src_length < 0 || D.channels < 1 || D.channels > 65535) return NVH_ERR_ARGUMENT;
     const bool work = D.rows > 0 && D.frames > 0;
     if (work && (!d_src || !d_dst)) return NVH_ERR_ARGUMENT;
@@ -171,11 +232,13 @@ extern "C" int nvh_mel_rows(nvh_ctx* c, const nvh_mel_desc* desc, const float* d
     if (!work) return NVH_OK;
     HIP_TRY(hipSetDevice(c->device));
     MelDev* tab = nullptr;
-    rc = get_mel(c, D, &tab);
+    rc = get_mel(c, D, front ? front->window : NVH_WIN_HANN, front ? front->triangles : NVH_TRI_HZ, &tab);
     if (rc != NVH_OK) return rc;
     if (!c->mel_lds_attr_set) {
-      HIP_TRY(hipFuncSetAttribute((const void*)k_mel_rows<true>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_MEL_LDS_BYTES));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_mel_rows<false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_MEL_LDS_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)k_mel_rows<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_MEL_LDS_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)k_mel_rows<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_MEL_LDS_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)k_mel_rows<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_MEL_LDS_BYTES));
+      HIP_TRY(hipFuncSetAttribute((const void*)k_mel_rows<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_MEL_LDS_BYTES));
       c->mel_lds_attr_set = true;
     }
     NvhMelArgs A{};
@@ -223,6 +286,13 @@ extern "C" int nvh_mel_rows(nvh_ctx* c, const nvh_mel_desc* desc, const float* d
     A.scale = D.scale;
     A.floor = D.floor;
     A.weights = tab->weights;
+    A.gain = 1.0f;
+    if (front) {
+      A.reflect = front->pad_mode == NVH_PAD_REFLECT ? 1 : 0;
+      A.remove_dc = front->remove_dc;
+      A.preemphasis = front->preemphasis;
+      A.gain = front->gain;
+    }
     const long long abs_f = D.dst_frame_stride < 0 ? -D.dst_frame_stride : D.dst_frame_stride;
     const long long abs_b = D.dst_band_stride < 0 ? -D.dst_band_stride : D.dst_band_stride;
     A.band_fast = abs_b <= abs_f ? 1 : 0;
@@ -238,8 +308,15 @@ extern "C" int nvh_mel_rows(nvh_ctx* c, const nvh_mel_desc* desc, const float* d
     if (blocks >= 16384) blocks = (blocks + 3) / 4;
     blocks = std::min<long long>(blocks, 1 << 20);
     const dim3 grid((unsigned)blocks), block(NVH_MEL_THREADS);
-    if (fits) hipLaunchKernelGGL(k_mel_rows<true>, grid, block, lds, c->stream, A);
-    else hipLaunchKernelGGL(k_mel_rows<false>, grid, block, lds, c->stream, A);
+    // only the windows and the triangles? then the tables alone differ, and the kernel is nvh_mel_rows' own instance
+    const bool in_kernel = front && (A.reflect || A.remove_dc || A.preemphasis > 0.0f || A.gain != 1.0f);
+    if (!in_kernel) {
+      if (fits) hipLaunchKernelGGL((k_mel_rows<true, false>), grid, block, lds, c->stream, A);
+      else hipLaunchKernelGGL((k_mel_rows<false, false>), grid, block, lds, c->stream, A);
+    } else {
+      if (fits) hipLaunchKernelGGL((k_mel_rows<true, true>), grid, block, lds, c->stream, A);
+      else hipLaunchKernelGGL((k_mel_rows<false, true>), grid, block, lds, c->stream, A);
+    }
     HIP_TRY(hipGetLastError());
     return NVH_OK;
   });

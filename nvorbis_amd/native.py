@@ -68,6 +68,21 @@ MEL_POWER, MEL_LN, MEL_DB = 0, 1, 2     # NVH_MEL_POWER / _LN / _DB
 MEL_FRAMES = 4  # NVH_MEL_FRAMES: consecutive frames of one (row, channel) per workgroup of k_mel_rows
 
 
+class MelFront(C.Structure):
+    """nvh_mel_front: what lies between a row's samples and the transform's input -- window, triangle kind, padding, DC removal,
+    pre-emphasis and gain.  MelFront() is today's front: nvh_mel_rows itself."""
+    _fields_ = [("window", C.c_int32), ("triangles", C.c_int32), ("pad_mode", C.c_int32), ("remove_dc", C.c_int32),
+                ("preemphasis", C.c_float), ("gain", C.c_float), ("reserved", C.c_int32 * 2)]
+
+    def __init__(self, window=0, triangles=0, pad_mode=0, remove_dc=0, preemphasis=0.0, gain=1.0):
+        super().__init__(window=window, triangles=triangles, pad_mode=pad_mode, remove_dc=remove_dc, preemphasis=preemphasis, gain=gain)
+
+
+WIN_HANN, WIN_HANN_SYM, WIN_HAMMING, WIN_POVEY, WIN_RECT = 0, 1, 2, 3, 4  # NVH_WIN_*
+TRI_HZ, TRI_MEL = 0, 1                                                    # NVH_TRI_*
+PAD_ZERO, PAD_REFLECT = 0, 1                                              # NVH_PAD_*
+
+
 
 class FnormDesc(C.Structure):
     """nvh_fnorm_desc: mode and axis, the shape, the rule's numbers, and the element strides of source and destination (row, channel,
@@ -197,6 +212,10 @@ SIGNATURES = {
     "nvh_mel_plan": (C.c_int, [C.POINTER(MelDesc), _i64p, _i64p, _i64p]),
     "nvh_mel_tables": (C.c_int, [C.POINTER(MelDesc), _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p, _i64p]),
     "nvh_mel_rows": (C.c_int, [_vp, C.POINTER(MelDesc), _vp, _vp, _vp]),
+    "nvh_mel_front_check": (C.c_int, [C.POINTER(MelDesc), C.POINTER(MelFront)]),
+    "nvh_mel_tables_front": (C.c_int, [C.POINTER(MelDesc), C.POINTER(MelFront), _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p,
+                                       _i64p]),
+    "nvh_mel_rows_front": (C.c_int, [_vp, C.POINTER(MelDesc), C.POINTER(MelFront), _vp, _vp, _vp]),
     # per-row normalisation of features (nvh_fnorm.hip)
     "nvh_fnorm_check": (C.c_int, [C.POINTER(FnormDesc)]),
     "nvh_fnorm_rows": (C.c_int, [_vp, C.POINTER(FnormDesc), _vp, _vp, _vp]),

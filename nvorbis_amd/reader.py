@@ -352,12 +352,17 @@ class Context:
                                       v.ctypes.data, None if r is None else r.ctypes.data,
                                       None if d_clipped is None else C.c_void_p(d_clipped)), "nvh_resample_rows")
 
-    def mel_rows(self, desc, d_src, d_dst, valid=None):
+    def mel_rows(self, desc, d_src, d_dst, valid=None, front=None):
         """nvh_mel_rows: `desc` a native.MelDesc, d_src / d_dst device addresses, `valid` None or a host sequence of desc.rows
-        ints.  Asynchronous on the context's stream (synchronize() waits for it)."""
+        ints.  `front`: None, or a native.MelFront, and the call is nvh_mel_rows_front (a front at today's values is nvh_mel_rows
+        again).  Asynchronous on the context's stream (synchronize() waits for it)."""
         v = _row_array("mel_rows", "valid holds", valid, desc.rows)
-        check(lib().nvh_mel_rows(self._h, C.byref(desc), C.c_void_p(d_src), C.c_void_p(d_dst), None if v is None else v.ctypes.data),
-              "nvh_mel_rows")
+        if front is None:
+            check(lib().nvh_mel_rows(self._h, C.byref(desc), C.c_void_p(d_src), C.c_void_p(d_dst), None if v is None else v.ctypes.data),
+                  "nvh_mel_rows")
+        else:
+            check(lib().nvh_mel_rows_front(self._h, C.byref(desc), C.byref(front), C.c_void_p(d_src), C.c_void_p(d_dst),
+                                           None if v is None else v.ctypes.data), "nvh_mel_rows_front")
 
     def fnorm_rows(self, desc, d_src, d_dst, valid_frames=None):
         """nvh_fnorm_rows: `desc` a native.FnormDesc, d_src / d_dst device addresses (the same address with the same strides: in

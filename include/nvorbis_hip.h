@@ -657,6 +657,11 @@ int nvh_resample_plan(int in_rate, int out_rate, int *up, int *down, int *half, 
 int nvh_resample_taps(int in_rate, int out_rate, float *taps, int64_t cap, int64_t *count);
 int nvh_resample_rows(nvh_ctx *ctx, const nvh_resample_desc *desc, const float *d_src, void *d_dst, const int64_t *origin,
                       const int64_t *start, const int64_t *valid, const int32_t *dst_row, int32_t *d_clipped);
+/* Diagnostics (like nvh_batch_kernels: which route a launch takes depends on the shape; the values are not part of the ABI):
+ * what nvh_resample_rows would launch for `desc`, computed on the host by the code that launches it -- no context, no GPU.
+ * out[4]: the tap table staged in LDS (0 | 1), tiles per row, workgroups per (row, channel), bytes of dynamic LDS.  Returns
+ * what nvh_resample_rows returns for the descriptor alone (no buffer or array is looked at). */
+int nvh_resample_route(const nvh_resample_desc *desc, int64_t *out);
 
 /* ---- log-mel features of rows: a short-time transform, a mel filter bank and a logarithm over rows of f32 samples ----
  * Rows in, features out: every value is a pure function of one frame of one (row, channel); nothing is carried from call to
@@ -804,6 +809,12 @@ int nvh_mel_tables_front(const nvh_mel_desc *desc, const nvh_mel_front *front, f
                          int64_t *bank_count);
 int nvh_mel_rows_front(nvh_ctx *ctx, const nvh_mel_desc *desc, const nvh_mel_front *front, const float *d_src, float *d_dst,
                        const int64_t *valid);
+/* Diagnostics (like nvh_resample_route; the values are not part of the ABI): what nvh_mel_rows_front would launch for `desc`
+ * and `front` (NULL: nvh_mel_rows), on the host -- no context, no GPU; the bank is built for its size.  out[6]: tables and span
+ * staged in LDS (0 | 1), floats of the staged span (0: none), bytes of dynamic LDS, workgroups, whether the kernel instance with
+ * the front runs (0: nvh_mel_rows' own, the tables alone differ), floats of the sparse bank.  Returns what nvh_mel_rows_front
+ * returns for the two descriptors alone (no buffer or array is looked at). */
+int nvh_mel_route(const nvh_mel_desc *desc, const nvh_mel_front *front, int64_t *out);
 
 /* ---- per-row normalisation of features: mean, variance or peak of each (row, channel), and the fill of its padded frames ----
  * Features in, features out: every value is a pure function of one (row, channel) of the input and of that row's frame count;
@@ -867,6 +878,10 @@ typedef struct nvh_fnorm_desc {
 } nvh_fnorm_desc;
 int nvh_fnorm_check(const nvh_fnorm_desc *desc);
 int nvh_fnorm_rows(nvh_ctx *ctx, const nvh_fnorm_desc *desc, const float *d_src, float *d_dst, const int64_t *valid_frames);
+/* Diagnostics (like nvh_resample_route; the values are not part of the ABI): what nvh_fnorm_rows would launch for `desc`, on the
+ * host -- no context, no GPU.  out[3]: normalised out of LDS (0: re-reading), bytes of dynamic LDS, workgroups.  Returns what
+ * nvh_fnorm_rows returns for the descriptor alone (no buffer or array is looked at). */
+int nvh_fnorm_route(const nvh_fnorm_desc *desc, int64_t *out);
 
 /* ---- multi-GPU: the gather of the file-parallel corpus transcode (SURVEY 8 e) ----
  * StreamDecoder holds per-stream state only (StreamDecoder.cs:35-39), so a corpus shards by file: every process decodes its

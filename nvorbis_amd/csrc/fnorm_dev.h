@@ -39,3 +39,19 @@ struct NvhFnormArgs {
   int src_band_fast;  // the source's band stride is the smaller one: a frame's bands run along the lanes, else a band's frames
   int dst_band_fast;  // the same for the destination
 };
+
+// The launch route of one call, from integers alone: what nvh_fnorm_rows launches and nvh_fnorm_route reports.
+struct NvhFnormRoute {
+  int resident;   // nvh_fnorm_resident: read once and normalised out of LDS; else the source is re-read
+  int lds_bytes;
+  int blocks;     // workgroups: each walks items b, b + blocks, ..
+};
+static inline constexpr NvhFnormRoute nvh_fnorm_route_for(int frames, int bands, long long total_items) {
+  const bool resident = nvh_fnorm_resident(frames, bands);
+  const long long data = resident ? (long long)nvh_fnorm_band_pitch(frames) * bands : nvh_fnorm_reread_floats(bands);
+  return {resident ? 1 : 0, (int)((NVH_FNORM_FIXED_FLOATS + data) * 4), (int)(total_items < NVH_FNORM_MAX_BLOCKS ? total_items : NVH_FNORM_MAX_BLOCKS)};
+}
+static_assert(nvh_fnorm_route_for(1244, 16, 12).resident == 1 && nvh_fnorm_route_for(1244, 16, 12).lds_bytes == 4 * (528 + 1245 * 16), "resident");
+static_assert(nvh_fnorm_route_for(1248, 16, 5000).resident == 0 && nvh_fnorm_route_for(1248, 16, 5000).lds_bytes == 4 * (528 + 64 * 17), "re-reading");
+static_assert(nvh_fnorm_route_for(1248, 16, 5000).blocks == NVH_FNORM_MAX_BLOCKS && nvh_fnorm_route_for(1244, 16, 12).blocks == 12, "");
+// (known cases away from the threshold: tests/test_row_routes.py walks its edge, (1246, 16) to (1248, 16), through nvh_fnorm_route's export)

@@ -47,3 +47,31 @@ struct NvhMelArgs {
   float preemphasis; // p, 0: none
   float gain;        // g, 1: none
 };
+
+// The launch route of one call, from integers alone: what nvh_mel_rows[_front] launches and nvh_mel_route reports.
+struct NvhMelRoute {
+  int staged;        // twiddles, band records, weights, window and the four frames' span lie in LDS beside the slices and the tile
+  int span;          // NvhMelArgs::span
+  int lds_bytes;
+  long long blocks;  // workgroups: each walks items b, b + blocks, ..
+};
+// Everything is staged where it fits the budget.  A workgroup stages the tables once and walks its items: several items each once
+// there are workgroups enough to fill the chip.  weights: floats of the sparse bank; total_items: NvhMelArgs::total.
+static inline constexpr NvhMelRoute nvh_mel_route_for(int n_fft, int win_length, int hop, int n_mels, int weights, long long total_items) {
+  const long long span = (long long)(NVH_MEL_WAVES - 1) * hop + win_length;
+  const long long fixed = nvh_mel_fixed_floats(n_fft);
+  const long long staged = fixed + 2 * nvh_mel_tw_slots(n_fft) + 3 * n_mels + weights + win_length + span;
+  const bool fits = staged * 4 <= NVH_MEL_LDS_BYTES;
+  const long long blocks = total_items >= 16384 ? (total_items + 3) / 4 : total_items;
+  return {fits ? 1 : 0, fits ? (int)span : 0, (int)((fits ? staged : fixed) * 4), blocks < (1 << 20) ? blocks : (1 << 20)};
+}
+// Which instance runs.  Windows and triangles change the tables alone, so such a front runs nvh_mel_rows' own instances; the
+// FRONT instances run where the kernel itself has something to do.  (Today's front, and no front, have nothing of it.)
+static inline constexpr bool nvh_mel_front_in_kernel(bool reflect, bool remove_dc, float preemphasis, float gain) {
+  return reflect || remove_dc || preemphasis > 0.0f || gain != 1.0f;
+}
+static_assert(nvh_mel_route_for(4096, 4096, 5000, 128, 0, 7).staged == 0 && nvh_mel_route_for(4096, 4096, 5000, 128, 0, 7).lds_bytes == 4 * (4 * 4608 + 4 * 257), "n_fft = 4096");
+static_assert(nvh_mel_route_for(512, 400, 160, 80, 1000, 20000).staged == 1 && nvh_mel_route_for(512, 400, 160, 80, 1000, 20000).span == 880, "Whisper's frames");
+static_assert(nvh_mel_route_for(512, 400, 160, 80, 1000, 20000).blocks == 5000 && nvh_mel_route_for(512, 400, 160, 80, 1000, 1000).blocks == 1000, "four items each");
+static_assert(!nvh_mel_front_in_kernel(false, false, 0.0f, 1.0f) && nvh_mel_front_in_kernel(false, false, 0.97f, 1.0f), "");
+// (known cases away from the thresholds: tests/test_row_routes.py walks the thresholds' edges through nvh_mel_route's export)

@@ -107,29 +107,12 @@ extern "C" void nvh_ctx_destroy(nvh_ctx* c) {
   nvh_guard_void([&] {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (auto& kv : c->mdct_cache) {
-      (void)hipFree(kv.second.a);
-      (void)hipFree(kv.second.b);
-      (void)hipFree(kv.second.c);
-      (void)hipFree(kv.second.br);
-      (void)hipFree(kv.second.tw);
-    }
+    for (auto& kv : c->mdct_cache) kv.second.free_tables();
     for (auto& kv : c->resample_cache) (void)hipFree(kv.second.taps);
-    if (c->resample_copied) (void)hipEventDestroy(c->resample_copied);
-    c->resample_rows_host.release();  // (back into the pools that are cleared below)
-    c->resample_rows_dev.release();
-    for (auto& kv : c->mel_cache) {
-      (void)hipFree(kv.second.tw);
-      (void)hipFree(kv.second.win);
-      (void)hipFree(kv.second.fbw);
-      (void)hipFree(kv.second.band);
-    }
-    if (c->mel_copied) (void)hipEventDestroy(c->mel_copied);
-    c->mel_rows_host.release();
-    c->mel_rows_dev.release();
-    if (c->fnorm_copied) (void)hipEventDestroy(c->fnorm_copied);
-    c->fnorm_rows_host.release();
-    c->fnorm_rows_dev.release();
+    c->resample_rows.release();  // (back into the pools that are cleared below)
+    for (auto& kv : c->mel_cache) kv.second.free_tables();
+    c->mel_rows.release();
+    c->fnorm_rows.release();
     c->setup_cache.clear();  // streams must have been closed: they share these entries and return their buffers here
     c->pool.clear();
     c->hpool.clear();

@@ -21,7 +21,41 @@ int fnorm_check(const nvh_fnorm_desc& D) {
 
 long long magnitude(long long v) { return v < 0 ? -v : v; }
 
+// Every check of nvh_fnorm_rows in front of its context's, in the header's order, and what the launch follows from.  io: the call
+// has its buffers (nvh_fnorm_route has none and checks the descriptor alone).
+struct FnormPrep {
+  bool work = false;
+  long long total = 0;  // rows * channels (the work items are counted in 64 bits)
+  NvhFnormRoute route;
+};
+int fnorm_prepare(const nvh_fnorm_desc* desc, bool io, const int64_t* valid_frames, FnormPrep* out) {
+  if (!desc) return NVH_ERR_ARGUMENT;
+  const nvh_fnorm_desc& D = *desc;
+  const int rc = fnorm_check(D);
+  if (rc != NVH_OK) return rc;
+  out->work = D.rows > 0 && D.frames > 0;
+  if (out->work && !io) return NVH_ERR_ARGUMENT;
+  for (int i = 0; valid_frames && i < D.rows; ++i) {
+    if (valid_frames[i] < 0 || valid_frames[i] > D.frames) return NVH_ERR_ARGUMENT;
+  }
+  out->total = (long long)D.rows * D.channels;
+  out->route = nvh_fnorm_route_for(D.frames, D.bands, out->total);
+  return NVH_OK;
+}
+
 }  // namespace
+
+extern "C" int nvh_fnorm_route(const nvh_fnorm_desc* desc, int64_t* out) {
+  return nvh_guard([&]() -> int {
+    if (!out) return NVH_ERR_ARGUMENT;
+    FnormPrep P;
+    const int rc = fnorm_prepare(desc, true, nullptr, &P);
+    if (rc != NVH_OK) return rc;
+    const int64_t v[3] = {P.route.resident, P.route.lds_bytes, P.route.blocks};
+    std::copy(v, v + 3, out);
+    return NVH_OK;
+  });
+}
 
 extern "C" int nvh_fnorm_check(const nvh_fnorm_desc* desc) {
   return nvh_guard([&]() -> int { return desc ? fnorm_check(*desc) : NVH_ERR_ARGUMENT; });
@@ -29,40 +63,26 @@ extern "C" int nvh_fnorm_check(const nvh_fnorm_desc* desc) {
 
 extern "C" int nvh_fnorm_rows(nvh_ctx* c, const nvh_fnorm_desc* desc, const float* d_src, float* d_dst, const int64_t* valid_frames) {
   return nvh_guard([&]() -> int {
-    if (!desc) return NVH_ERR_ARGUMENT;
-    const nvh_fnorm_desc& D = *desc;
-    int rc = fnorm_check(D);
+    FnormPrep P;
+    int rc = fnorm_prepare(desc, d_src && d_dst, valid_frames, &P);
     if (rc != NVH_OK) return rc;
-    const bool work = D.rows > 0 && D.frames > 0;
-    if (work && (!d_src || !d_dst)) return NVH_ERR_ARGUMENT;
-    for (int i = 0; valid_frames && i < D.rows; ++i) {
-      if (valid_frames[i] < 0 || valid_frames[i] > D.frames) return NVH_ERR_ARGUMENT;
-    }
     if (!c) return NVH_ERR_NO_GPU;
-    if (!work) return NVH_OK;
+    if (!P.work) return NVH_OK;
+    const nvh_fnorm_desc& D = *desc;
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->fnorm_lds_attr_set) {
-      HIP_TRY(hipFuncSetAttribute((const void*)k_fnorm_rows<true>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_FNORM_LDS_BYTES));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_fnorm_rows<false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_FNORM_LDS_BYTES));
-      c->fnorm_lds_attr_set = true;
-    }
+    rc = lds_opt_in(c->fnorm_lds_attr_set, NVH_FNORM_LDS_BYTES, {(const void*)k_fnorm_rows<true>, (const void*)k_fnorm_rows<false>});
+    if (rc != NVH_OK) return rc;
     NvhFnormArgs A{};
-    if (valid_frames) {
-      // the per-row block, one copy out of page-locked memory; the block of the call before may still be on its way: its copy
-      // is waited for (the kernel behind it is not) before the staging is written again
+    if (valid_frames) {  // the per-row block: the rows' counted frames
       const size_t bytes = (size_t)D.rows * sizeof(int64_t);
-      if (!c->fnorm_copied) HIP_TRY(hipEventCreateWithFlags(&c->fnorm_copied, hipEventDisableTiming));
-      else HIP_TRY(hipEventSynchronize(c->fnorm_copied));
-      c->fnorm_rows_host.host = true;
-      c->fnorm_rows_host.pool = &c->hpool;
-      c->fnorm_rows_dev.pool = &c->pool;
-      rc = c->fnorm_rows_host.reserve(bytes);
-      if (rc == NVH_OK) rc = c->fnorm_rows_dev.reserve(bytes);
+      void* image = nullptr;
+      const void* d_block = nullptr;
+      rc = c->fnorm_rows.begin(c, bytes, &image);
       if (rc != NVH_OK) return rc;
-      std::memcpy(c->fnorm_rows_host.p, valid_frames, bytes);
-      HIP_TRY(hipMemcpyAsync(c->fnorm_rows_dev.p, c->fnorm_rows_host.p, bytes, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(hipEventRecord(c->fnorm_copied, c->stream));
-      A.vf = static_cast<const long long*>(c->fnorm_rows_dev.p);
+      std::memcpy(image, valid_frames, bytes);
+      rc = c->fnorm_rows.send(c, bytes, &d_block);
+      if (rc != NVH_OK) return rc;
+      A.vf = static_cast<const long long*>(d_block);
     }
     A.src = d_src;
     A.dst = d_dst;
@@ -74,7 +94,7 @@ extern "C" int nvh_fnorm_rows(nvh_ctx* c, const nvh_fnorm_desc* desc, const floa
     A.dst_chan_stride = D.dst_chan_stride;
     A.dst_frame_stride = D.dst_frame_stride;
     A.dst_band_stride = D.dst_band_stride;
-    A.total = (long long)D.rows * D.channels;  // (the work items are counted in 64 bits)
+    A.total = P.total;
     A.channels = D.channels;
     A.frames = D.frames;
     A.bands = D.bands;
@@ -88,12 +108,9 @@ extern "C" int nvh_fnorm_rows(nvh_ctx* c, const nvh_fnorm_desc* desc, const floa
     A.src_band_fast = magnitude(D.src_band_stride) <= magnitude(D.src_frame_stride) ? 1 : 0;
     A.dst_band_fast = magnitude(D.dst_band_stride) <= magnitude(D.dst_frame_stride) ? 1 : 0;
     // a (row, channel) that fits the budget is read once and normalised out of LDS; a larger one re-reads its source
-    const bool resident = nvh_fnorm_resident(D.frames, D.bands);
-    const size_t data = resident ? (size_t)nvh_fnorm_band_pitch(D.frames) * D.bands : (size_t)nvh_fnorm_reread_floats(D.bands);
-    const size_t lds = (NVH_FNORM_FIXED_FLOATS + data) * sizeof(float);
-    const long long blocks = std::min<long long>(A.total, NVH_FNORM_MAX_BLOCKS);
-    const dim3 grid((unsigned)blocks), block(NVH_FNORM_THREADS);
-    if (resident) hipLaunchKernelGGL(k_fnorm_rows<true>, grid, block, lds, c->stream, A);
+    const dim3 grid((unsigned)P.route.blocks), block(NVH_FNORM_THREADS);
+    const size_t lds = (size_t)P.route.lds_bytes;
+    if (P.route.resident) hipLaunchKernelGGL(k_fnorm_rows<true>, grid, block, lds, c->stream, A);
     else hipLaunchKernelGGL(k_fnorm_rows<false>, grid, block, lds, c->stream, A);
     HIP_TRY(hipGetLastError());
     return NVH_OK;

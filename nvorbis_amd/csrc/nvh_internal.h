@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <iterator>
 #include <map>
 #include <memory>
@@ -281,10 +282,27 @@ struct DevBuf {  // growable device (or pinned host) allocation, optionally back
   }
 };
 
+// A host table into device memory of its own (the cached tables below; freed by their free_tables).  Where the call fails,
+// what it allocated is freed and *dst stays as it was.  An empty table gets 4 bytes: its pointer is one nonetheless.
+template <class T>
+static inline int upload_table(T** dst, const std::vector<T>& src) {
+  void* p = nullptr;
+  HIP_TRY(hipMalloc(&p, src.empty() ? 4 : src.size() * sizeof(T)));
+  const hipError_t e = src.empty() ? hipSuccess : hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(p);
+    g_last_hip_error = (int)e;
+    return NVH_ERR_DEVICE;
+  }
+  *dst = static_cast<T*>(p);
+  return NVH_OK;
+}
+
 struct MdctDev {
   int n = 0;
   float *a = nullptr, *b = nullptr, *c = nullptr, *tw = nullptr;
   uint16_t* br = nullptr;
+  void free_tables() const { for (void* p : {(void*)a, (void*)b, (void*)c, (void*)br, (void*)tw}) (void)hipFree(p); }
 };
 
 struct ResampleDev {  // the tap table of one ratio (nvh_resample.hip), [L][2 * half] floats in device memory
@@ -296,6 +314,7 @@ struct MelDev {  // the device tables of one parameter set (nvh_mel.hip): twiddl
   float *tw = nullptr, *win = nullptr, *fbw = nullptr;
   int* band = nullptr;
   int weights = 0;
+  void free_tables() const { for (void* p : {(void*)tw, (void*)win, (void*)fbw, (void*)band}) (void)hipFree(p); }
 };
 // (rate, n_fft, win_length, n_mels, mel_scale, norm, f_min, f_max, window, triangles): what the tables depend on
 typedef std::tuple<int, int, int, int, int, int, double, double, int, int> MelKey;
@@ -324,6 +343,24 @@ struct SharedSetup {
   std::vector<int> parse_routes;  // per book the four numbers of nvh_stream_parse_book_info (nvh_setup.hip: book_routes)
 };
 
+// The per-row block of a rows call (the arrays the caller passes on the host: nvh_resample.hip, nvh_mel.hip, nvh_fnorm.hip fill
+// their own): its image in page-locked memory, the device copy, and the event behind the last copy out of the image.
+//   begin: the block of the call before may still be on its way -- its copy is waited for (the kernel behind it is not) before the
+//     image is written again; then room for `bytes` on both sides.  A failed reserve returns before anything is queued.
+//   send: one asynchronous copy on the context's stream, and the event behind it.
+struct RowBlock {
+  DevBuf host, dev;
+  hipEvent_t copied = nullptr;
+  int begin(nvh_ctx* c, size_t bytes, void** image);
+  int send(nvh_ctx* c, size_t bytes, const void** d_block);
+  void release() {  // (the buffers go back into the context's pools)
+    if (copied) (void)hipEventDestroy(copied);
+    copied = nullptr;
+    host.release();
+    dev.release();
+  }
+};
+
 struct nvh_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -337,22 +374,42 @@ struct nvh_ctx {
   bool synth_lds_attr_set = false;  // k_synth8's 160 KB dynamic-LDS opt-in was made on this context's device
   bool parse_lds_attr_set = false;  // k_parse's 80 KB dynamic-LDS opt-in was made on this context's device
   int parse_lanes = 0;              // nvh_ctx_set_parse_lanes: packets per wavefront of the GPU parser, 0 = automatic
-  // nvh_resample_rows: the tap tables by (L, M), like the per-n IMDCT tables; the per-row block's staging and device copy, and
-  // the event behind the last copy out of the staging
+  // The row operations: their cached tables (resample by (L, M), like the per-n IMDCT tables; mel by parameter set), whether
+  // their kernels' 80 KB dynamic-LDS opt-in was made on this context's device, and their per-row blocks.  One block per
+  // operation, not one for all: decode_clip_features queues resample, mel and fnorm back to back, and a shared block would
+  // make each call wait for the copy of the call before it, which sits in the stream behind that call's predecessor's kernel.
   std::map<std::pair<int, int>, ResampleDev> resample_cache;
-  bool resample_lds_attr_set = false;  // k_resample_rows' 80 KB dynamic-LDS opt-in was made on this context's device
-  DevBuf resample_rows_host, resample_rows_dev;
-  hipEvent_t resample_copied = nullptr;
-  // nvh_mel_rows: the tables by parameter set, and the per-row block's staging, device copy and event as above
   std::map<MelKey, MelDev> mel_cache;
-  bool mel_lds_attr_set = false;  // k_mel_rows' 80 KB dynamic-LDS opt-in was made on this context's device
-  DevBuf mel_rows_host, mel_rows_dev;
-  hipEvent_t mel_copied = nullptr;
-  // nvh_fnorm_rows: the per-row block's staging, device copy and event as above
-  bool fnorm_lds_attr_set = false;  // k_fnorm_rows' 80 KB dynamic-LDS opt-in was made on this context's device
-  DevBuf fnorm_rows_host, fnorm_rows_dev;
-  hipEvent_t fnorm_copied = nullptr;
+  bool resample_lds_attr_set = false, mel_lds_attr_set = false, fnorm_lds_attr_set = false;
+  RowBlock resample_rows, mel_rows, fnorm_rows;
 };
+
+inline int RowBlock::begin(nvh_ctx* c, size_t bytes, void** image) {
+  if (!copied) HIP_TRY(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+  else HIP_TRY(hipEventSynchronize(copied));
+  host.host = true;
+  host.pool = &c->hpool;
+  dev.pool = &c->pool;
+  int rc = host.reserve(bytes);
+  if (rc == NVH_OK) rc = dev.reserve(bytes);
+  if (rc == NVH_OK) *image = host.p;
+  return rc;
+}
+
+inline int RowBlock::send(nvh_ctx* c, size_t bytes, const void** d_block) {
+  HIP_TRY(hipMemcpyAsync(dev.p, host.p, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(copied, c->stream));
+  *d_block = dev.p;
+  return NVH_OK;
+}
+
+// A kernel family's opt-in to more than 64 KB of dynamic LDS, once per context (`done` is the context's flag).
+static inline int lds_opt_in(bool& done, int bytes, std::initializer_list<const void*> kernels) {
+  if (done) return NVH_OK;
+  for (const void* k : kernels) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  done = true;
+  return NVH_OK;
+}
 
 // Wait for the context's stream.  A context of a worker pool (nvh_ctx_set_parse_lanes > 0: one of many host threads, each waiting
 // milliseconds for its own parse) polls and sleeps instead of calling hipStreamSynchronize, which spins: a pool may then have

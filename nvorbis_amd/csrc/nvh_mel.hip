@@ -62,12 +62,6 @@ int front_check(const nvh_mel_desc& D, const nvh_mel_front& Fr) {
   return NVH_OK;
 }
 
-// every field at today's value: the front that is nvh_mel_rows itself
-bool front_is_default(const nvh_mel_front* Fr) {
-  return !Fr || (Fr->window == NVH_WIN_HANN && Fr->triangles == NVH_TRI_HZ && Fr->pad_mode == NVH_PAD_ZERO && Fr->remove_dc == 0 &&
-                 Fr->preemphasis == 0.0f && Fr->gain == 1.0f);
-}
-
 void mel_window(const nvh_mel_desc& D, int kind, float* win) {
   const int W = D.win_length;
   const double den = kind == NVH_WIN_HANN ? (double)W : (W > 1 ? (double)(W - 1) : 1.0);
@@ -105,15 +99,34 @@ void mel_bank(const nvh_mel_desc& D, int triangles, float* fb) {
   }
 }
 
-int upload(void** dst, const void* src, size_t bytes) {
-  HIP_TRY(hipMalloc(dst, bytes ? bytes : 4));
-  if (!bytes) return NVH_OK;
-  const hipError_t e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    g_last_hip_error = (int)e;
-    return NVH_ERR_DEVICE;
+// What k_mel_rows reads of one parameter set, on the host: twiddles, window, and the sparse bank -- per band its first non-zero
+// bin, the bins up to its last non-zero one, and where their weights begin.  wts.size() is the `weights` of the route.
+struct MelTables {
+  std::vector<float> tw, win, wts;
+  std::vector<int> band;
+};
+
+MelTables mel_build(const nvh_mel_desc& D, int window, int triangles) {
+  const int bins = D.n_fft / 2 + 1, B = D.n_mels;
+  MelTables t;
+  t.tw.resize((size_t)2 * bins);
+  t.win.resize((size_t)D.win_length);
+  t.band.resize((size_t)3 * B);
+  std::vector<float> fb((size_t)B * bins);
+  mel_twiddles(D, t.tw.data());
+  mel_window(D, window, t.win.data());
+  mel_bank(D, triangles, fb.data());
+  for (int b = 0; b < B; ++b) {
+    const float* rowp = fb.data() + (size_t)b * bins;
+    int k0 = 0, k1 = bins;
+    while (k0 < bins && rowp[k0] == 0.0f) ++k0;
+    while (k1 > k0 && rowp[k1 - 1] == 0.0f) --k1;
+    t.band[(size_t)3 * b] = k0 < bins ? k0 : 0;
+    t.band[(size_t)3 * b + 1] = k1 - k0;
+    t.band[(size_t)3 * b + 2] = (int)t.wts.size();
+    t.wts.insert(t.wts.end(), rowp + k0, rowp + k1);
   }
-  return NVH_OK;
+  return t;
 }
 
 int get_mel(nvh_ctx* c, const nvh_mel_desc& D, int window, int triangles, MelDev** out) {
@@ -123,34 +136,15 @@ int get_mel(nvh_ctx* c, const nvh_mel_desc& D, int window, int triangles, MelDev
     *out = &it->second;
     return NVH_OK;
   }
-  const int bins = D.n_fft / 2 + 1, B = D.n_mels;
-  std::vector<float> tw((size_t)2 * bins), win((size_t)D.win_length), fb((size_t)B * bins), wts;
-  mel_twiddles(D, tw.data());
-  mel_window(D, window, win.data());
-  mel_bank(D, triangles, fb.data());
-  // the sparse bank: per band its first non-zero bin, the bins up to its last non-zero one, and where their weights begin
-  std::vector<int> band((size_t)3 * B);
-  for (int b = 0; b < B; ++b) {
-    const float* rowp = fb.data() + (size_t)b * bins;
-    int k0 = 0, k1 = bins;
-    while (k0 < bins && rowp[k0] == 0.0f) ++k0;
-    while (k1 > k0 && rowp[k1 - 1] == 0.0f) --k1;
-    band[(size_t)3 * b] = k0 < bins ? k0 : 0;
-    band[(size_t)3 * b + 1] = k1 - k0;
-    band[(size_t)3 * b + 2] = (int)wts.size();
-    wts.insert(wts.end(), rowp + k0, rowp + k1);
-  }
+  const MelTables t = mel_build(D, window, triangles);
   MelDev d;
-  d.weights = (int)wts.size();
-  int rc = upload((void**)&d.tw, tw.data(), tw.size() * sizeof(float));
-  if (rc == NVH_OK) rc = upload((void**)&d.win, win.data(), win.size() * sizeof(float));
-  if (rc == NVH_OK) rc = upload((void**)&d.fbw, wts.data(), wts.size() * sizeof(float));
-  if (rc == NVH_OK) rc = upload((void**)&d.band, band.data(), band.size() * sizeof(int));
+  d.weights = (int)t.wts.size();
+  int rc = upload_table(&d.tw, t.tw);
+  if (rc == NVH_OK) rc = upload_table(&d.win, t.win);
+  if (rc == NVH_OK) rc = upload_table(&d.fbw, t.wts);  // (a bank of zeros alone is an empty table)
+  if (rc == NVH_OK) rc = upload_table(&d.band, t.band);
   if (rc != NVH_OK) {
-    (void)hipFree(d.tw);
-    (void)hipFree(d.win);
-    (void)hipFree(d.fbw);
-    (void)hipFree(d.band);
+    d.free_tables();
     return rc;
   }
   auto ins = c->mel_cache.emplace(key, d);
@@ -158,7 +152,53 @@ int get_mel(nvh_ctx* c, const nvh_mel_desc& D, int window, int triangles, MelDev
   return NVH_OK;
 }
 
+// Every check of nvh_mel_rows[_front] in front of its context's, in the header's order, and what the launch follows from.  The
+// route itself waits for the sparse bank's size (route()): the cached tables have it, nvh_mel_route builds the bank for it.
+// io: the call has its buffers (nvh_mel_route has none and checks the descriptors alone).
+struct MelPrep {
+  int ld = 0, window = NVH_WIN_HANN, triangles = NVH_TRI_HZ;
+  bool work = false, front_in_kernel = false;
+  long long groups = 0, total = 0;
+  NvhMelRoute route(const nvh_mel_desc& D, int weights) const { return nvh_mel_route_for(D.n_fft, D.win_length, D.hop, D.n_mels, weights, total); }
+};
+int mel_prepare(const nvh_mel_desc* desc, const nvh_mel_front* front, bool io, const int64_t* valid, MelPrep* out) {
+  if (!desc) return NVH_ERR_ARGUMENT;
+  const nvh_mel_desc& D = *desc;
+  int rc = mel_check(D, &out->ld);
+  if (rc == NVH_OK && front) rc = front_check(D, *front);
+  if (rc != NVH_OK) return rc;
+  if (front) {
+    out->window = front->window;
+    out->triangles = front->triangles;
+    out->front_in_kernel = nvh_mel_front_in_kernel(front->pad_mode == NVH_PAD_REFLECT, front->remove_dc != 0, front->preemphasis, front->gain);
+  }
+  if (D.rows < 0 || D.src_length < 0 || D.channels < 1 || D.channels > 65535) return NVH_ERR_ARGUMENT;
+  out->work = D.rows > 0 && D.frames > 0;
+  if (out->work && !io) return NVH_ERR_ARGUMENT;
+  for (int i = 0; valid && i < D.rows; ++i) {
+    if (valid[i] < 0 || valid[i] > D.src_length) return NVH_ERR_ARGUMENT;
+  }
+  out->groups = (D.frames + NVH_MEL_WAVES - 1) / NVH_MEL_WAVES;
+  if (out->work && (int64_t)D.rows * D.channels > INT64_MAX / out->groups) return NVH_ERR_ARGUMENT;  // (the work items are counted in 64 bits)
+  out->total = out->work ? (long long)D.rows * D.channels * out->groups : 0;
+  return NVH_OK;
+}
+
 }  // namespace
+
+extern "C" int nvh_mel_route(const nvh_mel_desc* desc, const nvh_mel_front* front, int64_t* out) {
+  return nvh_guard([&]() -> int {
+    if (!out) return NVH_ERR_ARGUMENT;
+    MelPrep P;
+    const int rc = mel_prepare(desc, front, true, nullptr, &P);
+    if (rc != NVH_OK) return rc;
+    const int64_t weights = (int64_t)mel_build(*desc, P.window, P.triangles).wts.size();
+    const NvhMelRoute r = P.route(*desc, (int)weights);
+    const int64_t v[6] = {r.staged, r.span, r.lds_bytes, r.blocks, P.front_in_kernel ? 1 : 0, weights};
+    std::copy(v, v + 6, out);
+    return NVH_OK;
+  });
+}
 
 extern "C" int nvh_mel_plan(const nvh_mel_desc* desc, int64_t* twiddle_count, int64_t* window_count, int64_t* bank_count) {
   return nvh_guard([&]() -> int {
@@ -213,51 +253,30 @@ extern "C" int nvh_mel_rows(nvh_ctx* c, const nvh_mel_desc* desc, const float* d
 extern "C" int nvh_mel_rows_front(nvh_ctx* c, const nvh_mel_desc* desc, const nvh_mel_front* front, const float* d_src, float* d_dst,
                                   const int64_t* valid) {
   return nvh_guard([&]() -> int {
-    if (!desc) return NVH_ERR_ARGUMENT;
-    const nvh_mel_desc& D = *desc;
-    int ld = 0;
-    int rc = mel_check(D, &ld);
-    if (rc == NVH_OK && front) rc = front_check(D, *front);
+    MelPrep P;
+    int rc = mel_prepare(desc, front, d_src && d_dst, valid, &P);
     if (rc != NVH_OK) return rc;
-    if (front_is_default(front)) front = nullptr;  // nvh_mel_rows itself: its kernel instances, its LDS, its grid
-    if (D.rows < 0 || D.src_length < 0 || D.channels < 1 || D.channels > 65535) return NVH_ERR_ARGUMENT;
-    const bool work = D.rows > 0 && D.frames > 0;
-    if (work && (!d_src || !d_dst)) return NVH_ERR_ARGUMENT;
-    for (int i = 0; valid && i < D.rows; ++i) {
-      if (valid[i] < 0 || valid[i] > D.src_length) return NVH_ERR_ARGUMENT;
-    }
-    const int64_t groups = (D.frames + NVH_MEL_WAVES - 1) / NVH_MEL_WAVES;
-    if (work && (int64_t)D.rows * D.channels > INT64_MAX / groups) return NVH_ERR_ARGUMENT;  // (the work items are counted in 64 bits)
     if (!c) return NVH_ERR_NO_GPU;
-    if (!work) return NVH_OK;
+    if (!P.work) return NVH_OK;
+    const nvh_mel_desc& D = *desc;
     HIP_TRY(hipSetDevice(c->device));
     MelDev* tab = nullptr;
-    rc = get_mel(c, D, front ? front->window : NVH_WIN_HANN, front ? front->triangles : NVH_TRI_HZ, &tab);
+    rc = get_mel(c, D, P.window, P.triangles, &tab);
+    if (rc == NVH_OK)
+      rc = lds_opt_in(c->mel_lds_attr_set, NVH_MEL_LDS_BYTES, {(const void*)k_mel_rows<true, false>, (const void*)k_mel_rows<false, false>,
+                                                                (const void*)k_mel_rows<true, true>, (const void*)k_mel_rows<false, true>});
     if (rc != NVH_OK) return rc;
-    if (!c->mel_lds_attr_set) {
-      HIP_TRY(hipFuncSetAttribute((const void*)k_mel_rows<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_MEL_LDS_BYTES));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_mel_rows<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_MEL_LDS_BYTES));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_mel_rows<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_MEL_LDS_BYTES));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_mel_rows<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NVH_MEL_LDS_BYTES));
-      c->mel_lds_attr_set = true;
-    }
     NvhMelArgs A{};
-    if (valid) {
-      // the per-row block, one copy out of page-locked memory; the block of the call before may still be on its way: its copy
-      // is waited for (the kernel behind it is not) before the staging is written again
+    if (valid) {  // the per-row block: the rows' counts
       const size_t bytes = (size_t)D.rows * sizeof(int64_t);
-      if (!c->mel_copied) HIP_TRY(hipEventCreateWithFlags(&c->mel_copied, hipEventDisableTiming));
-      else HIP_TRY(hipEventSynchronize(c->mel_copied));
-      c->mel_rows_host.host = true;
-      c->mel_rows_host.pool = &c->hpool;
-      c->mel_rows_dev.pool = &c->pool;
-      rc = c->mel_rows_host.reserve(bytes);
-      if (rc == NVH_OK) rc = c->mel_rows_dev.reserve(bytes);
+      void* image = nullptr;
+      const void* d_block = nullptr;
+      rc = c->mel_rows.begin(c, bytes, &image);
       if (rc != NVH_OK) return rc;
-      std::memcpy(c->mel_rows_host.p, valid, bytes);
-      HIP_TRY(hipMemcpyAsync(c->mel_rows_dev.p, c->mel_rows_host.p, bytes, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(hipEventRecord(c->mel_copied, c->stream));
-      A.valid = static_cast<const long long*>(c->mel_rows_dev.p);
+      std::memcpy(image, valid, bytes);
+      rc = c->mel_rows.send(c, bytes, &d_block);
+      if (rc != NVH_OK) return rc;
+      A.valid = static_cast<const long long*>(d_block);
     }
     A.tw = tab->tw;
     A.win = tab->win;
@@ -275,11 +294,11 @@ extern "C" int nvh_mel_rows_front(nvh_ctx* c, const nvh_mel_desc* desc, const nv
     A.dst_chan_stride = D.dst_chan_stride;
     A.dst_frame_stride = D.dst_frame_stride;
     A.dst_band_stride = D.dst_band_stride;
-    A.groups = groups;
-    A.total = (long long)D.rows * D.channels * groups;
+    A.groups = P.groups;
+    A.total = P.total;
     A.channels = D.channels;
     A.n_fft = D.n_fft;
-    A.ld = ld;
+    A.ld = P.ld;
     A.win_length = D.win_length;
     A.hop = D.hop;
     A.n_mels = D.n_mels;
@@ -296,25 +315,15 @@ extern "C" int nvh_mel_rows_front(nvh_ctx* c, const nvh_mel_desc* desc, const nv
     const long long abs_f = D.dst_frame_stride < 0 ? -D.dst_frame_stride : D.dst_frame_stride;
     const long long abs_b = D.dst_band_stride < 0 ? -D.dst_band_stride : D.dst_band_stride;
     A.band_fast = abs_b <= abs_f ? 1 : 0;
-    // everything staged -- twiddles, band records, weights, window, the four frames' span -- where it fits beside the slices and
-    // the tile
-    const long long span = (long long)(NVH_MEL_WAVES - 1) * D.hop + D.win_length;
-    const long long staged = (long long)nvh_mel_fixed_floats(D.n_fft) + 2 * nvh_mel_tw_slots(D.n_fft) + 3 * D.n_mels + tab->weights + D.win_length + span;
-    const bool fits = staged * (long long)sizeof(float) <= NVH_MEL_LDS_BYTES;
-    A.span = fits ? (int)span : 0;
-    const size_t lds = (size_t)(fits ? staged : nvh_mel_fixed_floats(D.n_fft)) * sizeof(float);
-    // a workgroup stages the tables once and walks its items: several items each once there are workgroups enough to fill the chip
-    long long blocks = A.total;
-    if (blocks >= 16384) blocks = (blocks + 3) / 4;
-    blocks = std::min<long long>(blocks, 1 << 20);
-    const dim3 grid((unsigned)blocks), block(NVH_MEL_THREADS);
-    // only the windows and the triangles? then the tables alone differ, and the kernel is nvh_mel_rows' own instance
-    const bool in_kernel = front && (A.reflect || A.remove_dc || A.preemphasis > 0.0f || A.gain != 1.0f);
-    if (!in_kernel) {
-      if (fits) hipLaunchKernelGGL((k_mel_rows<true, false>), grid, block, lds, c->stream, A);
+    const NvhMelRoute route = P.route(D, tab->weights);
+    A.span = route.span;
+    const size_t lds = (size_t)route.lds_bytes;
+    const dim3 grid((unsigned)route.blocks), block(NVH_MEL_THREADS);
+    if (!P.front_in_kernel) {
+      if (route.staged) hipLaunchKernelGGL((k_mel_rows<true, false>), grid, block, lds, c->stream, A);
       else hipLaunchKernelGGL((k_mel_rows<false, false>), grid, block, lds, c->stream, A);
     } else {
-      if (fits) hipLaunchKernelGGL((k_mel_rows<true, true>), grid, block, lds, c->stream, A);
+      if (route.staged) hipLaunchKernelGGL((k_mel_rows<true, true>), grid, block, lds, c->stream, A);
       else hipLaunchKernelGGL((k_mel_rows<false, true>), grid, block, lds, c->stream, A);
     }
     HIP_TRY(hipGetLastError());

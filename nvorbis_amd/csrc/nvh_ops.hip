@@ -47,17 +47,14 @@ int get_mdct(nvh_ctx* c, int n, MdctDev** out) {
   nvh::build_mdct_tables(n, t);
   MdctDev d;
   d.n = n;
-  HIP_TRY(hipMalloc((void**)&d.a, t.a.size() * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&d.b, t.b.size() * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&d.c, t.c.size() * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&d.br, t.bitrev.size() * sizeof(uint16_t)));
-  HIP_TRY(hipMemcpy(d.a, t.a.data(), t.a.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d.b, t.b.data(), t.b.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d.c, t.c.data(), t.c.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d.br, t.bitrev.data(), t.bitrev.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  if (!t.tw.empty()) {
-    HIP_TRY(hipMalloc((void**)&d.tw, t.tw.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(d.tw, t.tw.data(), t.tw.size() * sizeof(float), hipMemcpyHostToDevice));
+  int rc = upload_table(&d.a, t.a);
+  if (rc == NVH_OK) rc = upload_table(&d.b, t.b);
+  if (rc == NVH_OK) rc = upload_table(&d.c, t.c);
+  if (rc == NVH_OK) rc = upload_table(&d.br, t.bitrev);
+  if (rc == NVH_OK && !t.tw.empty()) rc = upload_table(&d.tw, t.tw);
+  if (rc != NVH_OK) {
+    d.free_tables();  // (the tables that made it)
+    return rc;
   }
   auto ins = c->mdct_cache.emplace(n, d);
   *out = &ins.first->second;

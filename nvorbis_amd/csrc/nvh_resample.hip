@@ -77,19 +77,60 @@ int get_resample(nvh_ctx* c, const ResamplePlan& p, ResampleDev** out) {
   d.L = p.L;
   d.M = p.M;
   d.half = p.half;
-  HIP_TRY(hipMalloc((void**)&d.taps, h.size() * sizeof(float)));
-  const hipError_t e = hipMemcpy(d.taps, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d.taps);
-    g_last_hip_error = (int)e;
-    return NVH_ERR_DEVICE;
-  }
+  const int rc = upload_table(&d.taps, h);
+  if (rc != NVH_OK) return rc;
   auto ins = c->resample_cache.emplace(key, d);
   *out = &ins.first->second;
   return NVH_OK;
 }
 
+// The per-row arrays of a call, on the host (dst_row may be null: the identity).
+struct ResampleRows {
+  const int64_t *origin, *start, *valid;
+  const int32_t* dst_row;
+};
+
+// Every check of nvh_resample_rows in front of its context's, in the header's order, and what the launch follows from: the plan
+// and the route.  io: the call has its buffers and arrays (nvh_resample_route has none and checks the descriptor alone).
+struct ResamplePrep {
+  ResamplePlan plan;
+  NvhResampleRoute route;
+  bool work = false;
+};
+int resample_prepare(const nvh_resample_desc* desc, bool io, const ResampleRows& R, ResamplePrep* out) {
+  if (!desc) return NVH_ERR_ARGUMENT;
+  const nvh_resample_desc& D = *desc;
+  if (D.in_rate < 1 || D.out_rate < 1 || D.rows < 0 || D.length < 0 || D.src_length < 0 || D.channels < 1 || D.channels > 65535 ||
+      !PcmOut::format_ok(D.format))
+    return NVH_ERR_ARGUMENT;
+  out->work = D.rows > 0 && D.length > 0;
+  if (out->work && !io) return NVH_ERR_ARGUMENT;
+  constexpr int64_t kMaxTime = (int64_t)1 << 48;  // J * M stays inside 64 bits (M <= 8192 inside the limits)
+  if (D.length > kMaxTime || D.src_length > kMaxTime) return NVH_ERR_ARGUMENT;
+  for (int i = 0; out->work && R.origin && i < D.rows; ++i) {
+    if (R.origin[i] < 0 || R.origin[i] > kMaxTime || R.start[i] < 0 || R.start[i] > kMaxTime - D.length || R.valid[i] < 0 ||
+        R.valid[i] > D.length || (R.dst_row && R.dst_row[i] < 0))
+      return NVH_ERR_ARGUMENT;
+  }
+  const int rc = resample_plan(D.in_rate, D.out_rate, &out->plan);
+  if (rc != NVH_OK) return rc;
+  out->route = nvh_resample_route_for(out->plan.L, out->plan.half, D.rows, D.channels, D.length);
+  return NVH_OK;
+}
+
 }  // namespace
+
+extern "C" int nvh_resample_route(const nvh_resample_desc* desc, int64_t* out) {
+  return nvh_guard([&]() -> int {
+    if (!out) return NVH_ERR_ARGUMENT;
+    ResamplePrep P;
+    const int rc = resample_prepare(desc, true, ResampleRows{}, &P);
+    if (rc != NVH_OK) return rc;
+    const int64_t v[4] = {P.route.taps_in_lds, P.route.tiles, P.route.grid_y, P.route.lds_bytes};
+    std::copy(v, v + 4, out);
+    return NVH_OK;
+  });
+}
 
 extern "C" int nvh_resample_plan(int in_rate, int out_rate, int* up, int* down, int* half, int64_t* tap_count) {
   return nvh_guard([&]() -> int {
@@ -121,58 +162,38 @@ extern "C" int nvh_resample_taps(int in_rate, int out_rate, float* taps, int64_t
 extern "C" int nvh_resample_rows(nvh_ctx* c, const nvh_resample_desc* desc, const float* d_src, void* d_dst, const int64_t* origin,
                                  const int64_t* start, const int64_t* valid, const int32_t* dst_row, int32_t* d_clipped) {
   return nvh_guard([&]() -> int {
-    if (!desc) return NVH_ERR_ARGUMENT;
-    const nvh_resample_desc& D = *desc;
-    if (D.in_rate < 1 || D.out_rate < 1 || D.rows < 0 || D.length < 0 || D.src_length < 0 || D.channels < 1 || D.channels > 65535 ||
-        !PcmOut::format_ok(D.format))
-      return NVH_ERR_ARGUMENT;
-    const bool work = D.rows > 0 && D.length > 0;
-    if (work && (!d_src || !d_dst || !origin || !start || !valid)) return NVH_ERR_ARGUMENT;
-    constexpr int64_t kMaxTime = (int64_t)1 << 48;  // J * M stays inside 64 bits (M <= 8192 inside the limits)
-    if (D.length > kMaxTime || D.src_length > kMaxTime) return NVH_ERR_ARGUMENT;
-    for (int i = 0; work && i < D.rows; ++i) {
-      if (origin[i] < 0 || origin[i] > kMaxTime || start[i] < 0 || start[i] > kMaxTime - D.length || valid[i] < 0 || valid[i] > D.length ||
-          (dst_row && dst_row[i] < 0))
-        return NVH_ERR_ARGUMENT;
-    }
-    ResamplePlan p;
-    int rc = resample_plan(D.in_rate, D.out_rate, &p);
+    ResamplePrep P;
+    int rc = resample_prepare(desc, d_src && d_dst && origin && start && valid, ResampleRows{origin, start, valid, dst_row}, &P);
     if (rc != NVH_OK) return rc;
     if (!c) return NVH_ERR_NO_GPU;
-    if (!work) return NVH_OK;
+    if (!P.work) return NVH_OK;
+    const nvh_resample_desc& D = *desc;
+    const ResamplePlan& p = P.plan;
     HIP_TRY(hipSetDevice(c->device));
     ResampleDev* tab = nullptr;
     rc = get_resample(c, p, &tab);
+    if (rc == NVH_OK)
+      rc = lds_opt_in(c->resample_lds_attr_set, (int)kResampleLdsBytes, {(const void*)k_resample_rows<float>, (const void*)k_resample_rows<int16_t>});
     if (rc != NVH_OK) return rc;
-    if (!c->resample_lds_attr_set) {
-      HIP_TRY(hipFuncSetAttribute((const void*)k_resample_rows<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResampleLdsBytes));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_resample_rows<int16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResampleLdsBytes));
-      c->resample_lds_attr_set = true;
-    }
-    // the per-row block: three int64 arrays, then the int32 one; one copy out of page-locked memory.  The block of the call
-    // before may still be on its way: its copy is waited for (the kernel behind it is not) before the staging is written again.
+    // the per-row block: three int64 arrays, then the int32 one
     const size_t n = (size_t)D.rows;
     const size_t bytes = n * (3 * sizeof(int64_t) + sizeof(int32_t));
-    if (!c->resample_copied) HIP_TRY(hipEventCreateWithFlags(&c->resample_copied, hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(c->resample_copied));
-    c->resample_rows_host.host = true;
-    c->resample_rows_host.pool = &c->hpool;
-    c->resample_rows_dev.pool = &c->pool;
-    rc = c->resample_rows_host.reserve(bytes);
-    if (rc == NVH_OK) rc = c->resample_rows_dev.reserve(bytes);
+    void* image = nullptr;
+    rc = c->resample_rows.begin(c, bytes, &image);
     if (rc != NVH_OK) return rc;
-    int64_t* h64 = static_cast<int64_t*>(c->resample_rows_host.p);
+    int64_t* h64 = static_cast<int64_t*>(image);
     std::memcpy(h64, origin, n * sizeof(int64_t));
     std::memcpy(h64 + n, start, n * sizeof(int64_t));
     std::memcpy(h64 + 2 * n, valid, n * sizeof(int64_t));
     int32_t* h32 = reinterpret_cast<int32_t*>(h64 + 3 * n);
     if (dst_row) std::memcpy(h32, dst_row, n * sizeof(int32_t));
     else for (size_t i = 0; i < n; ++i) h32[i] = (int32_t)i;
-    HIP_TRY(hipMemcpyAsync(c->resample_rows_dev.p, h64, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->resample_copied, c->stream));
+    const void* d_block = nullptr;
+    rc = c->resample_rows.send(c, bytes, &d_block);
+    if (rc != NVH_OK) return rc;
 
     NvhResampleArgs A{};
-    const long long* d64 = static_cast<const long long*>(c->resample_rows_dev.p);
+    const long long* d64 = static_cast<const long long*>(d_block);
     A.taps = tab->taps;
     A.src = d_src;
     A.dst = d_dst;
@@ -192,16 +213,12 @@ extern "C" int nvh_resample_rows(nvh_ctx* c, const nvh_resample_desc* desc, cons
     A.L = p.L;
     A.M = p.M;
     A.half = p.half;
-    const int64_t padded = (int64_t)p.L * ((2 * p.half) | 1);
-    A.taps_in_lds = padded <= NVH_RS_TAP_FLOATS ? 1 : 0;
-    const int64_t tiles = (D.length + NVH_RS_TILE - 1) / NVH_RS_TILE;
-    A.tiles = (int)tiles;  // (length <= 2^48: inside an int)
-    // a workgroup stages the taps once and walks its tiles: four tiles each once there are workgroups enough to fill the chip
-    int64_t gy = tiles;
-    if ((int64_t)D.rows * D.channels * tiles >= 4096) gy = (tiles + 3) / 4;
-    gy = std::min<int64_t>(gy, 65535);
-    const size_t lds = ((A.taps_in_lds ? (size_t)padded : 0) + NVH_RS_SRC_FLOATS) * sizeof(float);
-    const dim3 grid((unsigned)D.rows, (unsigned)gy, (unsigned)D.channels), block(NVH_RS_THREADS);
+    A.taps_in_lds = P.route.taps_in_lds;
+    // The kernel counts tiles in an int: that holds a length below 2^40 (2^31 tiles of 512), not every length the checks let
+    // through (up to 2^48, 2^39 tiles).  Nothing refuses the lengths between; such a row would be 4 TiB of f32.
+    A.tiles = (int)P.route.tiles;
+    const dim3 grid((unsigned)D.rows, (unsigned)P.route.grid_y, (unsigned)D.channels), block(NVH_RS_THREADS);
+    const size_t lds = (size_t)P.route.lds_bytes;
     if (D.format == NVH_PCM_S16) hipLaunchKernelGGL(k_resample_rows<int16_t>, grid, block, lds, c->stream, A);
     else hipLaunchKernelGGL(k_resample_rows<float>, grid, block, lds, c->stream, A);
     HIP_TRY(hipGetLastError());

@@ -208,6 +208,7 @@ SIGNATURES = {
     "nvh_resample_plan": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _ip, _i64p]),
     "nvh_resample_taps": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int64, _i64p]),
     "nvh_resample_rows": (C.c_int, [_vp, C.POINTER(ResampleDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nvh_resample_route": (C.c_int, [C.POINTER(ResampleDesc), _i64p]),
     # log-mel features of rows (nvh_mel.hip)
     "nvh_mel_plan": (C.c_int, [C.POINTER(MelDesc), _i64p, _i64p, _i64p]),
     "nvh_mel_tables": (C.c_int, [C.POINTER(MelDesc), _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p, _i64p]),
@@ -216,9 +217,11 @@ SIGNATURES = {
     "nvh_mel_tables_front": (C.c_int, [C.POINTER(MelDesc), C.POINTER(MelFront), _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p,
                                        _i64p]),
     "nvh_mel_rows_front": (C.c_int, [_vp, C.POINTER(MelDesc), C.POINTER(MelFront), _vp, _vp, _vp]),
+    "nvh_mel_route": (C.c_int, [C.POINTER(MelDesc), C.POINTER(MelFront), _i64p]),
     # per-row normalisation of features (nvh_fnorm.hip)
     "nvh_fnorm_check": (C.c_int, [C.POINTER(FnormDesc)]),
     "nvh_fnorm_rows": (C.c_int, [_vp, C.POINTER(FnormDesc), _vp, _vp, _vp]),
+    "nvh_fnorm_route": (C.c_int, [C.POINTER(FnormDesc), _i64p]),
     # the corpus gather through RCCL's C API (nvh_comm.hip): what a host without torch.distributed binds to
     "nvh_comm_unique_id": (C.c_int, [_vp]),
     "nvh_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),

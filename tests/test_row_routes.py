@@ -23,7 +23,15 @@ test_resample_rows.py, test_mel_rows.py, test_fnorm_rows.py and test_clip_load.p
                                                              test_decode_clip_features_of_1001_frames[8-True], [24-True]
   k_fnorm_rows: eps doubled and gain negated for an item
     behind a re-reading workgroup's first                    test_fnorm_reread_walks_items
-Every case's CPU reference takes under 0.2 s and every gpu test under 0.4 s (the largest: (1001, 80) through the whole matrix)."""
+Every case's CPU reference takes under 0.2 s and every gpu test under 0.4 s (the largest: (1001, 80) through the whole matrix).
+
+Every route of a kernel gives the same bits, so the gpu tests cannot see a launcher that chooses another route than the functions
+here.  The library says what it would launch (nvh_resample_route, nvh_mel_route, nvh_fnorm_route: the launchers' own checks and
+route functions, no GPU), every CPU test here holds that to the restatement for its cases, and test_route_sweep_* walk both sides
+of every threshold.  In a copy of csrc/ with `>= 4096` turned into `> 4096` in resample_dev.h, `>= 16384` into `>` or the budget's
+`<=` into `<` in mel_dev.h, or `<=` into `<` in fnorm_dev.h, test_route_sweep_resample / _mel / _mel / _fnorm fail and no other CPU
+test does.  test_row_block_* queue three calls of each operation with no wait between them (nvh_internal.h: RowBlock)."""
+import ctypes as C
 import os
 import re
 
@@ -108,6 +116,82 @@ def fnorm_route(F, B, items):
     return (F | 1) * B <= D["NVH_FNORM_DATA_FLOATS"], min(items, D["NVH_FNORM_MAX_BLOCKS"]), F > D["NVH_FNORM_THREADS"]
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# the launchers' own choices: nvh_resample_route, nvh_mel_route and nvh_fnorm_route run the launchers' argument checks and route
+# functions on the host, so a launcher that drifts from the three functions above fails here, not only one whose budget moved.
+# full_*: the functions above with the fields they lack, written from the launchers' text as it stood before the exports existed
+# (nvh_resample.hip, nvh_mel.hip, nvh_fnorm.hip at c952e63..02176a0), in the exports' order.
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def lib_route(name, count, *descs):
+    from nvorbis_amd import native
+    out = (C.c_int64 * count)()
+    rc = getattr(native.lib(), name)(*[None if d is None else C.byref(d) for d in descs], out)
+    assert rc == native.OK, (name, rc)
+    return list(out)
+
+
+def lib_resample(fi, fo, channels, T, nrows):
+    """[taps_in_lds, tiles, gy, lds_bytes] of the library."""
+    from nvorbis_amd import native
+    return lib_route("nvh_resample_route", 4, native.ResampleDesc(in_rate=fi, out_rate=fo, rows=nrows, channels=channels, format=native.PCM_F32,
+                                                                   length=T, src_length=0))
+
+
+def full_resample(fi, fo, channels, T, nrows):
+    D = defines("resample_dev.h")
+    L, M, half, _ = rule_plan(fi, fo)
+    taps, gy, _ = resample_route(fi, fo, channels, T, [(0, 0, 0)] * nrows)
+    padded = L * ((2 * half) | 1)
+    return [int(taps), (T + D["NVH_RS_TILE"] - 1) // D["NVH_RS_TILE"], gy, ((padded if taps else 0) + D["NVH_RS_SRC_FLOATS"]) * 4]
+
+
+def sparse_weights(bank):
+    """Floats of the sparse bank: per band its first non-zero bin up to its last."""
+    total = 0
+    for row in bank:
+        nz = np.nonzero(row)[0]
+        total += int(nz[-1] - nz[0] + 1) if nz.size else 0
+    return total
+
+
+def lib_mel(cfg, rows=1, channels=1, frames=1, front=None):
+    """[staged, span, lds_bytes, blocks, front_in_kernel, weights] of the library."""
+    from tests.test_mel_plan import make_desc
+    rate, N, W, H, B = cfg
+    return lib_route("nvh_mel_route", 6, make_desc(rate, N, W, B, hop=H, rows=rows, channels=channels, frames=frames, src_length=4 * W), front)
+
+
+def full_mel(cfg, rows=1, channels=1, frames=1, front=None):
+    """`staged` is mel_route's (today's bank; a front with mel-domain triangles has a bank of its own: bank_of below)."""
+    D = defines("mel_dev.h")
+    rate, N, W, H, B = cfg
+    waves, points = D["NVH_MEL_WAVES"], N >> 1
+    staged = mel_route(cfg)[0]
+    weights = sparse_weights(lib_tables(rate, N, W, B)[2])
+    fixed = waves * 2 * (points + ((points >> 6) << 3)) + waves * D["NVH_MEL_OUT_STRIDE"]
+    span = (waves - 1) * H + W
+    floats = fixed + 2 * (points + (points >> 4) + 1) + 3 * B + weights + W + span
+    assert staged == (floats * 4 <= D["NVH_MEL_LDS_BYTES"])
+    total = rows * channels * ((frames + waves - 1) // waves)
+    blocks = min((total + 3) // 4 if total >= 16384 else total, 1 << 20)
+    default = front is None or (front.window, front.triangles, front.pad_mode, front.remove_dc, front.preemphasis, front.gain) == (0, 0, 0, 0, 0.0, 1.0)
+    in_kernel = not default and bool(front.pad_mode == 1 or front.remove_dc or front.preemphasis > 0.0 or front.gain != 1.0)
+    return [int(staged), span if staged else 0, (floats if staged else fixed) * 4, blocks, int(in_kernel), weights]
+
+
+def lib_fnorm(F, B, rows, channels=1):
+    """[resident, lds_bytes, blocks] of the library."""
+    return lib_route("nvh_fnorm_route", 3, make_fdesc("mean_var", "band", rows=rows, channels=channels, frames=F, bands=B))
+
+
+def full_fnorm(F, B, rows, channels=1):
+    D = defines("fnorm_dev.h")
+    resident, blocks, _ = fnorm_route(F, B, rows * channels)
+    data = (F | 1) * B if resident else max(B * (D["NVH_FNORM_TILE"] + 1), D["NVH_FNORM_TILE"] * (B | 1))
+    return [int(resident), (D["NVH_FNORM_FIXED_FLOATS"] + data) * 4, blocks]
+
+
 def test_the_headers_numbers_are_read():
     from nvorbis_amd import native
     rs, ml, fn = defines("resample_dev.h"), defines("mel_dev.h"), defines("fnorm_dev.h")
@@ -120,6 +204,11 @@ def test_the_headers_numbers_are_read():
     assert mel_route((22050, 1024, 1024, 256, 64)) == (True, [3, 3, 3])
     for F, B in fnr.KERNEL_SHAPES:
         assert fnorm_route(F, B, 12)[0] == fnr.takes_lds_path(F, B) and not fnorm_route(F, B, 12)[2]
+        assert lib_fnorm(F, B, 12) == full_fnorm(F, B, 12)
+    # ... and what the library launches for them
+    assert lib_resample(1024, 1, 1, 5, 1) == full_resample(1024, 1, 1, 5, 1) and lib_resample(44100, 16000, 2, 63, 1) == full_resample(44100, 16000, 2, 63, 1)
+    for cfg in ((48000, 4096, 4096, 5000, 128), (16000, 512, 400, 160, 80), (22050, 1024, 1024, 256, 64)):
+        assert lib_mel(cfg) == full_mel(cfg), cfg
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -153,6 +242,7 @@ def test_route_taps_in_lds_source_through_l2(fi, fo):
     rows = rs_case(fi, fo, T)[0]
     taps, gy, spans = resample_route(fi, fo, 2, T, rows)
     assert taps and gy == 3
+    assert lib_resample(fi, fo, 2, T, len(rows)) == full_resample(fi, fo, 2, T, len(rows)) and lib_resample(fi, fo, 2, T, len(rows))[::2] == [1, 3]
     assert [v for _, _, v in rows] == [T, T, 0, tile() + 100, T, T]
     for (_, _, v), per in zip(rows, spans):
         if v == T:
@@ -161,6 +251,7 @@ def test_route_taps_in_lds_source_through_l2(fi, fo):
     assert not in_lds(spans[3][0]) and in_lds(spans[3][1]) and spans[3][2] is None, spans[3]
     taps, gy, spans = resample_route(fi, fo, 2, 1, rs_case(fi, fo, 1)[0])
     assert taps and gy == 1 and all(per[0] is None or per[0] == 2 * rule_plan(fi, fo)[2] for per in spans)
+    assert lib_resample(fi, fo, 2, 1, len(spans)) == full_resample(fi, fo, 2, 1, len(spans)) and lib_resample(fi, fo, 2, 1, len(spans))[::2] == [1, 1]
 
 
 @pytest.mark.gpu
@@ -235,6 +326,8 @@ def test_route_span_boundary():
         rows = [(0, s, v) for s, v, _ in boundary_specs(fi, fo)]  # (the origin moves no route)
         taps, gy, spans = resample_route(fi, fo, 2, 3 * tile(), rows)
         assert taps and gy == 3
+        assert lib_resample(fi, fo, 2, 3 * tile(), len(rows)) == full_resample(fi, fo, 2, 3 * tile(), len(rows))
+        assert lib_resample(fi, fo, 2, 3 * tile(), len(rows))[::2] == [1, 3]
         seen = {s for per in spans for s in per}
         assert seen == want, (fi, fo, seen)
         assert {s for per in spans for s in per[:1]} == want  # ... both already among the rows' first tiles
@@ -288,6 +381,7 @@ def test_route_a_workgroup_walks_several_tiles(fi, fo):
     taps, gy, spans = resample_route(fi, fo, 2, T, [rows[i] for i in walk_rows()[0]])
     tiles = (T + tile() - 1) // tile()
     assert taps and tiles == 9 and gy == 3 and WALK_ROWS * 2 * tiles >= 4096
+    assert lib_resample(fi, fo, 2, T, WALK_ROWS) == full_resample(fi, fo, 2, T, WALK_ROWS) and lib_resample(fi, fo, 2, T, WALK_ROWS)[:3] == [1, 9, 3]
     assert all(s is None or in_lds(s) for per in spans for s in per)
     staged = [[s is not None for s in per] for per in spans[:8]]
     assert staged[1] == staged[6] == [False] * 9 and staged[0] == staged[5] == [True] * 9
@@ -361,6 +455,9 @@ _MEL_CASES = {}
 @pytest.mark.parametrize("cfg", sorted(MEL_ROUTES))
 def test_route_mel(cfg):
     assert mel_route(cfg) == MEL_ROUTES[cfg]
+    for frames in (1, 4, 7):  # (the gpu test's)
+        got = lib_mel(cfg, rows=6, channels=2, frames=frames)
+        assert got == full_mel(cfg, rows=6, channels=2, frames=frames) and bool(got[0]) == MEL_ROUTES[cfg][0], (frames, got)
 
 
 @pytest.mark.gpu
@@ -413,6 +510,7 @@ def test_route_fnorm_more_frames_than_threads(shape):
     F, B = shape
     resident, blocks, wraps = fnorm_route(F, B, 14)
     assert resident == LONG_SHAPES[shape] and blocks == 14 and wraps
+    assert lib_fnorm(F, B, 7, 2) == full_fnorm(F, B, 7, 2) and lib_fnorm(F, B, 7, 2)[::2] == [int(resident), 14]
     assert {0, 1, 511, 512, 513, F} <= set(long_vf(F))
 
 
@@ -435,6 +533,8 @@ def test_route_fnorm_reread_walks_items():
     resident, blocks, _ = fnorm_route(F, B, ITEMS_ROWS * 2)
     assert not resident and blocks < ITEMS_ROWS * 2
     assert fnorm_route(F - 1, B, 1)[0]  # ... the smallest shape of 256 bands that re-reads
+    assert lib_fnorm(F, B, ITEMS_ROWS, 2) == full_fnorm(F, B, ITEMS_ROWS, 2) and lib_fnorm(F, B, ITEMS_ROWS, 2)[::2] == [0, blocks]
+    assert lib_fnorm(F - 1, B, 1) == full_fnorm(F - 1, B, 1) and lib_fnorm(F - 1, B, 1)[0] == 1
 
 
 @pytest.mark.gpu
@@ -489,6 +589,9 @@ def test_route_features_of_1001_frames():
     F = mlr.LENGTH // 4 + 1
     assert F == 1001 and fnorm_route(F, 8, 1) == (True, 1, True) and fnorm_route(F, 24, 1) == (False, 1, True)
     assert mel_route((16000, 64, 64, 4, 8))[0] and mel_route((16000, 64, 64, 4, 24))[0]
+    for B in (8, 24):
+        assert lib_fnorm(F, B, 3) == full_fnorm(F, B, 3) and lib_fnorm(F, B, 3)[0] == int(B == 8)
+        assert lib_mel((16000, 64, 64, 4, B), rows=3, frames=F) == full_mel((16000, 64, 64, 4, B), rows=3, frames=F)
 
 
 @pytest.mark.gpu
@@ -510,3 +613,213 @@ def test_decode_clip_features_of_1001_frames(oracle, gpu_ctx, ogg_bytes, n_mels,
     host = feats.cpu().numpy()
     bad = [i for i in range(len(files)) if not same_bits(np.ascontiguousarray(host[i]), np.ascontiguousarray(want[i]))]
     assert not bad, (n_mels, band_major, bad, int(want_vf[bad[0]]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the edges of every threshold of the three route functions, through the exports
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def test_route_sweep_resample():
+    """rows * channels * tiles on both sides of 4096 (four tiles per workgroup from there on), gridDim.y at its cap, and the tap
+    table on both sides of NVH_RS_TAP_FLOATS: L * ((2 * half) | 1) has an odd factor of at least 33, so it is never the budget
+    itself (a power of two); 43 * 381 = budget - 1 (508 -> 43) and 1 * 16385 = budget + 1 (512 -> 1) are as close as rates get."""
+    T4 = 4 * tile()
+    # (in_rate, out_rate, channels, T, rows): the product 4095 keeps a workgroup per tile, 4096 and more gives it four
+    edge = [(44100, 16000, 1, 3 * tile(), 1365), (44100, 16000, 1, T4, 1024), (44100, 16000, 3, 5 * tile(), 273), (44100, 16000, 2, 2 * tile(), 1024),
+            (8000, 44100, 1, 4095 * tile(), 1), (8000, 44100, 1, 4095 * tile() + 1, 1), (8000, 44100, 1, T4 + 1, 819), (8000, 44100, 1, T4 + 1, 820),
+            (8000, 44100, 5, 7 * tile(), 117), (8000, 44100, 5, 7 * tile(), 118)]
+    want_gy = [3, 1, 5, 1, 4095, 1024, 5, 2, 7, 2]
+    for case, gy in zip(edge, want_gy):
+        want = full_resample(*case)
+        assert lib_resample(*case) == want and want[2] == gy, (case, want)
+    for tiles in (65535 * 4, 65535 * 4 + 1, 1 << 19):  # the cap: (tiles + 3) // 4 = 65535, 65536, 2^17
+        case = (44100, 16000, 1, tiles * tile(), 1)
+        want = full_resample(*case)
+        assert lib_resample(*case) == want and want[1:3] == [tiles, 65535], (case, want)
+    budget = defines("resample_dev.h")["NVH_RS_TAP_FLOATS"]
+    below, above = (508, 43), (512, 1)
+    for (fi, fo), padded in ((below, budget - 1), (above, budget + 1)):
+        L, M, half, _ = rule_plan(fi, fo)
+        assert L * ((2 * half) | 1) == padded and max(fi, fo) <= 192000
+        want = full_resample(fi, fo, 2, 63, 3)
+        assert lib_resample(fi, fo, 2, 63, 3) == want and want[0] == int(padded < budget), (fi, fo, want)
+    assert full_resample(*below, 1, 1, 1)[3] - full_resample(*above, 1, 1, 1)[3] == 4 * (budget - 1)
+
+
+def test_route_sweep_mel():
+    """The work items on both sides of 16384 (four items per workgroup from there on) and at the cap of 2^20 workgroups; for two
+    transforms the longest hop whose span is still staged, and the next; every field of a front on its own."""
+    from tests.test_mel_front_plan import front_tables, make_front
+    cfg = (16000, 512, 400, 160, 80)
+    waves = defines("mel_dev.h")["NVH_MEL_WAVES"]
+    for shape, blocks in (((16383, 1, waves), 16383), ((16384, 1, waves), 4096), ((16383, 1, waves + 1), 8192), ((1, 1, 16383 * waves), 16383),
+                          ((1, 1, 16383 * waves + 1), 4096), ((5461, 3, 1), 16383), ((8192, 2, 2), 4096), ((16385, 1, 1), 4097),
+                          (((4 << 20) - 3, 1, 1), 1 << 20), (((4 << 20) + 5, 1, 1), 1 << 20), (((4 << 20) - 4, 1, 1), (1 << 20) - 1)):
+        want = full_mel(cfg, *shape)
+        assert lib_mel(cfg, *shape) == want and want[3] == blocks, (shape, want)
+    budget = defines("mel_dev.h")["NVH_MEL_LDS_BYTES"]
+    for rate, N, B in ((16000, 512, 80), (22050, 2048, 128)):
+        # a hop longer by one is a span longer by waves - 1 floats, a window longer by one is two floats more: one of three
+        # neighbouring windows lets the longest staged hop meet the budget to the byte
+        W = next(w for w in (N, N - 1, N - 2) if (budget - full_mel((rate, N, w, 1, B))[2]) % (4 * (waves - 1)) == 0)
+        at_one = full_mel((rate, N, W, 1, B))
+        assert at_one[0] == 1
+        last = 1 + (budget - at_one[2]) // (4 * (waves - 1))
+        assert 2 < last < 65536
+        for H, staged in ((last - 1, 1), (last, 1), (last + 1, 0)):
+            want = full_mel((rate, N, W, H, B), 6, 2, 7)
+            assert lib_mel((rate, N, W, H, B), 6, 2, 7) == want and want[0] == staged and (want[1] > 0) == bool(staged), (N, H, want)
+            assert want[2] == budget - 4 * (waves - 1) * (last - H) if staged else want[2] < at_one[2]
+    # a front: the window and the triangles change tables alone, everything else is the kernel's
+    assert lib_mel(cfg, front=make_front()) == full_mel(cfg, front=make_front()) == lib_mel(cfg) and lib_mel(cfg)[4] == 0
+    for kw, in_kernel in ((dict(window="povey"), 0), (dict(window="rectangular"), 0), (dict(reflect=True), 1), (dict(remove_dc=True), 1),
+                          (dict(preemphasis=0.97), 1), (dict(gain=32768.0), 1), (dict(gain=0.5), 1), (dict(window="hamming", remove_dc=True), 1)):
+        want = full_mel(cfg, front=make_front(**kw))
+        assert lib_mel(cfg, front=make_front(**kw)) == want and want[4] == in_kernel, (kw, want)
+    got = lib_mel(cfg, front=make_front(triangles="mel"))  # (a bank of its own: its size is the front's tables')
+    rate, N, W, H, B = cfg
+    assert got[4] == 0 and got[5] == sparse_weights(front_tables(rate, N, W, B, triangles="mel")[2]) != lib_mel(cfg)[5]
+    assert got[:2] == [1, (waves - 1) * H + W] and got[2] - lib_mel(cfg)[2] == 4 * (got[5] - lib_mel(cfg)[5]) and got[3] == 1
+
+
+def test_route_sweep_fnorm():
+    """(F | 1) * B on both sides of NVH_FNORM_DATA_FLOATS = 19952 = 1247 * 16, and the work items on both sides of the 2048
+    workgroups of a launch."""
+    budget = defines("fnorm_dev.h")["NVH_FNORM_DATA_FLOATS"]
+    for (F, B), resident in (((1246, 16), 1), ((1247, 16), 1), ((1248, 16), 0), ((1245, 16), 1), ((77, 256), 1), ((78, 256), 0),
+                             ((19951, 1), 1), ((19952, 1), 0), ((1, 256), 1), ((1 << 24, 1), 0)):
+        assert ((F | 1) * B <= budget) == bool(resident)
+        for rows, channels in ((1, 1), (2048, 1), (2049, 1), (1024, 2), (683, 3), (5, 65535)):
+            want = full_fnorm(F, B, rows, channels)
+            assert lib_fnorm(F, B, rows, channels) == want and want[0] == resident and want[2] == min(rows * channels, 2048), (F, B, rows, want)
+    assert full_fnorm(1247, 16, 1)[1] == 4 * (528 + budget) == defines("fnorm_dev.h")["NVH_FNORM_LDS_BYTES"]
+
+
+def test_routes_return_the_rows_calls_argument_errors():
+    """The exports run the rows calls' own checks on the descriptor: a bad descriptor is the same error, without a context."""
+    from nvorbis_amd import native
+    from tests.test_mel_front_plan import make_front
+    from tests.test_mel_plan import make_desc
+    lib, out = native.lib(), (C.c_int64 * 6)()
+    no_ctx = lambda rc: native.ERR_NO_GPU if rc == native.OK else rc  # (what the rows call answers without a context)
+    rs = lambda **kw: native.ResampleDesc(**dict(dict(in_rate=44100, out_rate=16000, rows=2, channels=1, format=native.PCM_F32, length=9), **kw))
+    for d, rc in ((rs(channels=0), native.ERR_ARGUMENT), (rs(format=7), native.ERR_ARGUMENT), (rs(length=(1 << 48) + 1), native.ERR_ARGUMENT),
+                  (rs(in_rate=1, out_rate=4097), native.ERR_UNSUPPORTED), (rs(), native.OK), (rs(rows=0), native.OK)):
+        z = [(C.c_int64 * 2)() for _ in range(3)]
+        assert lib.nvh_resample_route(C.byref(d), out) == rc and lib.nvh_resample_rows(None, C.byref(d), 8, 8, z[0], z[1], z[2], None, None) == no_ctx(rc)
+    assert lib.nvh_resample_route(None, out) == lib.nvh_resample_route(C.byref(rs()), None) == native.ERR_ARGUMENT
+    for d, f, rc in ((make_desc(n_fft=100), None, native.ERR_ARGUMENT), (make_desc(rows=1, channels=0, frames=1), None, native.ERR_ARGUMENT),
+                     (make_desc(rows=1, channels=1, frames=1), make_front(gain=0.0), native.ERR_ARGUMENT),
+                     (make_desc(rows=1, channels=1, frames=1, src_length=1), make_front(reflect=True), native.ERR_ARGUMENT),
+                     (make_desc(rows=1 << 30, channels=65535, frames=1 << 40), None, native.ERR_ARGUMENT),
+                     (make_desc(rows=1, channels=1, frames=1), None, native.OK)):
+        fp = None if f is None else C.byref(f)
+        assert lib.nvh_mel_route(C.byref(d), fp, out) == rc and lib.nvh_mel_rows_front(None, C.byref(d), fp, 8, 8, None) == no_ctx(rc)
+    assert lib.nvh_mel_route(None, None, out) == lib.nvh_mel_route(C.byref(make_desc()), None, None) == native.ERR_ARGUMENT
+    for d, rc in ((make_fdesc("mean", bands=0), native.ERR_ARGUMENT), (make_fdesc(7), native.ERR_ARGUMENT),
+                  (make_fdesc("mean_var", eps=0.0), native.ERR_ARGUMENT), (make_fdesc("peak", rows=3, frames=4, bands=2), native.OK)):
+        assert lib.nvh_fnorm_route(C.byref(d), out) == rc and lib.nvh_fnorm_rows(None, C.byref(d), 8, 8, None) == no_ctx(rc)
+    assert lib.nvh_fnorm_route(None, out) == lib.nvh_fnorm_route(C.byref(make_fdesc()), None) == native.ERR_ARGUMENT
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the per-row block (nvh_internal.h: RowBlock) of the three calls: three calls queued with no wait between them, of 3, 700 and 5
+# rows.  700 rows outgrow the block's first size class, so the second call gives the image and the device copy back and takes
+# larger ones while the first call's work may still be in flight, and the third writes its image behind the second's copy.  A
+# context of its own: the block starts empty.  Every call has its own per-row arrays, source and destination; the 700 rows repeat
+# eight distinct ones, so that the reference is eight rows of the kernels' numpy rules.
+# ---------------------------------------------------------------------------------------------------------------------------
+
+BLOCK_CALLS = (3, 700, 5)
+
+
+def block_calls():
+    """Per call, which of eight distinct rows every row repeats: [0, 1, 2], 700 at random (every one among them), [7, 3, 5, 4, 6]."""
+    rng = np.random.default_rng(700)
+    idx = [np.arange(3), np.concatenate([np.arange(8), rng.integers(0, 8, 692)]), np.array([7, 3, 5, 4, 6])]
+    assert tuple(len(i) for i in idx) == BLOCK_CALLS
+    return idx
+
+
+def run_block_calls(launch, X, R, sent=fnr.SENT):
+    """launch(ctx, rows, d_src, d_dst, idx) queues one call; X[k] the distinct rows' sources, R[k] their expected outputs (float32).
+    The three calls back to back, one wait, every destination compared bit for bit and its tail for the sentinel."""
+    torch = _torch()
+    import nvorbis_amd as nv
+    ctx = nv.Context(0)
+    try:
+        idx = block_calls()
+        per = int(np.prod(R.shape[1:]))
+        src = [torch.from_numpy(np.ascontiguousarray(X[i])).cuda() for i in idx]
+        dst = [torch.full((len(i) * per + 64,), float(sent), dtype=torch.float32, device="cuda") for i in idx]
+        torch.cuda.synchronize()
+        for i, s, d in zip(idx, src, dst):
+            launch(ctx, len(i), s.data_ptr(), d.data_ptr(), i)
+        ctx.synchronize()
+        for call, (i, d) in enumerate(zip(idx, dst)):
+            got = d.cpu().numpy()
+            assert (got[len(i) * per:] == sent).all(), (call, "written behind the destination")
+            want = np.ascontiguousarray(R[i]).reshape(len(i), per)
+            bad = np.argwhere((got[:len(i) * per].reshape(len(i), per).view(np.uint32) != want.view(np.uint32)).any(axis=1))[:, 0]
+            assert not len(bad), (call, len(bad), [(int(r), int(i[r])) for r in bad[:6]])
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_row_block_resample():
+    from nvorbis_amd import native
+    fi, fo, T, S = 3, 2, 40, 110
+    L, M, half, _ = rule_plan(fi, fo)
+    rows = []
+    for start, valid in ((0, T), (1, T), (2 ** 33 + 1, 17), (5, 0), (77, 1), (2 ** 20, T - 1), (3, T), (40, 23)):
+        origin = max(0, start * M // L - half + 1)
+        assert not valid or (start + valid - 1) * M // L + half + 1 - origin <= S
+        rows.append((origin, start, valid))
+    X = (np.random.default_rng(40).uniform(-1.2, 1.2, size=(8, S)) * 0.05).astype(np.float32)
+    R = np.zeros((8, T), np.float32)  # (zeros behind `valid`)
+    for k, (origin, start, valid) in enumerate(rows):
+        R[k, :valid] = rsr.rule_outputs(X[k], origin, fi, fo, start, valid)[0]
+
+    def launch(ctx, n, d_src, d_dst, idx):
+        desc = native.ResampleDesc(in_rate=fi, out_rate=fo, rows=n, channels=1, format=native.PCM_F32, length=T, src_length=S, src_row_stride=S,
+                                   src_time_stride=1, src_chan_stride=0, dst_row_stride=T, dst_time_stride=1, dst_chan_stride=0)
+        ctx.resample_rows(desc, d_src, d_dst, *([rows[k][j] for k in idx] for j in range(3)))
+
+    run_block_calls(launch, X, R)
+
+
+@pytest.mark.gpu
+def test_row_block_mel():
+    from tests.test_mel_plan import make_desc, rule_frames, rule_mel, rule_power, rule_scale
+    rate, N, W, H, B, frames = 8000, 64, 64, 16, 8, 3
+    S = (frames - 1) * H + W
+    tw, win, fb = lib_tables(rate, N, W, B)
+    valid = [S, 0, 50, S - 1, 1, 64, 33, S]
+    X = np.random.default_rng(64).uniform(-1, 1, (8, S)).astype(np.float32)
+    u = np.concatenate([rule_frames(X[k], valid[k], 0, frames, N, W, H, win) for k in range(8)])
+    R = rule_scale(rule_mel(rule_power(u, tw), fb).reshape(8, frames, B), "ln", 1e-10)
+
+    def launch(ctx, n, d_src, d_dst, idx):
+        desc = make_desc(rate, N, W, B, hop=H, scale="ln", rows=n, channels=1, frames=frames, first=0, src_length=S, src_row_stride=S,
+                         src_time_stride=1, src_chan_stride=0, dst_row_stride=frames * B, dst_chan_stride=0, dst_frame_stride=B, dst_band_stride=1)
+        ctx.mel_rows(desc, d_src, d_dst, [valid[k] for k in idx])
+
+    run_block_calls(launch, X, R)
+
+
+@pytest.mark.gpu
+def test_row_block_fnorm():
+    F, B = 5, 3
+    vf = [5, 0, 1, 4, 2, 5, 3, 1]
+    X = normal_features(53, (8, 1, F, B))
+    R = rule_fnorm(X, vf, "mean_var", "band", **fnr.PARAMS)
+
+    def launch(ctx, n, d_src, d_dst, idx):
+        P = fnr.PARAMS
+        desc = make_fdesc("mean_var", "band", rows=n, channels=1, frames=F, bands=B, eps=P["eps"], pad_value=P["pad_value"], range=P["peak_range"],
+                          offset=P["peak_offset"], gain=P["peak_gain"], src_row_stride=F * B, src_chan_stride=0, src_frame_stride=B, src_band_stride=1,
+                          dst_row_stride=F * B, dst_chan_stride=0, dst_frame_stride=B, dst_band_stride=1)
+        ctx.fnorm_rows(desc, d_src, d_dst, [vf[k] for k in idx])
+
+    run_block_calls(launch, X, R)

@@ -883,6 +883,93 @@ int nvh_fnorm_rows(nvh_ctx *ctx, const nvh_fnorm_desc *desc, const float *d_src,
  * nvh_fnorm_rows returns for the descriptor alone (no buffer or array is looked at). */
 int nvh_fnorm_route(const nvh_fnorm_desc *desc, int64_t *out);
 
+/* ---- cepstra and deltas of features: a DCT-II over the bands with an optional lifter, and delta / delta-delta columns ----
+ * Features in, features out: every value is a pure function of a few frames of one (row, channel) of the input and of that row's
+ * frame count; nothing is carried from call to call, and neither nvh_mel_rows nor nvh_fnorm_rows takes part (the stage sits
+ * between them: MFCCs as Kaldi's compute-mfcc-feats and torchaudio.transforms.MFCC make them, deltas as Kaldi's add-deltas and
+ * torchaudio.functional.compute_deltas).  Everything on the device is f32 with separately rounded operations (fl(.) below; no
+ * fused multiply-add); every table is computed in double on the host and rounded once to f32 (fl32(.)).  THE RULE (about 40
+ * lines of numpy reproduce it bit for bit):
+ *   Input.  x[i, c, f, b] for row i < rows, channel c < channels, frame f < F, band b < B, and vf[i] in [0, F], the number of
+ *     counted frames of row i: valid_frames[i], or F for every row when valid_frames is NULL.  B in [1, 256], F in [0, 2^24],
+ *     channels in [1, 65535], rows >= 0.  Inputs are finite; anything else gives unspecified values (it is not an error, and
+ *     nothing faults).
+ *   Parameters.  transform: NVH_CEP_NONE (then K = B, `ceps` must say so, and c = x, the input's bits) or NVH_CEP_DCT2 with
+ *     ceps K in [1, B].  dct_norm: NVH_CEP_ORTHO or NVH_CEP_PLAIN.  lifter Lf: a finite f32 >= 0; 0: none.  order o in {0, 1, 2}.
+ *     window N in [1, 8].  dct_norm, lifter and window are checked whatever transform and order are.  The output has
+ *     Q = (1 + o) * K columns, and Q <= 256 (so that nvh_fnorm_rows takes the result).  reserved is 0.  NVH_ERR_ARGUMENT for
+ *     anything else; there is no NVH_ERR_UNSUPPORTED case.
+ *   Tables.  D[k][b] = fl32(w_k * lift_k * cos(pi * (b + 0.5) * k / B)) for k < K, b < B, in double and in this order of
+ *     operations: the product (w_k * lift_k) times the cosine of ((pi * (b + 0.5)) * k) / B.  NVH_CEP_ORTHO: w_0 = sqrt(1 / B),
+ *     w_k = sqrt(2 / B) for k > 0 -- Kaldi's DCT matrix, torchaudio's norm="ortho".  NVH_CEP_PLAIN: w_k = 2 for every k --
+ *     torchaudio's norm=None.  lift_k = 1 + (0.5 * Lf) * sin((pi * k) / Lf), Kaldi's cepstral_lifter; 1 when Lf = 0.  The lifter
+ *     is folded into the table: Kaldi multiplies the cepstra by lift_k afterwards, which is the same mathematics and one more
+ *     rounding.
+ *     Delta scales, with d = 2 * sum_{i = 1 .. N} i^2 (an integer):  s_1[j] = fl32(j / d) for j = -N .. N;  s_2[j] = fl32(n_j /
+ *     d^2) for j = -2N .. 2N, n_j = the sum over i of i * (j - i) with both |i| <= N and |j - i| <= N (an integer): the full
+ *     convolution of s_1 with itself, taken in double as one division of integers and rounded once.
+ *   Cepstra.  c[f][k] for every f < F: acc = +0; for b rising over all B: acc = fl(acc + fl(x[f][b] * D[k][b])).  One
+ *     accumulator.
+ *   Deltas.  For order m = 1 .. o and frame f < n = vf[i]: acc = +0; for j rising over the j in [-m N, m N] with s_m[j] != 0:
+ *     acc = fl(acc + fl(c[clamp(f + j, 0, n - 1)][k] * s_m[j])).  This is Kaldi's composite filter with the edge frames repeated:
+ *     one pass over the cepstra, never a delta of computed deltas.  First-order values are compute_deltas' with its replicate
+ *     padding; second-order values differ from torchaudio's twice-applied form only in the 2N frames at each end (there the
+ *     second application sees deltas of repeated frames, the composite filter repeated cepstra).  For f >= n the delta columns
+ *     are +0.
+ *   Output.  y[i, c, f, m * K + k], m = 0 .. o: the statics first, then the deltas, then the delta-deltas -- Kaldi's column
+ *     order.  The static columns are written for every f < F: the pad frames' statics are the transform of whatever x holds there.
+ *
+ * nvh_cep_check: NVH_OK or NVH_ERR_ARGUMENT for the descriptor's numbers.  Host only.
+ * nvh_cep_plan: nvh_cep_check, and the table sizes: *dct_count = K * B (0 under NVH_CEP_NONE), *scale_count = 6 N + 2.  Host
+ *   only; every pointer is required.
+ * nvh_cep_tables: the tables exactly as the kernel uses their values -- D row after row (k, then b), and the scales, s_1's 2 N + 1
+ *   then s_2's 4 N + 1.  Host only.  Both counts are set even when a cap is too small (NVH_ERR_ARGUMENT then); a table whose
+ *   pointer is NULL with cap 0 is left out.
+ * nvh_cep_rows: asynchronous on the context's HIP stream.  x[i, c, f, b] lies at d_src + i * src_row_stride + c *
+ *   src_chan_stride + f * src_frame_stride + b * src_band_stride, y[i, c, f, q] at d_dst + i * dst_row_stride + c *
+ *   dst_chan_stride + f * dst_frame_stride + q * dst_col_stride (f32 elements): [N, C, Q, F] and [N, C, F, Q] are stride
+ *   choices, on each side independently.  Out of place only: any overlap of the two buffers is the caller's error and gives
+ *   unspecified values.  valid_frames: NULL, or a host array of one int64 per row, read during the call and uploaded in one
+ *   copy.  The device tables are cached per context and parameter set.  Errors, before any device is touched and in this order:
+ *   NVH_ERR_ARGUMENT for no descriptor; a transform, dct_norm, order or window that is none of the above; rows, channels, F or B
+ *   outside the limits; a K outside [1, B], or other than B under NVH_CEP_NONE; Q above 256; a lifter that is negative or not
+ *   finite; a reserved word that is not 0; a missing buffer with rows and F above 0; a valid_frames[i] outside [0, F]; more than
+ *   2^63 - 1 work items (rows * channels * tiles).  Then NVH_ERR_NO_GPU for no context.
+ *   The kernel: a workgroup takes NVH_CEP_FRAMES consecutive frames of one (row, channel) at a time, with o * N more frames on
+ *   each side (clamped as the rule clamps); it stages them in LDS, computes their cepstra into LDS, forms the deltas from there
+ *   and writes the Q columns along the destination's smaller stride.  The DCT table lies in LDS where it fits the workgroup's
+ *   80 KB beside the frames, and is read through the caches where it does not. */
+#define NVH_CEP_NONE 0
+#define NVH_CEP_DCT2 1
+#define NVH_CEP_ORTHO 0
+#define NVH_CEP_PLAIN 1
+#define NVH_CEP_FRAMES 24
+#define NVH_CEP_MAX_WINDOW 8
+typedef struct nvh_cep_desc {
+  int32_t transform, dct_norm; /* NVH_CEP_* */
+  int32_t order;               /* o: 0 statics alone, 1 + deltas, 2 + delta-deltas */
+  int32_t window;              /* N */
+  int32_t rows;                /* rows of the batch */
+  int32_t channels;            /* channels per row */
+  int32_t frames;              /* F: frames per row and channel */
+  int32_t bands;               /* B */
+  int32_t ceps;                /* K */
+  float lifter;                /* Lf; 0: none */
+  int32_t reserved[2];         /* 0 */
+  int64_t src_row_stride, src_chan_stride, src_frame_stride, src_band_stride; /* in f32 elements */
+  int64_t dst_row_stride, dst_chan_stride, dst_frame_stride, dst_col_stride;  /* in f32 elements */
+} nvh_cep_desc;
+int nvh_cep_check(const nvh_cep_desc *desc);
+int nvh_cep_plan(const nvh_cep_desc *desc, int64_t *dct_count, int64_t *scale_count);
+int nvh_cep_tables(const nvh_cep_desc *desc, float *dct, float *scales, int64_t dct_cap, int64_t scale_cap, int64_t *dct_count,
+                   int64_t *scale_count);
+int nvh_cep_rows(nvh_ctx *ctx, const nvh_cep_desc *desc, const float *d_src, float *d_dst, const int64_t *valid_frames);
+/* Diagnostics (like nvh_resample_route; the values are not part of the ABI): what nvh_cep_rows would launch for `desc`, on the
+ * host -- no context, no GPU.  out[4]: the DCT table staged in LDS (0: read through the caches, or no table at all under
+ * NVH_CEP_NONE), bytes of dynamic LDS, workgroups, tiles per (row, channel).  Returns what nvh_cep_rows returns for the
+ * descriptor alone (no buffer or array is looked at). */
+int nvh_cep_route(const nvh_cep_desc *desc, int64_t *out);
+
 /* ---- multi-GPU: the gather of the file-parallel corpus transcode (SURVEY 8 e) ----
  * StreamDecoder holds per-stream state only (StreamDecoder.cs:35-39), so a corpus shards by file: every process decodes its
  * files on its own GPU (one nvh_ctx per process) and the PCM is gathered on one of them -- the path's one collective, through

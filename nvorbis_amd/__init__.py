@@ -24,4 +24,4 @@ if _os.environ.get("NVH_HW_QUEUES"):  # the same through the environment: NVH_HW
 
 from .native import NvhError, lib, lib_path  # noqa: F401
 from .reader import Batch, Comm, Context, PacketArray, Stream, StreamDecoder, VorbisReader, demux_ogg, demux_ogg_array, ogg_stream_count, wave_channel_map  # noqa: F401
-from .clips import decode_clip_features, decode_clip_rows, decode_clips, kaldi_fbank_keywords  # noqa: F401
+from .clips import cep_desc, decode_clip_features, decode_clip_rows, decode_clips, kaldi_fbank_keywords, kaldi_mfcc_keywords  # noqa: F401

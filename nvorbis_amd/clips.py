@@ -831,12 +831,78 @@ def fnorm_desc(normalize=None, normalize_axis="band", norm_eps=1e-5, pad_value=0
     return d
 
 
+_CEP_NORMS = {"ortho": native.CEP_ORTHO, None: native.CEP_PLAIN}
+
+
+def cep_desc(cepstra=None, dct_norm="ortho", lifter=0.0, deltas=0, delta_window=2, frames=0, bands=1):
+    """A native.CepDesc with the rule's numbers filled in (include/nvorbis_hip.h: nvh_cep_rows), checked on the host: ValueError for
+    anything outside the rule's limits.  cepstra: None (no transform: the bands themselves are the static columns) or the number K
+    of DCT-II coefficients, 1 <= K <= bands.  dct_norm: "ortho" (Kaldi's matrix, torchaudio's norm="ortho") or None (torchaudio's
+    norm=None).  lifter: Kaldi's cepstral_lifter, 0 for none.  deltas: 0, 1 or 2 orders of delta columns over a window of
+    delta_window frames on each side (1 .. 8).  (1 + deltas) * K columns come out, at most 256.  Every number is checked whatever
+    the others are.  rows, channels and the strides are left 0 for the caller."""
+    bands = _int_in("bands", bands, 1, 256)
+    frames = _int_in("frames", frames, 0, 2 ** 24)
+    ceps = bands if cepstra is None else _int_in("cepstra", cepstra, 1, bands)
+    if dct_norm is not None and (not isinstance(dct_norm, str) or dct_norm not in _CEP_NORMS):
+        raise ValueError("dct_norm must be 'ortho' or None, not %r" % (dct_norm,))
+    with np.errstate(over="ignore"):
+        l32 = np.float32(_real("lifter", lifter, False))
+    if not np.isfinite(l32) or not l32 >= 0:
+        raise ValueError("lifter must be a finite f32 >= 0 (0: none), not %r" % (lifter,))
+    deltas = _int_in("deltas", deltas, 0, 2)
+    delta_window = _int_in("delta_window", delta_window, 1, native.CEP_MAX_WINDOW)
+    if (1 + deltas) * ceps > 256:
+        raise ValueError("(1 + deltas) * %d columns are more than 256" % ceps)
+    d = native.CepDesc(transform=native.CEP_NONE if cepstra is None else native.CEP_DCT2, dct_norm=_CEP_NORMS[dct_norm], order=deltas,
+                       window=delta_window, channels=1, frames=frames, bands=bands, ceps=ceps, lifter=float(l32))
+    rc = native.lib().nvh_cep_check(C.byref(d))
+    if rc == native.ERR_ARGUMENT:
+        raise ValueError("the cepstral parameters are outside the rule's limits (include/nvorbis_hip.h)")
+    native.check(rc, "nvh_cep_check")
+    d.channels = 0
+    return d
+
+
+def cep_tables(bands, cepstra=None, dct_norm="ortho", lifter=0.0, delta_window=2):
+    """The tables of nvh_cep_tables as float32 arrays, exactly the values k_cep_rows uses: (D (K, bands), or None without a
+    transform; s_1 (2 N + 1,); s_2 (4 N + 1,))."""
+    d = cep_desc(cepstra, dct_norm, lifter, 0, delta_window, 0, bands)
+    d.channels = 1
+    n = d.window
+    dct = np.zeros(d.ceps * d.bands if cepstra is not None else 0, np.float32)
+    scales = np.zeros(6 * n + 2, np.float32)
+    counts = [C.c_int64(0), C.c_int64(0)]
+    native.check(native.lib().nvh_cep_tables(C.byref(d), dct.ctypes.data if dct.size else None, scales.ctypes.data, dct.size, scales.size,
+                                             C.byref(counts[0]), C.byref(counts[1])), "nvh_cep_tables")
+    return (dct.reshape(d.ceps, d.bands) if cepstra is not None else None), scales[:2 * n + 1], scales[2 * n + 1:]
+
+
+def kaldi_mfcc_keywords(rate, num_ceps=13, num_mel_bins=23, cepstral_lifter=22.0, frame_length_ms=25.0, frame_shift_ms=10.0, low_freq=20.0,
+                        high_freq=0.0, preemphasis=0.97, remove_dc=True, window="povey"):
+    """The keywords that make decode_clip_features compute Kaldi's MFCCs (compute-mfcc-feats --use-energy=false,
+    torchaudio.compliance.kaldi.mfcc with use_energy=False) at `rate` Hz, under Kaldi's own option names: kaldi_fbank_keywords(rate,
+    ...) with Kaldi's MFCC defaults (23 mel bins), plus cepstra=num_ceps, dct_norm="ortho" (Kaldi's DCT matrix) and
+    lifter=cepstral_lifter.  The lifter is folded into the DCT table where Kaldi multiplies afterwards (one rounding apart).
+    C0 is the DCT's coefficient 0: the energy column (use_energy, Kaldi's default) is out of scope, because the mel stage does
+    not emit the frame's raw energy; so is dither.  add-deltas is deltas=2, delta_window=2 beside the dict."""
+    kw = kaldi_fbank_keywords(rate, frame_length_ms, frame_shift_ms, num_mel_bins, low_freq, high_freq, preemphasis, remove_dc, window)
+    num_ceps = _int_in("num_ceps", num_ceps, 1, _int_in("num_mel_bins", num_mel_bins, 1, 256))
+    with np.errstate(over="ignore"):
+        l32 = np.float32(_real("cepstral_lifter", cepstral_lifter, False))
+    if not np.isfinite(l32) or not l32 >= 0:
+        raise ValueError("cepstral_lifter must be a finite f32 >= 0 (0: none), not %r" % (cepstral_lifter,))
+    kw.update(cepstra=num_ceps, dct_norm="ortho", lifter=float(cepstral_lifter))
+    return kw
+
+
 def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=512, win_length=400, hop=160, n_mels=80, f_min=0.0,
                          f_max=None, mel_scale="htk", norm=None, scale="ln", floor=1e-10, center=True, band_major=True, mix=None,
                          channel_map=None, ctx=None, device=0, batch_frames=4096, gpu_parse=True, device_out=True,
                          return_clipped=False, normalize=None, normalize_axis="band", norm_eps=1e-5, pad_value=_PAD_DEFAULT,
                          peak_range=80.0, peak_offset=40.0, peak_gain=1 / 40, mask_padding=True, window="hann", remove_dc=False,
-                         preemphasis=0.0, sample_gain=1.0, pad_mode="constant", mel_triangles="hz", frame_count="n_fft"):
+                         preemphasis=0.0, sample_gain=1.0, pad_mode="constant", mel_triangles="hz", frame_count="n_fft", cepstra=None,
+                         dct_norm="ortho", lifter=0.0, deltas=0, delta_window=2):
     """Log-mel features of fixed-length rows: decode_clip_rows(clips, length, starts, sample_format="f32", layout="planar",
     device_out=True, sample_rate=sample_rate, ...) as it is, then nvh_mel_rows over the buffer the planar kernels wrote (the one
     plane of mix="mono").  Returns (features, valid, valid_frames); with return_clipped=True ((features, valid, valid_frames),
@@ -871,6 +937,16 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
     frame behind the last counted one reads one counted sample through the mirror; the counted frames stay a prefix).  Without
     sample_rate all clips must share one rate (ValueError otherwise); with it, clips at other
     rates are resampled as decode_clip_rows does.  Every keyword is checked, with ValueError, before any device is touched.
+
+    cepstra, deltas: a stage between the mel bank and the normalisation, nvh_cep_rows (include/nvorbis_hip.h states its rule; with
+    the five keywords of this paragraph left away nothing new runs).  cepstra=K: the first K coefficients of a DCT-II over the
+    bands replace them (MFCCs where scale is "ln" or "db"), with dct_norm "ortho" (Kaldi, torchaudio's norm="ortho") or None
+    (torchaudio's norm=None) and lifter = Kaldi's cepstral_lifter folded into the table (0: none).  deltas=1 or 2: delta and
+    delta-delta columns over delta_window frames on each side (Kaldi's add-deltas; order 1 is torchaudio's compute_deltas), from
+    the row's counted frames alone with the edge frames repeated -- the counted frames are the first valid_frames[i] with
+    mask_padding=True, all of them without -- and +0 behind them.  The features then have Q = (1 + deltas) * K columns in place
+    of n_mels (K = n_mels without cepstra), statics first; Q is at most 256.  The mel stage writes a temporary (N, C, n_mels, F)
+    tensor, and the normalisation runs over the Q columns as it does over bands.  kaldi_mfcc_keywords() returns Kaldi's set.
 
     normalize: the last stage, nvh_fnorm_rows in place on the features (include/nvorbis_hip.h states its rule).  "mean": the mean
     over the row's counted frames is subtracted, per band with normalize_axis="band" (utterance CMVN, NeMo's per_feature) or one
@@ -918,7 +994,10 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
     if not isinstance(mask_padding, (bool, np.bool_)):
         raise ValueError("mask_padding must be True or False, not %r" % (mask_padding,))
     pad_given = pad_value is not _PAD_DEFAULT
-    ndesc = fnorm_desc(normalize, normalize_axis, norm_eps, pad_value, peak_range, peak_offset, peak_gain, 0, B)
+    cdesc = cep_desc(cepstra, dct_norm, lifter, deltas, delta_window, 0, B)  # (checked whether the stage runs or not)
+    run_cep = cepstra is not None or cdesc.order > 0
+    Q = (1 + cdesc.order) * cdesc.ceps if run_cep else B
+    ndesc = fnorm_desc(normalize, normalize_axis, norm_eps, pad_value, peak_range, peak_offset, peak_gain, 0, Q)
     run_fnorm = normalize is not None or (bool(mask_padding) and pad_given)
     if center:
         first, F = (N_ - W) // 2 - N_ // 2, length // H + 1
@@ -935,6 +1014,8 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
         first, F = (N_ - W) // 2, (length - N_) // H + 1
     if run_fnorm and F > 2 ** 24:
         raise ValueError("normalize takes at most 2**24 frames per row (%d)" % F)
+    if run_cep and F > 2 ** 24:
+        raise ValueError("cepstra and deltas take at most 2**24 frames per row (%d)" % F)
     begins = np.arange(F, dtype=np.int64) * H + first
     import torch
     with _context(ctx, device) as ctx:
@@ -943,8 +1024,9 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
         mono = mix is not None
         n = rows.shape[0]
         och = 1 if mono else rows.shape[1]
-        shape = (n, och, B, F) if band_major else (n, och, F, B)
+        shape = (n, och, Q, F) if band_major else (n, och, F, Q)
         feats = torch.empty(shape, dtype=torch.float32, device=rows.device)
+        mel_out, mel_major = (torch.empty((n, och, B, F), dtype=torch.float32, device=rows.device), True) if run_cep else (feats, band_major)
         if n and och:
             desc.rows, desc.channels, desc.frames, desc.first, desc.src_length = n, och, F, first, length
             if length:
@@ -952,18 +1034,26 @@ def decode_clip_features(clips, length, starts=None, *, sample_rate=None, n_fft=
                 desc.src_chan_stride = 0 if mono else rows.stride(1)
             else:  # no samples at all: every frame is the transform of zeros (the source is never read)
                 rows = torch.zeros(1, dtype=torch.float32, device=rows.device)
-            desc.dst_row_stride, desc.dst_chan_stride = feats.stride(0), feats.stride(1)
-            desc.dst_band_stride, desc.dst_frame_stride = (feats.stride(2), feats.stride(3)) if band_major else (feats.stride(3), feats.stride(2))
+            desc.dst_row_stride, desc.dst_chan_stride = mel_out.stride(0), mel_out.stride(1)
+            desc.dst_band_stride, desc.dst_frame_stride = (mel_out.stride(2), mel_out.stride(3)) if mel_major else (mel_out.stride(3), mel_out.stride(2))
             torch.cuda.current_stream(rows.device).synchronize()  # (a gather of several setups' rows runs on torch's stream)
-            ctx.mel_rows(desc, rows.data_ptr(), feats.data_ptr(), valid, front)
+            ctx.mel_rows(desc, rows.data_ptr(), mel_out.data_ptr(), valid, front)
         valid_frames = (np.maximum(begins, 0)[None, :] < np.minimum(begins[None, :] + W, valid[:, None])).sum(axis=1).astype(np.int64)
         if n and och:
-            if run_fnorm:  # behind k_mel_rows on the context's stream, in place
+            col_stride, frame_stride = (feats.stride(2), feats.stride(3)) if band_major else (feats.stride(3), feats.stride(2))
+            if run_cep:  # behind k_mel_rows on the context's stream, out of the temporary tensor
+                cdesc.rows, cdesc.channels, cdesc.frames = n, och, F
+                cdesc.src_row_stride, cdesc.src_chan_stride = desc.dst_row_stride, desc.dst_chan_stride
+                cdesc.src_frame_stride, cdesc.src_band_stride = desc.dst_frame_stride, desc.dst_band_stride
+                cdesc.dst_row_stride, cdesc.dst_chan_stride = feats.stride(0), feats.stride(1)
+                cdesc.dst_frame_stride, cdesc.dst_col_stride = frame_stride, col_stride
+                ctx.cep_rows(cdesc, mel_out.data_ptr(), feats.data_ptr(), valid_frames if mask_padding else None)
+            if run_fnorm:  # behind the kernels before it on the context's stream, in place
                 ndesc.rows, ndesc.channels, ndesc.frames = n, och, F
-                ndesc.src_row_stride = ndesc.dst_row_stride = desc.dst_row_stride
-                ndesc.src_chan_stride = ndesc.dst_chan_stride = desc.dst_chan_stride
-                ndesc.src_frame_stride = ndesc.dst_frame_stride = desc.dst_frame_stride
-                ndesc.src_band_stride = ndesc.dst_band_stride = desc.dst_band_stride
+                ndesc.src_row_stride = ndesc.dst_row_stride = feats.stride(0)
+                ndesc.src_chan_stride = ndesc.dst_chan_stride = feats.stride(1)
+                ndesc.src_frame_stride = ndesc.dst_frame_stride = frame_stride
+                ndesc.src_band_stride = ndesc.dst_band_stride = col_stride
                 ctx.fnorm_rows(ndesc, feats.data_ptr(), feats.data_ptr(), valid_frames if mask_padding else None)
             ctx.synchronize()
     if mono:

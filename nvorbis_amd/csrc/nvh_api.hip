@@ -113,6 +113,8 @@ extern "C" void nvh_ctx_destroy(nvh_ctx* c) {
     for (auto& kv : c->mel_cache) kv.second.free_tables();
     c->mel_rows.release();
     c->fnorm_rows.release();
+    for (auto& kv : c->cep_cache) kv.second.free_tables();
+    c->cep_rows.release();
     c->setup_cache.clear();  // streams must have been closed: they share these entries and return their buffers here
     c->pool.clear();
     c->hpool.clear();

@@ -28,6 +28,7 @@
 #include "host_slab.h"
 #include "kernels_common.h"
 #include "nvh_parse_format.h"
+#include "cep_dev.h"
 #include "fnorm_dev.h"
 #include "mel_dev.h"
 #include "resample_dev.h"
@@ -141,6 +142,12 @@ template <bool RESIDENT>
 __global__ void k_fnorm_rows(NvhFnormArgs A);
 extern template __global__ void k_fnorm_rows<true>(NvhFnormArgs);
 extern template __global__ void k_fnorm_rows<false>(NvhFnormArgs);
+
+// ... and the cepstra and deltas of features (kernels_cep.hip), with the DCT table staged in LDS or read through the caches
+template <bool STAGED>
+__global__ void k_cep_rows(NvhCepArgs A);
+extern template __global__ void k_cep_rows<true>(NvhCepArgs);
+extern template __global__ void k_cep_rows<false>(NvhCepArgs);
 
 extern thread_local int g_last_hip_error;
 
@@ -319,6 +326,13 @@ struct MelDev {  // the device tables of one parameter set (nvh_mel.hip): twiddl
 // (rate, n_fft, win_length, n_mels, mel_scale, norm, f_min, f_max, window, triangles): what the tables depend on
 typedef std::tuple<int, int, int, int, int, int, double, double, int, int> MelKey;
 
+struct CepDev {  // the device table of one parameter set (nvh_cep.hip): the DCT table as k_cep_rows reads it, then the delta scales
+  float* tab = nullptr;
+  void free_tables() const { (void)hipFree(tab); }
+};
+// (transform, bands, ceps, dct_norm, the lifter's bits, window): what the table depends on
+typedef std::tuple<int, int, int, int, uint32_t, int> CepKey;
+
 // Everything derived from a stream's headers: parsed tables on the host, their device image, kernel-selection
 // flags.  Immutable once built, so streams with byte-identical identification + setup packets (the normal case
 // inside one corpus: same encoder, same settings) share one entry per context.
@@ -374,14 +388,15 @@ struct nvh_ctx {
   bool synth_lds_attr_set = false;  // k_synth8's 160 KB dynamic-LDS opt-in was made on this context's device
   bool parse_lds_attr_set = false;  // k_parse's 80 KB dynamic-LDS opt-in was made on this context's device
   int parse_lanes = 0;              // nvh_ctx_set_parse_lanes: packets per wavefront of the GPU parser, 0 = automatic
-  // The row operations: their cached tables (resample by (L, M), like the per-n IMDCT tables; mel by parameter set), whether
+  // The row operations: their cached tables (resample by (L, M), like the per-n IMDCT tables; mel and cep by parameter set), whether
   // their kernels' 80 KB dynamic-LDS opt-in was made on this context's device, and their per-row blocks.  One block per
-  // operation, not one for all: decode_clip_features queues resample, mel and fnorm back to back, and a shared block would
+  // operation, not one for all: decode_clip_features queues resample, mel, cep and fnorm back to back, and a shared block would
   // make each call wait for the copy of the call before it, which sits in the stream behind that call's predecessor's kernel.
   std::map<std::pair<int, int>, ResampleDev> resample_cache;
   std::map<MelKey, MelDev> mel_cache;
-  bool resample_lds_attr_set = false, mel_lds_attr_set = false, fnorm_lds_attr_set = false;
-  RowBlock resample_rows, mel_rows, fnorm_rows;
+  std::map<CepKey, CepDev> cep_cache;
+  bool resample_lds_attr_set = false, mel_lds_attr_set = false, fnorm_lds_attr_set = false, cep_lds_attr_set = false;
+  RowBlock resample_rows, mel_rows, fnorm_rows, cep_rows;
 };
 
 inline int RowBlock::begin(nvh_ctx* c, size_t bytes, void** image) {

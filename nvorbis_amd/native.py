@@ -99,6 +99,23 @@ FNORM_NONE, FNORM_MEAN, FNORM_MEAN_VAR, FNORM_PEAK = 0, 1, 2, 3  # NVH_FNORM_NON
 FNORM_PER_BAND, FNORM_ALL = 0, 1                                 # NVH_FNORM_PER_BAND / _ALL
 FNORM_RESIDENT_FLOATS = 19952  # NVH_FNORM_RESIDENT_FLOATS: (F | 1) * B up to here is normalised out of LDS
 
+
+class CepDesc(C.Structure):
+    """nvh_cep_desc: transform, DCT norm, delta order and window, the shape, the cepstra's count, the lifter, and the element strides
+    of source (row, channel, frame, band) and destination (row, channel, frame, column)."""
+    _fields_ = [("transform", C.c_int32), ("dct_norm", C.c_int32), ("order", C.c_int32), ("window", C.c_int32), ("rows", C.c_int32),
+                ("channels", C.c_int32), ("frames", C.c_int32), ("bands", C.c_int32), ("ceps", C.c_int32), ("lifter", C.c_float),
+                ("reserved", C.c_int32 * 2),
+                ("src_row_stride", C.c_int64), ("src_chan_stride", C.c_int64), ("src_frame_stride", C.c_int64),
+                ("src_band_stride", C.c_int64), ("dst_row_stride", C.c_int64), ("dst_chan_stride", C.c_int64),
+                ("dst_frame_stride", C.c_int64), ("dst_col_stride", C.c_int64)]
+
+
+CEP_NONE, CEP_DCT2 = 0, 1    # NVH_CEP_NONE / _DCT2
+CEP_ORTHO, CEP_PLAIN = 0, 1  # NVH_CEP_ORTHO / _PLAIN
+CEP_FRAMES = 24              # NVH_CEP_FRAMES: consecutive frames of one (row, channel) per work item of k_cep_rows
+CEP_MAX_WINDOW = 8           # NVH_CEP_MAX_WINDOW
+
 # symbol -> (restype, argtypes); also the list tests check against the header
 _u8p, _f32p, _i64p, _i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
 _vp, _vpp, _ip = C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)
@@ -222,6 +239,12 @@ SIGNATURES = {
     "nvh_fnorm_check": (C.c_int, [C.POINTER(FnormDesc)]),
     "nvh_fnorm_rows": (C.c_int, [_vp, C.POINTER(FnormDesc), _vp, _vp, _vp]),
     "nvh_fnorm_route": (C.c_int, [C.POINTER(FnormDesc), _i64p]),
+    # cepstra and deltas of features (nvh_cep.hip)
+    "nvh_cep_check": (C.c_int, [C.POINTER(CepDesc)]),
+    "nvh_cep_plan": (C.c_int, [C.POINTER(CepDesc), _i64p, _i64p]),
+    "nvh_cep_tables": (C.c_int, [C.POINTER(CepDesc), _vp, _vp, C.c_int64, C.c_int64, _i64p, _i64p]),
+    "nvh_cep_rows": (C.c_int, [_vp, C.POINTER(CepDesc), _vp, _vp, _vp]),
+    "nvh_cep_route": (C.c_int, [C.POINTER(CepDesc), _i64p]),
     # the corpus gather through RCCL's C API (nvh_comm.hip): what a host without torch.distributed binds to
     "nvh_comm_unique_id": (C.c_int, [_vp]),
     "nvh_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),

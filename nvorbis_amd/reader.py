@@ -372,6 +372,13 @@ class Context:
         check(lib().nvh_fnorm_rows(self._h, C.byref(desc), C.c_void_p(d_src), C.c_void_p(d_dst), None if v is None else v.ctypes.data),
               "nvh_fnorm_rows")
 
+    def cep_rows(self, desc, d_src, d_dst, valid_frames=None):
+        """nvh_cep_rows: `desc` a native.CepDesc, d_src / d_dst device addresses of two buffers that do not overlap, `valid_frames`
+        None or a host sequence of desc.rows ints.  Asynchronous on the context's stream (synchronize() waits for it)."""
+        v = _row_array("cep_rows", "valid_frames holds", valid_frames, desc.rows)
+        check(lib().nvh_cep_rows(self._h, C.byref(desc), C.c_void_p(d_src), C.c_void_p(d_dst), None if v is None else v.ctypes.data),
+              "nvh_cep_rows")
+
     def close(self):
         if self._h:
             lib().nvh_ctx_destroy(self._h)

@@ -175,6 +175,23 @@ def _flat_payload(parts, torch, dev):
     return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
+def _views_to_host(arena, mine, views):
+    """{file index -> host PCM} of decode_files_to_device's result: the arena is read back once and every view that is a slice of
+    it is cut from that copy at the view's own address; a view that is a tensor of its own (a file the pass decoded again from
+    its checked packet list: another length than its arena slot) is copied by itself.  No file's place depends on another's."""
+    host = arena.cpu().numpy()
+    base, size = arena.data_ptr(), int(arena.numel())
+    local = {}
+    for i, v in zip(mine, views):
+        n = int(v.numel())
+        off, rem = divmod(v.data_ptr() - base, 4)
+        if v.is_contiguous() and rem == 0 and 0 <= off and off + n <= size:
+            local[i] = host[off:off + n]
+        else:
+            local[i] = v.cpu().numpy().reshape(-1)
+    return local
+
+
 def transcode(files, decode_fn=None, rank=0, world=1, dist=None, device="cpu", gpu=0, workers=16, to_host=True, layout="interleaved",
               mix=None):
     """Decode `files` (list of bytes) file-parallel; rank 0 returns the list of PCM arrays in file order.
@@ -193,11 +210,7 @@ def transcode(files, decode_fn=None, rank=0, world=1, dist=None, device="cpu", g
         arena, views = decode_files_to_device([files[i] for i in mine], device=gpu, workers=workers)
         local = {i: v for i, v in zip(mine, views)}
         if device == "cpu":  # host exchange (gloo): one read-back of the whole arena
-            host = arena.cpu().numpy()
-            off = 0
-            for i, v in zip(mine, views):
-                local[i] = host[off:off + v.numel()]
-                off += v.numel()
+            local = _views_to_host(arena, mine, views)
     else:
         local = {i: np.ascontiguousarray(decode_fn(files[i]), dtype=np.float32) for i in mine}
     return gather_pcm(local, len(files), rank, world, dist, device, to_host)

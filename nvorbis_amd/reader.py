@@ -216,8 +216,9 @@ def index_ogg_array(data: bytes, stream_index=0):
     total = C.c_int64(0)
     payload = C.c_int64(0)
     src = np.frombuffer(data if data else b"\0", dtype=np.uint8)
-    # heads + headers: 8 bytes per packet and the setup header; a page (>= 27 bytes of header) starts at most 255 packets, and only
-    # lacing values of 0..254 end one, so len / 27 + len / 64 is far beyond any audio stream -- the call says so if it is not
+    # heads + headers: 8 bytes per packet and the setup header.  The first guess is a packet per 48 bytes (len // 48 + 64: audio
+    # packets are longer); a file laced more densely -- a page of 27 + 255 bytes can end 255 one-byte packets -- makes the call
+    # report what it needs (NVH_ERR_ARGUMENT with the counts), and the second round runs with exactly that
     cap_n = len(data) // 48 + 64
     cap_b = min(len(data), 8 * cap_n + (1 << 16)) + 64
     # The call writes into scratch arrays of the calling thread, kept from file to file (a pool of index threads would otherwise
@@ -240,6 +241,8 @@ def index_ogg_array(data: bytes, stream_index=0):
             continue
         check(rc, "nvh_ogg_index_packets")
         break
+    else:  # the retry with the sizes the first call reported was refused for room as well: no truncated list
+        check(rc, "nvh_ogg_index_packets")
     m = n.value
     return PacketArray(pk[:max(total.value, 1)].copy(), offs[:m + 1].copy(), gran[:max(m, 1)].copy(), flags[:max(m, 1)].copy()), int(payload.value)
 

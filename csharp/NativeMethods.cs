@@ -85,6 +85,8 @@ namespace NVorbis.Hip
         [DllImport(Lib)] public static extern unsafe int nvh_stream_synth_segments_clipped(IntPtr stream, int* clipped, int cap, out int count);
         /// <summary>[frames][8] ints: block size (0 = drained tail), start, valid, total, ... of every pending frame.</summary>
         [DllImport(Lib)] public static extern unsafe int nvh_stream_pending_geometry(IntPtr stream, int* geometry, int capFrames);
+        [DllImport(Lib)] public static extern unsafe int nvh_stream_steady_groups(IntPtr stream, int* groups);
+        [DllImport(Lib)] public static extern unsafe int nvh_batch_steady_groups(IntPtr batch, int* groups);
         /// <summary>Page table of one logical Ogg stream + IPacketProvider.SeekTo over it (Ogg/PacketProvider.cs:56-295), for hosts
         /// that do not bring NVorbis' own container code.</summary>
         [DllImport(Lib)] public static extern unsafe int nvh_ogg_index_open(byte* bytes, UIntPtr len, int streamIndex, out IntPtr index);

@@ -523,6 +523,18 @@ int nvh_batch_stats(const nvh_batch *b, int64_t *out8);
 int nvh_batch_kernels(const nvh_batch *b, char *buf, int cap);
 /* The same for the batch nvh_stream_synth / nvh_stream_synth_begin launched last (the stream's own look-ahead batch). */
 int nvh_stream_kernels(const nvh_stream *s, char *buf, int cap);
+/* Diagnostics (like nvh_batch_kernels; the values are not part of the ABI): how many of the batch's groups of two frames the
+ * frame-group synthesis takes through its steady body -- two long stereo blocks between neighbours of the same size, both
+ * channels executing, nothing carried in or out -- instead of the general one.  Counted at upload from the slab headers by the
+ * test the kernel itself applies; 0 for batches the GPU parser wrote, and with NVH_NO_STEADY=1. */
+int nvh_batch_steady_groups(const nvh_batch *b, int *groups);
+/* The same for the batch nvh_stream_synth / nvh_stream_synth_begin launched last. */
+int nvh_stream_steady_groups(const nvh_stream *s, int *groups);
+/* The same for the stream's pending frames as an upload would lay them out; host-parsing streams only, needs no GPU. */
+int nvh_stream_pending_steady(const nvh_stream *s, int *groups);
+/* The same test on `frames` slab headers of sixteen 32-bit words each (groups are frames 2 g and 2 g + 1) of a stream of
+ * `channels` channels whose larger block size is block1: no stream, no GPU. */
+int nvh_steady_count(const uint32_t *headers, int frames, int channels, int block1, int *groups);
 /* Launch the synthesis kernels for a resident batch (asynchronous on the context's stream) into the destination `out`
  * describes (nvh_pcm_out, above); may be repeated, results are identical each time. */
 int nvh_batch_synth_out(nvh_batch *b, const nvh_pcm_out *out, void *d_pcm);

@@ -354,7 +354,11 @@ struct WalkFrame {
   FloorRef F;
 };
 
-template <int NT>
+// LEAN (steady groups, synth_group_steady: a floor curve on every channel, the caller checked): stage 0 peeled and unmasked -- a
+// lane without a group walks group 0 and stores nothing, so its sums need no mask; `0.0f + v` stays an add (+0 + -0 is +0) --, the
+// later stages in a loop a wavefront enters only when some lane's chain goes on (the bench's chains: 94 % one stage), and there the
+// record is read again only by the lanes that advance.  Same additions in the same order per element.
+template <int NT, bool LEAN = false>
 __device__ __forceinline__ void residue_walk_two(const WalkFrame (&W)[2], const uint32_t* __restrict__ s_lat, int tid) {
   constexpr int G = 8;
   const uint32_t* heads[2];
@@ -391,6 +395,47 @@ __device__ __forceinline__ void residue_walk_two(const WalkFrame (&W)[2], const 
 #ifdef NVH_ABL_NO_CHAIN2
     more[0] = more[1] = false;  // (ablation build: the walk without its cascade stages)
 #endif
+    if constexpr (LEAN) {
+      float v[2][G];
+#pragma unroll
+      for (int f = 0; f < 2; ++f) {
+        const char* vb = reinterpret_cast<const char*>(s_lat) + ((rec[f].y & 0xFFFu) << 2);
+        const uint2 w = *reinterpret_cast<const uint2*>(ent[f] + ((rec[f].x & 0xFFFFu) << 1) + i0[f]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          v[f][k] = *reinterpret_cast<const float*>(vb + ((w.x >> (8 * k)) & 0xFFu));
+          v[f][4 + k] = *reinterpret_cast<const float*>(vb + ((w.y >> (8 * k)) & 0xFFu));
+        }
+      }
+#pragma unroll
+      for (int f = 0; f < 2; ++f) {
+#pragma unroll
+        for (int k = 0; k < G; ++k) a[f][k] = a[f][k] + v[f][k];
+        more[f] = more[f] && (rec[f].y & 0x80000000u) != 0u;
+      }
+      while (__builtin_amdgcn_ballot_w64(more[0] | more[1]) != 0ull) {  // (uniform: the whole wavefront, or none of it)
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+          if (more[f]) rec[f] = recs[f][++o[f]];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          const char* vb = reinterpret_cast<const char*>(s_lat) + ((rec[f].y & 0xFFFu) << 2);
+          const uint2 w = *reinterpret_cast<const uint2*>(ent[f] + ((rec[f].x & 0xFFFFu) << 1) + i0[f]);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            v[f][k] = *reinterpret_cast<const float*>(vb + ((w.x >> (8 * k)) & 0xFFu));
+            v[f][4 + k] = *reinterpret_cast<const float*>(vb + ((w.y >> (8 * k)) & 0xFFu));
+          }
+        }
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          const uint32_t keep = more[f] ? 0xFFFFFFFFu : 0u;  // one mask per frame: a chain that has ended adds +0.0f
+#pragma unroll
+          for (int k = 0; k < G; ++k) a[f][k] = a[f][k] + __uint_as_float(__float_as_uint(v[f][k]) & keep);
+          more[f] = more[f] && (rec[f].y & 0x80000000u) != 0u;
+        }
+      }
+    } else
     while (more[0] | more[1]) {
       float v[2][G];
 #pragma unroll
@@ -439,7 +484,7 @@ __device__ __forceinline__ void residue_walk_two(const WalkFrame (&W)[2], const 
 #ifdef NVH_ABL_NO_FLOOR2
           if (false) {  // (ablation build: the walk without its floor multiply)
 #else
-          if (W[f].F.md[c] == 1) {
+          if (LEAN || W[f].F.md[c] == 1) {
 #endif
             float m[4];
             floor_walk_fx<4>(W[f].F.seg[c], W[f].F.tab[c], W[f].F.s_db, (int)xb, m);
@@ -1738,6 +1783,196 @@ __device__ __forceinline__ void synth_body(const NvhSynthArgs& A, float* smem NV
 #undef SY_T
 }
 
+// One emission task of a frame group (synth_group_body, synth_group_steady): the overlap-add + clip + interleave of the overlap of
+// two blocks over m samples for the group g of four compact indices -- sample times 4 g .. 4 g + 3 and m/2 - 4 - 4 g .. m/2 - 1 - 4 g
+// of every channel (kernels.hip: ola_sym).  woff / wpoff: the later block's window at its start, the earlier block's at its valid;
+// pos: the output position; aoff, astr / boff, bstr: float offset from smem and channel stride of the later block's quarter values
+// (the last m/4 of its first quarter) and of the earlier block's (the last m/4 of its third quarter).
+template <typename PCM, int LAYOUT>
+__device__ __forceinline__ void group_emit_task(const NvhSynthArgs& A, const float* smem, unsigned woff, unsigned wpoff, unsigned pos,
+                                                unsigned aoff, unsigned astr, unsigned boff, unsigned bstr, int n, int g, int nch,
+                                                int cbit, int* clipped) {
+  constexpr bool PLANAR = LAYOUT == NVH_LAYOUT_PLANAR, MONO = LAYOUT == NVH_LAYOUT_MONO;
+  const int half = n >> 1, i0 = 4 * g;
+  const float* __restrict__ w = A.windows + woff;
+  const float* __restrict__ wp = A.windows + wpoff;
+  const float4 wf = *reinterpret_cast<const float4*>(w + i0);
+  const float4 wm = *reinterpret_cast<const float4*>(w + (half - 4 - i0));
+  const float4 pf = *reinterpret_cast<const float4*>(wp + i0);
+  const float4 pm = *reinterpret_cast<const float4*>(wp + (half - 4 - i0));
+  float fwd[8], mir[8];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    if (c < nch) {
+      const float4 a = *reinterpret_cast<const float4*>(smem + aoff + c * astr + i0);
+      const float4 b = *reinterpret_cast<const float4*>(smem + boff + c * bstr + i0);
+      float4 v = make_float4(a.x * wf.x, a.y * wf.y, a.z * wf.z, a.w * wf.w);
+      const float4 tt = make_float4(b.x * pf.x, b.y * pf.y, b.z * pf.z, b.w * pf.w);
+      v.x = v.x + tt.x; v.y = v.y + tt.y; v.z = v.z + tt.z; v.w = v.w + tt.w;
+      float4 u = make_float4(-a.w * wm.x, -a.z * wm.y, -a.y * wm.z, -a.x * wm.w);
+      const float4 r = make_float4(b.w * pm.x, b.z * pm.y, b.y * pm.z, b.x * pm.w);
+      u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
+      if (!MONO && A.clip) {  // (the mono form clips the mix)
+        v.x = clip_value(v.x, clipped, cbit); v.y = clip_value(v.y, clipped, cbit);
+        v.z = clip_value(v.z, clipped, cbit); v.w = clip_value(v.w, clipped, cbit);
+        u.x = clip_value(u.x, clipped, cbit); u.y = clip_value(u.y, clipped, cbit);
+        u.z = clip_value(u.z, clipped, cbit); u.w = clip_value(u.w, clipped, cbit);
+      }
+      if constexpr (PLANAR) {  // channel-planar: the channel leaves at once (nothing is held for an interleave)
+        pcm_store_plane(reinterpret_cast<PCM*>(A.pcm) + (long long)pos + (long long)c * A.plane_stride, g, (n >> 3) - 1 - g, v, u);
+      } else {
+        fwd[c] = v.x; fwd[2 + c] = v.y; fwd[4 + c] = v.z; fwd[6 + c] = v.w;
+        mir[c] = u.x; mir[2 + c] = u.y; mir[4 + c] = u.z; mir[6 + c] = u.w;
+      }
+    }
+  }
+  PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)pos * (PLANAR || MONO ? 1 : nch);
+  if constexpr (PLANAR) {
+    // (stored per channel above)
+  } else if constexpr (MONO) {  // the mean of the channels, clipped once: one vector per half
+    pcm_store_plane(out, g, (n >> 3) - 1 - g, mono_mix2(fwd, nch, A.clip, clipped, cbit), mono_mix2(mir, nch, A.clip, clipped, cbit));
+  } else if (nch == 2) {
+    pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
+    pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
+    if constexpr (std::is_same<PCM, int16_t>::value) {  // four stereo sample times: one 16-byte store where aligned
+      pcm_store4x2(of, fwd);
+      pcm_store4x2(om, mir);
+    } else {
+      pcm_store4(of, fwd[0], fwd[1], fwd[2], fwd[3]);
+      pcm_store4(of + 1, fwd[4], fwd[5], fwd[6], fwd[7]);
+      pcm_store4(om, mir[0], mir[1], mir[2], mir[3]);
+      pcm_store4(om + 1, mir[4], mir[5], mir[6], mir[7]);
+    }
+  } else {
+    pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + g, fwd[0], fwd[2], fwd[4], fwd[6]);
+    pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + ((n >> 3) - 1 - g), mir[0], mir[2], mir[4], mir[6]);
+  }
+}
+
+#ifdef NVH_DEBUG
+// profiling build: shader-clock stamps of thread 0 in the row of the group's first frame (tools/dbg_phase_group.py): 0 entry,
+// 1 slabs + constants arrived, 2 / 3 the frames' walks, 4 table + barrier, 5 transform of wavefront 0, 6 staging drained, 7 emitted
+#define GR_T(k) do { if (dbg && tid == 0 && fa < A.nframes) dbg[(long long)fa * 24 + (k)] = clock64(); } while (0)
+#else
+#define GR_T(k) do { } while (0)
+#endif
+
+// The lean body of a STEADY group of two (nvh_format.h: nvh_steady_pair -- two long stereo blocks of n = 1 << LD = block1 samples
+// between neighbours of that size, both channels with a floor curve, the walk's common shape, the emission flags the host sets by
+// position): synth_group_body's arithmetic on the same LDS map with everything the predicate fixes folded in.  H: the two slabs'
+// header words, fetched by scalar loads next to the DMA -- every header field, floor reference and overlap parameter is a
+// register read, where the general body goes to the slab's LDS image and back through readfirstlane.  No overlap table: in a
+// steady group overlap j spans m = n samples, its windows and PCM position are header words 10-15, its quarters lie at fixed
+// offsets, and task-wavefront r (64 tasks) belongs to one overlap, r >> (LD - 10): the parameters stay in scalar registers.
+// `import`: a group of the second launch (it stages B(first - 1) and A(last + 1) and emits all three overlaps; one of the first
+// launch leaves those two quarters in the planes and emits the inner overlap).  Called behind the entry barrier.
+template <int LD, typename PCM, int LAYOUT>
+__device__ __forceinline__ void synth_group_steady(const NvhSynthArgs& A, float* smem, const unsigned (&H)[2][NVH_SLAB_HDR_WORDS], bool import,
+                                                   int fa, int tid, int wv, int lane NVH_DBG_PARAMS) {
+  constexpr int NT = 256, n = 1 << LD, half = n >> 1, quarter = n >> 2;
+  constexpr int slice_words = half + (n >> 4), S0 = n, SK = 2 * slice_words;  // (two channels: the staged quarters take n floats)
+  float* s_db = smem;
+  const uint32_t* s_lat = reinterpret_cast<const uint32_t*>(smem + 256);
+  float* slab0 = smem + A.const_vecs * 4;
+  const int slab_words = A.lds_vecs * 4;
+  float* spec0 = slab0 + 2 * slab_words;
+  // ---- spectra: the two frames' walks in one loop ----
+  {
+    WalkFrame W[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      W[k].slab = slab0 + k * slab_words;
+      W[k].nheads = H[k][1] & 0xFFFFu; W[k].off_heads = H[k][2] & 0xFFFFu; W[k].off_rec = H[k][2] >> 16; W[k].off_ent = H[k][3] & 0xFFFFu;
+      W[k].lpc = H[k][4] & 0xFFFFu; W[k].lpc_magic = H[k][5]; W[k].flags = H[k][0] >> 24;
+      W[k].spec = spec0 + k * n; W[k].half = half;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const unsigned cw = H[k][8 + c], ns = (cw >> 8) & 0xFFu, oseg = cw >> 16;
+        W[k].F.seg[c] = reinterpret_cast<const uint4*>(W[k].slab + oseg * 4);
+        W[k].F.tab[c] = reinterpret_cast<const uint8_t*>(W[k].slab + (oseg + ns) * 4);
+        W[k].F.md[c] = 1;
+      }
+      W[k].F.s_db = s_db;
+    }
+    residue_walk_two<NT, true>(W, s_lat, tid);
+    GR_T(2); GR_T(3);
+  }
+  __syncthreads();  // the walks are through everywhere: constants and slabs are dead, the spectra complete
+  GR_T(4);
+
+  // ---- stage the neighbours' third / first quarter (import): n / 16 16-byte units per channel, B(first - 1) at 0, A(last + 1) at n/2 ----
+  if (import) {
+    constexpr int units = n >> 3;  // both channels
+    const float* pB = A.work + (long long)(fa - 1) * 2 * n + half;
+    const float* pA = A.work + (long long)(fa + 2) * 2 * n;
+    for (int u0 = wv * 64; u0 < units; u0 += NT) {
+      const int u = u0 + lane, c = u >> (LD - 4), r = u & ((n >> 4) - 1);
+      dma16<kStageAux>(reinterpret_cast<const uint4*>(pB + c * n + 4 * r), smem + 4 * u0);
+      dma16<kStageAux>(reinterpret_cast<const uint4*>(pA + c * n + 4 * r), smem + half + 4 * u0);
+    }
+  }
+
+  // ---- inverse MDCT: wavefront wv = (frame k, channel c); the outer quarters of an exporting group go to the planes ----
+  {
+    const int k = wv >> 1, c = wv & 1;
+    const unsigned f0w = H[0][0], f1w = H[1][0];  // (read first, chosen after: a chosen address would put the headers into memory)
+    const unsigned flags = (k ? f1w : f0w) >> 24;
+    const int sl = (flags & NVH_SLAB_MDCT_SLOT) ? 1 : 0;
+    const float* X = spec0 + k * n + c * half;
+    float* slice = smem + S0 + (k * 2 + c) * slice_words;
+    float4 ca[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)}, cb[2] = {ca[0], ca[0]};
+    auto sink = [&](int slot, int, float4 v) {  // slot = 4 h + q: q = 0 first quarter, q = 2 third quarter (1, 3: their mirrors)
+      if (slot == 0) ca[0] = v; else if (slot == 2) cb[0] = v; else if (slot == 4) ca[1] = v; else if (slot == 6) cb[1] = v;
+    };
+    imdct_wave_sink<LD, false, decltype(sink), true, true, false, kSynthPFEmit, true>(X, nullptr, slice, A.mdct_a[sl], A.mdct_b[sl], A.mdct_c[sl],
+                                                                                       A.mdct_tw[sl], lane, sink, nullptr, kAblSkip);
+    if (lane < (n >> 5)) {  // lanes with output: four values of each quarter at 4 i8, i8 = lane and i8 = n/16 - 1 - lane
+      const int i8a = lane, i8b = (n >> 4) - 1 - lane;
+      if (!import) {  // A of the first frame, B of the last: the neighbouring groups' overlaps
+        float* plane = A.work + ((long long)(fa + k) * 2 + c) * n;
+        if (k == 0) {
+          *reinterpret_cast<float4*>(plane + 4 * i8a) = ca[0];
+          *reinterpret_cast<float4*>(plane + 4 * i8b) = ca[1];
+        } else {
+          *reinterpret_cast<float4*>(plane + half + 4 * i8a) = cb[0];
+          *reinterpret_cast<float4*>(plane + half + 4 * i8b) = cb[1];
+        }
+      }
+      // the channel's own quarters, for the overlap-adds below: A in [0, n/4), B in [n/4, n/2) of its dead slice
+      *reinterpret_cast<float4*>(slice + 4 * i8a) = ca[0];
+      *reinterpret_cast<float4*>(slice + 4 * i8b) = ca[1];
+      *reinterpret_cast<float4*>(slice + quarter + 4 * i8a) = cb[0];
+      *reinterpret_cast<float4*>(slice + quarter + 4 * i8b) = cb[1];
+    }
+  }
+  GR_T(5);
+  __syncthreads();  // drains the staging DMA; every own quarter is in LDS
+  GR_T(6);
+
+  // ---- overlap-add + interleave + clip (group_emit_task): overlap j = the PCM of frame fa + j, n / 16 tasks each ----
+  {
+    constexpr int WPO = 1 << (LD - 10);  // task-wavefronts per overlap
+    int clipped = 0;
+    const int r0 = import ? 0 : WPO, r1 = import ? 3 * WPO : 2 * WPO;
+    // (read first, chosen by j below: see the transform's flags)
+    const unsigned win0 = H[0][10], ovw0 = H[0][11], nxw0 = H[0][12], pos0 = H[0][14], nxp0 = H[0][15];
+    const unsigned win1 = H[1][10], nxw1 = H[1][12], nxp1 = H[1][15];
+    for (int r = r0 + wv; r < r1; r += NT / 64) {
+      const int j = r >> (LD - 10), g = ((r & (WPO - 1)) << 6) + lane;
+      // window of the later block, of the earlier block at its valid (n/2), output position; the later block's first quarter, the
+      // earlier block's third quarter
+      const unsigned woff = j == 0 ? win0 : (j == 1 ? nxw0 : nxw1);
+      const unsigned wpoff = (j == 0 ? ovw0 : (j == 1 ? win0 : win1)) + (unsigned)half;
+      const unsigned pos = j == 0 ? pos0 : (j == 1 ? nxp0 : nxp1);
+      const unsigned aoff = j == 2 ? (unsigned)half : (unsigned)(S0 + j * SK), astr = j == 2 ? (unsigned)quarter : (unsigned)slice_words;
+      const unsigned boff = j == 0 ? 0u : (unsigned)(S0 + (j - 1) * SK + quarter), bstr = j == 0 ? (unsigned)quarter : (unsigned)slice_words;
+      group_emit_task<PCM, LAYOUT>(A, smem, woff, wpoff, pos, aoff, astr, boff, bstr, n, g, 2, 1 << j, &clipped);
+    }
+    if (A.clip) report_clipped<3>(clipped, A.clipped_flag, fa);
+  }
+  GR_T(7);
+}
+
 // ---- frame groups (round 6): FPW consecutive frames per workgroup, the overlaps between them on chip -----------------------------
 // Paired emission with one frame per workgroup sends every second frame through HBM: the odd frames' planes go out (two quarters
 // per channel) and come back in through the even frames' staging -- 16.8 MB out and 16.8 MB back per 4096-frame pass of C2, a
@@ -1774,13 +2009,6 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int nch = A.channels;
   const int fa = A.f0 + (int)blockIdx.x * A.fstep;  // the group's first frame
-#ifdef NVH_DEBUG
-  // profiling build: shader-clock stamps of thread 0 in the row of the group's first frame (tools/dbg_phase_group.py): 0 entry,
-  // 1 slabs + constants arrived, 2 / 3 the frames' walks, 4 table + barrier, 5 transform of wavefront 0, 6 staging drained, 7 emitted
-#define GR_T(k) do { if (dbg && tid == 0 && fa < A.nframes) dbg[(long long)fa * 24 + (k)] = clock64(); } while (0)
-#else
-#define GR_T(k) do { } while (0)
-#endif
   GR_T(0);
   const int half_max = A.block1 >> 1, pad_max = A.block1 >> 4;
   float* s_db = smem;
@@ -1796,14 +2024,27 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
   typedef const __attribute__((address_space(4))) uint32_t* const_words;
   // ---- one round trip: constants, the first NT * 16 bytes of every slab, the headers' size words by scalar loads; spectra
   // cleared meanwhile ----
+  // (groups of two: the whole header, for the steady predicate and the steady body -- synth_group_steady)
+  constexpr bool STEADY = FPW == 2 && NT == 256;
   unsigned w0[FPW], w3[FPW];
+  unsigned H[STEADY ? 2 : 1][NVH_SLAB_HDR_WORDS];
 #pragma unroll
   for (int k = 0; k < FPW; ++k) {
     w0[k] = 0u; w3[k] = 0u;
+    if constexpr (STEADY) {
+#pragma unroll
+      for (int i = 0; i < NVH_SLAB_HDR_WORDS; ++i) H[k][i] = 0u;
+    }
     if (fa + k < A.nframes) {  // (uniform)
       const uint4* gslab = A.slabs + (long long)(fa + k) * A.stride_vecs;
       const_words gh = (const_words)(unsigned long long)gslab;
-      w0[k] = gh[0]; w3[k] = gh[3];
+      if constexpr (STEADY) {
+#pragma unroll
+        for (int i = 0; i < NVH_SLAB_HDR_WORDS; ++i) H[k][i] = gh[i];
+        w0[k] = H[k][0]; w3[k] = H[k][3];
+      } else {
+        w0[k] = gh[0]; w3[k] = gh[3];
+      }
       if (tid < A.cap_vecs) dma16<kSlabAux>(gslab + tid, slab0 + k * slab_words + wv * 256);
     }
   }
@@ -1844,6 +2085,16 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
   __syncthreads();  // drains the DMA (vmcnt(0)) in front of the barrier
   if (!any) return;
   GR_T(1);
+
+  // ---- a steady group (nvh_format.h: nvh_steady_pair; A.walk_two bit 1: NVH_NO_STEADY clears it): the lean body ----
+  if constexpr (STEADY) {
+    bool import = false;
+    if ((A.walk_two & 2) && A.pcm != nullptr && nvh_steady_pair(H[0], H[1], nch, A.block1, &import)) {  // (uniform)
+      if (A.block1 == 2048) synth_group_steady<11, PCM, LAYOUT>(A, smem, H, import, fa, tid, wv, lane NVH_DBG_ARGS);
+      else synth_group_steady<10, PCM, LAYOUT>(A, smem, H, import, fa, tid, wv, lane NVH_DBG_ARGS);
+      return;
+    }
+  }
 
   // a slab's header word i, from its LDS image (uniform)
   auto hdr = [&](int k, int i) { return __builtin_amdgcn_readfirstlane(reinterpret_cast<const uint32_t*>(slab0 + k * slab_words)[i]); };
@@ -2088,61 +2339,8 @@ __device__ __forceinline__ void synth_group_body(const NvhSynthArgs& A, float* s
 #pragma unroll
     for (int jj = 1; jj <= FPW; ++jj) g = j == jj ? t - cnt[jj] : g;
     const uint4 r0 = reinterpret_cast<const uint4*>(otab)[2 * j], r1 = reinterpret_cast<const uint4*>(otab)[2 * j + 1];
-    const int n = (int)r0.w, half = n >> 1, i0 = 4 * g;  // (n: the overlap's m)
-    const int cbit = 1 << j;  // overlap j is the PCM of frame fa + j (report_clipped<FPW + 1>)
-    const float* __restrict__ w = A.windows + r0.x;
-    const float* __restrict__ wp = A.windows + r0.y;
-    const float4 wf = *reinterpret_cast<const float4*>(w + i0);
-    const float4 wm = *reinterpret_cast<const float4*>(w + (half - 4 - i0));
-    const float4 pf = *reinterpret_cast<const float4*>(wp + i0);
-    const float4 pm = *reinterpret_cast<const float4*>(wp + (half - 4 - i0));
-    float fwd[8], mir[8];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      if (c < nch) {
-        const float4 a = *reinterpret_cast<const float4*>(smem + r1.x + c * r1.y + i0);
-        const float4 b = *reinterpret_cast<const float4*>(smem + r1.z + c * r1.w + i0);
-        float4 v = make_float4(a.x * wf.x, a.y * wf.y, a.z * wf.z, a.w * wf.w);
-        const float4 tt = make_float4(b.x * pf.x, b.y * pf.y, b.z * pf.z, b.w * pf.w);
-        v.x = v.x + tt.x; v.y = v.y + tt.y; v.z = v.z + tt.z; v.w = v.w + tt.w;
-        float4 u = make_float4(-a.w * wm.x, -a.z * wm.y, -a.y * wm.z, -a.x * wm.w);
-        const float4 r = make_float4(b.w * pm.x, b.z * pm.y, b.y * pm.z, b.x * pm.w);
-        u.x = u.x + r.x; u.y = u.y + r.y; u.z = u.z + r.z; u.w = u.w + r.w;
-        if (!MONO && A.clip) {  // (the mono form clips the mix)
-          v.x = clip_value(v.x, &clipped, cbit); v.y = clip_value(v.y, &clipped, cbit);
-          v.z = clip_value(v.z, &clipped, cbit); v.w = clip_value(v.w, &clipped, cbit);
-          u.x = clip_value(u.x, &clipped, cbit); u.y = clip_value(u.y, &clipped, cbit);
-          u.z = clip_value(u.z, &clipped, cbit); u.w = clip_value(u.w, &clipped, cbit);
-        }
-        if constexpr (PLANAR) {  // channel-planar: the channel leaves at once (nothing is held for an interleave)
-          pcm_store_plane(reinterpret_cast<PCM*>(A.pcm) + (long long)r0.z + (long long)c * A.plane_stride, g, (n >> 3) - 1 - g, v, u);
-        } else {
-          fwd[c] = v.x; fwd[2 + c] = v.y; fwd[4 + c] = v.z; fwd[6 + c] = v.w;
-            mir[c] = u.x; mir[2 + c] = u.y; mir[4 + c] = u.z; mir[6 + c] = u.w;
-        }
-      }
-    }
-    PCM* out = reinterpret_cast<PCM*>(A.pcm) + (long long)r0.z * (PLANAR || MONO ? 1 : nch);
-    if constexpr (PLANAR) {
-      // (stored per channel above)
-    } else if constexpr (MONO) {  // the mean of the channels, clipped once: one vector per half
-      pcm_store_plane(out, g, (n >> 3) - 1 - g, mono_mix2(fwd, nch, A.clip, &clipped, cbit), mono_mix2(mir, nch, A.clip, &clipped, cbit));
-    } else if (nch == 2) {
-      pcm4_t<PCM>* of = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)g;
-      pcm4_t<PCM>* om = reinterpret_cast<pcm4_t<PCM>*>(out) + 2 * (long long)((n >> 3) - 1 - g);
-      if constexpr (std::is_same<PCM, int16_t>::value) {  // four stereo sample times: one 16-byte store where aligned
-        pcm_store4x2(of, fwd);
-        pcm_store4x2(om, mir);
-      } else {
-        pcm_store4(of, fwd[0], fwd[1], fwd[2], fwd[3]);
-        pcm_store4(of + 1, fwd[4], fwd[5], fwd[6], fwd[7]);
-        pcm_store4(om, mir[0], mir[1], mir[2], mir[3]);
-        pcm_store4(om + 1, mir[4], mir[5], mir[6], mir[7]);
-      }
-    } else {
-      pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + g, fwd[0], fwd[2], fwd[4], fwd[6]);
-      pcm_store4(reinterpret_cast<pcm4_t<PCM>*>(out) + ((n >> 3) - 1 - g), mir[0], mir[2], mir[4], mir[6]);
-    }
+    // (r0.w: the overlap's m; overlap j is the PCM of frame fa + j: report_clipped<FPW + 1>)
+    group_emit_task<PCM, LAYOUT>(A, smem, r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, r1.w, (int)r0.w, g, nch, 1 << j, &clipped);
   }
   // ---- what a frame emits alone: lane task = four consecutive sample times of R1 or R2 of one frame (window multiply of
   // Mode.cs:160-166 on the block's own values, nothing overlapped onto them; kernels.hip: compact_value) ----

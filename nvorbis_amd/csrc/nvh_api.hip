@@ -26,6 +26,7 @@ const NvhToggles& nvh_toggles() {
     x.no_emit8 = on("NVH_NO_EMIT8");
     x.no_prefetch = on("NVH_NO_PREFETCH");
     x.no_walk_two = on("NVH_NO_WALK_TWO");
+    x.no_steady = on("NVH_NO_STEADY");
     x.fpw = std::getenv("NVH_FPW") ? num("NVH_FPW") : 2;
     if (x.fpw != 1 && x.fpw != 2 && x.fpw != 4) x.fpw = 2;
     x.copy_upload = on("NVH_COPY_UPLOAD");
@@ -1098,6 +1099,34 @@ extern "C" int nvh_batch_kernels(const nvh_batch* b, char* buf, int cap) {
 
 extern "C" int nvh_stream_kernels(const nvh_stream* s, char* buf, int cap) {
   return nvh_batch_kernels(s ? &s->scratch : nullptr, buf, cap);
+}
+
+extern "C" int nvh_batch_steady_groups(const nvh_batch* b, int* groups) {
+  return nvh_guard([&]() -> int {
+    if (!b || !groups) return NVH_ERR_ARGUMENT;
+    *groups = b->steady_groups;
+    return NVH_OK;
+  });
+}
+
+extern "C" int nvh_stream_steady_groups(const nvh_stream* s, int* groups) {
+  return nvh_batch_steady_groups(s ? &s->scratch : nullptr, groups);
+}
+
+extern "C" int nvh_steady_count(const uint32_t* headers, int frames, int channels, int block1, int* groups) {
+  return nvh_guard([&]() -> int {
+    if (!groups || frames < 0 || (frames > 0 && !headers)) return NVH_ERR_ARGUMENT;
+    *groups = count_steady_groups((const uint8_t*)headers, NVH_SLAB_HDR_WORDS * sizeof(uint32_t), frames, channels, block1);
+    return NVH_OK;
+  });
+}
+
+extern "C" int nvh_stream_pending_steady(const nvh_stream* s, int* groups) {
+  return nvh_guard([&]() -> int {
+    if (!s || !groups) return NVH_ERR_ARGUMENT;
+    if (s->parser->light()) return NVH_ERR_UNSUPPORTED;  // GPU-parse mode: the host writes no slabs
+    return pending_steady_groups(s, groups);
+  });
 }
 
 // nvh_batch_synth_out: the resident batch into the destination the descriptor describes

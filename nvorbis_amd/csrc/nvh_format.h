@@ -202,6 +202,7 @@ struct NvhFrame {
 #define NVH_SLAB_GEO(prev_n, next_n, start, valid) \
   ((uint32_t)((prev_n) >> 6) | ((uint32_t)((next_n) >> 6) << 8) | ((uint32_t)((start) >> 6) << 16) | ((uint32_t)((valid) >> 6) << 24))
 #define NVH_SLAB_HDR_VECS 4
+#define NVH_SLAB_HDR_WORDS 16
 #define NVH_SLAB_MAX_CH 8          // channels a slab describes (k_synth: 2, k_synth8: 8)
 #define NVH_SLAB_MAX_COUPLE 4      // coupling steps of a pass of its own (3 + 3 bits each in NvhSlabHdr::coupling)
 struct NvhSlabHdr {      // 64 bytes
@@ -226,3 +227,38 @@ struct NvhSlabHdr {      // 64 bytes
                                    // is this frame's window_off)
 };
 
+// ---- steady frame groups (kernels_synth.hip: synth_group_steady) -----------------------------------------------------
+// A group of two frames is STEADY when nothing of the general group body's generality is used: both frames long blocks of the
+// stream's larger size (1024 or 2048) between neighbours of that size, stereo, both channels executing with a floor curve each,
+// the shape the two-frame walk takes (digit form, stereo Residue2, eight components per lane, fused floor, no floor fault), the
+// emission flags exactly those the host sets by position in a group (nvh_launch.hip: assign_emission -- a group of the first
+// launch emits its inner overlap only, one of the second launch all three), no carried tail in or out and nothing left for
+// k_ola_compact.  One function, on the two slabs' header words (NvhSlabHdr as sixteen uint32) and the launch's channels and block1:
+// the kernel evaluates it on scalar registers at its top, the host counts a batch's steady groups with it at upload
+// (nvh_batch_steady_groups).  *import: the group is one of the second launch.
+#ifdef __HIPCC__
+#define NVH_HD __host__ __device__ inline __attribute__((always_inline))  // (a call would take the addresses of headers the kernel holds in registers)
+#else
+#define NVH_HD inline
+#endif
+// one frame of the pair: its header, the block size, the emission flags its place in the group asks for
+// (no pointer is chosen at run time in here: the kernel's copy of the headers has to stay in scalar registers)
+NVH_HD bool nvh_steady_frame(const uint32_t* h, uint32_t n, uint32_t want) {
+  const uint32_t flags = h[0] >> 24, xm = (h[0] >> 16) & 0xFFu;
+  const uint32_t geo = NVH_SLAB_GEO(n, (want & NVH_SLAB_EMIT_NEXT) ? n : 0u, 0u, n >> 1);  // (a frame without NEXT names no successor)
+  bool ok = (h[0] & 0xFFFFu) == n && xm == (3u | NVH_SLABX_DONE);  // both channels execute; no SELF_CARRY, no CARRY_OUT
+  ok = ok && (flags & (NVH_SLAB_FUSE_FLOOR | NVH_SLAB_FLOOR_FAULT | NVH_SLAB_COUPLE_PASS)) == NVH_SLAB_FUSE_FLOOR;
+  ok = ok && ((h[4] >> 16) & 0xFFu) == (2u | NVH_SLAB_RGEOM_DIGITS | (2u << 4)) && (h[4] >> 24) == 8u;
+  ok = ok && (h[1] & 0xFFFFu) != 0u && (h[4] & 0xFFFFu) != 0u;  // chains to walk
+  ok = ok && (h[8] & 0xFFu) == 1u && (h[9] & 0xFFu) == 1u;     // a floor curve on either channel
+  return ok && (flags & (NVH_SLAB_EMIT_SELF | NVH_SLAB_EMIT_NEXT)) == want && h[13] == geo;
+}
+NVH_HD bool nvh_steady_pair(const uint32_t* h0, const uint32_t* h1, int channels, int block1, bool* import) {
+  const uint32_t n = (uint32_t)block1;
+  const bool imp = ((h0[0] >> 24) & NVH_SLAB_EMIT_SELF) != 0u;
+  if (import) *import = imp;
+  if (channels != 2 || (n != 2048u && n != 1024u)) return false;
+  // frame 0 emits frame 1's PCM, frame 1 its own; the outer overlaps both (second launch) or neither (first launch)
+  const uint32_t outer0 = imp ? NVH_SLAB_EMIT_SELF : 0u, outer1 = imp ? NVH_SLAB_EMIT_NEXT : 0u;
+  return nvh_steady_frame(h0, n, NVH_SLAB_EMIT_NEXT | outer0) && nvh_steady_frame(h1, n, NVH_SLAB_EMIT_SELF | outer1);
+}

@@ -194,6 +194,7 @@ struct NvhToggles {
   int fpw;           // NVH_FPW: frames per workgroup of the mono / stereo synthesis with paired emission (kernels_synth.hip: frame groups):
                      // 1 = k_synth + k_synth_emit (the round-3..5 form), 2 (default) = k_synth_group2, 4 = k_synth_group4
   bool no_walk_two;  // NVH_NO_WALK_TWO: a frame group's two residue walks one after the other (A/B aid)
+  bool no_steady;    // NVH_NO_STEADY: steady groups of two take the general group body like every other (kernels_synth.hip: synth_group_steady; A/B aid)
   bool no_prefetch;  // NVH_NO_PREFETCH: the odd launch of a paired-emission pass does not touch the even launch's slabs (A/B aid)
   bool uncached_planes;  // NVH_UNCACHED_PLANES: a batch's work planes in hipDeviceMallocUncached memory (the round-4 experiment whose
                          // wrong PCM with GPU-parsed batches was never explained: tools/repro_uncached.py)
@@ -212,6 +213,9 @@ struct NvhToggles {
   int phase_mask;  // debug build only (NVH_DEBUG_SPECTRUM_MASK)
 };
 const NvhToggles& nvh_toggles();
+int count_steady_groups(const uint8_t* slabs, size_t stride_bytes, int nframes, int channels, int block1);  // nvh_launch.hip
+struct nvh_stream;
+int pending_steady_groups(const nvh_stream* s, int* groups);  // nvh_launch.hip
 #ifdef NVH_DEBUG
 extern void* g_dbg_buf;  // per-workgroup phase timestamps of the spectrum kernels (nvh_debug_set_buffer)
 #define NVH_DBG_LAUNCH , (long long*)g_dbg_buf, nvh_toggles().phase_mask
@@ -473,6 +477,7 @@ struct nvh_batch {
   // paired emission (nvh_format.h: NVH_EMIT_*): frames whose PCM k_synth writes itself, and the frames left to k_ola_compact
   int emit_frames = 0;           // frames with NVH_EMIT_DONE
   bool emit_planar_ok = true;    // every frame the emission covers starts on a whole group of four samples (the _planar twins' vectors)
+  int steady_groups = 0;         // groups of two the synthesis takes through its steady body (batch_upload_frames: count_steady_groups)
   int fpw = 1;                   // frames per workgroup the emission flags were laid out for (1: odd / even frames; 2, 4: frame groups)
   bool ola_all = false;          // GPU-parsed batch in which k_parse_links withdrew an emission candidate: k_ola_compact over every frame
   int ola_count = 0;             // entries of d_ola_list

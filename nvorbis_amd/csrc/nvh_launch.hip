@@ -372,6 +372,7 @@ static void assign_emission(nvh_stream* s, nvh_batch* b, nvh::FrameBatch& P, int
   ola_list.clear();
   b->emit_frames = 0;
   b->fpw = 1;
+  b->steady_groups = 0;
   {
     const int ch = s->setup.channels;
     // mono / stereo with blocks up to 2048 (k_synth_emit: from registers and LDS-staged quarters), or the wide kernel's shapes --
@@ -480,6 +481,45 @@ static void assign_emission(nvh_stream* s, nvh_batch* b, nvh::FrameBatch& P, int
       if ((fr.emit_count > 0 && !(fr.emit_flags & NVH_EMIT_DONE)) || (g == last && !(fr.emit_flags & NVH_EMIT_CARRY_OUT))) ola_list.push_back(g);
     }
   }
+}
+
+// The host's twin of the kernel's steady test (nvh_format.h: nvh_steady_pair, the one function both evaluate): how many groups of
+// two of a batch take k_synth_group2's steady body, counted on the slab headers the host wrote (`stride_bytes` apart, frames in
+// order) with the switches the launch will pass.  It serves nvh_batch_steady_groups alone; nothing is launched by it.
+int count_steady_groups(const uint8_t* slabs, size_t stride_bytes, int nframes, int channels, int block1) {
+  const NvhToggles& T = nvh_toggles();
+  if (T.no_steady || T.no_walk_two) return 0;
+  int groups = 0;
+  for (int f = 0; f + 1 < nframes; f += 2) {
+    uint32_t h[2][NVH_SLAB_HDR_WORDS];
+    std::memcpy(h[0], slabs + (size_t)f * stride_bytes, sizeof h[0]);
+    std::memcpy(h[1], slabs + ((size_t)f + 1) * stride_bytes, sizeof h[1]);
+    groups += nvh_steady_pair(h[0], h[1], channels, block1, nullptr) ? 1 : 0;
+  }
+  return groups;
+}
+
+// ... and the same count for the frames a host-parsing stream holds pending, as an upload at the process's frames per workgroup would
+// lay them out (emission flags, then slabs), without a device: nvh_stream_pending_steady.  The stream is left as it was.
+int pending_steady_groups(const nvh_stream* s, int* groups) {
+  // (the emission flags of pending frames mean nothing until an upload writes them: they are lent to this count and put back)
+  nvh::FrameBatch& P = const_cast<nvh::FrameBatch&>(s->pending);
+  std::vector<uint32_t> saved;
+  for (const NvhFrame& fr : P.frames) saved.push_back(fr.emit_flags);
+  nvh_batch tmp;
+  std::vector<int> ola_list;
+  assign_emission(const_cast<nvh_stream*>(s), &tmp, P, nvh_toggles().fpw, ola_list);  // (reads the stream, writes tmp and the flags)
+  *groups = 0;
+  nvh::SlabBatch SB;
+  const int rc = tmp.fpw == 2 ? nvh::build_slabs(s->setup, s->shared->slab, P, SB) : NVH_ERR_UNSUPPORTED;
+  for (size_t f = 0; f < saved.size(); f++) P.frames[f].emit_flags = saved[f];
+  if (rc == NVH_ERR_UNSUPPORTED) return NVH_OK;  // (outside the slab kernels' contract: no frame groups)
+  if (rc != NVH_OK) return rc;
+  const size_t nf = P.frames.size();
+  std::vector<uint32_t> hdrs(nf * NVH_SLAB_HDR_WORDS);
+  for (size_t f = 0; f < nf; f++) std::memcpy(&hdrs[f * NVH_SLAB_HDR_WORDS], &SB.data[SB.first[f]], NVH_SLAB_HDR_WORDS * sizeof(uint32_t));
+  *groups = count_steady_groups((const uint8_t*)hdrs.data(), NVH_SLAB_HDR_WORDS * sizeof(uint32_t), (int)nf, s->setup.channels, s->setup.block1);
+  return NVH_OK;
 }
 
 // The batch's gap list to the device (one small copy, on the stream, and only for a batch that has gaps)
@@ -671,6 +711,8 @@ static int batch_upload_frames(nvh_stream* s, nvh_batch* b) {
         std::memcpy(h + o_sl + f * stride * 16, &SB.data[SB.first[f]], v * 16);
         slab_bytes += (int64_t)v * 16;
       }
+      // (the GPU parser writes the entry form, which the steady body does not take: its batches count none)
+      if (b->fpw == 2) b->steady_groups = count_steady_groups(h + o_sl, stride * 16, (int)nf, s->setup.channels, s->setup.block1);
       b->descriptor_bytes = (int64_t)(nf * sizeof(NvhFrame) + P.chans.size() * sizeof(NvhChan)) + slab_bytes;
       hipStream_t st = s->ctx->stream;
       HIP_TRY(hipMemcpyAsync(b->blob.p, h, o_sl + nf * stride * 16, hipMemcpyHostToDevice, st));
@@ -1011,7 +1053,7 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
     A.nframes = b->nframes;
     A.prefetch_prev = 0;
     A.xcd_map = 0;
-    A.walk_two = nvh_toggles().no_walk_two ? 0 : 1;
+    A.walk_two = nvh_toggles().no_walk_two ? 0 : (nvh_toggles().no_steady ? 1 : 3);  // bit 1: steady groups take the lean body
     const bool wide = slab_wide(s);
     // paired emission (nvh_format.h: NVH_EMIT_*): the host marked the frames at upload; it needs the PCM buffer and the slabs
     // in frame order

@@ -204,6 +204,10 @@ SIGNATURES = {
     "nvh_batch_stats": (C.c_int, [_vp, _i64p]),
     "nvh_batch_kernels": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "nvh_stream_kernels": (C.c_int, [_vp, C.c_char_p, C.c_int]),
+    "nvh_batch_steady_groups": (C.c_int, [_vp, _ip]),
+    "nvh_stream_steady_groups": (C.c_int, [_vp, _ip]),
+    "nvh_stream_pending_steady": (C.c_int, [_vp, _ip]),
+    "nvh_steady_count": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip]),
     "nvh_batch_synth": (C.c_int, [_vp, _vp, C.c_int64]),
     "nvh_batch_synth_pcm": (C.c_int, [_vp, C.c_int, _vp, C.c_int64]),
     "nvh_batch_synth_planar": (C.c_int, [_vp, C.c_int, _vp, C.c_int64]),

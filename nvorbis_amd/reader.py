@@ -418,6 +418,12 @@ class Batch:
         check(lib().nvh_batch_kernels(self._h, buf, 256), "nvh_batch_kernels")
         return buf.value.decode().split(",")
 
+    def steady_groups(self):
+        """Groups of two frames the frame-group synthesis takes through its steady body (counted at upload)."""
+        n = C.c_int(0)
+        check(lib().nvh_batch_steady_groups(self._h, C.byref(n)), "nvh_batch_steady_groups")
+        return n.value
+
     def synth(self, d_pcm_ptr, capacity, dtype=np.float32, plane_stride=None, mix=None, channel_map=None):
         """Launch the synthesis into d_pcm_ptr (capacity in samples) as float32 or int16 PCM (a 16-byte aligned int16 destination).
         plane_stride (samples, >= self.samples): channel-planar PCM instead, channel c at d_pcm_ptr + c * plane_stride samples
@@ -581,6 +587,18 @@ class Stream:
         buf = C.create_string_buffer(256)
         check(lib().nvh_stream_kernels(self._h, buf, 256), "nvh_stream_kernels")
         return buf.value.decode().split(",")
+
+    def steady_groups(self):
+        """Steady groups of two frames (Batch.steady_groups) of the batch the stream's last synthesis launched."""
+        n = C.c_int(0)
+        check(lib().nvh_stream_steady_groups(self._h, C.byref(n)), "nvh_stream_steady_groups")
+        return n.value
+
+    def pending_steady(self):
+        """The same count for the pending frames, as an upload would lay them out (host parser; no GPU needed)."""
+        n = C.c_int(0)
+        check(lib().nvh_stream_pending_steady(self._h, C.byref(n)), "nvh_stream_pending_steady")
+        return n.value
 
     def pending_slabs(self):
         """The pending frames as the synthesis kernels fetch them (per-frame slabs, nvh_format.h: NvhSlabHdr), written on the

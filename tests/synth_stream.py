@@ -680,6 +680,59 @@ CONFIG_NAMES = ["mono_res0_small_blocks", "stereo_res1_coupled", "three_ch_res2_
                 "table_books_pair", "table_books_general", "table_books_b1", "ch9_res2", "ch16_res1_4096", "ch40_res1"] + list(LONGCODE_NAMES)
 
 
+def _residue_args(residue):
+    """write_residue's arguments behind one of a configuration's residue writers, read back from the bits it writes."""
+    w = BitWriter()
+    residue(w)
+    bits, pos = int.from_bytes(w.bytes(), "little"), [0]
+
+    def rd(n):
+        v = (bits >> pos[0]) & ((1 << n) - 1)
+        pos[0] += n
+        return v
+
+    rtype, begin, end, psize, nclass, classbook = rd(16), rd(24), rd(24), rd(24) + 1, rd(6) + 1, rd(8)
+    cascades = []
+    for _ in range(nclass):
+        low = rd(3)
+        cascades.append(low | ((rd(5) if rd(1) else 0) << 3))
+    books = [rd(8) for c in cascades for _ in range(bin(c).count("1"))]
+    return rtype, begin, end, psize, classbook, cascades, books
+
+
+ROUNDING_STAGES = 3
+FLOOR0_LSP_BOOK = 10
+
+
+def rounding(name):
+    """config(name) with residue sums that round (tests/test_residue_rounding.py).  config()'s value books are dyadic with a
+    mantissa of a few bits and most classes have at most two cascade stages: every partial sum is exact and two addends commute,
+    so no order of additions can be told from another.  Here every class of every residue has three stages (cascade 7), its
+    books taken cyclically from the residue's own list -- the dimensions and lookup types, and with them the kernel route, stay
+    -- and every value book a residue uses gets a minimum and a delta with a full 21-bit mantissa, at a scale that changes by up
+    to 2^15 from one book to the next: sums of three terms round, and the rounded sum depends on the order.  All values stay in
+    the normal range.  The Floor0 LSP book keeps its values (its curves must stay bounded); multiplicands, entry counts,
+    sequence_p and lookup types are config()'s.  Kept out of CONFIG_NAMES, as GRID_NAMES is."""
+    import copy
+    c = dict(config(name))
+    books = list(c["books"])
+    residues, used = [], set()
+    for r in c["residues"]:
+        rtype, begin, end, psize, classbook, cascades, rbooks = _residue_args(r)
+        cyc = [rbooks[i % len(rbooks)] for i in range(ROUNDING_STAGES * len(cascades))]
+        used.update(cyc)
+        args = (rtype, begin, end, psize, classbook, [(1 << ROUNDING_STAGES) - 1] * len(cascades), cyc)
+        residues.append(lambda w, args=args: write_residue(w, *args))
+    for i in sorted(used):
+        if books[i].lookup == 0 or i == FLOOR0_LSP_BOOK:
+            continue
+        books[i] = copy.copy(books[i])
+        books[i].min_me = (-(0x155555 ^ (i * 0x1357)), -21 - 5 * (i % 4))
+        books[i].delta_me = (0x1C71C7 ^ (i * 0x2461), -22 - 5 * (i % 4))
+    c.update(books=books, residues=residues)
+    return c
+
+
 def filtered_stream(oracle, name, npackets, seed, consistent_windows=True):
     """make_stream, with every audio packet that makes the reference algorithm throw (a floor curve leaving the
     dB table) replaced by a fresh random one, so that the stream as a whole decodes."""

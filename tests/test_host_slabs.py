@@ -290,10 +290,14 @@ def test_slab_general_group_list(oracle, name):
         s.close()
 
 
-def _slab_residue_sums(words, h, lat, nch, half, vq=None):
+REFERENCE_ORDER = lambda w: (w[0], w[1], w[2])  # (pass, cascade stage, the partition's first bin)
+
+
+def _slab_residue_sums(words, h, lat, nch, half, vq=None, key=REFERENCE_ORDER):
     """The residue sums [nch][half] a slab's chains encode, added in the reference's order (cascade stage by stage, inside a
     stage the partitions in order; Residue0.cs:132-175), for every walk of the synthesis kernels: the pair walk (group 2 / 8 /
-    2 * channels), the quirk-B-1 bin walk (group 0) and the general one (group 1, with its group list)."""
+    2 * channels), the quirk-B-1 bin walk (group 0) and the general one (group 1, with its group list).  `key` sorts the
+    vector writes (pass, stage, first bin, ...): another one adds them in another order (tests/test_residue_rounding.py)."""
     spec = np.zeros((nch, half), np.float32)
     if h["nrec"] == 0:
         return spec
@@ -327,7 +331,7 @@ def _slab_residue_sums(words, h, lat, nch, half, vq=None):
             if not (y >> 31):
                 break
             o += 1
-    writes.sort(key=lambda w: (w[0], w[1], w[2]))
+    writes.sort(key=key)
     for pss, stage, x0, cix, x, y in writes:
         _, rtype, rch, psz = geo[cix]
         dims, lv, lat_off, chan = (y >> 20) & 31, (y >> 12) & 0xFF, y & 0xFFF, (y >> 25) & 7
@@ -372,7 +376,6 @@ def test_slab_residue_sums_match_oracle(oracle, ogg_bytes, name):
     the host's symbol decode (prefix table, the slot's group, the plain scan), packets that end inside a long code."""
     import nvorbis_amd as nv
     from tests import synth_stream as ss
-    from tests.test_gpu_parity import _open_headers
     if name in ogg_bytes:
         pk, _, _ = nv.demux_ogg(ogg_bytes[name])
         ids = list(range(3, 40)) + list(range(40, len(pk), max(1, (len(pk) - 40) // 12)))
@@ -383,6 +386,21 @@ def test_slab_residue_sums_match_oracle(oracle, ogg_bytes, name):
     else:
         pk, _, _ = ss.filtered_stream(oracle, name, 40, 9)
         ids = range(3, len(pk))
+    frames = vectors = 0
+    for i, words, h, want, lat, vq in slab_frames(oracle, pk, ids):
+        nch, half = want.shape
+        got = _slab_residue_sums(words, h, lat, nch, half, vq)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (name, i, float(np.abs(got - want).max()))
+        frames += 1
+        vectors += h["nrec"]
+    assert frames >= 10 and vectors > 100, (frames, vectors)
+
+
+def slab_frames(oracle, pk, ids):
+    """(packet index, slab words, parsed header, the oracle's residue [channels][n / 2], lattice pool, VQ pool) of every audio
+    packet of `ids` that the oracle decodes and the host parser writes a slab for."""
+    import nvorbis_amd as nv
+    from tests.test_gpu_parity import _open_headers
     d = _open_headers(oracle, pk)
     s = nv.Stream(None, pk[0], pk[1], pk[2])
     try:
@@ -390,7 +408,6 @@ def test_slab_residue_sums_match_oracle(oracle, ogg_bytes, name):
         vq = s.vq_pool()
         nch, b1 = s.channels, s.block1
         scratch = np.zeros(nch * b1, np.float32)
-        frames = vectors = 0
         for i in ids:
             a, b, c, e = C.c_int(), C.c_int(), C.c_int(), C.c_int()
             if oracle.L.orc_decode_packet_block(d, pk[i], len(pk[i]), scratch.ctypes.data, C.byref(a), C.byref(b), C.byref(c), C.byref(e)) != 1:
@@ -410,12 +427,7 @@ def test_slab_residue_sums_match_oracle(oracle, ogg_bytes, name):
                 bits = C.c_int()
                 assert oracle.L.orc_residue_decode_at(d, int(idx[k]), pk[i], len(pk[i]), int(pos[k]), anyx.value, n, ref.ctypes.data,
                                                       C.byref(bits)) == 0
-            got = _slab_residue_sums(words, h, lat, nch, n // 2, vq)
-            want = ref.reshape(nch, b1)[:, :n // 2]
-            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (name, i, float(np.abs(got - want).max()))
-            frames += 1
-            vectors += h["nrec"]
-        assert frames >= 10 and vectors > 100, (frames, vectors)
+            yield i, words, h, ref.reshape(nch, b1)[:, :n // 2], lat, vq
     finally:
         oracle.L.orc_close(d)
         s.close()

@@ -27,6 +27,7 @@ const NvhToggles& nvh_toggles() {
     x.no_prefetch = on("NVH_NO_PREFETCH");
     x.no_walk_two = on("NVH_NO_WALK_TWO");
     x.no_steady = on("NVH_NO_STEADY");
+    x.group_prefetch = on("NVH_GROUP_PREFETCH");
     x.fpw = std::getenv("NVH_FPW") ? num("NVH_FPW") : 2;
     if (x.fpw != 1 && x.fpw != 2 && x.fpw != 4) x.fpw = 2;
     x.copy_upload = on("NVH_COPY_UPLOAD");
@@ -1086,11 +1087,9 @@ extern "C" int nvh_batch_stats(const nvh_batch* b, int64_t* out8) {
 extern "C" int nvh_batch_kernels(const nvh_batch* b, char* buf, int cap) {
   return nvh_guard([&]() -> int {
     if (!b || !buf || cap <= 0) return NVH_ERR_ARGUMENT;
-    std::string t;
-    for (int k = 0; k < 4; k++) {
-      if (k) t += ",";
-      t += b->slot_name[k];
-    }
+    std::string names[4];
+    batch_route_names(b->route, names);
+    const std::string t = names[0] + "," + names[1] + "," + names[2] + "," + names[3];
     if ((int)t.size() + 1 > cap) return NVH_ERR_ARGUMENT;
     std::memcpy(buf, t.c_str(), t.size() + 1);
     return NVH_OK;

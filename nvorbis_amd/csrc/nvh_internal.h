@@ -194,6 +194,7 @@ struct NvhToggles {
   int fpw;           // NVH_FPW: frames per workgroup of the mono / stereo synthesis with paired emission (kernels_synth.hip: frame groups):
                      // 1 = k_synth + k_synth_emit (the round-3..5 form), 2 (default) = k_synth_group2, 4 = k_synth_group4
   bool no_walk_two;  // NVH_NO_WALK_TWO: a frame group's two residue walks one after the other (A/B aid)
+  bool group_prefetch;  // NVH_GROUP_PREFETCH: the odd launch of a frame-group pass touches the even launch's slabs (measured: 181.6 with, 184.5 M frames/s without)
   bool no_steady;    // NVH_NO_STEADY: steady groups of two take the general group body like every other (kernels_synth.hip: synth_group_steady; A/B aid)
   bool no_prefetch;  // NVH_NO_PREFETCH: the odd launch of a paired-emission pass does not touch the even launch's slabs (A/B aid)
   bool uncached_planes;  // NVH_UNCACHED_PLANES: a batch's work planes in hipDeviceMallocUncached memory (the round-4 experiment whose
@@ -443,6 +444,91 @@ inline hipError_t nvh_wait_stream(const nvh_ctx* c, hipStream_t st) {
   }
 }
 
+// A PCM destination: the sample format (NVH_PCM_*: float, or int16_t for the kernels' _s16 twins) and the layout -- interleaved
+// (plane_stride == 0), or channel-planar with channel c's samples at base + c * plane_stride (the _planar twins) -- and the mix
+// (NVH_MIX_*): NVH_MIX_MONO is ONE plane holding the mean of the channels (the _mono twins; never together with a plane stride)
+// -- and the channel map (the *_map calls; never together with a mix): map.oc output slots, interleaved or one plane each (the
+// _map twins).  map.oc == 0: no map.  The identity map is no map (pcm_map below), so the un-mapped kernels run.
+struct PcmOut {
+  int format = NVH_PCM_F32;
+  int64_t plane_stride = 0;
+  int mix = NVH_MIX_NONE;
+  NvhChanMap map = NvhChanMap{0u, 0u, 0};
+  bool mapped() const { return map.oc > 0; }
+  int out_channels(int ch) const { return mapped() ? map.oc : ch; }  // samples per sample time of an interleaved destination / planes
+  static bool mix_ok(int mix) { return mix == NVH_MIX_NONE || mix == NVH_MIX_MONO; }
+  bool mono() const { return mix == NVH_MIX_MONO; }
+  int layout() const {
+    if (mapped()) return planar() ? NVH_LAYOUT_PLANAR_MAP : NVH_LAYOUT_INTERLEAVED_MAP;
+    return mono() ? NVH_LAYOUT_MONO : planar() ? NVH_LAYOUT_PLANAR : NVH_LAYOUT_INTERLEAVED;
+  }
+  static bool format_ok(int format) { return format == NVH_PCM_F32 || format == NVH_PCM_S16; }
+  bool s16() const { return format == NVH_PCM_S16; }
+  bool planar() const { return plane_stride > 0; }
+  size_t sample_bytes() const { return s16() ? sizeof(int16_t) : sizeof(float); }
+  // a device destination: interleaved 16-bit PCM 16-byte aligned (the stereo twins store eight samples at a time), planar PCM
+  // the mono mix and mapped PCM aligned to their samples (their vector stores run where the base is 16-byte aligned, else the
+  // fall-back)
+  bool dest_ok(const void* d_pcm) const {
+    return planar() || mono() || mapped() ? ((uintptr_t)d_pcm % sample_bytes()) == 0 : (!s16() || ((uintptr_t)d_pcm & 15u) == 0);
+  }
+};
+// What one batch_launch launches (nvh_launch.hip: plan_batch_route decides all of it from the batch's upload-time fields, the
+// setup, the switches and the destination; batch_launch executes it and decides nothing).  The batch keeps the route of its
+// last launch: nvh_batch_kernels / nvh_batch_launches read it.
+enum class SynthStage : uint8_t {
+  kNone,  // a batch without frames (pads only)
+  // slab routes (kernels_synth.hip): the inverse MDCT is inside
+  kSynth, kSynthG, kSynth8, kSynth8G,
+  kSynth8Emit,     // k_synth8 over the odd frames, k_synth8_emit* over the even ones
+  kSynthEmit,      // k_synth | k_synth_tail over the odd frames, k_synth_emit* over the even ones
+  kGroup2, kGroup4,  // k_synth_group2* / 4*: the odd groups, then the even ones
+  // descriptor routes (kernels_spectrum.hip)
+  kSpectrumF0, kSpectrumGen, kSpectrumGenImdct, kSpectrumGen8, kSpectrumGen8Imdct, kSpectrum, kSpectrumImdct,
+  kResidueCoupleFloor,  // k_residue (slot 0) + k_couple_floor: the frame does not fit the LDS
+};
+enum class TransformStage : uint8_t { kNone, kImdctCompact, kImdctWave, kImdctWindow };
+enum class OverlapStage : uint8_t {
+  kNone,
+  kCompactAll,         // k_ola_compact over every frame
+  kCompactAllEmitted,  // ... after paired emission (ola_all): the emitted frames return at once
+  kCompactList,        // ... over the list of frames the emission left
+  kEmit, kEmitSeq,     // k_ola_emit, k_ola_emit_seq
+};
+enum class LdsFamily : uint8_t { kNone, kSpectrum, kSynth8, kGroups };  // which kernels opt in to more than 64 KB of dynamic LDS
+struct BatchRoute {
+  struct Launch {
+    int slot;  // the timing slot, 0..3
+    unsigned gx, gy, threads;
+    size_t lds;  // dynamic LDS bytes
+    int f0, fstep, prefetch_prev;  // NvhSynthArgs of this launch (the synthesis launches only)
+  };
+  PcmOut out;  // as the kernels take it: a mono stream's plane_stride = 0, mix = NONE
+  bool nothing = false;  // no frames, no gaps, no pads: the launcher returns and the batch keeps the route it had
+  bool planar_emit = false, emitted = false, compact = false;
+  SynthStage synth = SynthStage::kNone;
+  bool odd_launch = false;  // the two-launch routes: the launch over the odd frames / groups exists (more than one of them)
+  bool odd_tail = false;    // kSynthEmit: the odd frames through k_synth_tail (the last decoded block is odd: it writes the carried tail)
+  bool debug_occ = false;   // NVH_DEBUG_OCC: the launcher prints the occupancy of k_spectrum / the frame groups
+  TransformStage transform = TransformStage::kNone;
+  OverlapStage overlap = OverlapStage::kNone;
+  bool gap_fill = false, row_fill = false;  // k_zero_gaps, k_zero_rows
+  bool carry_copy = false;                  // the last decoded block is copied out as the carried tail
+  LdsFamily opt_in = LdsFamily::kNone;
+  int opt_in_bytes = 0;
+  const char* sfx = "";  // the PCM twins' suffix of the slot names
+  Launch launch[6];      // in launch order
+  int nlaunch = 0;
+  // kernel arguments that are no launch shape: the spectrum kernels' staging capacities, NvhSynthArgs fields, k_ola_compact's
+  int cap_pass = 0, cap_ops = 0, cap_ent = 0;
+  size_t words = 0;  // the spectrum kernels' LDS words before a fused transform's padding
+  int lds_vecs = 0, xcd_map = 0, walk_two = 0, plane_stride = 0;
+  int segs = 1, ola_threads = 128, no_ola_sym = 0, emitted_frames = 0;
+};
+struct nvh_batch;
+BatchRoute plan_batch_route(const nvh_batch& b, PcmOut out, bool have_pcm, bool pcm_aligned16, bool have_carry_out);  // nvh_launch.hip
+void batch_route_names(const BatchRoute& r, std::string names[4]);                                                    // nvh_launch.hip
+
 struct nvh_batch {
   nvh_stream* s = nullptr;
   DevBuf blob;          // all descriptor arrays, one allocation
@@ -457,8 +543,7 @@ struct nvh_batch {
   int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // frames, chans, passes, ops, entries, posts, coeffs, -
   bool sequential_ola = false;
   int last_decoded = -1;  // last frame with n != 0 (its block becomes the next carried tail)
-  const char* slot_name[4] = {"-", "-", "-", "-"};  // kernels behind the four timing slots of the last launch
-  std::string slot_name_buf[4];  // storage of the names built with a twin's suffix (_s16, _planar, _s16_planar, _mono, _s16_mono, *_map)
+  BatchRoute route;  // of the last launch: the kernels behind the four timing slots, their grids and LDS sizes
   bool links_ok = false;  // op_link chains usable (every frame has < 32767 ops): k_spectrum's chain walk
   int max_ops = 0, max_ent = 0, max_pass = 0;  // largest per-frame op / entry / pass slice (LDS staging capacity of k_spectrum)
   int max_vecs = 0;     // GPU-parsed batch in slab mode: its largest slab, as k_parse reported it
@@ -629,35 +714,6 @@ int upload_setup(nvh_stream* s);                                 // nvh_setup.hi
 int upload_parse_tables(nvh_stream* s);                          // nvh_setup.hip
 int parse_book_routes(const nvh_stream* s, int book, int* gpu_parse_ok, int out[4]);  // nvh_setup.hip
 int batch_upload(nvh_stream* s, nvh_batch* b);                   // nvh_launch.hip
-// A PCM destination: the sample format (NVH_PCM_*: float, or int16_t for the kernels' _s16 twins) and the layout -- interleaved
-// (plane_stride == 0), or channel-planar with channel c's samples at base + c * plane_stride (the _planar twins) -- and the mix
-// (NVH_MIX_*): NVH_MIX_MONO is ONE plane holding the mean of the channels (the _mono twins; never together with a plane stride)
-// -- and the channel map (the *_map calls; never together with a mix): map.oc output slots, interleaved or one plane each (the
-// _map twins).  map.oc == 0: no map.  The identity map is no map (pcm_map below), so the un-mapped kernels run.
-struct PcmOut {
-  int format = NVH_PCM_F32;
-  int64_t plane_stride = 0;
-  int mix = NVH_MIX_NONE;
-  NvhChanMap map = NvhChanMap{0u, 0u, 0};
-  bool mapped() const { return map.oc > 0; }
-  int out_channels(int ch) const { return mapped() ? map.oc : ch; }  // samples per sample time of an interleaved destination / planes
-  static bool mix_ok(int mix) { return mix == NVH_MIX_NONE || mix == NVH_MIX_MONO; }
-  bool mono() const { return mix == NVH_MIX_MONO; }
-  int layout() const {
-    if (mapped()) return planar() ? NVH_LAYOUT_PLANAR_MAP : NVH_LAYOUT_INTERLEAVED_MAP;
-    return mono() ? NVH_LAYOUT_MONO : planar() ? NVH_LAYOUT_PLANAR : NVH_LAYOUT_INTERLEAVED;
-  }
-  static bool format_ok(int format) { return format == NVH_PCM_F32 || format == NVH_PCM_S16; }
-  bool s16() const { return format == NVH_PCM_S16; }
-  bool planar() const { return plane_stride > 0; }
-  size_t sample_bytes() const { return s16() ? sizeof(int16_t) : sizeof(float); }
-  // a device destination: interleaved 16-bit PCM 16-byte aligned (the stereo twins store eight samples at a time), planar PCM
-  // the mono mix and mapped PCM aligned to their samples (their vector stores run where the base is 16-byte aligned, else the
-  // fall-back)
-  bool dest_ok(const void* d_pcm) const {
-    return planar() || mono() || mapped() ? ((uintptr_t)d_pcm % sample_bytes()) == 0 : (!s16() || ((uintptr_t)d_pcm & 15u) == 0);
-  }
-};
 int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms,
                  hipEvent_t* ext_ev = nullptr, PcmOut out = PcmOut());  // nvh_launch.hip
 int collect_flags(nvh_stream* s);                                // nvh_launch.hip

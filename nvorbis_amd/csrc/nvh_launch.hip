@@ -260,17 +260,12 @@ static int batch_upload_gpu(nvh_stream* s, nvh_batch* b, const std::vector<int>&
     if (!in_lds) scratch_words = pkt_words = 0;
     const size_t stage_words = cur ? (size_t)kParseWaves * (size_t)lanes * (16 + cls_words) + sub_words : 0;
     const size_t parse_lds = (table_words + std::max(per_wg * (size_t)(scratch_words + pkt_words), stage_words) + floor_words) * sizeof(uint32_t);
-    if (!s->ctx->parse_lds_attr_set) {  // the opt-in is per device: once per context (contexts are single-threaded)
-      HIP_TRY(hipFuncSetAttribute((const void*)k_parse, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_parse_g, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_parse_slab, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_parse_slab_g, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_parse_slab_u, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_parse_slab_c, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_parse_slab_f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_parse_slab_t, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      s->ctx->parse_lds_attr_set = true;
-    }
+    // the opt-in is per device: once per context (contexts are single-threaded)
+    if (int oc = lds_opt_in(s->ctx->parse_lds_attr_set, 160 * 1024,
+                            {(const void*)k_parse, (const void*)k_parse_g, (const void*)k_parse_slab, (const void*)k_parse_slab_g,
+                             (const void*)k_parse_slab_u, (const void*)k_parse_slab_c, (const void*)k_parse_slab_f, (const void*)k_parse_slab_t});
+        oc != NVH_OK)
+      return oc;
     // one packet per wavefront (every batch of up to 4096 packets): the wave-uniform form of the slab parser
     const bool uni = slab_mode && in_lds && lanes == 1 && T.dm_in_lds && !nvh_toggles().no_parse_uni;
     if (lean) {
@@ -912,16 +907,6 @@ static auto with_pcm_twins(const PcmOut& out, F&& f) {
   __builtin_unreachable();
 }
 
-// f(tag) for every set (the kernels that need a launch attribute); the mapped sets apart: they lack the narrow families
-template <typename F>
-static void for_pcm_twins(F&& f) {
-#define NVH_PCM_EACH(PCM, LAYOUT, SFX) f(PcmTwins<PCM, LAYOUT>());
-  NVH_FOR_PCM_TWINS(NVH_PCM_EACH)
-}
-template <typename F>
-static void for_pcm_map_twins(F&& f) {
-  NVH_FOR_PCM_MAP_TWINS(NVH_PCM_EACH)
-}
 // f(tag) for the un-mapped set that writes `out` (the narrow families' kernels: never launched for a mapped call)
 template <typename F>
 static auto with_unmapped_twins(PcmOut out, F&& f) {
@@ -932,66 +917,336 @@ static auto with_unmapped_twins(PcmOut out, F&& f) {
   __builtin_unreachable();
 }
 
-// Segments: the gaps between them are zeros in the destination, whatever its form -- gap x out_channels interleaved samples, or
-// the gap in each plane (one plane for the mono mix).  One launch of k_zero_gaps, and none for a batch without gaps.  The long
-// gaps -- a windowed segment's pad up to its pitch -- go through k_zero_rows, one workgroup per (chunk, plane) of the chunk table
-// behind the gap list, and only then is that kernel named (behind the fourth slot's name).  `out` as batch_launch adjusted it.
-static void launch_gap_fill(nvh_batch* b, const PcmOut& out, void* d_pcm, hipStream_t st) {
-  if (b->gaps.empty() && b->row_chunks.empty()) return;
-  const int oc = out.out_channels(b->s->setup.channels);
-  const bool planar = out.planar(), planes = planar || out.mono();
-  if (!b->gaps.empty())
-    hipLaunchKernelGGL(k_zero_gaps, dim3((unsigned)b->gaps.size(), planar ? (unsigned)oc : 1u), dim3(256), 0, st,
-                       (const long long*)b->gap_dev.p, (unsigned char*)d_pcm, (int)out.sample_bytes(), planes ? 1 : oc,
-                       (long long)out.plane_stride);
-  if (!b->row_chunks.empty()) {
-    hipLaunchKernelGGL(k_zero_rows, dim3((unsigned)b->row_chunks.size(), planar ? (unsigned)oc : 1u), dim3(256), 0, st,
-                       (const long long*)b->gap_dev.p + 2 * b->gaps.size(), (unsigned char*)d_pcm, (int)out.sample_bytes(),
-                       planes ? 1 : oc, (long long)out.plane_stride);
-    const std::string was = b->slot_name[3];
-    b->slot_name_buf[3] = was == "-" ? std::string("k_zero_rows") : was + "+k_zero_rows";
-    b->slot_name[3] = b->slot_name_buf[3].c_str();
+// ---- the route of a batch (nvh_internal.h: BatchRoute) ----
+// plan_batch_route is where a batch's kernels, grids and LDS sizes are chosen, and the only place: it reads the batch's upload-time
+// fields, the setup, the switches and the destination, calls no HIP function and writes nothing but its result.
+
+static void route_add(BatchRoute& r, int slot, unsigned gx, unsigned gy, unsigned threads, size_t lds, int f0 = 0, int fstep = 1,
+                      int prefetch_prev = 0) {
+  r.launch[r.nlaunch++] = BatchRoute::Launch{slot, gx, gy, threads, lds, f0, fstep, prefetch_prev};
+}
+
+// Slab synthesis kernels (kernels_synth.hip): spectrum + inverse MDCT from per-frame slabs fetched by LDS-DMA.
+static void plan_slab_synth(BatchRoute& r, const nvh_batch& b, bool have_pcm) {
+  const nvh_stream* s = b.s;
+  const NvhToggles& T = nvh_toggles();
+  const bool wide = slab_wide(s), general = s->shared->slab_general;
+  const unsigned nf = (unsigned)b.nframes;
+  r.lds_vecs = (int)slab_lds_vecs(&b);
+  r.walk_two = T.no_walk_two ? 0 : (T.no_steady ? 1 : 3);  // bit 1: steady groups take the lean body
+  // paired emission (nvh_format.h: NVH_EMIT_*): the host marked the frames at upload; it needs the PCM buffer and the slabs
+  // in frame order
+  r.emitted = b.emit_frames > 0 && have_pcm && !b.block_only && !T.no_emit && !general && r.planar_emit && (wide || !r.out.mapped());
+  r.plane_stride = r.out.planar() && r.planar_emit ? (int)r.out.plane_stride : 0;
+  const size_t lds = slab_lds_bytes(&b) + (size_t)T.lds_pad;
+  const bool groups = !wide && r.emitted && b.fpw > 1;
+  if (lds > 64 * 1024) r.opt_in = groups ? LdsFamily::kGroups : LdsFamily::kSynth8, r.opt_in_bytes = 160 * 1024;
+  if (wide && r.emitted) {
+    // odd frames first, then the even frames, which overlap-add the steady-state overlaps they take part in (synth_emit8)
+    r.synth = SynthStage::kSynth8Emit;
+    if ((r.odd_launch = nf > 1)) route_add(r, 1, nf / 2, 1, 512, lds, 1, 2);
+    route_add(r, 1, (nf + 1) / 2, 1, 512, lds, 0, 2);
+  } else if (wide) {
+    r.synth = general ? SynthStage::kSynth8G : SynthStage::kSynth8;
+    route_add(r, 1, nf, 1, 512, lds);
+  } else if (general) {  // (never with paired emission: batch_upload)
+    r.synth = SynthStage::kSynthG;
+    route_add(r, 1, nf, 1, 256, lds);
+  } else if (!r.emitted) {
+    r.synth = SynthStage::kSynth;
+    route_add(r, 1, nf, 1, NVH_SYNTH_NT, lds);
+  } else if (groups) {
+    // frame groups (kernels_synth.hip): fpw consecutive frames per workgroup, the overlaps inside a group on chip.  The groups
+    // with an odd index first (they leave their outer quarters in the planes), then the even ones, which emit the overlaps
+    // between groups as well.
+    const int gw = b.fpw;
+    const unsigned ngroups = (nf + (unsigned)gw - 1) / (unsigned)gw, nt = gw == 2 ? 256u : 512u;
+    r.synth = gw == 2 ? SynthStage::kGroup2 : SynthStage::kGroup4;
+    if ((r.odd_launch = ngroups / 2 > 0)) route_add(r, 1, ngroups / 2, 1, nt, lds, gw, 2 * gw, T.group_prefetch ? 1 : 0);
+    route_add(r, 1, (ngroups + 1) / 2, 1, nt, lds, 0, 2 * gw);
+  } else {
+    // odd frames first (their planes are what the even frames overlap-add with), then the even frames, which emit
+    // (the odd frames never emit: the plain kernel, or the one that can write the carried tail when the last decoded block is odd)
+    r.synth = SynthStage::kSynthEmit;
+    r.odd_tail = b.last_decoded >= 0 && (b.last_decoded & 1);
+    r.xcd_map = T.xcd_map ? 1 : 0;  // opt-in: one stream 36.3 -> 35.6 us per pass, three streams 174 -> 172 M frames/s
+    if ((r.odd_launch = nf > 1)) route_add(r, 1, nf / 2, 1, NVH_SYNTH_NT, lds, 1, 2, T.no_prefetch ? 0 : 1);
+    route_add(r, 1, (nf + 1) / 2, 1, NVH_SYNTH_NT, lds, 0, 2);
   }
 }
 
-int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms, hipEvent_t* ext_ev,
-                 PcmOut out) {
-  nvh_stream* s = b->s;
-  hipStream_t st = s->ctx->stream;
+// Descriptor kernels: the fused spectrum kernel when a frame's spectrum (+ staged side information) fits the dynamic LDS window
+// (LDS map in kernels_spectrum.hip), with the inverse MDCT inside where it fits as well; else the global-memory kernels.
+// Returns whether the transform is inside the synthesis kernel.
+static bool plan_descriptor_synth(BatchRoute& r, const nvh_batch& b) {
+  const nvh_stream* s = b.s;
+  const NvhToggles& T = nvh_toggles();
   const int ch = s->setup.channels;
-  if (b->nframes == 0) {
-    // no frames: nothing to synthesise -- but a batch of windowed segments may still hold pads (rows of zeros)
-    if (b->gaps.empty() && b->row_chunks.empty()) return NVH_OK;
-    for (int k = 0; k < 4; k++) b->slot_name[k] = "-";
-    if (ch == 1 && !out.mapped()) out.plane_stride = 0, out.mix = NVH_MIX_NONE;
-    if (d_pcm && !b->block_only) launch_gap_fill(b, out, d_pcm, st);
-    HIP_TRY(hipGetLastError());
-    return NVH_OK;
+  const size_t b1 = (size_t)s->setup.block1;
+  const unsigned nf = (unsigned)b.nframes;
+  const bool has_floor0 = s->has_floor0;
+  const bool fast = s->fast_spectrum && b.links_ok;  // k_spectrum proper (pair path by chain walk, fused tail)
+  const bool may_fuse = r.compact && !T.no_fused_imdct;
+  // more than four channels without Floor0: 8 wavefronts per workgroup (k_spectrum_gen8), one floor scratch block each
+  const bool gen8 = !has_floor0 && !fast && ch > 4 && !T.no_gen8;
+  const int scratch_blocks = gen8 ? (ch < 8 ? ch : 8) : (ch < 4 ? ch : 4);
+  const size_t scratch_words = (size_t)scratch_blocks * NVH_SP_FLOOR_SCRATCH_WORDS;
+  // staging capacities; the entry slice is copied from its enclosing 16-byte boundary (up to 7 entries of slack)
+  r.cap_pass = b.max_pass, r.cap_ops = (b.max_ops + 7) & ~7, r.cap_ent = (b.max_ent + 14) & ~7;
+  const size_t staging_words = (size_t)s->setup.books.size() * 8 + (size_t)((s->dev.lattice_words + 3) & ~3) + (size_t)r.cap_pass * 16 +
+                               (size_t)r.cap_ops * 6 + (size_t)r.cap_ops / 2 + (size_t)r.cap_ent / 2;  // ops 2 + pair records 4 + links 1/2 words per op
+  // k_spectrum_gen8 overlays the floor scratch on the staged side information (dead by the time the floors are prepared)
+  size_t words = (size_t)(has_floor0 ? 512 : 256) + (gen8 ? std::max(scratch_words, staging_words) : scratch_words + staging_words) +
+                 (size_t)ch * (b1 / 2);
+  if (T.unfused) words = 1u << 20;  // test aid: force the unfused kernels below
+  r.words = words;
+  // A frame that does not fit the default 64 KB dynamic-LDS window (six channels at n = 4096 with full-depth packets:
+  // 48 KB of spectrum + ~25 KB of staged ops and entries) still fits the CU's 160 KB: the general kernels opt in to a larger
+  // window, one workgroup per CU, instead of falling back to the global-memory kernels (measured on the C4 full-depth
+  // stream: k_residue + k_couple_floor 510 us per 2048 frames).
+  size_t lds_limit = 64 * 1024;
+  // (not for residues that replay the reference's partition order, one vector write at a time: a lone 8-wavefront workgroup
+  // per CU is the worst shape for that -- 1135 us against 840 us for the global-memory kernels on the psize-32 C4 stream)
+  if (!has_floor0 && !fast && !T.unfused && !s->shared->has_sequential && words * 4 > lds_limit && words * 4 <= 152 * 1024)
+    r.opt_in = LdsFamily::kSpectrum, r.opt_in_bytes = 152 * 1024, lds_limit = 152 * 1024;
+  if (words * 4 > lds_limit) {
+    r.synth = SynthStage::kResidueCoupleFloor;
+    route_add(r, 0, nf, 1, 256, 0);
+    route_add(r, 1, nf, 1, 256, 0);
+    return false;
   }
-  // Channel-planar output: the _planar twins.  One channel is the same bytes either way: mono takes the interleaved kernels.
-  // The twins' vector stores need every plane's first sample of a frame on a 16-byte boundary: an aligned base, a plane stride in
-  // whole groups of four samples (below 2^31: NvhSynthArgs::plane_stride) and a frame position in whole groups of four
-  // (batch_upload: emit_planar_ok); otherwise the batch runs without paired emission and k_ola_compact<PCM, true> takes each frame
-  // by its vector form where that frame's own position allows it, else sample by sample.
-  // The mono mix (the _mono twins): one plane, so the same condition without the stride, and the same fall-back; the mix of one
-  // channel is that channel.
+  // the padding of slices laid over the dead front of the LDS area (floor scratch, side information) has to fit in front of the spectra
+  const bool front_fits = 256 + (size_t)ch * (b1 / 16) <= words - (size_t)ch * (b1 / 2);
+  bool fused = false;
+  if (has_floor0) {
+    r.synth = SynthStage::kSpectrumF0;
+    route_add(r, 1, nf, 1, 256, words * 4);
+  } else if (gen8) {
+    // the inverse MDCT in the same workgroup (one wavefront per channel): block sizes the in-register spectrum covers
+    fused = may_fuse && ch <= 8 && b1 <= 4096 && front_fits;
+    r.synth = fused ? SynthStage::kSpectrumGen8Imdct : SynthStage::kSpectrumGen8;
+    route_add(r, 1, nf, 1, 512, words * 4);
+  } else if (!fast) {
+    // the inverse MDCT in the same workgroup where a wavefront per channel exists: mono / stereo setups take the kernel's
+    // fused tail and k_spectrum_imdct's transform (one n/16-float pad behind the spectra), three and four channels the general
+    // tail and the transform of k_spectrum_gen8_imdct (slices over the dead front of the LDS area)
+    size_t extra = 0;
+    if (may_fuse && ch <= 4) {
+      if (s->dev.fused_tail_ok) {
+        fused = b1 <= 2048 && (words + b1 / 16) * 4 <= lds_limit;
+        if (fused) extra = (b1 / 16) * 4;
+      } else {
+        fused = b1 <= 4096 && front_fits;
+      }
+    }
+    r.synth = fused ? SynthStage::kSpectrumGenImdct : SynthStage::kSpectrumGen;
+    route_add(r, 1, nf, 1, 256, words * 4 + extra);
+  } else {
+    // spectrum + IMDCT in one kernel: block sizes the single-pass wavefront IMDCT covers, + the IMDCT padding of the last
+    // channel (n/16 floats past the spectrum area) inside the default window
+    fused = may_fuse && b1 <= 2048 && (words + b1 / 16) * 4 <= 64 * 1024;
+    r.synth = fused ? SynthStage::kSpectrumImdct : SynthStage::kSpectrum;
+    route_add(r, 1, nf, 1, 256, words * 4 + (fused ? (b1 / 16) * 4 : 0) + (size_t)T.lds_pad);
+  }
+  return fused;
+}
+
+// Segments: the gaps between them are zeros in the destination, whatever its form -- gap x out_channels interleaved samples, or
+// the gap in each plane (one plane for the mono mix).  One launch of k_zero_gaps, and none for a batch without gaps.  The long
+// gaps -- a windowed segment's pad up to its pitch -- go through k_zero_rows, one workgroup per (chunk, plane) of the chunk table
+// behind the gap list.
+static void plan_gap_fill(BatchRoute& r, const nvh_batch& b, bool have_pcm) {
+  if (!have_pcm || b.block_only) return;
+  const unsigned planes = r.out.planar() ? (unsigned)r.out.out_channels(b.s->setup.channels) : 1u;
+  if ((r.gap_fill = !b.gaps.empty())) route_add(r, 3, (unsigned)b.gaps.size(), planes, 256, 0);
+  if ((r.row_fill = !b.row_chunks.empty())) route_add(r, 3, (unsigned)b.row_chunks.size(), planes, 256, 0);
+}
+
+BatchRoute plan_batch_route(const nvh_batch& b, PcmOut out, bool have_pcm, bool pcm_aligned16, bool have_carry_out) {
+  const nvh_stream* s = b.s;
+  const NvhToggles& T = nvh_toggles();
+  const int ch = s->setup.channels, b0 = s->setup.block0, b1 = s->setup.block1;
+  const unsigned nf = (unsigned)b.nframes;
+  BatchRoute r;
+  // One channel is the same bytes in every layout: mono takes the interleaved kernels; the mix of one channel is that channel.
+  if (ch == 1 && !out.mapped()) out.plane_stride = 0, out.mix = NVH_MIX_NONE;
+  r.out = out;
+  r.sfx = with_pcm_twins(out, [](auto t) { return t.sfx; });
+  r.debug_occ = T.debug_occ;
+  if (b.nframes == 0) {
+    // no frames: nothing to synthesise -- but a batch of windowed segments may still hold pads (rows of zeros)
+    r.nothing = b.gaps.empty() && b.row_chunks.empty();
+    plan_gap_fill(r, b, have_pcm);
+    return r;
+  }
+  // Channel-planar output: the _planar twins.  The twins' vector stores need every plane's first sample of a frame on a 16-byte
+  // boundary: an aligned base, a plane stride in whole groups of four samples (below 2^31: NvhSynthArgs::plane_stride) and a
+  // frame position in whole groups of four (batch_upload: emit_planar_ok); otherwise the batch runs without paired emission and
+  // k_ola_compact<PCM, true> takes each frame by its vector form where that frame's own position allows it, else sample by sample.
+  // The mono mix (the _mono twins): one plane, so the same condition without the stride, and the same fall-back.
   // A channel map (the _map twins): interleaved, the vector stores need the aligned base and every emitted frame at
   // out_pos * out_channels in whole groups of four -- asked of out_pos itself, the planar condition; planar, the planar condition
   // as it is.  Only the wide emitting kernel has mapped forms: a mono / stereo stream's mapped batch (blocks up to 2048) runs
   // without paired emission, k_synth + the mapped k_ola_compact, the route of a misaligned planar destination.
-  if (ch == 1 && !out.mapped()) out.plane_stride = 0, out.mix = NVH_MIX_NONE;
   const bool planar = out.planar();
-  const int64_t plane_stride = out.plane_stride;
-  const bool planar_emit = out.mono() || (out.mapped() && !planar)
-                               ? (((uintptr_t)d_pcm & 15u) == 0 && b->emit_planar_ok)
-                               : !planar || (((uintptr_t)d_pcm & 15u) == 0 && (plane_stride & 3) == 0 &&
-                                             plane_stride <= 0x7FFFFFFFll && b->emit_planar_ok);
-  const char* sfx = with_pcm_twins(out, [](auto t) { return t.sfx; });
+  r.planar_emit = out.mono() || (out.mapped() && !planar)
+                      ? (pcm_aligned16 && b.emit_planar_ok)
+                      : !planar || (pcm_aligned16 && (out.plane_stride & 3) == 0 && out.plane_stride <= 0x7FFFFFFFll && b.emit_planar_ok);
+  // compact hand-over (two independent quarters per block, windowed in the overlap kernel) whenever no overlap
+  // ever modifies a tail (the in-place sequential form needs the full windowed blocks)
+  r.compact = b0 >= 256 && !b.sequential_ola && !T.no_compact && !b.block_only;
+  bool fused = true;  // the slab kernels have the inverse MDCT inside
+  if (b.slabs_ready && r.compact && !T.no_fused_imdct) plan_slab_synth(r, b, have_pcm);
+  else fused = plan_descriptor_synth(r, b);
+
+  if (fused) r.transform = TransformStage::kNone;
+  else if (r.compact || b0 >= 256) {
+    r.transform = r.compact ? TransformStage::kImdctCompact : TransformStage::kImdctWave;
+    route_add(r, 2, nf * (unsigned)ch, 1, 64, wave_lds_bytes(b1));
+  } else {
+    r.transform = TransformStage::kImdctWindow;
+    route_add(r, 2, nf * (unsigned)ch, 1, 256, (size_t)b1 * sizeof(float));
+  }
+
+  if (b.block_only) {
+    r.overlap = OverlapStage::kNone;  // nvh_mode_decode: the caller wants the windowed blocks themselves
+  } else if (r.compact) {
+    // (frame order by XCD -- blocks f and f-1, which share a quarter, behind the same L2 -- measured slower: 23.3 us, not 21.8)
+    // 128 lanes per frame: 21.4 us instead of 24.8 us on its own (more loads in flight per frame); with two batches
+    // in flight it is a wash against 64, and 256 lanes start to take wave slots from the other batch's spectrum kernel
+    r.ola_threads = (T.ola_threads == 64 || T.ola_threads == 128 || T.ola_threads == 256) ? T.ola_threads : 128;
+    // large frames are shared by several workgroups (kernels.hip): aim at one group of four sample times per lane
+    int segs = T.ola_segs > 0 ? T.ola_segs : (int)(((size_t)b1 / 8 * (size_t)ch) / (size_t)(2 * 256));
+    if (segs < 1) segs = 1;
+    if (segs > 8) segs = 8;
+    if (segs > (b1 / 8) / r.ola_threads) segs = (b1 / 8) / r.ola_threads;
+    if (segs < 1) segs = 1;
+    // more than two channels: the steady-state path splits a frame into runs of NVH_OLA_GW groups of four sample times, one
+    // workgroup each, and interleaves through LDS (ola_sym_lds)
+    if (ch > 2 && !T.no_ola_sym && T.ola_segs <= 0) segs = ((b1 / 16) + NVH_OLA_GW - 1) / NVH_OLA_GW;
+    r.segs = segs;
+    r.no_ola_sym = T.no_ola_sym ? 1 : 0;
+    r.emitted_frames = r.emitted ? 1 : 0;
+    if (!r.emitted) r.overlap = OverlapStage::kCompactAll;
+    else if (b.ola_all) r.overlap = OverlapStage::kCompactAllEmitted;  // GPU-parsed batch, some candidate withdrawn on the device
+    else if (b.ola_count == 0) r.overlap = OverlapStage::kNone;  // paired emission covered every frame, the carried tail included
+    else r.overlap = OverlapStage::kCompactList;                 // paired emission: only the frames k_synth left over
+    if (r.overlap != OverlapStage::kNone)
+      route_add(r, 3, r.overlap == OverlapStage::kCompactList ? (unsigned)b.ola_count : nf, (unsigned)segs, (unsigned)r.ola_threads, 0);
+  } else if (!b.sequential_ola) {
+    r.overlap = OverlapStage::kEmit;
+    route_add(r, 3, nf, 1, 256, 0);
+  } else {
+    r.overlap = OverlapStage::kEmitSeq;
+    route_add(r, 3, 1, 1, 256, 0);
+  }
+  // the last decoded block becomes the carried tail (StreamDecoder's _prevPacketBuf), always fully windowed
+  r.carry_copy = !r.compact && !b.block_only && b.last_decoded >= 0 && have_carry_out;
+  plan_gap_fill(r, b, have_pcm);
+  return r;
+}
+
+// The names behind the four timing slots (nvh_batch_kernels), from the stages and the PCM twins' suffix: "-" for an empty slot,
+// the two kernels of a paired emission joined by "+", and k_zero_rows named behind the fourth slot's kernel when it ran.
+void batch_route_names(const BatchRoute& r, std::string names[4]) {
+  static const struct { const char* name; bool twin; } synth[] = {
+      {"-", false},
+      {"k_synth", false}, {"k_synth_g", false}, {"k_synth8", false}, {"k_synth8_g", false},
+      {"k_synth8+k_synth8_emit", true}, {"k_synth+k_synth_emit", true}, {"k_synth_group2", true}, {"k_synth_group4", true},
+      {"k_spectrum_f0", false}, {"k_spectrum_gen", false}, {"k_spectrum_gen_imdct", false}, {"k_spectrum_gen8", false},
+      {"k_spectrum_gen8_imdct", false}, {"k_spectrum", false}, {"k_spectrum_imdct", false},
+      {"k_couple_floor", false}};
+  static const char* const transform[] = {"-", "k_imdct_compact", "k_imdct_wave", "k_imdct_window"};
+  static const char* const overlap[] = {"-", "k_ola_compact", "k_ola_compact", "k_ola_compact", "k_ola_emit", "k_ola_emit_seq"};
+  static_assert(sizeof synth / sizeof synth[0] == (size_t)SynthStage::kResidueCoupleFloor + 1, "one name per SynthStage");
+  static_assert(sizeof overlap / sizeof overlap[0] == (size_t)OverlapStage::kEmitSeq + 1, "one name per OverlapStage");
+  names[0] = r.synth == SynthStage::kResidueCoupleFloor ? "k_residue" : "-";
+  names[1] = synth[(int)r.synth].name;
+  if (synth[(int)r.synth].twin) names[1] += r.sfx;
+  names[2] = transform[(int)r.transform];
+  names[3] = overlap[(int)r.overlap];
+  if (r.overlap != OverlapStage::kNone) names[3] += r.sfx;
+  if (r.row_fill) names[3] = r.overlap == OverlapStage::kNone ? "k_zero_rows" : names[3] + "+k_zero_rows";
+}
+
+// ---- the launcher: executes a route and decides nothing ----
+
+// Launches the route's records in order, each with the grid, block and LDS bytes the planner wrote; with `timing`, the event
+// that opens a slot is recorded in front of the slot's first launch (and the remaining ones by finish).
+struct RouteLauncher {
+  const BatchRoute& r;
+  hipStream_t st;
+  hipEvent_t* ev;  // five events, or null: no timing
+  int next = 0, slot = 0;
+  hipError_t err = hipSuccess;
+  void open(int upto) {
+    while (ev && slot < upto && err == hipSuccess) err = hipEventRecord(ev[++slot], st);
+  }
+  const BatchRoute::Launch& peek() const { return r.launch[next]; }
+  template <typename K, typename... Args>
+  void operator()(K kern, const Args&... args) {
+    const BatchRoute::Launch& L = r.launch[next++];
+    open(L.slot);
+    hipLaunchKernelGGL(kern, dim3(L.gx, L.gy), dim3(L.threads), L.lds, st, args...);
+  }
+};
+
+static void launch_gap_fill(nvh_batch* b, RouteLauncher& go, void* d_pcm) {
+  const PcmOut& out = go.r.out;
+  const int oc = out.planar() || out.mono() ? 1 : out.out_channels(b->s->setup.channels);
+  if (go.r.gap_fill)
+    go(k_zero_gaps, (const long long*)b->gap_dev.p, (unsigned char*)d_pcm, (int)out.sample_bytes(), oc, (long long)out.plane_stride);
+  if (go.r.row_fill)
+    go(k_zero_rows, (const long long*)b->gap_dev.p + 2 * b->gaps.size(), (unsigned char*)d_pcm, (int)out.sample_bytes(), oc,
+       (long long)out.plane_stride);
+}
+
+static void print_occupancy(const char* what, const void* kern, const BatchRoute::Launch& L, const NvhSynthArgs* A) {
+  int nb = -1;
+  hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, (int)L.threads, L.lds);
+  hipFuncAttributes fa;
+  (void)hipFuncGetAttributes(&fa, kern);
+  fprintf(stderr, "%s: %u threads, lds %zu B, occupancy %d WG/CU (err %d), regs %d, static lds %zu, max dyn lds %d\n", what, L.threads,
+          L.lds, nb, (int)oe, fa.numRegs, fa.sharedSizeBytes, fa.maxDynamicSharedSizeBytes);
+  if (A) fprintf(stderr, "%s: constants %d, slab area %d, largest slab %d vecs\n", what, A->const_vecs, A->lds_vecs, A->cap_vecs);
+}
+
+// A kernel family's opt-in to the CU's LDS, once per context (nvh_internal.h: lds_opt_in)
+static int route_opt_in(nvh_ctx* c, const BatchRoute& r) {
+#define NVH_K_SYNTH8_EMIT(PCM, LAYOUT, SFX) (const void*)k_synth8_emit##SFX,
+#define NVH_K_GROUPS(PCM, LAYOUT, SFX) (const void*)k_synth_group2##SFX, (const void*)k_synth_group4##SFX,
+  switch (r.opt_in) {
+    case LdsFamily::kNone: return NVH_OK;
+    case LdsFamily::kSpectrum:
+      return lds_opt_in(c->big_lds_attr_set, r.opt_in_bytes, {(const void*)k_spectrum_gen, (const void*)k_spectrum_gen8,
+                                                              (const void*)k_spectrum_gen8_imdct, (const void*)k_spectrum_gen_imdct});
+    case LdsFamily::kSynth8:
+      return lds_opt_in(c->synth_lds_attr_set, r.opt_in_bytes, {(const void*)k_synth8, (const void*)k_synth8_g,
+                                                                NVH_FOR_PCM_TWINS(NVH_K_SYNTH8_EMIT) NVH_FOR_PCM_MAP_TWINS(NVH_K_SYNTH8_EMIT)});
+    case LdsFamily::kGroups: return lds_opt_in(c->group_lds_attr_set, r.opt_in_bytes, {NVH_FOR_PCM_TWINS(NVH_K_GROUPS)});
+  }
+  return NVH_OK;
+}
+
+int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm, bool timing, float* kernel_ms, hipEvent_t* ext_ev,
+                 PcmOut out_asked) {
+  nvh_stream* s = b->s;
+  hipStream_t st = s->ctx->stream;
+  const BatchRoute r = plan_batch_route(*b, out_asked, d_pcm != nullptr, ((uintptr_t)d_pcm & 15u) == 0, carry_out != nullptr);
+  if (r.nothing) return NVH_OK;
+  b->route = r;
+  const PcmOut& out = r.out;
+  if (r.synth == SynthStage::kNone) {  // no frames, pads only
+    RouteLauncher go{b->route, st, nullptr};
+    launch_gap_fill(b, go, d_pcm);
+    HIP_TRY(hipGetLastError());
+    return NVH_OK;
+  }
   // the k_ola_* kernels' last argument: the planes' stride, nothing in the interleaved forms
   auto ola_stride = [&](auto t) {
-    if constexpr (decltype(t)::layout == NVH_LAYOUT_PLANAR) return (long long)plane_stride;
+    if constexpr (decltype(t)::layout == NVH_LAYOUT_PLANAR) return (long long)out.plane_stride;
     else if constexpr (decltype(t)::layout == NVH_LAYOUT_INTERLEAVED_MAP) return out.map;
-    else if constexpr (decltype(t)::layout == NVH_LAYOUT_PLANAR_MAP) return NvhStrideMap{(long long)plane_stride, out.map};
+    else if constexpr (decltype(t)::layout == NVH_LAYOUT_PLANAR_MAP) return NvhStrideMap{(long long)out.plane_stride, out.map};
     else return NvhNoStride();
   };
   float* work = (float*)b->work.p;
@@ -1003,7 +1258,7 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
     else HIP_TRY(hipMemsetAsync(flags + 2, 0, sizeof table, st));
     s->seg_table_set = table;
   }
-  const size_t lds = (size_t)s->setup.block1 * sizeof(float);
+  if (int rc = route_opt_in(s->ctx, r); rc != NVH_OK) return rc;
   ScopedEvent sev[5];
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   // timing: five event records bracket the four slots.  With the caller's events (ext_ev) nothing is waited for here: the caller
@@ -1020,308 +1275,129 @@ int batch_launch(nvh_batch* b, const float* carry, float* carry_out, void* d_pcm
       ev[k] = sev[k].e;
     }
   if (timing) HIP_TRY(hipEventRecord(ev[0], st));
-  // compact hand-over (two independent quarters per block, windowed in the overlap kernel) whenever no overlap
-  // ever modifies a tail (the in-place sequential form needs the full windowed blocks)
-  const NvhToggles& T = nvh_toggles();
-  const bool no_compact = T.no_compact, no_fused_imdct = T.no_fused_imdct;
-  const bool compact = s->setup.block0 >= 256 && !b->sequential_ola && !no_compact && !b->block_only;
-  // spectrum + IMDCT in one kernel: pair-path / fused-tail streams with block sizes the single-pass wavefront IMDCT covers
-  const bool fast = s->fast_spectrum && b->links_ok;  // k_spectrum proper (pair path by chain walk, fused tail)
-  bool fuse_imdct = compact && fast && s->setup.block1 <= 2048 && !no_fused_imdct;  // and the LDS-resident path is taken (below)
-  bool fuse_gen8 = false;  // k_spectrum_gen8_imdct (below)
-  // ---- slab synthesis kernels (kernels_synth.hip): spectrum + inverse MDCT from per-frame slabs fetched by LDS-DMA ----
-  bool slab_done = false;
-  bool emitted = false;  // paired emission ran: k_synth wrote the PCM of the frames marked NVH_EMIT_DONE
-  if (b->slabs_ready && compact && !no_fused_imdct) {
-    NvhSynthArgs A;
-    A.consts = s->shared->synth_consts;
-    A.slabs = b->slab_host ? b->d_slabs : (const uint4*)b->slab3.p;
-    A.work = work;
-    A.err = flags;
-    for (int w = 0; w < 2; w++) {
-      A.mdct_a[w] = s->dev.mdct_a[w]; A.mdct_b[w] = s->dev.mdct_b[w]; A.mdct_c[w] = s->dev.mdct_c[w]; A.mdct_tw[w] = s->dev.mdct_tw[w];
-    }
-    A.ipool = s->dev.ipool;
-    A.vq = s->dev.vq;
-    A.const_vecs = s->shared->synth_const_vecs;
-    A.stride_vecs = b->slab_stride_vecs;
-    A.cap_vecs = b->slab_cap_vecs;
-    A.lds_vecs = (int)slab_lds_vecs(b);
-    A.channels = ch;
-    A.block1 = s->setup.block1;
-    A.f0 = 0; A.fstep = 1;
-    A.nframes = b->nframes;
-    A.prefetch_prev = 0;
-    A.xcd_map = 0;
-    A.walk_two = nvh_toggles().no_walk_two ? 0 : (nvh_toggles().no_steady ? 1 : 3);  // bit 1: steady groups take the lean body
-    const bool wide = slab_wide(s);
-    // paired emission (nvh_format.h: NVH_EMIT_*): the host marked the frames at upload; it needs the PCM buffer and the slabs
-    // in frame order
-    emitted = b->emit_frames > 0 && d_pcm != nullptr && !b->block_only && !T.no_emit && !s->shared->slab_general && planar_emit &&
-              (wide || !out.mapped());
-    A.pcm = emitted ? (float*)d_pcm : nullptr;  // (int16_t samples for the _s16 twins)
-    A.windows = s->dev.windows;
-    A.clip = s->clip;
-    A.plane_stride = planar && planar_emit ? (int)plane_stride : 0;
-    A.clipped_flag = flags + 1;
-    A.carry = carry;
-    A.carry_out = emitted ? carry_out : nullptr;
-    A.frames = b->dev.frames;
-    const size_t synth_lds = slab_lds_bytes(b) + (size_t)T.lds_pad;
-    if (synth_lds > 64 * 1024 && !s->ctx->synth_lds_attr_set) {
-      HIP_TRY(hipFuncSetAttribute((const void*)k_synth8, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_synth8_g, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      hipError_t attr_err = hipSuccess;
-      auto big_lds = [&](auto t) {
-        if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void*)t.synth8_emit, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      };
-      for_pcm_twins(big_lds);
-      for_pcm_map_twins(big_lds);
-      HIP_TRY(attr_err);
-      s->ctx->synth_lds_attr_set = true;
-    }
-    if (timing) HIP_TRY(hipEventRecord(ev[1], st));  // slot 0 stays empty: slot 1 = the synthesis kernel
-    b->slot_name[0] = "-";
-    const bool narrow_general = !wide && s->shared->slab_general;  // (never with paired emission: batch_upload)
-    const bool wide_general = wide && s->shared->slab_general;
-    b->slot_name[1] = wide ? (wide_general ? "k_synth8_g" : "k_synth8") : (narrow_general ? "k_synth_g" : "k_synth");
-    if (wide && emitted) {
-      // odd frames first, then the even frames, which overlap-add the steady-state overlaps they take part in (synth_emit8)
-      A.fstep = 2;
-      A.f0 = 1;
-      if (b->nframes > 1) hipLaunchKernelGGL(k_synth8, dim3((unsigned)(b->nframes / 2)), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
-      A.f0 = 0;
-      with_pcm_twins(out, [&](auto t) {
-        const dim3 grid((unsigned)((b->nframes + 1) / 2));
-        if constexpr (nvh_layout_mapped(decltype(t)::layout)) hipLaunchKernelGGL(t.synth8_emit, grid, dim3(512), synth_lds, st, A, out.map NVH_DBG_LAUNCH);
-        else hipLaunchKernelGGL(t.synth8_emit, grid, dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
-      });
-    } else if (wide_general) hipLaunchKernelGGL(k_synth8_g, dim3((unsigned)b->nframes), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
-    else if (wide) hipLaunchKernelGGL(k_synth8, dim3((unsigned)b->nframes), dim3(512), synth_lds, st, A NVH_DBG_LAUNCH);
-    else if (narrow_general) hipLaunchKernelGGL(k_synth_g, dim3((unsigned)b->nframes), dim3(256), synth_lds, st, A NVH_DBG_LAUNCH);
-    else if (!emitted) hipLaunchKernelGGL(k_synth, dim3((unsigned)b->nframes), dim3(NVH_SYNTH_NT), synth_lds, st, A NVH_DBG_LAUNCH);
-    else if (b->fpw > 1) {
-      // frame groups (kernels_synth.hip): fpw consecutive frames per workgroup, the overlaps inside a group on chip.  The groups
-      // with an odd index first (they leave their outer quarters in the planes), then the even ones, which emit the overlaps
-      // between groups as well.
-      const int gw = b->fpw, ngroups = (b->nframes + gw - 1) / gw;
-      if (synth_lds > 64 * 1024 && !s->ctx->group_lds_attr_set) {
-        hipError_t attr_err = hipSuccess;
-        for_pcm_twins([&](auto t) {
-          for (const void* k : {(const void*)t.group2, (const void*)t.group4})
-            if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        });
-        HIP_TRY(attr_err);
-        s->ctx->group_lds_attr_set = true;
+  RouteLauncher go{b->route, st, timing ? ev : nullptr};
+
+  // ---- synthesis: slot 1 (and slot 0 for k_residue) ----
+  NvhSynthArgs A;
+  // a slab launch: the frames it takes (f0, fstep) and its prefetch hint are the launch record's
+  auto slab = [&](auto kern, const auto&... more) {
+    const BatchRoute::Launch& L = go.peek();
+    A.f0 = L.f0, A.fstep = L.fstep, A.prefetch_prev = L.prefetch_prev;
+    go(kern, A, more... NVH_DBG_LAUNCH);
+  };
+  auto spectrum = [&](auto kern) { go(kern, s->dev, b->dev, work, flags, r.cap_pass, r.cap_ops, r.cap_ent NVH_DBG_LAUNCH); };
+  switch (r.synth) {
+    case SynthStage::kNone: break;
+    case SynthStage::kSpectrumF0: go(k_spectrum_f0, s->dev, b->dev, work, flags, r.cap_pass, r.cap_ops, r.cap_ent); break;
+    case SynthStage::kSpectrumGen: spectrum(k_spectrum_gen); break;
+    case SynthStage::kSpectrumGenImdct: spectrum(k_spectrum_gen_imdct); break;
+    case SynthStage::kSpectrumGen8: spectrum(k_spectrum_gen8); break;
+    case SynthStage::kSpectrumGen8Imdct: spectrum(k_spectrum_gen8_imdct); break;
+    case SynthStage::kSpectrum:
+    case SynthStage::kSpectrumImdct:
+      if (r.debug_occ) print_occupancy("k_spectrum", (const void*)k_spectrum, go.peek(), nullptr);
+      spectrum(r.synth == SynthStage::kSpectrum ? k_spectrum : k_spectrum_imdct);
+      break;
+    case SynthStage::kResidueCoupleFloor:
+      go(k_residue, s->dev, b->dev, work, 1);
+      go(k_couple_floor, s->dev, b->dev, work, flags);
+      break;
+    default: {  // the slab routes
+      A.consts = s->shared->synth_consts;
+      A.slabs = b->slab_host ? b->d_slabs : (const uint4*)b->slab3.p;
+      A.work = work;
+      A.err = flags;
+      for (int w = 0; w < 2; w++) {
+        A.mdct_a[w] = s->dev.mdct_a[w]; A.mdct_b[w] = s->dev.mdct_b[w]; A.mdct_c[w] = s->dev.mdct_c[w]; A.mdct_tw[w] = s->dev.mdct_tw[w];
       }
-      auto kern = with_unmapped_twins(out, [gw](auto t) { return gw == 2 ? t.group2 : t.group4; });
-      const unsigned nt = gw == 2 ? 256u : 512u;
-      if (T.debug_occ) {
-        int nb = -1;
-        hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, (int)nt, synth_lds);
-        hipFuncAttributes fa;
-        (void)hipFuncGetAttributes(&fa, (const void*)kern);
-        fprintf(stderr, "frame groups of %d: %u threads, lds %zu B (constants %d, slab area %d, largest slab %d vecs), occupancy %d WG/CU (err %d), regs %d\n",
-                gw, nt, synth_lds, A.const_vecs, A.lds_vecs, A.cap_vecs, nb, (int)oe, fa.numRegs);
-      }
-      A.fstep = 2 * gw;
-      A.f0 = gw;
-      static const bool group_prefetch = std::getenv("NVH_GROUP_PREFETCH") != nullptr;  // (measured: 181.6 with, 184.5 M frames/s without)
-      A.prefetch_prev = group_prefetch ? 1 : 0;
-      if (ngroups / 2 > 0) hipLaunchKernelGGL(kern, dim3((unsigned)(ngroups / 2)), dim3(nt), synth_lds, st, A NVH_DBG_LAUNCH);
-      A.f0 = 0;
-      A.prefetch_prev = 0;
-      hipLaunchKernelGGL(kern, dim3((unsigned)((ngroups + 1) / 2)), dim3(nt), synth_lds, st, A NVH_DBG_LAUNCH);
-    } else {
-      // odd frames first (their planes are what the even frames overlap-add with), then the even frames, which emit
-      // (the odd frames never emit: the plain kernel, or the one that can write the carried tail when the last decoded block is odd)
-      A.fstep = 2;
-      A.f0 = 1;
-      A.prefetch_prev = nvh_toggles().no_prefetch ? 0 : 1;
-      A.xcd_map = nvh_toggles().xcd_map ? 1 : 0;  // opt-in: one stream 36.3 -> 35.6 us per pass, three streams 174 -> 172 M frames/s
-      if (b->nframes > 1) {
-        if (b->last_decoded >= 0 && (b->last_decoded & 1))
-          hipLaunchKernelGGL(k_synth_tail, dim3((unsigned)(b->nframes / 2)), dim3(NVH_SYNTH_NT), synth_lds, st, A NVH_DBG_LAUNCH);
-        else
-          hipLaunchKernelGGL(k_synth, dim3((unsigned)(b->nframes / 2)), dim3(NVH_SYNTH_NT), synth_lds, st, A NVH_DBG_LAUNCH);
-      }
-      A.f0 = 0;
-      A.prefetch_prev = 0;
-      auto kern = with_unmapped_twins(out, [](auto t) { return t.synth_emit; });
-      hipLaunchKernelGGL(kern, dim3((unsigned)((b->nframes + 1) / 2)), dim3(NVH_SYNTH_NT), synth_lds, st, A NVH_DBG_LAUNCH);
-    }
-    if (emitted) {  // odd frames, then the emitting even frames; the twins' names carry the format's / layout's suffix
-      b->slot_name_buf[1] = std::string(wide ? "k_synth8+k_synth8_emit" : (b->fpw == 2 ? "k_synth_group2" : b->fpw == 4 ? "k_synth_group4" : "k_synth+k_synth_emit")) + sfx;
-      b->slot_name[1] = b->slot_name_buf[1].c_str();
-    }
-    slab_done = true;
-    fuse_gen8 = true;  // the inverse MDCT is inside: no transform kernel behind it
-  }
-  // Fused spectrum kernel when a frame's spectrum (+ staged side information) fits the default 64 KB dynamic
-  // LDS window; LDS map in kernels_spectrum.hip.
-  if (!slab_done) {
-    const bool has_floor0 = s->has_floor0;
-    // more than four channels without Floor0: 8 wavefronts per workgroup (k_spectrum_gen8), one floor scratch block each
-    const bool no_gen8 = T.no_gen8;
-    const bool gen8 = !has_floor0 && !fast && ch > 4 && !no_gen8;
-    const int scratch_blocks = gen8 ? (ch < 8 ? ch : 8) : (ch < 4 ? ch : 4);
-    const size_t scratch_words = (size_t)scratch_blocks * NVH_SP_FLOOR_SCRATCH_WORDS;
-    // staging capacities; the entry slice is copied from its enclosing 16-byte boundary (up to 7 entries of slack)
-    int cap_pass = b->max_pass, cap_ops = (b->max_ops + 7) & ~7, cap_ent = (b->max_ent + 14) & ~7;
-    const size_t staging_words = (size_t)s->setup.books.size() * 8 + (size_t)((s->dev.lattice_words + 3) & ~3) + (size_t)cap_pass * 16 +
-                                 (size_t)cap_ops * 6 + (size_t)cap_ops / 2 + (size_t)cap_ent / 2;  // ops 2 + pair records 4 + links 1/2 words per op
-    // k_spectrum_gen8 overlays the floor scratch on the staged side information (dead by the time the floors are prepared)
-    size_t words = (size_t)(has_floor0 ? 512 : 256) + (gen8 ? std::max(scratch_words, staging_words) : scratch_words + staging_words) +
-                   (size_t)ch * (size_t)(s->setup.block1 / 2);
-    if (T.unfused) words = 1u << 20;  // test aid: force the unfused kernels below
-    if ((words + (size_t)(s->setup.block1 / 16)) * 4 > 64 * 1024) fuse_imdct = false;
-    const size_t lds_pad = (size_t)T.lds_pad;  // occupancy experiments
-    // A frame that does not fit the default 64 KB dynamic-LDS window (six channels at n = 4096 with full-depth packets:
-    // 48 KB of spectrum + ~25 KB of staged ops and entries) still fits the CU's 160 KB: the general kernels opt in to a larger
-    // window, one workgroup per CU, instead of falling back to the global-memory kernels (measured on the C4 full-depth
-    // stream: k_residue + k_couple_floor 510 us per 2048 frames).
-    size_t lds_limit = 64 * 1024;
-    // (not for residues that replay the reference's partition order, one vector write at a time: a lone 8-wavefront workgroup
-    // per CU is the worst shape for that -- 1135 us against 840 us for the global-memory kernels on the psize-32 C4 stream)
-    if (!has_floor0 && !fast && !T.unfused && !s->shared->has_sequential && words * 4 > lds_limit && words * 4 <= 152 * 1024) {
-      if (!s->ctx->big_lds_attr_set) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_spectrum_gen, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_spectrum_gen8, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_spectrum_gen8_imdct, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_spectrum_gen_imdct, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        s->ctx->big_lds_attr_set = true;
-      }
-      lds_limit = 152 * 1024;
-    }
-    if (words * 4 <= lds_limit) {
-      if (timing) HIP_TRY(hipEventRecord(ev[1], st));  // slot 0 stays empty: slot 1 = fused spectrum kernel
-      b->slot_name[0] = "-";
-      b->slot_name[1] = has_floor0 ? "k_spectrum_f0" : (fast ? "k_spectrum" : "k_spectrum_gen");
-      if (has_floor0) {
-        hipLaunchKernelGGL(k_spectrum_f0, dim3((unsigned)b->nframes), dim3(256), words * 4, st, s->dev, b->dev, work, flags,
-                           cap_pass, cap_ops, cap_ent);
-      } else if (gen8) {
-        // the inverse MDCT in the same workgroup (one wavefront per channel, slices laid over the dead floor scratch, side
-        // information and spectra): block sizes the in-register spectrum covers, and the padding has to fit in front of the spectra
-        const size_t front_words = words - (size_t)ch * (size_t)(s->setup.block1 / 2);
-        fuse_gen8 = compact && !no_fused_imdct && ch <= 8 && s->setup.block1 <= 4096 &&
-                    256 + (size_t)ch * (size_t)(s->setup.block1 / 16) <= front_words;
-        b->slot_name[1] = fuse_gen8 ? "k_spectrum_gen8_imdct" : "k_spectrum_gen8";
-        hipLaunchKernelGGL(fuse_gen8 ? k_spectrum_gen8_imdct : k_spectrum_gen8, dim3((unsigned)b->nframes), dim3(512), words * 4, st, s->dev,
-                           b->dev, work, flags, cap_pass, cap_ops, cap_ent NVH_DBG_LAUNCH);
-      } else if (!fast) {
-        // the inverse MDCT in the same workgroup where a wavefront per channel exists: mono / stereo setups take the kernel's
-        // fused tail and k_spectrum_imdct's transform (one n/16-float pad behind the spectra), three and four channels the general
-        // tail and the transform of k_spectrum_gen8_imdct (slices over the dead front of the LDS area)
-        size_t extra = 0;
-        if (compact && !no_fused_imdct && ch <= 4) {
-          if (s->dev.fused_tail_ok) {
-            fuse_gen8 = s->setup.block1 <= 2048 && (words + (size_t)(s->setup.block1 / 16)) * 4 <= lds_limit;
-            if (fuse_gen8) extra = (size_t)(s->setup.block1 / 16) * 4;
-          } else {
-            const size_t front_words = words - (size_t)ch * (size_t)(s->setup.block1 / 2);
-            fuse_gen8 = s->setup.block1 <= 4096 && 256 + (size_t)ch * (size_t)(s->setup.block1 / 16) <= front_words;
-          }
+      A.ipool = s->dev.ipool;
+      A.vq = s->dev.vq;
+      A.const_vecs = s->shared->synth_const_vecs;
+      A.stride_vecs = b->slab_stride_vecs;
+      A.cap_vecs = b->slab_cap_vecs;
+      A.lds_vecs = r.lds_vecs;
+      A.channels = s->setup.channels;
+      A.block1 = s->setup.block1;
+      A.nframes = b->nframes;
+      A.xcd_map = r.xcd_map;
+      A.walk_two = r.walk_two;
+      A.pcm = r.emitted ? (float*)d_pcm : nullptr;  // (int16_t samples for the _s16 twins)
+      A.windows = s->dev.windows;
+      A.clip = s->clip;
+      A.plane_stride = r.plane_stride;
+      A.clipped_flag = flags + 1;
+      A.carry = carry;
+      A.carry_out = r.emitted ? carry_out : nullptr;
+      A.frames = b->dev.frames;
+      switch (r.synth) {
+        case SynthStage::kSynth: slab(k_synth); break;
+        case SynthStage::kSynthG: slab(k_synth_g); break;
+        case SynthStage::kSynth8: slab(k_synth8); break;
+        case SynthStage::kSynth8G: slab(k_synth8_g); break;
+        case SynthStage::kSynth8Emit:
+          if (r.odd_launch) slab(k_synth8);
+          with_pcm_twins(out, [&](auto t) {
+            if constexpr (nvh_layout_mapped(decltype(t)::layout)) slab(t.synth8_emit, out.map);
+            else slab(t.synth8_emit);
+          });
+          break;
+        case SynthStage::kSynthEmit:
+          if (r.odd_launch) slab(r.odd_tail ? k_synth_tail : k_synth);
+          slab(with_unmapped_twins(out, [](auto t) { return t.synth_emit; }));
+          break;
+        case SynthStage::kGroup2:
+        case SynthStage::kGroup4: {
+          auto kern = with_unmapped_twins(out, [&](auto t) { return r.synth == SynthStage::kGroup2 ? t.group2 : t.group4; });
+          if (r.debug_occ) print_occupancy("frame groups", (const void*)kern, go.peek(), &A);
+          if (r.odd_launch) slab(kern);
+          slab(kern);
+          break;
         }
-        if (fuse_gen8) b->slot_name[1] = "k_spectrum_gen_imdct";
-        hipLaunchKernelGGL(fuse_gen8 ? k_spectrum_gen_imdct : k_spectrum_gen, dim3((unsigned)b->nframes), dim3(256), words * 4 + extra, st,
-                           s->dev, b->dev, work, flags, cap_pass, cap_ops, cap_ent NVH_DBG_LAUNCH);
-      } else {
-        if (T.debug_occ) {
-          int nb = -1;
-          hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_spectrum, 256, words * 4 + lds_pad);
-          hipFuncAttributes fa;
-          (void)hipFuncGetAttributes(&fa, (const void*)k_spectrum);
-          fprintf(stderr, "k_spectrum: lds %zu B, occupancy %d WG/CU (err %d), regs %d, static lds %zu, max dyn lds %d\n", words * 4 + lds_pad, nb,
-                  (int)oe, fa.numRegs, fa.sharedSizeBytes, fa.maxDynamicSharedSizeBytes);
-        }
-        if (fuse_imdct) {
-          // + the IMDCT padding of the last channel (n/16 floats past the spectrum area)
-          b->slot_name[1] = "k_spectrum_imdct";
-          hipLaunchKernelGGL(k_spectrum_imdct, dim3((unsigned)b->nframes), dim3(256), words * 4 + (size_t)(s->setup.block1 / 16) * 4 + lds_pad,
-                             st, s->dev, b->dev, work, flags, cap_pass, cap_ops, cap_ent NVH_DBG_LAUNCH);
-        } else {
-          hipLaunchKernelGGL(k_spectrum, dim3((unsigned)b->nframes), dim3(256), words * 4 + lds_pad, st, s->dev, b->dev, work, flags,
-                             cap_pass, cap_ops, cap_ent NVH_DBG_LAUNCH);
-        }
+        default: break;
       }
-    } else {
-      b->slot_name[0] = "k_residue"; b->slot_name[1] = "k_couple_floor";
-      hipLaunchKernelGGL(k_residue, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, work, 1);
-      if (timing) HIP_TRY(hipEventRecord(ev[1], st));
-      hipLaunchKernelGGL(k_couple_floor, dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev, work, flags);
     }
   }
-  if (timing) HIP_TRY(hipEventRecord(ev[2], st));
-  const size_t plane_bytes = (size_t)ch * (size_t)s->setup.block1 * sizeof(float);
-  {
-    b->slot_name[2] = (fuse_imdct || fuse_gen8) ? "-" : compact ? "k_imdct_compact" : (s->setup.block0 >= 256 ? "k_imdct_wave" : "k_imdct_window");
-    b->slot_name_buf[3] = std::string(compact ? "k_ola_compact" : (!b->sequential_ola ? "k_ola_emit" : "k_ola_emit_seq")) + sfx;
-    b->slot_name[3] = b->slot_name_buf[3].c_str();
-    if (fuse_imdct || fuse_gen8)
-      ;  // done inside k_spectrum_imdct / k_spectrum_gen8_imdct
-    else if (compact)
-      hipLaunchKernelGGL(k_imdct_compact, dim3((unsigned)(b->nframes * ch)), dim3(64), wave_lds_bytes(s->setup.block1), st, s->dev,
-                         b->dev, work);
-    else if (s->setup.block0 >= 256)
-      hipLaunchKernelGGL(k_imdct_wave, dim3((unsigned)(b->nframes * ch)), dim3(64), wave_lds_bytes(s->setup.block1), st, s->dev,
-                         b->dev, work);
-    else
-      hipLaunchKernelGGL(k_imdct_window, dim3((unsigned)(b->nframes * ch)), dim3(256), lds, st, s->dev, b->dev, work);
-    if (timing) HIP_TRY(hipEventRecord(ev[3], st));
-    if (b->block_only) {
-      b->slot_name[3] = "-";  // nvh_mode_decode: the caller wants the windowed blocks themselves
-    } else if (compact) {
-      // (frame order by XCD -- blocks f and f-1, which share a quarter, behind the same L2 -- measured slower: 23.3 us, not 21.8)
-      // 128 lanes per frame: 21.4 us instead of 24.8 us on its own (more loads in flight per frame); with two batches
-      // in flight it is a wash against 64, and 256 lanes start to take wave slots from the other batch's spectrum kernel
-      const int ola_env = T.ola_threads;
-      const int ola_threads = (ola_env == 64 || ola_env == 128 || ola_env == 256) ? ola_env : 128;
-      // large frames are shared by several workgroups (kernels.hip): aim at one group of four sample times per lane
-      int segs = T.ola_segs > 0 ? T.ola_segs : (int)(((size_t)s->setup.block1 / 8 * (size_t)ch) / (size_t)(2 * 256));
-      if (segs < 1) segs = 1;
-      if (segs > 8) segs = 8;
-      if (segs > (s->setup.block1 / 8) / ola_threads) segs = (s->setup.block1 / 8) / ola_threads;
-      if (segs < 1) segs = 1;
-      // more than two channels: the steady-state path splits a frame into runs of NVH_OLA_GW groups of four sample times, one
-      // workgroup each, and interleaves through LDS (ola_sym_lds)
-      if (ch > 2 && !T.no_ola_sym && T.ola_segs <= 0) segs = ((s->setup.block1 / 16) + NVH_OLA_GW - 1) / NVH_OLA_GW;
-      auto ola_compact = [&](unsigned nwg, float* c_out, const int* list, int emitted_frames) {
-        with_pcm_twins(out, [&](auto t) {
-          typedef decltype(t) TW;
-          hipLaunchKernelGGL((k_ola_compact<typename TW::pcm, TW::layout>), dim3(nwg, (unsigned)segs), dim3((unsigned)ola_threads), 0, st,
-                             s->dev, b->dev, (const float*)work, carry, (typename TW::pcm*)d_pcm, s->clip, flags + 1, c_out,
-                             b->last_decoded, T.no_ola_sym ? 1 : 0, list, emitted_frames, ola_stride(t));
-        });
-      };
-      if (!emitted)
-        ola_compact((unsigned)b->nframes, carry_out, (const int*)nullptr, 0);
-      else if (b->ola_all)  // GPU-parsed batch, some candidate withdrawn on the device: every frame, the emitted ones return at once
-        ola_compact((unsigned)b->nframes, (float*)nullptr /* k_synth wrote the carried tail */, (const int*)nullptr, 1);
-      else if (b->ola_count == 0)
-        b->slot_name[3] = "-";  // paired emission covered every frame, the carried tail included: no launch
-      else  // paired emission: only the frames k_synth left over
-        ola_compact((unsigned)b->ola_count, (float*)nullptr /* k_synth wrote the carried tail */, b->d_ola_list, 1);
-    } else if (!b->sequential_ola) {
-      with_pcm_twins(out, [&](auto t) {
-        typedef decltype(t) TW;
-        hipLaunchKernelGGL((k_ola_emit<typename TW::pcm, TW::layout>), dim3((unsigned)b->nframes), dim3(256), 0, st, s->dev, b->dev,
-                           (const float*)work, carry, (typename TW::pcm*)d_pcm, s->clip, flags + 1, ola_stride(t));
-      });
-    } else {
-      with_pcm_twins(out, [&](auto t) {
-        typedef decltype(t) TW;
-        hipLaunchKernelGGL((k_ola_emit_seq<typename TW::pcm, TW::layout>), dim3(1), dim3(256), 0, st, s->dev, b->dev, work, carry,
-                           (typename TW::pcm*)d_pcm, s->clip, flags + 1, ola_stride(t));
-      });
-    }
-    // the last decoded block becomes the carried tail (StreamDecoder's _prevPacketBuf), always fully windowed
-    if (!compact && !b->block_only && b->last_decoded >= 0 && carry_out)
-      HIP_TRY(hipMemcpyAsync(carry_out, (const uint8_t*)b->work.p + (size_t)b->last_decoded * plane_bytes, plane_bytes,
-                             hipMemcpyDeviceToDevice, st));
+  go.open(2);
+
+  // ---- transform: slot 2 ----
+  switch (r.transform) {
+    case TransformStage::kNone: break;  // done inside the synthesis kernel
+    case TransformStage::kImdctCompact: go(k_imdct_compact, s->dev, b->dev, work); break;
+    case TransformStage::kImdctWave: go(k_imdct_wave, s->dev, b->dev, work); break;
+    case TransformStage::kImdctWindow: go(k_imdct_window, s->dev, b->dev, work); break;
   }
-  if (d_pcm && !b->block_only) launch_gap_fill(b, out, d_pcm, st);
-  if (timing) HIP_TRY(hipEventRecord(ev[4], st));
+  go.open(3);
+
+  // ---- overlap-add: slot 3 ----
+  with_pcm_twins(out, [&](auto t) {
+    typedef decltype(t) TW;
+    typedef typename TW::pcm PCM;
+    switch (r.overlap) {
+      case OverlapStage::kNone: break;
+      case OverlapStage::kCompactAll:
+      case OverlapStage::kCompactAllEmitted:
+      case OverlapStage::kCompactList:
+        // (after paired emission k_synth wrote the carried tail)
+        go((k_ola_compact<PCM, TW::layout>), s->dev, b->dev, (const float*)work, carry, (PCM*)d_pcm, s->clip, flags + 1,
+           r.emitted ? (float*)nullptr : carry_out, b->last_decoded, r.no_ola_sym,
+           r.overlap == OverlapStage::kCompactList ? b->d_ola_list : (const int*)nullptr, r.emitted_frames, ola_stride(t));
+        break;
+      case OverlapStage::kEmit:
+        go((k_ola_emit<PCM, TW::layout>), s->dev, b->dev, (const float*)work, carry, (PCM*)d_pcm, s->clip, flags + 1, ola_stride(t));
+        break;
+      case OverlapStage::kEmitSeq:
+        go((k_ola_emit_seq<PCM, TW::layout>), s->dev, b->dev, work, carry, (PCM*)d_pcm, s->clip, flags + 1, ola_stride(t));
+        break;
+    }
+  });
+  if (r.carry_copy) {
+    const size_t plane_bytes = (size_t)s->setup.channels * (size_t)s->setup.block1 * sizeof(float);
+    HIP_TRY(hipMemcpyAsync(carry_out, (const uint8_t*)b->work.p + (size_t)b->last_decoded * plane_bytes, plane_bytes,
+                           hipMemcpyDeviceToDevice, st));
+  }
+  launch_gap_fill(b, go, d_pcm);
+  go.open(4);
+  HIP_TRY(go.err);
   HIP_TRY(hipGetLastError());
   if (timing && !ext_ev) {
     HIP_TRY(hipEventSynchronize(ev[4]));

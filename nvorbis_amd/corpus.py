@@ -8,6 +8,7 @@ point-to-point, each peer has one direct link to the root; a ring collective wou
 shape).  Works with backend "nccl" (= RCCL, device tensors) and "gloo" (CPU tensors, used by the CPU
 test suite).
 """
+import collections
 import os
 
 import numpy as np
@@ -234,6 +235,20 @@ def _decode_file_packets(st, pa, batch_frames, sink):
             break
 
 
+def _open_stream(ctx, pa, gpu_parse):
+    """A worker's stream on the headers of `pa`; gpu_parse: its packets go to k_parse where the stream's shape allows it
+    (reader._enable_gpu_parse: only "unsupported" keeps the host parser, any other failure is raised)."""
+    from .reader import Stream, _enable_gpu_parse
+    st = Stream(ctx, pa[0], pa[1], pa[2])
+    if gpu_parse:
+        try:
+            _enable_gpu_parse(st)
+        except Exception:
+            st.close()
+            raise
+    return st
+
+
 _MALLOC_TUNED = [False]
 
 
@@ -314,7 +329,7 @@ def _warm_contexts(device, nthreads, sample, batch_frames, gpu_parse, parse_lane
 
     import torch
 
-    from .reader import Context, Stream, demux_ogg_array
+    from .reader import Context, demux_ogg_array
     out = [have[t] if (have is not None and t < len(have)) else None for t in range(nthreads)]
 
     def one(t, pa):
@@ -322,13 +337,8 @@ def _warm_contexts(device, nthreads, sample, batch_frames, gpu_parse, parse_lane
         try:
             ctx = Context(device)
             ctx.set_parse_lanes(parse_lanes)
-            st = Stream(ctx, pa[0], pa[1], pa[2])
+            st = _open_stream(ctx, pa, gpu_parse)
             try:
-                if gpu_parse:
-                    try:
-                        st.set_gpu_parse(True)
-                    except Exception:
-                        pass
                 if len(pa) > 3:
                     st.push_packets(pa, 3, batch_frames)
                 need = st.pending()[1] * st.channels
@@ -408,6 +418,20 @@ def _early_arena(files, device):
     th = threading.Thread(target=run, daemon=True)
     th.start()
     return th, box
+
+
+def _settle_arena(box, total, device):
+    """The arena of `total` floats: the first `total` of _early_arena's block (box[0], or None) when at most 2 % or 4 MB of it
+    stays unused -- the slice pins the whole block for the arena's lifetime --, else a block of exactly that size.  Short files
+    (a 1-second stereo file's bound is ~37 % above its length), chained or damaged ones take the second way; the early block then
+    goes back to the device first, so that both do not sit in torch's cache next to the library's own pools."""
+    import torch
+    if box[0] is not None and 1 <= total <= int(box[0].numel()) <= total + max(total // 50, 1 << 20):
+        return box[0][:total]
+    if box[0] is not None:
+        box[0] = None
+        torch.cuda.empty_cache()
+    return torch.empty(max(total, 1), dtype=torch.float32, device="cuda:%d" % device)
 
 
 def _run_pool(n_items, workers, device, fn, need_ctx=True, keep_contexts=False, parse_lanes=0, contexts=None):
@@ -553,6 +577,76 @@ def _index_pass(files, workers, full_index=False):
     return shape, totals, chans, errors
 
 
+class _Slot(collections.namedtuple("_Slot", "off ch per_ch stride reserved count planar mono")):
+    """Where one file's PCM goes in a float32 tensor (_plan_slots makes them): `off` elements from the tensor's start, `ch` channels
+    of `per_ch` samples, planes `stride` elements apart, `reserved` elements up to the next slot.  The file's decode counts its
+    progress in the units synth_device returns for the form, from 0 to `count`."""
+    __slots__ = ()
+
+    def view(self, t):
+        """The file's PCM cut out of the tensor the slot lies in: (count,), or planar (ch, per_ch) with strides (stride, 1)."""
+        if self.planar:
+            return t[self.off:self.off + self.reserved].view(self.ch, self.stride)[:, :self.per_ch]
+        return t[self.off:self.off + self.count]
+
+    def synth_args(self, base_ptr, done):
+        """(d_ptr, capacity, plane_stride) of the synth_device call behind `done` units of progress, `base_ptr` the tensor's address."""
+        d_ptr = base_ptr + 4 * (self.off + done)
+        return (d_ptr, 0, self.stride) if self.planar else (d_ptr, self.count - done, None)
+
+
+def _plan_slots(per_ch, chans, planar=False, mono=False):
+    """(slots, total elements) of files with per_ch[i] samples in chans[i] channels, in list order.  Interleaved files lie back to
+    back and count floats; planar and mono slots are whole planes -- the plane stride is per_ch rounded up to a multiple of four,
+    so that the kernels' vector stores run -- and count samples per channel (planar) or of the mix (mono: floats again)."""
+    slots, off = [], 0
+    for p, c in zip(per_ch, chans):
+        p, c = int(p), int(c)
+        stride = (p + 3) & ~3
+        count = p if (planar or mono) else c * p
+        reserved = c * stride if planar else stride if mono else count
+        slots.append(_Slot(off, c, p, stride, reserved, count, bool(planar), bool(mono)))
+        off += reserved
+    return slots, off
+
+
+def _decode_into(ctx, pa, slot, base_ptr, file_no, batch_frames=4096, gpu_parse=False, phase=None, checked=False):
+    """Decode the packet list `pa` on `ctx` into `slot` of the device tensor at `base_ptr`: the synthesis kernels write every
+    look-ahead batch at its final address.  A batch that would pass the slot's end is refused before anything is written, and
+    a decode that ends short of it raises.  `file_no` and `checked` (the slot was sized from the checked packet list, not from
+    the index) word the errors; `phase`: a dict whose "open", "push", "synth" and "close" gain this file's seconds."""
+    import time
+    says = "checked index" if checked else "index"
+    unit = "samples per channel" if slot.planar else "floats"
+    per_sample = 1 if (slot.planar or slot.mono) else slot.ch  # units of progress per sample time
+    done, in_sink = 0, 0.0
+
+    def sink(s):
+        nonlocal done, in_sink
+        ts = time.perf_counter()
+        if s.pending()[1] * per_sample > slot.count - done:  # (the planar call takes no capacity: this is its only guard)
+            raise RuntimeError("file %d produces more than the %d %s its %s says" % (file_no, slot.count, unit, says))
+        d_ptr, capacity, plane_stride = slot.synth_args(base_ptr, done)
+        done += s.synth_device(d_ptr, capacity, plane_stride=plane_stride, mix="mono" if slot.mono else None)
+        in_sink += time.perf_counter() - ts
+
+    t0 = time.perf_counter()
+    st = _open_stream(ctx, pa, gpu_parse)
+    t1 = time.perf_counter()
+    try:
+        _decode_file_packets(st, pa, batch_frames, sink)
+        if done != slot.count:
+            raise RuntimeError("file %d produced %d %s, its %s says %d" % (file_no, done, "samples" if checked else unit, says, slot.count))
+    finally:
+        t2 = time.perf_counter()
+        st.close()
+        if phase is not None:
+            phase["open"] += t1 - t0
+            phase["synth"] += in_sink
+            phase["push"] += t2 - t1 - in_sink
+            phase["close"] += time.perf_counter() - t2
+
+
 def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_parse=False, keep_contexts=False, timings=None, tune_process=False,
                            layout="interleaved", mix=None):
     """Decode .ogg byte strings on ONE GPU into ONE device arena: returns (arena, views) with views[i] the interleaved
@@ -572,25 +666,28 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
     number, window flags -- how many samples the serial decoder emits), which sizes the arena; then the decode, whose
     overlap-add kernels write each batch's PCM at its final address (nvh_stream_synth with a device destination).  No
     PCM crosses PCIe.  tune_process: see _tune_malloc (process-wide, opt-in)."""
+    import sys
+    import time
+
     import torch
 
-    from .reader import Context, Stream, _layout, _mix, demux_ogg_array, index_ogg_array
+    from .reader import Context, Stream, _layout, _mix, demux_ogg_array
+    # ---- the switches ----
     planar = _layout(layout)
     _mix(mix, planar)
     mono = mix is not None
     n = len(files)
     full_index = bool(os.environ.get("NVH_CORPUS_FULL_INDEX"))  # A/B aid: the round-5 index (checksums + a copy of every packet)
-
-    import time
     if tune_process or os.environ.get("NVH_CORPUS_MALLOPT"):  # process-wide allocator settings: opt-in (see _tune_malloc)
         _tune_malloc()
     wait_contexts_closed()  # the job before gives its workers' device / page-locked pools back first
-    timing = bool(os.environ.get("NVH_CORPUS_TIMING"))
+    phase = {"open": 0.0, "push": 0.0, "synth": 0.0, "close": 0.0} if os.environ.get("NVH_CORPUS_TIMING") else None  # seconds summed over the workers
     if os.environ.get("NVH_CORPUS_BATCH"):  # A/B aid: packets per parse / synthesis batch
         batch_frames = int(os.environ["NVH_CORPUS_BATCH"])
     t_start = time.perf_counter()
     keep = keep_contexts or bool(os.environ.get("NVH_CORPUS_KEEP_CTX"))
     lanes = PARSE_LANES_POOL if (gpu_parse and min(workers, n) >= 8) else 0
+    # ---- the warm-up and the early arena, beside the index pass ----
     warm_thread, warm = None, None
     if n and not os.environ.get("NVH_CORPUS_NO_WARM"):  # the GPU side of the workers gets ready while the index pass keeps the CPUs busy
         sample = max(range(n), key=lambda i: len(files[i]))
@@ -617,32 +714,17 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
                     c.close()
         raise RuntimeError("index failed for files %s: %r" % ([i for i, _ in errors], errors[0][1]))
     t_index = time.perf_counter()
-    # planar: per file C planes of S = T rounded up to whole groups of four samples
-    per_ch = [int(totals[i]) // max(int(chans[i]), 1) for i in range(n)]
-    if mono:  # one sample per sample time
-        totals = np.asarray(per_ch, np.int64)
-    strides = [(t + 3) & ~3 for t in per_ch]
-    offs = np.zeros(n + 1, np.int64)
-    offs[1:] = np.cumsum([int(chans[i]) * strides[i] for i in range(n)] if planar else strides if mono else totals)
-    ends = [int(offs[i]) + int(totals[i]) for i in range(n)]  # (interleaved: offs[i + 1]; mono: in front of the slot's padding)
-    total = int(offs[-1])
-    if arena_box[0] is not None and total >= 1 and total <= int(arena_box[0].numel()) <= total + max(total // 50, 1 << 20):
-        # allocated during the index pass from an upper bound (two maximal blocks per file beyond its last granule position): taken
-        # when at most 2 % (or 4 MB) of it stays unused -- the slice pins the whole block for the arena's lifetime
-        arena = arena_box[0][:total]
-    else:
-        # short files (a 1-second stereo file's bound is ~37 % above its length), chained or damaged ones: the exact size, and the
-        # early block goes back to the device first so that both do not sit in torch's cache next to the library's own pools
-        if arena_box[0] is not None:
-            arena_box[0] = None
-            torch.cuda.empty_cache()
-        arena = torch.empty(max(total, 1), dtype=torch.float32, device="cuda:%d" % device)
+    # ---- every file's slot, and the arena that holds them ----
+    slots, total = _plan_slots([int(totals[i]) // max(int(chans[i]), 1) for i in range(n)], chans, planar, mono)
+    arena = _settle_arena(arena_box, total, device)
     torch.cuda.synchronize(device)
     base = arena.data_ptr()
+    t_alloc = time.perf_counter()
+    if warm_thread is not None:
+        warm_thread.join()
+    t_warm = time.perf_counter()
+    # ---- the decode pass ----
     order = sorted(range(n), key=lambda i: (-len(files[i]), i))  # longest first: shorter tail
-
-    phase = {"open": 0.0, "synth": 0.0, "push": 0.0, "close": 0.0}  # NVH_CORPUS_TIMING: seconds summed over the workers
-
     redo = []  # files whose checked demultiplex disagrees with the index (a damaged page): decoded again below, the slow way
 
     def decode_one(k, ctx):
@@ -650,116 +732,47 @@ def decode_files_to_device(files, device=0, workers=16, batch_frames=4096, gpu_p
         pa = demux_ogg_array(files[i])  # with the page checksums
         if shape[i] != (len(pa), int(pa.offsets[-1])):
             redo.append(i)
-            return
-        t0 = time.perf_counter()
-        st = Stream(ctx, pa[0], pa[1], pa[2])
-        try:
-            if gpu_parse:
-                try:
-                    st.set_gpu_parse(True)
-                except Exception:
-                    pass
-            pos = [int(offs[i])]
-            t1 = time.perf_counter()
-            in_sink = [0.0]
+        else:
+            _decode_into(ctx, pa, slots[i], base, i, batch_frames, gpu_parse, phase)
 
-            def sink(s):
-                ts = time.perf_counter()
-                if planar:  # pos[0]: samples per channel written so far; plane c at offs[i] + c * strides[i]
-                    if s.pending()[1] > per_ch[i] - pos[0]:
-                        raise RuntimeError("file %d produces more than the %d samples per channel its index says" % (i, per_ch[i]))
-                    pos[0] += s.synth_device(base + 4 * (int(offs[i]) + pos[0]), 0, plane_stride=strides[i])
-                    in_sink[0] += time.perf_counter() - ts
-                    return
-                room = ends[i] - pos[0]
-                need = s.pending()[1] * (1 if mono else s.channels)
-                if need > room:
-                    raise RuntimeError("file %d produces more than the %d floats its index says" % (i, totals[i]))
-                pos[0] += s.synth_device(base + 4 * pos[0], room, mix=mix)
-                in_sink[0] += time.perf_counter() - ts
-
-            if planar:
-                pos[0] = 0
-            _decode_file_packets(st, pa, batch_frames, sink)
-            if planar and pos[0] != per_ch[i]:
-                raise RuntimeError("file %d produced %d samples per channel, its index says %d" % (i, pos[0], per_ch[i]))
-            if not planar and pos[0] != ends[i]:
-                raise RuntimeError("file %d produced %d floats, its index says %d" % (i, pos[0] - int(offs[i]), totals[i]))
-        finally:
-            t2 = time.perf_counter()
-            st.close()
-            if timing:
-                t3 = time.perf_counter()
-                phase["open"] += t1 - t0
-                phase["synth"] += in_sink[0]
-                phase["push"] += t2 - t1 - in_sink[0]
-                phase["close"] += t3 - t2
-
-    t_alloc = time.perf_counter()
-    if warm_thread is not None:
-        warm_thread.join()
-    t_warm = time.perf_counter()
     errors = _run_pool(n, workers, device, decode_one, keep_contexts=keep, parse_lanes=lanes, contexts=warm)
     if errors:
         raise RuntimeError("decode failed for files %s: %r" % ([order[k] for k, _ in errors], errors[0][1]))
-    if timings is not None:  # (a dict of the caller's: where the call's time went)
+    t_decoded = time.perf_counter()
+    views = [s.view(arena) for s in slots]
+    # ---- the files to decode again ----
+    # A page the index took at its word failed its checksum: the reference's reader drops it and resynchronises, the file's
+    # packet list -- and with it its length -- is another.  Such a file gets a tensor of its own (views[i] is then not a slice
+    # of the arena; the gather copes), decoded from the checked packet list into a one-file plan.
+    ctx = Context(device) if redo else None
+    try:
+        for i in sorted(redo):
+            pa = demux_ogg_array(files[i])
+            st = Stream(None, pa[0], pa[1], pa[2])
+            try:
+                (slot,), size = _plan_slots([int(st.index_total(pa, 3))], [st.channels], planar, mono)
+            finally:
+                st.close()
+            own = torch.empty(max(size, 1), dtype=torch.float32, device="cuda:%d" % device)
+            torch.cuda.synchronize(device)
+            _decode_into(ctx, pa, slot, own.data_ptr(), i, batch_frames, gpu_parse, checked=True)
+            ctx.synchronize()
+            views[i] = slot.view(own)
+    finally:
+        if ctx is not None:
+            ctx.close()
+    # ---- where the call's time went ----
+    if timings is not None:  # (a dict of the caller's)
         timings.update({"index_s": t_index - t_start, "arena_s": t_alloc - t_index, "wait_for_warm_contexts_s": t_warm - t_alloc,
-                        "decode_pass_s": time.perf_counter() - t_warm, "parse_lanes": lanes})
-    if timing:
-        import sys
+                        "decode_pass_s": t_decoded - t_warm, "parse_lanes": lanes})
+        if redo:
+            timings["files_reindexed"] = sorted(redo)
+    if phase is not None:
         sys.stderr.write("decode_files_to_device: demux + index pass %.3f s, arena %.3f s, decode pass %.3f s (%d workers)\n" % (
-            t_index - t_start, t_alloc - t_index, time.perf_counter() - t_alloc, workers))
+            t_index - t_start, t_alloc - t_index, t_decoded - t_alloc, workers))
         sys.stderr.write("decode_files_to_device: waited %.3f s for the warmed contexts; summed over the workers: stream open %.3f s, "
                          "push (+ upload and parse on the GPU in GPU-parse mode) %.3f s, synthesis %.3f s, close %.3f s\n" % (
                              t_warm - t_alloc, phase["open"], phase["push"], phase["synth"], phase["close"]))
-    if planar:
-        views = [arena[int(offs[i]):int(offs[i + 1])].view(int(chans[i]), strides[i])[:, :per_ch[i]] for i in range(n)]
-    else:
-        views = [arena[int(offs[i]):ends[i]] for i in range(n)]
-    if redo:
-        # A page the index took at its word failed its checksum: the reference's reader drops it and resynchronises, the file's
-        # packet list -- and with it its length -- is another.  Such a file gets a tensor of its own (views[i] is then not a slice
-        # of the arena; the gather copes), decoded from the checked packet list.
-        ctx = Context(device)
-        try:
-            for i in sorted(redo):
-                pa = demux_ogg_array(files[i])
-                st = Stream(None, pa[0], pa[1], pa[2])
-                try:
-                    per = int(st.index_total(pa, 3))
-                    nch = st.channels
-                    tot = per * (1 if mono else nch)
-                finally:
-                    st.close()
-                stride = (per + 3) & ~3
-                own = torch.empty(max(nch * stride if planar else tot, 1), dtype=torch.float32, device="cuda:%d" % device)
-                torch.cuda.synchronize(device)
-                st = Stream(ctx, pa[0], pa[1], pa[2])
-                try:
-                    if gpu_parse:
-                        try:
-                            st.set_gpu_parse(True)
-                        except Exception:
-                            pass
-                    pos = [0]
-
-                    def sink(s_):
-                        if planar:
-                            pos[0] += s_.synth_device(own.data_ptr() + 4 * pos[0], 0, plane_stride=stride)
-                        else:
-                            pos[0] += s_.synth_device(own.data_ptr() + 4 * pos[0], tot - pos[0], mix=mix)
-
-                    _decode_file_packets(st, pa, batch_frames, sink)
-                    if pos[0] != (per if planar else tot):
-                        raise RuntimeError("file %d produced %d samples, its checked index says %d" % (i, pos[0], per if planar else tot))
-                finally:
-                    st.close()
-                ctx.synchronize()
-                views[i] = own[:nch * stride].view(nch, stride)[:, :per] if planar else own[:tot]
-        finally:
-            ctx.close()
-        if timings is not None:
-            timings["files_reindexed"] = sorted(redo)
     return arena, views
 
 
@@ -774,7 +787,7 @@ def decode_files_threaded(files, device=0, workers=16, batch_frames=4096, gpu_pa
     (nvh_stream_push_packets), so the pool scales with cores.  gpu_parse=True moves the packet parse to the GPU as well
     (kernels_parse.hip): less host work per file, at ~0.8 ms of kernel latency per batch.  Results are byte-identical
     to a serial decode either way."""
-    from .reader import Stream, demux_ogg_array
+    from .reader import demux_ogg_array
     out = [None] * len(files)
     order = sorted(range(len(files)), key=lambda i: (-len(files[i]), i))  # longest first: shorter tail
 
@@ -782,13 +795,8 @@ def decode_files_threaded(files, device=0, workers=16, batch_frames=4096, gpu_pa
         i = order[k]
         out[i] = np.zeros(0, np.float32)
         pa = demux_ogg_array(files[i])
-        st = Stream(ctx, pa[0], pa[1], pa[2])
+        st = _open_stream(ctx, pa, gpu_parse)  # (gpu_parse: packets parsed by k_parse; shapes outside its limits keep the host parser)
         try:
-            if gpu_parse:  # packets parsed by k_parse; shapes outside its limits keep the host parser
-                try:
-                    st.set_gpu_parse(True)
-                except Exception:
-                    pass
             chunks = []
 
             def sink(s):
@@ -890,17 +898,12 @@ def decode_stream_chunk(ctx, packets, granules, flags, chunk, final, batch_frame
     the cut already accounts for them -- then the state is set and the chunk's own packets follow.  Only the stream's
     final chunk ends with the provider running dry (push_end); the others simply stop: the tail of their last block is
     emitted by the next chunk."""
-    from .reader import Stream
-    from . import native
+    from .reader import Stream, _enable_gpu_parse
     st = Stream(ctx, packets[0], packets[1], packets[2])
     try:
         st.set_clip(clip)
         if gpu_parse:
-            try:
-                st.set_gpu_parse(True)
-            except native.NvhError as e:
-                if e.code != native.ERR_UNSUPPORTED:
-                    raise
+            _enable_gpu_parse(st)
         first, last = chunk["first"], chunk["last"]
         if first > 3:
             st.push_packet(packets[first - 1], -1, 0)
